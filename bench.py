@@ -26,9 +26,16 @@ A step does everything a training step does, including rebuilding the graph inde
 raw COO edge_index (the cache is cleared every step: a new batch would arrive every step).
 The only collective is one RCCL all-reduce of the flat gradient buffer per step.
 
-Prints ONE JSON line of at most 6 KB on stdout (rank 0).  ``roofline`` describes the dominant fused
-gather-MLP kernel from HIP-event timings taken inside the timed region; ``cpu_baseline`` is the CPU
-oracle (oracle/ref_cpu.py, a restatement of the reference pinned against it) timed on this box's
+A plain run does only what the headline needs: set up, warm up, time exactly ``--steps`` steps and
+print the line (``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``, ...).
+``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy`` (``dump_outputs``).
+Everything else the benchmark measures or checks runs only with ``--full``: the per-kernel and
+per-stage HIP-event timings and the roofline block, the access floors, the CPU baseline, the parity
+check against the CPU oracle, the parameter checksum and the short runs of the other configurations.
+
+Prints ONE JSON line of at most 6 KB on stdout (rank 0).  With ``--full``, ``roofline`` describes the
+dominant fused gather-MLP kernel from HIP-event timings taken inside the timed region; ``cpu_baseline``
+is the CPU oracle (oracle/ref_cpu.py, a restatement of the reference pinned against it) timed on the
 host cores on one event of the same workload; ``kernels`` / ``extra`` are digests (a few numbers per
 kernel / per short run of the other configurations at N = 1): the full records go to
 ``bench_extra.json`` next to this file (and under ``gpurun_out/``) and to stderr (``emit``).
@@ -84,8 +91,17 @@ def parse(argv=None):
     ap.add_argument("--node-ids", default="random", choices=("random", "phi"),
                     help="synthetic events with hit ids random w.r.t. the geometry (default: worst case for the "
                          "node-row gathers) or numbered by phi (edges join neighbouring ids: best case)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the short runs of the other configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: per-kernel / per-stage HIP-event "
+                         "timings and the roofline block, the access floors, the CPU baseline, the parity check "
+                         "against the CPU oracle, the parameter checksum and the short runs of the other configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (rank 0: the model's outputs, "
+                         "the loss, the parameters after the optimizer step and their gradients) as DIR/<name>.npy in "
+                         "float32 / float64, at most 64 MB in all (larger arrays as a fixed, seeded sample of rows)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity check")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the short runs of the other configurations and the access floors")
     ap.add_argument("--cpu-iters", type=int, default=3)
     ap.add_argument("--backend", default=None, choices=("nccl", "gloo"),
                     help="process-group backend (default: nccl = RCCL).  gloo also works with device tensors "
@@ -100,6 +116,28 @@ def parse(argv=None):
 
 
 # ------------------------------------------------------------------------------- launcher
+def use_built_library() -> None:
+    """Point the loader at the library ``build()`` made (``GNNTRK_LIB``) when that library is current, so that a
+    user who may read the built tree but not write it can run the benchmark.  The loader's own check relinks under
+    a lock file in ``csrc/_obj`` and so needs write access even when nothing changed; this is the same check read
+    only: every object's stamp matches its source, flags and headers, and the library is newer than every object.
+    A stale, partial or missing build is left to the loader, which rebuilds it."""
+    if "GNNTRK_LIB" in os.environ:
+        return
+    from gnn_tracking_amd import _build
+
+    try:
+        mtimes = []
+        for src in sorted(_build.CSRC.glob("*.hip")):
+            if (_build.OBJ / (src.stem + ".stamp")).read_text() != _build._stamp(src):
+                return
+            mtimes.append((_build.OBJ / (src.stem + ".o")).stat().st_mtime)
+        if mtimes and _build.LIB.stat().st_mtime >= max(mtimes):
+            os.environ["GNNTRK_LIB"] = str(_build.LIB)
+    except OSError:
+        return
+
+
 def _free_port() -> int:
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -110,7 +148,7 @@ def launch_ranks(n: int, argv: list[str]) -> int:
     """``python bench.py --gpus N`` without torchrun: start N copies of this script, one per
     GPU, with torchrun's environment contract (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*).
     Rank 0 inherits stdout (it prints the line).  Returns the worst exit code."""
-    if "--stub" not in argv:
+    if "--stub" not in argv and "GNNTRK_LIB" not in os.environ:
         from gnn_tracking_amd import _build
         if _build.have_hipcc():
             _build.build_lib()   # (stamp check; the ranks then all find the library up to date)
@@ -473,7 +511,7 @@ class ECWorkload(Workload):
             events = [synthetic.make_event(seed0 + i, n_hits, n_edges, dev,
                                            phi_sorted_ids=getattr(args, "node_ids", "random") == "phi")
                       for i in range(n_ev)]
-            if rank == 0 and world == 1:
+            if rank == 0 and world == 1 and getattr(args, "full", False):   # (the CPU baseline's and parity check's event)
                 self.first_event_cpu = events[0].cpu()
             if loader_renumbered:   # (what io.GraphDataset(renumber=True) does per graph, once)
                 from gnn_tracking_amd import io as gio
@@ -754,18 +792,25 @@ def barrier(world: int) -> None:
         torch.cuda.synchronize()
 
 
-def timed_steps(wl: Workload, world: int, dev, steps: int, warmup: int, *, kernel_timer: bool):
+def timed_steps(wl: Workload, world: int, dev, steps: int, warmup: int, *, kernel_timer: bool,
+                stage_timer: bool = True, capture: "OutputCapture | None" = None):
     """W untimed steps, then EXACTLY K steps between barrier + synchronize on both sides;
-    returns (seconds = max over ranks, last loss, kernel summary)."""
+    returns (seconds = max over ranks, last loss, kernel summary).  ``capture`` keeps what the
+    model returned in the last timed step (``--dump-outputs``)."""
     # the per-kernel / per-stage HIP-event brackets are armed during the warm-up as well (their
     # first use costs tens of milliseconds of host time inside the HIP runtime - a one-time cost
     # like the first launch of a kernel) and emptied before the timed region
     timer = ops.KernelTimer() if kernel_timer and not os.environ.get("GNNTRK_BENCH_NO_TIMER") else None
     ops.set_kernel_timer(timer)
     if hasattr(wl, "stage"):
-        wl.stage.on = True
+        wl.stage.on = stage_timer
     for i in range(warmup):
+        if capture is not None and i == warmup - 1:
+            capture.arm()   # (the last warm-up step holds its outputs as the last timed step will: the allocator grows now)
         wl.step()
+        if capture is not None:
+            capture.disarm()
+            capture.outputs = []
         if i == warmup - 2:
             # one synchronisation INSIDE the warm-up: on a fresh box the first step after the process's
             # first device synchronisation costs its host thread 130 ms (measured: the runtime defers
@@ -791,12 +836,16 @@ def timed_steps(wl: Workload, world: int, dev, steps: int, warmup: int, *, kerne
     if debug:
         evs[0].record()
     for i in range(steps):
+        if capture is not None and i == steps - 1:
+            capture.arm()
         loss = wl.step()
         marks.append(time.perf_counter())   # (host-side enqueue times: no synchronisation)
         if debug:
             evs[i + 1].record()
     barrier(world)
     dt = time.perf_counter() - t0
+    if capture is not None:
+        capture.disarm()
     if debug:
         print("host ms per step:", [round((b - a) * 1e3, 1) for a, b in zip([t0] + marks, marks)], file=sys.stderr)
         print("gpu  ms per step:", [round(a.elapsed_time(b), 1) for a, b in zip(evs, evs[1:])], file=sys.stderr)
@@ -817,6 +866,70 @@ def timed_steps(wl: Workload, world: int, dev, steps: int, warmup: int, *, kerne
 
 
 PER_RANK_MS: list = []
+
+
+# ----------------------------------------------------------------------------- --dump-outputs
+DUMP_BUDGET = 48 << 20   # bytes of all arrays together (at most 64 MB with the .npy headers)
+
+
+class OutputCapture:
+    """What ``model``'s forward returned in the steps it is armed for: a forward hook registered only for
+    those steps, so every other step runs without it."""
+
+    def __init__(self, model):
+        self.model, self.outputs, self._handle = model, [], None
+
+    def arm(self) -> None:
+        self.outputs = []
+        self._handle = self.model.register_forward_hook(lambda mod, args, out: self.outputs.append(out))
+
+    def disarm(self) -> None:
+        if self._handle is not None:
+            self._handle.remove()
+            self._handle = None
+
+
+def _tensors(name: str, v, out: list) -> None:
+    if isinstance(v, torch.Tensor):
+        out.append((name, v))
+    elif isinstance(v, dict):
+        for k, x in v.items():
+            _tensors(f"{name}_{k}", x, out)
+    elif isinstance(v, (list, tuple)):
+        for j, x in enumerate(v):
+            _tensors(f"{name}_{j}", x, out)
+
+
+def dump_outputs(path: str, wl: Workload, capture: OutputCapture, final_loss: float) -> list[str]:
+    """``DIR/<name>.npy`` of what the last timed step computed: the model's outputs (``out_<key>``; one set per
+    micro-batch, ``out<j>_<key>``, where a step runs several), ``loss``, the parameters after the optimizer step
+    (``params``) and their gradients (``grads``).  Floating-point arrays as float32 (float64 stays float64),
+    integer and boolean ones as float64.  An array over its share of DUMP_BUDGET is written as a sample of its
+    rows drawn by a fixed seed from its row count alone, so that equal arguments give equal samples."""
+    import numpy as np
+
+    arrays: list = []
+    for j, out in enumerate(capture.outputs):
+        _tensors("out" if len(capture.outputs) == 1 else f"out{j}", out, arrays)
+    arrays += [("params", wl.flat.flat), ("grads", wl.flat.grad),
+               ("loss", torch.tensor([final_loss], dtype=torch.float64))]
+    share = DUMP_BUDGET // len(arrays)
+    os.makedirs(path, exist_ok=True)
+    names = []
+    for name, t in arrays:
+        t = t.detach()
+        wide = t.dtype == torch.float64 or not t.is_floating_point()
+        item = 8 if wide else 4
+        if t.dim() and t.numel() * item > share:
+            per_row = t.numel() // t.shape[0]
+            if per_row * item > share:
+                t, per_row = t.reshape(-1), 1
+            rows = np.unique(np.random.default_rng(0).integers(0, t.shape[0], size=share // (per_row * item)))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        a = (t.double() if wide else t.float()).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        names.append(name)
+    return names
 
 
 def collective_info(dist_backend: str) -> dict:
@@ -1249,6 +1362,8 @@ def emit(line: dict, kernels: dict | None, extra: dict | None) -> None:
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse(argv)
+    if not args.stub:
+        use_built_library()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, argv))
 
@@ -1277,20 +1392,25 @@ def main(argv=None):
         else:
             wl = ECWorkload(args, rank, world, dev, workload=args.workload, dtype=args.dtype, index=args.index)
 
-    dt, final_loss, ks = timed_steps(wl, world, dev, args.steps, args.warmup, kernel_timer=not args.stub)
+    capture = OutputCapture(wl.model) if args.dump_outputs and rank == 0 else None
+    dt, final_loss, ks = timed_steps(wl, world, dev, args.steps, args.warmup, kernel_timer=args.full and not args.stub,
+                                     stage_timer=args.full, capture=capture)
+    if capture is not None:
+        dump_outputs(args.dump_outputs, wl, capture, final_loss)
+        del capture
     # sum of |parameters| after the run: equal (to rounding) at every rank count for cfg4, whose
     # step is the same arithmetic however the shards are spread over ranks
     param_checksum = (float(sum(p.detach().double().abs().sum() for p in wl.model.parameters()))
-                      if hasattr(wl, "model") else None)
-    want_extra = not args.no_extra and not args.stub and args.workload == "cfg3" and args.dtype == "bf16"
+                      if args.full and hasattr(wl, "model") else None)
+    want_extra = args.full and not args.no_extra and not args.stub and args.workload == "cfg3" and args.dtype == "bf16"
     model_for_cpu = (getattr(wl, "first_event_cpu", None), getattr(wl, "model", None))
     describe, info, scaling, wdtype = wl.describe, wl.info, wl.scaling, getattr(wl, "dtype", args.dtype)
     edges_per_step = wl.edges_per_step_global
     roof_fn = getattr(wl, "roofline", None)
     cpu_fn = getattr(wl, "cpu_baseline", None)
-    stages = wl.stages() if hasattr(wl, "stages") else None
+    stages = wl.stages() if args.full and hasattr(wl, "stages") else None
     floor = None
-    if (rank == 0 and world == 1 and not args.stub and isinstance(wl, ECWorkload) and args.workload == "cfg3"
+    if (args.full and rank == 0 and world == 1 and not args.stub and isinstance(wl, ECWorkload) and args.workload == "cfg3"
             and args.dtype == "bf16" and not args.no_extra):
         try:
             floor = access_floor(wl, dev)
@@ -1304,14 +1424,13 @@ def main(argv=None):
         extra = extras(args, rank, world, dev)
 
     if rank == 0:
-        if roof_fn is not None:
-            roof, kernels = roof_fn(ks)
-        else:
-            roof, kernels = roofline_of(ks, args.dtype)
+        roof = kernels = None
+        if args.full:
+            roof, kernels = roof_fn(ks) if roof_fn is not None else roofline_of(ks, args.dtype)
         if roof is not None and floor is not None:
             roof["access_floor"] = floor
         cpu = parity = None
-        if world == 1 and not args.no_cpu_baseline and not args.stub:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.stub:
             if cpu_fn is not None:
                 cpu = cpu_fn(args.cpu_iters)
             elif model_for_cpu[0] is not None:
@@ -1339,6 +1458,7 @@ def main(argv=None):
             "vs_baseline": None,
             "dtype": wdtype,
             "data": "synthetic" if not args.stub else "stub",
+            "full": args.full,
             "config": {
                 "workload": describe,
                 "graph_index": args.index,

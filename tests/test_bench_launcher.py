@@ -198,3 +198,109 @@ def test_stub_run_prints_one_small_line():
     assert len(out) == 1 and len(out[0].encode()) < 8192
     d = json.loads(out[0])
     assert d["metric"] == "stub_not_a_measurement" and d["n_gpus"] == 1 and d["steps"] == 2
+
+
+def test_plain_run_dumps_its_last_step_the_same_every_time(tmp_path):
+    """``--dump-outputs DIR`` through the real control flow (stub workload): the model's output, loss, parameters
+    and gradients of the last timed step as float32 / float64 .npy files, identical from run to run; a plain
+    run's line carries the contract's keys and none of what ``--full`` adds."""
+    import numpy as np
+
+    runs = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--stub", "--steps", "3", "--warmup", "2",
+                            "--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=300, env=_env())
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _line(r.stdout)
+        assert d["steps"] == 3 and d["warmup"] == 2 and d["full"] is False and d["ms_per_step"] > 0
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["param_checksum"] is None
+        runs.append({f.stem: np.load(f) for f in (tmp_path / name).glob("*.npy")})
+    a, b = runs
+    assert set(a) == {"out", "loss", "params", "grads"}
+    assert a["out"].shape == (64, 1) and a["loss"].shape == (1,) and a["params"].shape == a["grads"].shape == (21,)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert abs(float(a["loss"][0]) - d["final_loss"]) <= 1e-5 * abs(d["final_loss"])   # (the line: six digits)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
+def test_dump_outputs_samples_what_exceeds_the_budget(tmp_path, monkeypatch):
+    """Arrays over their share of ``DUMP_BUDGET`` are written as a seeded sample of their rows (the same rows for
+    the same row count), integer / boolean outputs as float64, bf16 ones as float32; the rest in full."""
+    import types
+
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 6 * 40_000)   # six arrays below: 40 000 bytes each
+    g = torch.Generator().manual_seed(3)
+    out = {"W": torch.rand(100_000, generator=g), "y": torch.rand(100_000, generator=g) > 0.5,
+           "h": torch.rand(30_000, 5, generator=g).bfloat16()}
+    wl = types.SimpleNamespace(flat=types.SimpleNamespace(flat=torch.rand(1000, generator=g), grad=torch.rand(1000, generator=g)))
+    cap = bench.OutputCapture(torch.nn.Identity())
+    cap.outputs = [out]
+    names = bench.dump_outputs(str(tmp_path / "a"), wl, cap, 0.25)
+    assert sorted(names) == ["grads", "loss", "out_W", "out_h", "out_y", "params"]
+    bench.dump_outputs(str(tmp_path / "b"), wl, cap, 0.25)
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    for n in names:
+        assert np.array_equal(a[n], np.load(tmp_path / "b" / f"{n}.npy")), n
+        assert a[n].nbytes <= 40_000, n
+    rows = lambda n, k: np.unique(np.random.default_rng(0).integers(0, n, size=k))   # noqa: E731
+    assert a["out_W"].dtype == np.float32 and np.array_equal(a["out_W"], out["W"].numpy()[rows(100_000, 10_000)])
+    assert a["out_y"].dtype == np.float64 and np.array_equal(a["out_y"], out["y"].numpy()[rows(100_000, 5_000)])
+    assert a["out_h"].dtype == np.float32 and a["out_h"].shape[1] == 5
+    assert np.array_equal(a["out_h"], out["h"].float().numpy()[rows(30_000, 2_000)])
+    assert np.array_equal(a["params"], wl.flat.flat.numpy()) and np.array_equal(a["grads"], wl.flat.grad.numpy())
+    assert a["loss"].dtype == np.float64 and a["loss"].tolist() == [0.25]
+
+
+def test_a_current_build_is_used_without_write_access(tmp_path, monkeypatch):
+    """``bench.use_built_library``: a library whose objects all carry the stamps of their sources and which is newer
+    than every object is handed to the loader as it is (no build lock, nothing written: the tree may be read-only);
+    a stale stamp, a missing object or a library older than an object leaves the loader to rebuild."""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    from gnn_tracking_amd import _build
+
+    csrc, obj, lib = tmp_path / "csrc", tmp_path / "csrc" / "_obj", tmp_path / "libgnntrk.so"
+    obj.mkdir(parents=True)
+    monkeypatch.setattr(_build, "CSRC", csrc)
+    monkeypatch.setattr(_build, "OBJ", obj)
+    monkeypatch.setattr(_build, "LIB", lib)
+    for name in ("a", "b"):
+        (csrc / f"{name}.hip").write_text(f"// {name}\n")
+        (obj / f"{name}.o").write_bytes(b"o")
+        (obj / f"{name}.stamp").write_text(_build._stamp(csrc / f"{name}.hip"))
+        os.utime(obj / f"{name}.o", (1000, 1000))
+    lib.write_bytes(b"so")
+    os.utime(lib, (2000, 2000))
+
+    def chosen():
+        monkeypatch.delenv("GNNTRK_LIB", raising=False)
+        bench.use_built_library()
+        return os.environ.get("GNNTRK_LIB")
+
+    for p in (csrc / "a.hip", csrc / "b.hip", obj, csrc, tmp_path):
+        p.chmod(0o555)
+    try:
+        assert chosen() == str(lib)
+    finally:
+        for p in (csrc / "a.hip", csrc / "b.hip", obj, csrc, tmp_path):
+            p.chmod(0o755)
+    assert not (obj / ".lock").exists()
+    os.utime(lib, (500, 500))                       # library older than an object
+    assert chosen() is None
+    os.utime(lib, (2000, 2000))
+    (csrc / "b.hip").write_text("// b, edited\n")   # a source changed after its object was built
+    assert chosen() is None
+    (obj / "b.stamp").write_text(_build._stamp(csrc / "b.hip"))
+    assert chosen() == str(lib)
+    (obj / "a.o").unlink()                          # a missing object
+    assert chosen() is None
+    monkeypatch.setenv("GNNTRK_LIB", "/elsewhere/libgnntrk.so")   # a library named by the caller stays
+    bench.use_built_library()
+    assert os.environ["GNNTRK_LIB"] == "/elsewhere/libgnntrk.so"

@@ -295,7 +295,7 @@ def test_bench_cfg4_two_ranks_match_one_rank(dev, dtype):
     outs = {}
     for n in (1, 2):
         cmd = [sys.executable, str(root / "bench.py"), "--gpus", str(n), "--workload", "cfg4",
-               "--steps", "2", "--warmup", "1", "--no-extra", "--no-cpu-baseline", "--dtype", dtype]
+               "--steps", "2", "--warmup", "1", "--full", "--no-extra", "--no-cpu-baseline", "--dtype", dtype]
         if n > 1:
             cmd += ["--backend", "gloo"]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500)
@@ -331,7 +331,7 @@ def test_bench_cfg5_step_runs_in_both_storage_modes(dev):
     outs = {}
     for dt in ("f32", "bf16"):
         cmd = [sys.executable, str(root / "bench.py"), "--workload", "cfg5", "--events", "30000", "--dtype", dt,
-               "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+               "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         outs[dt] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -377,7 +377,7 @@ def test_cfg3_full_size_event_second_seed_low_pt_falsified(dev):
 
 
 def test_bench_default_line_is_one_small_json_line(dev):
-    """``python bench.py`` (here: two events, no side runs) prints exactly ONE stdout line, well below the size the
+    """``python bench.py --full`` (here: two events, no side runs) prints exactly ONE stdout line, well below the size the
     driver's parser lost in round 5, carrying ``roofline`` (with the live access floors), ``cpu_baseline`` and
     ``parity_check``; the full record goes to ``bench_extra.json`` and stderr."""
     import json
@@ -387,7 +387,7 @@ def test_bench_default_line_is_one_small_json_line(dev):
 
     root = pathlib.Path(__file__).resolve().parent.parent
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--events", "2", "--steps", "3", "--warmup", "2",
-                        "--cpu-iters", "1", "--no-extra"], capture_output=True, text=True, timeout=1500)
+                        "--full", "--cpu-iters", "1", "--no-extra"], capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     out = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(out) == 1 and len(out[0].encode()) < 8192, (len(out), [len(o) for o in out])
@@ -399,6 +399,38 @@ def test_bench_default_line_is_one_small_json_line(dev):
     assert d["parity_check"]["ok"] is True and d["parity_check"]["max_abs_W"] <= d["parity_check"]["bound"] <= 5e-4
     full = json.loads((root / "bench_extra.json").read_text())
     assert full["ms_per_step"] == __import__("pytest").approx(d["ms_per_step"], rel=1e-4) and len(full["kernels"]) >= 8
+
+
+def test_bench_plain_run_dumps_its_last_step(dev, tmp_path):
+    """A plain ``python bench.py`` times the steps and nothing else (no roofline, CPU baseline or parity check),
+    and ``--dump-outputs`` writes what the last timed step computed: the edge weights in edge_index order (a seeded
+    sample of the rows), the embeddings, loss, parameters and gradients, float32 / float64, within 64 MB."""
+    import json
+    import math
+    import pathlib
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = pathlib.Path(__file__).resolve().parent.parent
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--events", "2", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["metric"] == "edges_per_sec_fwd_bwd" and d["steps"] == 2 and d["dtype"] == "bf16" and d["full"] is False
+    assert d["ms_per_step"] > 0 and d["value"] == __import__("pytest").approx(
+        d["config"]["global_edges_per_step"] / (d["ms_per_step"] * 1e-3), rel=1e-4)
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["parity_check"] is None and d["kernels"] is None
+    a = {f.stem: np.load(f) for f in out.glob("*.npy")}
+    assert set(a) == {"out_W", "out_node_embedding", "out_edge_embedding", "loss", "params", "grads"}, sorted(a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(f.stat().st_size for f in out.glob("*.npy")) <= 64 << 20
+    w = a["out_W"]
+    assert w.ndim == 1 and 0 < w.size <= 4_000_000 and np.all((w > 0) & (w < 1))
+    assert math.isclose(float(a["loss"][0]), d["final_loss"], rel_tol=1e-5)   # (the line carries six digits)
+    assert a["params"].shape == a["grads"].shape and np.isfinite(a["grads"]).all() and np.abs(a["grads"]).max() > 0
 
 
 def test_reference_configs_from_class_path(dev):
