@@ -20,6 +20,8 @@ from .losses_ec import (EdgeWeightBCELoss, EdgeWeightFocalLoss, HaughtyFocalLoss
                         falsify_low_pt_edges)
 from .losses_ml import GraphConstructionHingeEmbeddingLoss
 from .losses_oc import CondensationLossRG, CondensationLossTiger, MultiLossFctReturn
+from .metrics import (BinaryClassificationStats, ec_validation_metrics, get_maximized_bcs, get_roc_auc_scores,
+                      roc_auc_score)
 from .mlp import MLP
 from .locality import node_order
 from .precision import bf16_storage
@@ -39,4 +41,6 @@ __all__ = ["Data", "collate", "MLP", "InteractionNetwork", "ResIN", "ECForGraphT
            "PreTrainedECGraphTCN", "ResFCNN", "GraphConstructionHingeEmbeddingLoss",
            "GraphConstructionFCNN", "HeterogeneousResFCNN", "GraphConstructionHeteroResFCNN",
            "GraphConstructionHeteroEncResFCNN", "GraphConstructionResIN", "PerfectECGraphTCN",
-           "GraphTCNForMLGCPipeline", "PerfectEdgeClassification", "MLPCTransformer", "knn_scan", "EdgeWeightFocalLoss", "HaughtyFocalLoss", "binary_focal_loss", "DBSCANFastRescan", "dbscan", "load_graph", "GraphDataset", "PrefetchLoader", "ResidentDataset", "renumber_nodes"]
+           "GraphTCNForMLGCPipeline", "PerfectEdgeClassification", "MLPCTransformer", "knn_scan", "EdgeWeightFocalLoss", "HaughtyFocalLoss", "binary_focal_loss", "DBSCANFastRescan", "dbscan", "load_graph", "GraphDataset", "PrefetchLoader", "ResidentDataset", "renumber_nodes",
+           "BinaryClassificationStats", "get_maximized_bcs", "roc_auc_score", "get_roc_auc_scores",
+           "ec_validation_metrics"]

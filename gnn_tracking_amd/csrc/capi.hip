@@ -104,6 +104,13 @@ size_t oc_backward_ws_bytes(int64_t, int);
 int oc_backward_launch(const gnntrk_oc_args *, const float *, const float *, float *, float *, int64_t, void *,
                        size_t, hipStream_t);
 
+// metrics.hip
+int bcs_counts(const float *, const void *, int32_t, const int32_t *, const void *, const void *, int32_t, const float *,
+               const float *, int32_t, const float *, int32_t, int64_t, int64_t *, hipStream_t);
+size_t roc_auc_ws_bytes(int64_t);
+int roc_auc(const float *, const void *, int32_t, const int32_t *, const void *, const void *, int32_t, const float *,
+            const float *, int32_t, const double *, int32_t, int64_t, int64_t *, void *, size_t, hipStream_t);
+
 }  // namespace gnntrk
 
 using namespace gnntrk;
@@ -372,6 +379,20 @@ size_t gnntrk_oc_backward_workspace_bytes(int64_t n, int32_t dim) { return oc_ba
 int gnntrk_oc_backward(const gnntrk_oc_args *args, const float *g, const float *fwd, float *gx,
                        float *gbeta, int64_t max_cps, void *workspace, size_t workspace_bytes, void *stream) {
     return oc_backward_launch(args, g, fwd, gx, gbeta, max_cps, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int gnntrk_bcs_counts(const float *w, const void *y, int32_t y_kind, const int32_t *perm, const void *src,
+                      const void *tgt, int32_t ids_i64, const float *pt, const float *cuts, int32_t n_cuts,
+                      const float *thr, int32_t n_thr, int64_t n, int64_t *counts, void *stream) {
+    return bcs_counts(w, y, y_kind, perm, src, tgt, ids_i64, pt, cuts, n_cuts, thr, n_thr, n, counts,
+                      (hipStream_t)stream);
+}
+size_t gnntrk_roc_auc_workspace_bytes(int64_t n) { return roc_auc_ws_bytes(n); }
+int gnntrk_roc_auc(const float *w, const void *y, int32_t y_kind, const int32_t *perm, const void *src, const void *tgt,
+                   int32_t ids_i64, const float *pt, const float *cuts, int32_t n_cuts, const double *max_fprs,
+                   int32_t n_fpr, int64_t n, int64_t *out, void *workspace, size_t workspace_bytes, void *stream) {
+    return roc_auc(w, y, y_kind, perm, src, tgt, ids_i64, pt, cuts, n_cuts, max_fprs, n_fpr, n, out, workspace,
+                   workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -118,7 +118,7 @@ class TrackingModule:
 
 
 class ECModule(TrackingModule):
-    """Edge-classifier training (``training/ec.py:25-53``)."""
+    """Edge-classifier training and validation (``training/ec.py:25-87``)."""
 
     def __init__(self, model: nn.Module, *, loss_fct: nn.Module, **kwargs):
         super().__init__(model, **kwargs)
@@ -134,6 +134,24 @@ class ECModule(TrackingModule):
         batch = self.data_preproc(batch)
         out = self(batch, _preprocessed=True)
         return self.get_losses(out, batch)
+
+    def validation_step(self, batch, batch_idx: int = 0) -> dict[str, float]:
+        """``training/ec.py:55-84``: the loss (``total``) and, for the pt cuts 0, 0.5, 0.9 and 1.5, the ROC
+        AUCs (full, 0.01 and 0.001 FPR) and the maximised binary-classification stats - what the reference
+        logs, returned as one dict.  The metrics run on the device (``metrics.ec_validation_metrics``: W is
+        not scattered into ``edge_index`` order) and the host reads them once.  ``train()`` / ``eval()``
+        is the caller's business, as in Lightning's loop."""
+        from .metrics import ec_validation_metrics
+
+        with torch.no_grad(), bf16_storage(self.bf16):
+            batch = self.data_preproc(batch)
+            out = self(batch, _preprocessed=True)
+            loss = self.get_losses(out, batch)
+            metrics = ec_validation_metrics(out["W"], batch.y, batch.pt, batch.edge_index, total=loss)
+        return metrics
+
+    def highlight_metric(self, metric: str) -> bool:
+        return metric in ["max_mcc_pt0.9", "total", "tpr_eq_tnr_pt0.9"]
 
 
 class TCModule(TrackingModule):

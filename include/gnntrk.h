@@ -787,6 +787,54 @@ int gnntrk_hinge_forward(const gnntrk_hinge_args *args, const int64_t *edges /* 
 int gnntrk_hinge_backward(const gnntrk_hinge_args *args, const gnntrk_graph_index *index, const float *g,
                           const float *denom, float *gx, int32_t gx_stride, int32_t accumulate, void *stream);
 
+/* ------------------------------------------------------------ validation metrics
+ * The figures of merit of the edge classifier's validation step (training/ec.py:55-84): for every
+ * pt cut, get_maximized_bcs (metrics/binary_classification.py:147-195) and get_roc_auc_scores
+ * (:198-231) of the masked edges - from two launches and no mask, with exact integer results.
+ *
+ * Shared edge inputs (n edges, n < 2^31; all device pointers):
+ *   w        [n] fp32 scores;
+ *   y        labels, read as y[perm[i]] when perm is non-NULL (CSR-ordered w against edge_index-ordered
+ *            y, as gnntrk_edge_targets_csr): y_kind 0 = uint8/bool, 1 = fp32.  Positive iff
+ *            int(y) == 1 (BinaryClassificationStats: y.int() == 1, :30-35);
+ *   src, tgt [n] node ids of the edge's two ends, int32, or int64 with ids_i64 = 1 (edge_index rows
+ *            as they are);
+ *   pt       per-node fp32 values in the ids' numbering, or NULL = every edge passes every cut;
+ *   cuts     HOST array of n_cuts (1..8) ascending pt cuts: cut c <= 0 takes every edge, c > 0 takes
+ *            the edge iff pt[src] > c || pt[tgt] > c (ec.py:66-75; a NaN pt fails every c > 0).
+ * GNNTRK_EINVAL for n_cuts, n_thr, n_fpr out of range, unordered cuts, NULL required pointers, a small
+ * workspace; GNNTRK_EUNSUPPORTED for n >= 2^31. */
+#define GNNTRK_METRICS_MAX_CUTS 8
+#define GNNTRK_METRICS_MAX_THR 1024
+#define GNNTRK_AUC_MAX_FPR 4
+#define GNNTRK_AUC_STRIDE 28 /* int64 per cut in gnntrk_roc_auc's output: 4 + 6 * GNNTRK_AUC_MAX_FPR */
+
+/* The threshold scan of get_maximized_bcs (BinaryClassificationStats at every threshold,
+ * metrics/binary_classification.py:14-144): ONE pass over the edges.
+ *   counts[c][l][k] (int64, [n_cuts][2][n_thr + 1], overwritten) = number of edges passing cut c with
+ *   label l whose bin k = #{j : !(w < thr[j])} - the reference predicts true iff !(w < thld), so
+ *   TP(thr[j]) = sum over k > j of counts[c][1][k], and a NaN score lands in bin n_thr.
+ * thr: DEVICE table of n_thr <= 1024 ascending fp32 thresholds (the caller checks the order). */
+int gnntrk_bcs_counts(const float *w, const void *y, int32_t y_kind, const int32_t *perm, const void *src,
+                      const void *tgt, int32_t ids_i64, const float *pt, const float *cuts, int32_t n_cuts,
+                      const float *thr, int32_t n_thr, int64_t n, int64_t *counts, void *stream);
+
+/* Exact ROC AUC and partial AUCs (get_roc_auc_scores / roc_auc_score, metrics/binary_classification.py:
+ * 198-231) of every cut from ONE radix sort of the scores (-0.0 and +0.0 are one tie group) and integer
+ * scans over the tie groups.  out (int64, [n_cuts][GNNTRK_AUC_STRIDE], overwritten) per cut:
+ *   [0] P, [1] N (positives, negatives passing the cut), [2] U2 = sum over tie groups, highest score
+ *   first, of fp_g * (2 tp_before + tp_g): AUC = U2 / (2 P N); [3] number of NaN scores (AUCs NaN if
+ *   > 0, as the reference's wrapper turns sklearn's error into NaN; P == 0 or N == 0 likewise).
+ *   Per max_fpr m (HOST array of n_fpr <= 4 values in (0, 1]) at [4 + 6m ..]: fp_lim = the largest
+ *   count with fp_lim / N <= max_fpr in fp64 (sklearn's fpr), the U2 of the whole groups up to it, and
+ *   the group that crosses it as (tp_before, fp_before, tp_g, fp_g) - the caller interpolates linearly
+ *   and applies McClish's standardisation in fp64, as sklearn's _binary_roc_auc_score does.
+ * workspace: gnntrk_roc_auc_workspace_bytes(n) (16 n bytes of sorted pairs + the sort's scratch). */
+size_t gnntrk_roc_auc_workspace_bytes(int64_t n);
+int gnntrk_roc_auc(const float *w, const void *y, int32_t y_kind, const int32_t *perm, const void *src, const void *tgt,
+                   int32_t ids_i64, const float *pt, const float *cuts, int32_t n_cuts, const double *max_fprs,
+                   int32_t n_fpr, int64_t n, int64_t *out, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
