@@ -22,11 +22,14 @@ from .losses_ml import GraphConstructionHingeEmbeddingLoss
 from .losses_oc import CondensationLossRG, CondensationLossTiger, MultiLossFctReturn
 from .metrics import (BinaryClassificationStats, ec_validation_metrics, get_maximized_bcs, get_roc_auc_scores,
                       roc_auc_score)
+from .cluster_metrics import (TrackingMetrics, flatten_track_metrics, tracking_metrics, tracking_metrics_data,
+                              tracking_metrics_trials)
 from .mlp import MLP
 from .locality import node_order
 from .precision import bf16_storage
 from .resin import ResIN
-from .postprocessing import DBSCANFastRescan, dbscan
+from .postprocessing import (ClusterScanner, CombinedClusterScanner, DBSCANFastRescan, DBSCANHyperParamScanner,
+                             DBSCANHyperParamScannerFixed, OCScanResults, dbscan)
 from .track_condensation_networks import (GraphConstructionFCNN, GraphConstructionHeteroEncResFCNN,
                                             GraphConstructionHeteroResFCNN, GraphConstructionResIN, GraphTCN,
                                             GraphTCNForMLGCPipeline, PerfectECGraphTCN,
@@ -43,4 +46,6 @@ __all__ = ["Data", "collate", "MLP", "InteractionNetwork", "ResIN", "ECForGraphT
            "GraphConstructionHeteroEncResFCNN", "GraphConstructionResIN", "PerfectECGraphTCN",
            "GraphTCNForMLGCPipeline", "PerfectEdgeClassification", "MLPCTransformer", "knn_scan", "EdgeWeightFocalLoss", "HaughtyFocalLoss", "binary_focal_loss", "DBSCANFastRescan", "dbscan", "load_graph", "GraphDataset", "PrefetchLoader", "ResidentDataset", "renumber_nodes",
            "BinaryClassificationStats", "get_maximized_bcs", "roc_auc_score", "get_roc_auc_scores",
-           "ec_validation_metrics"]
+           "ec_validation_metrics", "TrackingMetrics", "tracking_metrics", "tracking_metrics_data",
+           "tracking_metrics_trials", "flatten_track_metrics", "ClusterScanner", "CombinedClusterScanner",
+           "DBSCANHyperParamScanner", "DBSCANHyperParamScannerFixed", "OCScanResults"]

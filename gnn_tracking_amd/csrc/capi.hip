@@ -111,6 +111,11 @@ size_t roc_auc_ws_bytes(int64_t);
 int roc_auc(const float *, const void *, int32_t, const int32_t *, const void *, const void *, int32_t, const float *,
             const float *, int32_t, const double *, int32_t, int64_t, int64_t *, void *, size_t, hipStream_t);
 
+// tracking_metrics.hip
+size_t tracking_metrics_ws_bytes(int64_t, int32_t);
+int tracking_metrics(const int64_t *, int32_t, const int64_t *, const float *, const float *, const float *, int64_t,
+                     const float *, int32_t, float, int32_t, int64_t *, void *, size_t, hipStream_t);
+
 }  // namespace gnntrk
 
 using namespace gnntrk;
@@ -393,6 +398,17 @@ int gnntrk_roc_auc(const float *w, const void *y, int32_t y_kind, const int32_t 
                    int32_t n_fpr, int64_t n, int64_t *out, void *workspace, size_t workspace_bytes, void *stream) {
     return roc_auc(w, y, y_kind, perm, src, tgt, ids_i64, pt, cuts, n_cuts, max_fprs, n_fpr, n, out, workspace,
                    workspace_bytes, (hipStream_t)stream);
+}
+
+size_t gnntrk_tracking_metrics_workspace_bytes(int64_t n, int32_t n_trials) {
+    return tracking_metrics_ws_bytes(n, n_trials);
+}
+int gnntrk_tracking_metrics(const int64_t *labels, int32_t n_trials, const int64_t *particle_id, const float *pt,
+                            const float *eta, const float *reconstructable, int64_t n, const float *cuts,
+                            int32_t n_cuts, float max_eta, int32_t predicted_count_thld, int64_t *out,
+                            void *workspace, size_t workspace_bytes, void *stream) {
+    return tracking_metrics(labels, n_trials, particle_id, pt, eta, reconstructable, n, cuts, n_cuts, max_eta,
+                            predicted_count_thld, out, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

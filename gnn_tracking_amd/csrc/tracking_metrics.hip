@@ -1,0 +1,392 @@
+// Tracking metrics of the object-condensation validation (metrics/cluster_metrics.py:76-259 as
+// postprocessing/dbscanscanner.py:146-187 calls it once per DBSCAN trial): for every trial and pt cut
+// the integer counts behind TrackingMetrics - clusters passing the cluster mask and their perfect /
+// double-majority / LHC matches - plus the number of particles passing the hit mask.
+//
+// The reference groups hits with pandas (value_counts of (cluster, particle), groupby means per
+// particle).  Here both groupings are open-addressing hash tables in the workspace whose slots hold
+// "first hit + 1" of their group (claimed by compare-and-swap; a probe compares the keys of the slot's
+// hit), so particle ids of any size need no sort and no densification:
+//
+//   once per call (hits)        tm_particles_kernel   particle table; per particle its hit count, fp64
+//                                                     sums and non-NaN counts of pt / eta / reconstructable
+//                                                     and the highest cut class of its hits (hit mask)
+//                     (slots)   tm_particle_kernel    per particle the cut class of its means (cluster
+//                                                     mask) and n_particles per cut
+//   all trials at once (hits)   tm_pairs_kernel       (cluster, particle) table per trial; pair counts
+//                                                     and cluster sizes
+//                     (slots)   tm_best_count_kernel  per cluster the largest pair count
+//                     (slots)   tm_best_pid_kernel    per cluster the smallest particle id with that count
+//                     (labels)  tm_clusters_kernel    per valid cluster its flags, summed per cut: wave
+//                                                     sums, LDS, one int64 atomic per workgroup and value
+//
+// Every output is an integer count, so the result does not depend on the order in which atomics land.
+// Tie rule: the majority particle of a cluster is the one with the most hits in it and, among equals,
+// the smallest particle id (pandas' value_counts leaves ties to an unstable sort).
+#include <math.h>
+#include <stdio.h>
+
+#include "host_util.h"
+
+namespace gnntrk {
+namespace {
+
+constexpr int kTpb = 256;
+constexpr int kMaxCuts = GNNTRK_METRICS_MAX_CUTS;
+constexpr int kProps = 3;   // pt, eta, reconstructable
+
+struct Cuts {
+    float v[kMaxCuts];
+    int32_t n;
+};
+
+// The atomics beyond the common integer set.  The CPU emulator build of this unit (g++, host
+// pointers) takes the GCC builtins.
+__device__ __forceinline__ int32_t cas_i32(int32_t *p, int32_t expect, int32_t desired) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return atomicCAS(p, expect, desired);
+#else
+    __atomic_compare_exchange_n(p, &expect, desired, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
+    return expect;
+#endif
+}
+__device__ __forceinline__ void add_f64(double *p, double v) {
+#ifdef __HIP_DEVICE_COMPILE__
+    atomicAdd(p, v);
+#else
+    double old, nw;
+    __atomic_load(p, &old, __ATOMIC_RELAXED);
+    do {
+        nw = old + v;
+    } while (!__atomic_compare_exchange(p, &old, &nw, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED));
+#endif
+}
+__device__ __forceinline__ void min_u64(unsigned long long *p, unsigned long long v) {
+#ifdef __HIP_DEVICE_COMPILE__
+    atomicMin(p, v);
+#else
+    unsigned long long old = __atomic_load_n(p, __ATOMIC_RELAXED);
+    while (old > v && !__atomic_compare_exchange_n(p, &old, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {
+    }
+#endif
+}
+
+__device__ __forceinline__ uint64_t mix64(uint64_t x) {   // (murmur3's finaliser)
+    x ^= x >> 33;
+    x *= 0xff51afd7ed558ccdull;
+    x ^= x >> 33;
+    x *= 0xc4ceb9fe1a85ec53ull;
+    x ^= x >> 33;
+    return x;
+}
+
+// signed particle id -> unsigned key of the same order (the tie rule's atomic minimum)
+__device__ __forceinline__ unsigned long long pid_key(int64_t pid) { return (unsigned long long)pid ^ (1ull << 63); }
+
+// number of ascending cuts c with !(v < c) and v >= c: NaN passes none
+__device__ __forceinline__ int cut_class(float v, const Cuts &cuts) {
+    int k = 0;
+    for (int j = 0; j < cuts.n; ++j) k += (v >= cuts.v[j]) ? 1 : 0;
+    return k;
+}
+
+// the particle table's slot of pid (present: every particle id of the hits was inserted)
+__device__ __forceinline__ int64_t find_particle(const int32_t *ptab, const int64_t *pid, uint64_t mask, int64_t key) {
+    uint64_t s = mix64((uint64_t)key) & mask;
+    for (;;) {
+        const int32_t h = ptab[s];
+        if (h == 0 || pid[h - 1] == key) return (int64_t)s;
+        s = (s + 1) & mask;
+    }
+}
+
+struct Ws {
+    int32_t *ptab;            // [S]  particle table: first hit + 1, 0 = empty
+    uint32_t *pcnt;           // [S]  hits per particle
+    uint32_t *phit;           // [S]  highest hit cut class of the particle (n_particles)
+    uint32_t *pcls;           // [S]  cut class of the particle's means (cluster mask)
+    uint32_t *pnn;            // [3][S] non-NaN values per property
+    double *psum;             // [3][S] fp64 sums of the non-NaN values
+    uint32_t *hslot;          // [n]  particle slot of every hit
+    int32_t *ttab;            // [T][S] (cluster, particle) table per trial: first hit + 1
+    uint32_t *tcnt;           // [T][S] hits per (cluster, particle)
+    uint32_t *csize;          // [T][n] cluster sizes
+    uint32_t *cbest;          // [T][n] largest pair count per cluster
+    unsigned long long *cpid; // [T][n] smallest pid_key with that count (filled with ones)
+    size_t zero_bytes;        // everything before cpid is cleared
+    size_t total;
+    uint64_t S;
+};
+
+uint64_t table_size(int64_t n) {   // power of two, at least twice the hits: load factor <= 1/2
+    uint64_t s = 64;
+    while (s < 2 * (uint64_t)n) s <<= 1;
+    return s;
+}
+
+Ws make_ws(void *base, int64_t n, int32_t T) {
+    Ws w{};
+    w.S = table_size(n);
+    const size_t S = w.S, N = (size_t)n, TS = (size_t)T * S, TN = (size_t)T * N;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off = align_up(off + bytes, 256);
+        return (char *)base + at;
+    };
+    w.psum = (double *)take(8 * kProps * S);
+    w.ptab = (int32_t *)take(4 * S);
+    w.pcnt = (uint32_t *)take(4 * S);
+    w.phit = (uint32_t *)take(4 * S);
+    w.pcls = (uint32_t *)take(4 * S);
+    w.pnn = (uint32_t *)take(4 * kProps * S);
+    w.hslot = (uint32_t *)take(4 * N);
+    w.ttab = (int32_t *)take(4 * TS);
+    w.tcnt = (uint32_t *)take(4 * TS);
+    w.csize = (uint32_t *)take(4 * TN);
+    w.cbest = (uint32_t *)take(4 * TN);
+    w.zero_bytes = off;
+    w.cpid = (unsigned long long *)take(8 * TN);
+    w.total = off;
+    return w;
+}
+
+// ------------------------------------------------------------------ once per call
+__global__ __launch_bounds__(kTpb) void tm_particles_kernel(const int64_t *__restrict__ pid,
+                                                            const float *__restrict__ pt,
+                                                            const float *__restrict__ eta,
+                                                            const float *__restrict__ reco, int64_t n, Cuts cuts,
+                                                            float max_eta, Ws w) {
+    const uint64_t mask = w.S - 1;
+    for (int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTpb) {
+        const int64_t key = pid[i];
+        uint64_t s = mix64((uint64_t)key) & mask;
+        for (;;) {   // (terminates: the table has more slots than there are hits)
+            const int32_t h = cas_i32(&w.ptab[s], 0, (int32_t)(i + 1));
+            if (h == 0 || pid[h - 1] == key) break;
+            s = (s + 1) & mask;
+        }
+        w.hslot[i] = (uint32_t)s;
+        atomicAdd(&w.pcnt[s], 1u);
+        const float v[kProps] = {pt[i], eta[i], reco[i]};
+        for (int k = 0; k < kProps; ++k) {
+            if (v[k] != v[k]) continue;   // (pandas' mean skips NaN)
+            add_f64(&w.psum[(size_t)k * w.S + s], (double)v[k]);
+            atomicAdd(&w.pnn[(size_t)k * w.S + s], 1u);
+        }
+        // hit mask: pt >= cut, reconstructable truthy (NaN is), |eta| < max_eta (NaN is not)
+        const int hc = (v[2] != 0.f && fabsf(v[1]) < max_eta) ? cut_class(v[0], cuts) : 0;
+        if (hc) atomicMax(&w.phit[s], (uint32_t)hc);
+    }
+}
+
+// wave sum of an integer (every lane of the wave calls it)
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+__global__ __launch_bounds__(kTpb) void tm_particle_kernel(Cuts cuts, float max_eta, Ws w,
+                                                           unsigned long long *__restrict__ n_particles) {
+    __shared__ uint32_t acc[kMaxCuts];
+    if (threadIdx.x < kMaxCuts) acc[threadIdx.x] = 0u;
+    __syncthreads();
+    uint32_t cnt[kMaxCuts] = {};
+    const int64_t S = (int64_t)w.S;
+    for (int64_t base = (int64_t)blockIdx.x * kTpb; base < S; base += (int64_t)gridDim.x * kTpb) {
+        const int64_t s = base + threadIdx.x;
+        if (s >= S || w.ptab[s] == 0) continue;
+        float mean[kProps];
+        for (int k = 0; k < kProps; ++k) {
+            const uint32_t c = w.pnn[(size_t)k * S + s];
+            // fp64 mean rounded once to fp32 (groupby().mean() keeps a float32 column's dtype)
+            mean[k] = c ? (float)(w.psum[(size_t)k * S + s] / (double)c) : NAN;
+        }
+        // cluster mask of a cluster with this majority particle: maj_pt >= cut, maj_reconstructable
+        // truthy (non-zero and not NaN), |maj_eta| < max_eta
+        const bool ok = mean[2] != 0.f && mean[2] == mean[2] && fabsf(mean[1]) < max_eta;
+        w.pcls[s] = ok ? (uint32_t)cut_class(mean[0], cuts) : 0u;
+        const uint32_t hc = w.phit[s];
+        for (int c = 0; c < kMaxCuts; ++c) cnt[c] += (uint32_t)c < hc ? 1u : 0u;
+    }
+    for (int c = 0; c < cuts.n; ++c) {
+        const uint32_t t = wave_sum(cnt[c]);
+        if ((threadIdx.x & 63) == 0 && t) atomicAdd(&acc[c], t);
+    }
+    __syncthreads();
+    if (threadIdx.x < cuts.n && acc[threadIdx.x]) atomicAdd(&n_particles[threadIdx.x], (unsigned long long)acc[threadIdx.x]);
+}
+
+// ------------------------------------------------------------------- all trials
+// hits of every trial (flattened [T][n]); noise (label < 0) joins no cluster; labels >= n are
+// counted in *bad and otherwise ignored
+__global__ __launch_bounds__(kTpb) void tm_pairs_kernel(const int64_t *__restrict__ labels, int64_t n, int64_t tn,
+                                                        Ws w, unsigned long long *__restrict__ bad) {
+    const uint64_t mask = w.S - 1;
+    for (int64_t idx = (int64_t)blockIdx.x * kTpb + threadIdx.x; idx < tn; idx += (int64_t)gridDim.x * kTpb) {
+        const int64_t lab = labels[idx];
+        if (lab < 0) continue;
+        if (lab >= n) {
+            atomicAdd(bad, 1ull);
+            continue;
+        }
+        const int64_t t = idx / n, i = idx - t * n;
+        const int64_t *lt = labels + t * n;
+        int32_t *tab = w.ttab + (size_t)t * w.S;
+        const uint32_t ps = w.hslot[i];
+        uint64_t s = mix64(((uint64_t)lab << 32) | ps) & mask;
+        for (;;) {
+            const int32_t h = cas_i32(&tab[s], 0, (int32_t)(i + 1));
+            if (h == 0 || (lt[h - 1] == lab && w.hslot[h - 1] == ps)) break;
+            s = (s + 1) & mask;
+        }
+        atomicAdd(&w.tcnt[(size_t)t * w.S + s], 1u);
+        atomicAdd(&w.csize[t * n + lab], 1u);
+    }
+}
+
+// the cluster of an occupied pair slot e of trial t (-1: empty)
+__device__ __forceinline__ int64_t pair_cluster(const int64_t *labels, int64_t n, const Ws &w, int64_t t, int64_t e,
+                                                int32_t &hit) {
+    hit = w.ttab[e];
+    if (hit == 0) return -1;
+    return labels[t * n + hit - 1];
+}
+
+__global__ __launch_bounds__(kTpb) void tm_best_count_kernel(const int64_t *__restrict__ labels, int64_t n, int64_t ts,
+                                                             Ws w) {
+    for (int64_t e = (int64_t)blockIdx.x * kTpb + threadIdx.x; e < ts; e += (int64_t)gridDim.x * kTpb) {
+        const int64_t t = e / (int64_t)w.S;
+        int32_t hit;
+        const int64_t lab = pair_cluster(labels, n, w, t, e, hit);
+        if (lab >= 0) atomicMax(&w.cbest[t * n + lab], w.tcnt[e]);
+    }
+}
+
+__global__ __launch_bounds__(kTpb) void tm_best_pid_kernel(const int64_t *__restrict__ labels,
+                                                           const int64_t *__restrict__ pid, int64_t n, int64_t ts,
+                                                           Ws w) {
+    for (int64_t e = (int64_t)blockIdx.x * kTpb + threadIdx.x; e < ts; e += (int64_t)gridDim.x * kTpb) {
+        const int64_t t = e / (int64_t)w.S;
+        int32_t hit;
+        const int64_t lab = pair_cluster(labels, n, w, t, e, hit);
+        if (lab >= 0 && w.tcnt[e] == w.cbest[t * n + lab]) min_u64(&w.cpid[t * n + lab], pid_key(pid[hit - 1]));
+    }
+}
+
+// one trial per blockIdx.y; a cluster is a label with at least one hit
+__global__ __launch_bounds__(kTpb) void tm_clusters_kernel(const int64_t *__restrict__ pid, int64_t n, Cuts cuts,
+                                                           int32_t count_thld, Ws w,
+                                                           unsigned long long *__restrict__ out) {
+    __shared__ uint32_t acc[kMaxCuts * 4];
+    if (threadIdx.x < kMaxCuts * 4) acc[threadIdx.x] = 0u;
+    __syncthreads();
+    const int64_t t = blockIdx.y;
+    const uint64_t mask = w.S - 1;
+    // per cut: clusters, perfect, double majority, lhc
+    uint32_t cnt[kMaxCuts][4] = {};
+    for (int64_t lab = (int64_t)blockIdx.x * kTpb + threadIdx.x; lab < n; lab += (int64_t)gridDim.x * kTpb) {
+        const uint32_t size = w.csize[t * n + lab];
+        if (size == 0 || (int64_t)size < (int64_t)count_thld) continue;   // not a valid cluster
+        const uint32_t maj = w.cbest[t * n + lab];
+        const int64_t key = (int64_t)(w.cpid[t * n + lab] ^ (1ull << 63));
+        const int64_t ps = find_particle(w.ptab, pid, mask, key);
+        const uint32_t cls = w.pcls[ps];
+        if (cls == 0) continue;
+        const uint32_t pid_hits = w.pcnt[ps];
+        // (fp64 ratios as the reference evaluates them)
+        const double frac = (double)maj / (double)size, pid_frac = (double)maj / (double)pid_hits;
+        const uint32_t perfect = (pid_hits == maj && frac > 0.99) ? 1u : 0u;
+        const uint32_t dm = (pid_frac > 0.5 && frac > 0.5) ? 1u : 0u;
+        const uint32_t lhc = frac > 0.75 ? 1u : 0u;
+        for (int c = 0; c < kMaxCuts; ++c) {
+            if ((uint32_t)c >= cls) break;
+            cnt[c][0] += 1u;
+            cnt[c][1] += perfect;
+            cnt[c][2] += dm;
+            cnt[c][3] += lhc;
+        }
+    }
+    for (int c = 0; c < cuts.n; ++c)
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t s = wave_sum(cnt[c][k]);
+            if ((threadIdx.x & 63) == 0 && s) atomicAdd(&acc[c * 4 + k], s);
+        }
+    __syncthreads();
+    if (threadIdx.x < cuts.n * 4 && acc[threadIdx.x])
+        atomicAdd(&out[(size_t)t * cuts.n * 4 + threadIdx.x], (unsigned long long)acc[threadIdx.x]);
+}
+
+int grid_for(int64_t n, int per_cu) {
+    const int64_t g = ceil_div(n, kTpb), cap = (int64_t)cu_count() * per_cu;
+    return (int)(g < 1 ? 1 : (g < cap ? g : cap));
+}
+
+}  // namespace
+
+size_t tracking_metrics_ws_bytes(int64_t n, int32_t n_trials) {
+    return make_ws(nullptr, n < 0 ? 0 : n, n_trials < 1 ? 1 : n_trials).total;
+}
+
+int tracking_metrics(const int64_t *labels, int32_t n_trials, const int64_t *pid, const float *pt, const float *eta,
+                     const float *reco, int64_t n, const float *cuts, int32_t n_cuts, float max_eta,
+                     int32_t count_thld, int64_t *out, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+    char msg[160];
+    if (n < 0) return fail(GNNTRK_EINVAL, "tracking_metrics: negative hit count");
+    if (n >= (int64_t(1) << 30)) {
+        snprintf(msg, sizeof(msg), "tracking_metrics: %lld hits; at most 2^30-1", (long long)n);
+        return fail(GNNTRK_EUNSUPPORTED, msg);
+    }
+    if (n_trials < 1 || n_trials > GNNTRK_TRACKING_MAX_TRIALS) {
+        snprintf(msg, sizeof(msg), "tracking_metrics: n_trials = %d, expected 1..%d", (int)n_trials,
+                 GNNTRK_TRACKING_MAX_TRIALS);
+        return fail(GNNTRK_EINVAL, msg);
+    }
+    if (n_cuts < 1 || n_cuts > kMaxCuts) {
+        snprintf(msg, sizeof(msg), "tracking_metrics: n_cuts = %d, expected 1..%d", (int)n_cuts, kMaxCuts);
+        return fail(GNNTRK_EINVAL, msg);
+    }
+    if (!cuts) return fail(GNNTRK_EINVAL, "tracking_metrics: NULL cuts");
+    Cuts c{};
+    c.n = n_cuts;
+    for (int j = 0; j < n_cuts; ++j) {
+        c.v[j] = cuts[j];
+        if (!(cuts[j] == cuts[j]) || (j > 0 && !(cuts[j] >= cuts[j - 1])))
+            return fail(GNNTRK_EINVAL, "tracking_metrics: the pt cuts must be ascending numbers");
+    }
+    if (!out) return fail(GNNTRK_EINVAL, "tracking_metrics: NULL output");
+    if (n > 0 && (!labels || !pid || !pt || !eta || !reco))
+        return fail(GNNTRK_EINVAL, "tracking_metrics: NULL labels, particle ids, pt, eta or reconstructable");
+    const Ws need = make_ws(nullptr, n, n_trials);
+    if (n > 0 && (!workspace || workspace_bytes < need.total)) {
+        snprintf(msg, sizeof(msg),
+                 "tracking_metrics: workspace of %zu bytes, need %zu (gnntrk_tracking_metrics_workspace_bytes)",
+                 workspace_bytes, need.total);
+        return fail(GNNTRK_EINVAL, msg);
+    }
+    const size_t n_out = (size_t)n_cuts + (size_t)n_trials * n_cuts * 4 + 1;
+    int rc = check_hip(hipMemsetAsync(out, 0, sizeof(int64_t) * n_out, stream), "tracking_metrics: clear");
+    if (rc || n == 0) return rc;
+    const Ws w = make_ws(workspace, n, n_trials);
+    if ((rc = check_hip(hipMemsetAsync(workspace, 0, w.zero_bytes, stream), "tracking_metrics: clear workspace")))
+        return rc;
+    if ((rc = check_hip(hipMemsetAsync(w.cpid, 0xFF, 8 * (size_t)n_trials * n, stream),
+                        "tracking_metrics: clear workspace")))
+        return rc;
+    auto *o = reinterpret_cast<unsigned long long *>(out);
+    const int64_t S = (int64_t)w.S, tn = (int64_t)n_trials * n, ts = (int64_t)n_trials * S;
+    hipLaunchKernelGGL(tm_particles_kernel, dim3(grid_for(n, 8)), dim3(kTpb), 0, stream, pid, pt, eta, reco, n, c,
+                       max_eta, w);
+    hipLaunchKernelGGL(tm_particle_kernel, dim3(grid_for(S, 4)), dim3(kTpb), 0, stream, c, max_eta, w, o);
+    if ((rc = check_launch("tracking_metrics: particles"))) return rc;
+    hipLaunchKernelGGL(tm_pairs_kernel, dim3(grid_for(tn, 8)), dim3(kTpb), 0, stream, labels, n, tn, w,
+                       o + n_out - 1);
+    hipLaunchKernelGGL(tm_best_count_kernel, dim3(grid_for(ts, 8)), dim3(kTpb), 0, stream, labels, n, ts, w);
+    hipLaunchKernelGGL(tm_best_pid_kernel, dim3(grid_for(ts, 8)), dim3(kTpb), 0, stream, labels, pid, n, ts, w);
+    const int gx = (int)((grid_for(n, 8) + n_trials - 1) / n_trials);
+    hipLaunchKernelGGL(tm_clusters_kernel, dim3(gx < 1 ? 1 : gx, (unsigned)n_trials), dim3(kTpb), 0, stream, pid, n,
+                       c, count_thld, w, o + n_cuts);
+    return check_launch("tracking_metrics: clusters");
+}
+
+}  // namespace gnntrk

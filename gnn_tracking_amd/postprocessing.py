@@ -5,19 +5,27 @@ Reference: postprocessing/fastrescanner.py:6-66 (``DBSCANFastRescan``: one radiu
 hyperparameter scanners of postprocessing/dbscanscanner.py:146-187 call it).  Same
 constructor, same ``cluster`` signature, same labels (cluster numbering, border points,
 noise = -1); the graph and the clustering stay on the GPU, ``cluster`` hands back a numpy
-array like the reference (``cluster_device`` the device tensor).  The tracking metrics that
-consume the labels are CPU validation code and stay with the caller.
+array like the reference (``cluster_device`` the device tensor).
+
+The DBSCAN hyperparameter scanners of the object-condensation validation
+(postprocessing/clusterscanner.py, dbscanscanner.py:29-187) are here too: per batch one radius graph,
+every trial's labels into one device buffer, and the tracking metrics of all trials from one C call
+(``cluster_metrics.tracking_metrics_trials``) and one host copy.
 """
 
 from __future__ import annotations
 
+import math
 import os
+from abc import ABC, abstractmethod
+from typing import Any
 
 import numpy as np
 import torch
 from torch import Tensor
 
 from . import _capi, ops
+from .hparams import HyperparametersMixin
 
 
 #: bit 0: pruned radius graph below its size threshold too; bit 1: brute force only (tests, measurements)
@@ -110,3 +118,188 @@ class DBSCANFastRescan:
 def dbscan(x, eps: float, min_samples: int, device=None) -> np.ndarray:
     """``sklearn.cluster.DBSCAN(eps, min_samples).fit_predict(x)`` on the device."""
     return DBSCANFastRescan(x, max_eps=eps, device=device).cluster(eps, min_samples)
+
+
+# ------------------------------------------------------------------ cluster scanners
+class ClusterScanner(HyperparametersMixin, ABC):
+    """``postprocessing/clusterscanner.py:9-31``: base class of the validation-time scanners."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+
+    @abstractmethod
+    def __call__(self, data, out: dict[str, Tensor], i_batch: int) -> None:
+        pass
+
+    def reset(self) -> None:
+        pass
+
+    def get_foms(self) -> dict[str, Any]:
+        return {}
+
+
+class CombinedClusterScanner(ClusterScanner):
+    """``clusterscanner.py:34-54``: several scanners as one."""
+
+    def __init__(self, scanners: list[ClusterScanner]):
+        super().__init__()
+        self._scanners = scanners
+
+    def __call__(self, *args, **kwargs):
+        for scanner in self._scanners:
+            scanner(*args, **kwargs)
+
+    def reset(self) -> None:
+        for scanner in self._scanners:
+            scanner.reset()
+
+    def get_foms(self) -> dict[str, Any]:
+        foms = {}
+        for scanner in self._scanners:
+            foms |= scanner.get_foms()
+        return foms
+
+
+def _nanmean(v: np.ndarray) -> float:
+    v = v[~np.isnan(v)]
+    return float(v.mean()) if v.size else float("nan")
+
+
+def _nanstd(v: np.ndarray) -> float:   # (ddof = 1, as pandas)
+    v = v[~np.isnan(v)]
+    return float(v.std(ddof=1)) if v.size > 1 else float("nan")
+
+
+class OCScanResults:
+    """``dbscanscanner.py:29-73`` without pandas.  ``records``: one dict per (batch, trial) with
+    ``i_batch``, ``eps``, ``min_samples`` and the flattened tracking metrics.  Grouped by (eps,
+    min_samples) in ascending order, every other column (``i_batch`` included, as in the reference)
+    gets its NaN-skipping mean and a ``_std`` column: the ddof = 1 std over the group's rows divided
+    by the square root of the number of GROUPS - the reference's expression, kept as it is."""
+
+    def __init__(self, records: list[dict[str, float]]):
+        self._parameters = ["eps", "min_samples"]
+        self._records = list(records)
+        cols: dict[str, None] = {}
+        for r in self._records:
+            cols.update(dict.fromkeys(r))
+        self._cols = [c for c in cols if c not in self._parameters]
+        groups: dict[tuple, list[dict]] = {}
+        for r in self._records:
+            groups.setdefault((r["eps"], r["min_samples"]), []).append(r)
+        norm = math.sqrt(len(groups))
+        self._rows = []
+        for key in sorted(groups):
+            rows = groups[key]
+            vals = {c: np.array([float(r.get(c, float("nan"))) for r in rows], dtype=np.float64) for c in self._cols}
+            row = {"eps": key[0], "min_samples": key[1]}
+            row.update({c: _nanmean(v) for c, v in vals.items()})
+            row.update({c + "_std": _nanstd(v) / norm for c, v in vals.items()})
+            self._rows.append(row)
+
+    @property
+    def records(self) -> list[dict[str, float]]:
+        return self._records
+
+    @property
+    def mean_rows(self) -> list[dict[str, float]]:
+        """Mean and std grouped by hyperparameters (the reference's ``df_mean``, one dict per row)."""
+        return self._rows
+
+    def get_foms(self, guide="double_majority_pt0.9") -> dict[str, float]:
+        """Figures of merit of the (eps, min_samples) with the largest mean ``guide`` (first one on
+        ties, NaN skipped): every mean and std column with the prefix ``trk.``, then
+        ``best_dbscan_eps`` and ``best_dbscan_min_samples`` (floats, as the reference's row)."""
+        fom_cols = [c for c in self._rows[0] if c not in self._parameters] if self._rows else []
+        assert guide in fom_cols
+        g = np.array([r[guide] for r in self._rows], dtype=np.float64)
+        if np.isnan(g).all():
+            raise ValueError(f"OCScanResults: {guide} is NaN for every parameter set")
+        best = self._rows[int(np.nanargmax(g))]
+        foms = {f"trk.{c}": float(best[c]) for c in fom_cols}
+        for param in self._parameters:
+            foms[f"best_dbscan_{param}"] = float(best[param])
+        return foms
+
+    def get_n_best_trials(self, n: int, guide="double_majority_pt0.9") -> list[dict[str, float]]:
+        g = np.array([r[guide] for r in self._rows], dtype=np.float64)
+        order = sorted(range(len(g)), key=lambda i: (np.isnan(g[i]), -g[i] if not np.isnan(g[i]) else 0.0))
+        return [{p: self._rows[i][p] for p in self._parameters} for i in order[:n]]
+
+
+class DBSCANHyperParamScanner(ClusterScanner):
+    def __init__(self, *, eps_range=(0, 1), min_samples_range=(1, 4), n_trials=10, keep_best=0,
+                 n_jobs: int | None = None, guide: str = "double_majority_pt0.9", pt_thlds=(0.0, 0.5, 0.9, 1.5),
+                 max_eta: float = 4.0):
+        """``dbscanscanner.py:76-187``: random (eps, min_samples) DBSCAN trials per batch, tracking metrics
+        per trial, figures of merit of the best trial over the epoch.  Same arguments (``n_jobs`` is
+        accepted and ignored).  Per batch: one ``DBSCANFastRescan`` on ``out["H"]`` where it lies, all
+        trials' labels into one device buffer, one metrics call and one host copy."""
+        super().__init__()
+        self.save_hyperparameters()
+        # (the reference's backwards compatibility: a "trk." prefix of the guide is dropped)
+        self.hparams.guide = self.hparams.guide.removeprefix("trk.")
+        self._results: list[dict[str, float]] = []
+        self._rng = np.random.default_rng()
+        self._trials: list[dict[str, float]] = []
+        self.reset()
+
+    def get_results(self) -> OCScanResults:
+        return OCScanResults(self._results)
+
+    def get_foms(self) -> dict[str, float]:
+        return self.get_results().get_foms()
+
+    def _get_best_trials(self) -> list[dict[str, float]]:
+        if not self._results:
+            return []
+        return self.get_results().get_n_best_trials(self.hparams.keep_best)
+
+    def _reset_trials(self) -> None:
+        # As the reference (dbscanscanner.py:133-142), kept for parity rather than fixed: the best
+        # trials only shorten the random draw, which then replaces them.
+        self._trials = self._get_best_trials()
+        size_random = self.hparams.n_trials - len(self._trials)
+        eps = self._rng.uniform(*self.hparams.eps_range, size=size_random)
+        min_samples = self._rng.integers(self.hparams.min_samples_range[0], self.hparams.min_samples_range[1] + 1,
+                                         size=size_random)
+        self._trials = [{"eps": e, "min_samples": n} for e, n in zip(eps, min_samples)]
+
+    def reset(self):
+        """Reset the results; called on every batch with ``i_batch == 0``."""
+        self._reset_trials()
+        self._best_trials = []
+        self._results = []
+
+    def __call__(self, data, out: dict[str, Tensor], i_batch: int, *, progress=False):
+        from .cluster_metrics import tracking_metrics_trials
+
+        ec_hit_mask = out.get("ec_hit_mask")
+        if ec_hit_mask is not None and not bool(ec_hit_mask.all()):
+            raise NotImplementedError("Handling of orphan node pruning not implemented")
+        if i_batch == 0:
+            self.reset()
+        if not self._trials:
+            return
+        scanner = DBSCANFastRescan(out["H"].detach(), max_eps=max(v["eps"] for v in self._trials),
+                                   n_jobs=self.hparams.n_jobs)
+        n = int(scanner.x.shape[0])
+        labels = torch.empty((len(self._trials), n), dtype=torch.int64, device=scanner.x.device)
+        for k, trial in enumerate(self._trials):
+            labels[k] = scanner.cluster_device(eps=trial["eps"], min_pts=trial["min_samples"])
+        metrics = tracking_metrics_trials(labels, truth=data.particle_id, pts=data.pt, eta=data.eta,
+                                          reconstructable=data.reconstructable, pt_thlds=self.hparams.pt_thlds,
+                                          max_eta=self.hparams.max_eta)
+        for trial, m in zip(self._trials, metrics):
+            self._results.append({"i_batch": i_batch, "eps": trial["eps"], "min_samples": trial["min_samples"], **m})
+
+
+class DBSCANHyperParamScannerFixed(DBSCANHyperParamScanner):
+    def __init__(self, trials: list[dict[str, float]], *, n_jobs: int | None = None, pt_thlds=(0.0, 0.5, 0.9, 1.5),
+                 max_eta: float = 4.0):
+        """``dbscanscanner.py:190-214``: the given trials on every batch."""
+        super().__init__(n_jobs=n_jobs, pt_thlds=pt_thlds, max_eta=max_eta)
+        self._trials = trials
+
+    def _reset_trials(self) -> None:
+        pass

@@ -155,12 +155,15 @@ class ECModule(TrackingModule):
 
 
 class TCModule(TrackingModule):
-    """Object-condensation training (``training/tc.py:20-84``): ``loss_fct`` is a
-    ``MultiLossFct`` (``CondensationLossRG`` / ``CondensationLossTiger``)."""
+    """Object-condensation training and validation (``training/tc.py:20-114``): ``loss_fct`` is a
+    ``MultiLossFct`` (``CondensationLossRG`` / ``CondensationLossTiger``), ``cluster_scanner`` an
+    optional ``postprocessing.ClusterScanner`` (``DBSCANHyperParamScanner``) run on every validation
+    batch."""
 
-    def __init__(self, model: nn.Module, *, loss_fct: nn.Module, **kwargs):
+    def __init__(self, model: nn.Module, *, loss_fct: nn.Module, cluster_scanner=None, **kwargs):
         super().__init__(model, **kwargs)
         self.loss_fct = loss_fct
+        self.cluster_scanner = cluster_scanner
 
     def get_losses(self, out: dict[str, Any], data, *, metrics: bool = True):
         losses = self.loss_fct(x=out["H"], particle_id=data.particle_id, beta=out["B"], pt=data.pt,
@@ -179,6 +182,26 @@ class TCModule(TrackingModule):
         data = self.data_preproc(data)
         out = self(data, _preprocessed=True)
         return self.get_losses(out, data, metrics=metrics)
+
+    def validation_step(self, data, batch_idx: int = 0, *, last_batch: bool = False) -> dict[str, float]:
+        """``training/tc.py:86-105``: the losses and, on the last validation batch, the cluster
+        scanner's figures of merit (``trk.*``, ``best_dbscan_*``) - what the reference logs, as one
+        dict.  The scanner sees every batch (``batch_idx == 0`` resets it).  Without a Lightning
+        trainer the caller says which batch is the last one (``last_batch``, the reference's
+        ``is_last_val_batch``)."""
+        with torch.no_grad(), bf16_storage(self.bf16):
+            data = self.data_preproc(data)
+            out = self(data, _preprocessed=True)
+            _, metrics = self.get_losses(out, data, metrics=True)
+            if self.cluster_scanner is not None:
+                self.cluster_scanner(data, out, batch_idx)
+                if last_batch:
+                    metrics |= self.cluster_scanner.get_foms()
+        return metrics
+
+    def highlight_metric(self, metric: str) -> bool:
+        return metric in ["attractive", "repulsive", "trk.lhc_pt0.9", "trk.perfect_pt0.9",
+                          "trk.double_majority_pt0.9"]
 
 
 class MLModule(TrackingModule):

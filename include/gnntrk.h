@@ -835,6 +835,44 @@ int gnntrk_roc_auc(const float *w, const void *y, int32_t y_kind, const int32_t 
                    int32_t ids_i64, const float *pt, const float *cuts, int32_t n_cuts, const double *max_fprs,
                    int32_t n_fpr, int64_t n, int64_t *out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------ tracking metrics
+ * The counts behind the object-condensation stage's TrackingMetrics (metrics/cluster_metrics.py:
+ * 76-259) for n_trials cluster labellings of the same n hits at once, as DBSCANHyperParamScanner
+ * (postprocessing/dbscanscanner.py:146-187) evaluates them once per DBSCAN trial.  All device pointers
+ * except cuts:
+ *   labels          [n_trials][n] int64 cluster labels; every label < 0 is noise (no cluster); a label
+ *                   >= n is ignored and counted in the last output value;
+ *   particle_id     [n] int64 ids of any value (no densification needed);
+ *   pt, eta, reconstructable  [n] fp32 per hit;
+ *   cuts            HOST array of n_cuts (1..GNNTRK_METRICS_MAX_CUTS) ascending pt cuts.
+ * Semantics (the reference's with pandas 2 / numpy 2):
+ *   - a cluster is a label >= 0 with at least one hit; valid iff its size >= predicted_count_thld;
+ *   - per particle the means over its hits of pt, eta and reconstructable (NaN values skipped, fp64
+ *     sums rounded once to fp32); the cluster mask at cut c is: majority particle's mean pt >= c,
+ *     mean reconstructable non-zero and not NaN, |mean eta| < max_eta, valid cluster;
+ *   - the hit mask at cut c is: pt >= c, reconstructable != 0, |eta| < max_eta; comparisons in fp32;
+ *   - the majority particle of a cluster is the one with the most hits in it; TIES go to the
+ *     SMALLEST particle id (the reference leaves them to pandas' unstable sort - a tie never decides
+ *     a perfect, double-majority or LHC match, only whether the cluster passes the mask);
+ *   - perfect: maj_pid_hits == maj_hits && maj_hits / size > 0.99; double majority: maj_hits /
+ *     maj_pid_hits > 0.5 && maj_hits / size > 0.5; lhc: maj_hits / size > 0.75 (fp64 ratios).
+ * out (int64, n_cuts + n_trials * n_cuts * 4 + 1 values, overwritten):
+ *   [c]                              n_particles at cut c: distinct particle ids among the hits that
+ *                                    pass the hit mask (independent of the trial);
+ *   [n_cuts + (t * n_cuts + c) * 4 + k]  for trial t and cut c: k = 0 clusters passing the cluster
+ *                                    mask, 1 perfect, 2 double-majority, 3 lhc matches among them;
+ *   [last]                           number of labels >= n over all trials (0 for valid input).
+ * workspace: gnntrk_tracking_metrics_workspace_bytes(n, n_trials) (hash tables of 2n..4n slots per
+ * trial and for the particles, per-cluster tables).  No host synchronisation.
+ * GNNTRK_EINVAL for n_trials or n_cuts out of range, unordered or NaN cuts, NULL required pointers, a
+ * small workspace; GNNTRK_EUNSUPPORTED for n >= 2^30. */
+#define GNNTRK_TRACKING_MAX_TRIALS 4096
+size_t gnntrk_tracking_metrics_workspace_bytes(int64_t n, int32_t n_trials);
+int gnntrk_tracking_metrics(const int64_t *labels, int32_t n_trials, const int64_t *particle_id, const float *pt,
+                            const float *eta, const float *reconstructable, int64_t n, const float *cuts,
+                            int32_t n_cuts, float max_eta, int32_t predicted_count_thld, int64_t *out,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
