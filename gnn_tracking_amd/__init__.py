@@ -24,6 +24,8 @@ from .metrics import (BinaryClassificationStats, ec_validation_metrics, get_maxi
                       roc_auc_score)
 from .cluster_metrics import (TrackingMetrics, flatten_track_metrics, tracking_metrics, tracking_metrics_data,
                               tracking_metrics_trials)
+from .graph_analysis import get_cc_labels, get_efficiency_purity_edges, get_largest_segment_fracs
+from .k_scanner import GraphConstructionKNNScanner, KScanResults
 from .mlp import MLP
 from .locality import node_order
 from .precision import bf16_storage
@@ -48,4 +50,6 @@ __all__ = ["Data", "collate", "MLP", "InteractionNetwork", "ResIN", "ECForGraphT
            "BinaryClassificationStats", "get_maximized_bcs", "roc_auc_score", "get_roc_auc_scores",
            "ec_validation_metrics", "TrackingMetrics", "tracking_metrics", "tracking_metrics_data",
            "tracking_metrics_trials", "flatten_track_metrics", "ClusterScanner", "CombinedClusterScanner",
-           "DBSCANHyperParamScanner", "DBSCANHyperParamScannerFixed", "OCScanResults"]
+           "DBSCANHyperParamScanner", "DBSCANHyperParamScannerFixed", "OCScanResults", "get_cc_labels",
+           "get_largest_segment_fracs", "get_efficiency_purity_edges", "GraphConstructionKNNScanner",
+           "KScanResults"]

@@ -116,6 +116,14 @@ size_t tracking_metrics_ws_bytes(int64_t, int32_t);
 int tracking_metrics(const int64_t *, int32_t, const int64_t *, const float *, const float *, const float *, int64_t,
                      const float *, int32_t, float, int32_t, int64_t *, void *, size_t, hipStream_t);
 
+// kscan.hip
+size_t cc_labels_ws_bytes(int64_t);
+int cc_labels(const int64_t *, int64_t, const int32_t *, const int32_t *, int32_t, int32_t, const int64_t *,
+              const uint8_t *, int64_t, int64_t *, int64_t *, void *, size_t, hipStream_t);
+size_t kscan_counts_ws_bytes(int64_t);
+int kscan_counts(const int32_t *, const int32_t *, int64_t, int32_t, const int32_t *, int32_t, const int64_t *,
+                 const uint8_t *, const int64_t *, int64_t, int64_t *, int64_t *, void *, size_t, hipStream_t);
+
 }  // namespace gnntrk
 
 using namespace gnntrk;
@@ -409,6 +417,22 @@ int gnntrk_tracking_metrics(const int64_t *labels, int32_t n_trials, const int64
                             void *workspace, size_t workspace_bytes, void *stream) {
     return tracking_metrics(labels, n_trials, particle_id, pt, eta, reconstructable, n, cuts, n_cuts, max_eta,
                             predicted_count_thld, out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t gnntrk_cc_labels_workspace_bytes(int64_t n) { return cc_labels_ws_bytes(n); }
+int gnntrk_cc_labels(const int64_t *edge_index, int64_t n_edges, const int32_t *nbr, const int32_t *cnt,
+                     int32_t k_stride, int32_t k, const int64_t *same_pid, const uint8_t *node_mask, int64_t n,
+                     int64_t *labels, int64_t *n_bad, void *workspace, size_t workspace_bytes, void *stream) {
+    return cc_labels(edge_index, n_edges, nbr, cnt, k_stride, k, same_pid, node_mask, n, labels, n_bad, workspace,
+                     workspace_bytes, (hipStream_t)stream);
+}
+size_t gnntrk_kscan_counts_workspace_bytes(int64_t n) { return kscan_counts_ws_bytes(n); }
+int gnntrk_kscan_counts(const int32_t *nbr, const int32_t *cnt, int64_t n, int32_t k_stride, const int32_t *ks,
+                        int32_t n_ks, const int64_t *particle_id, const uint8_t *node_mask,
+                        const int64_t *true_edge_index, int64_t n_true_edges, int64_t *out, int64_t *labels,
+                        void *workspace, size_t workspace_bytes, void *stream) {
+    return kscan_counts(nbr, cnt, n, k_stride, ks, n_ks, particle_id, node_mask, true_edge_index, n_true_edges, out,
+                        labels, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

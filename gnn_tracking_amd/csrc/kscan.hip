@@ -1,0 +1,492 @@
+// The k-scan of the metric-learning validation (graph_construction/k_scanner.py:203-285): connected
+// components on the device and the integer counts around them, for every k of a list on ONE neighbour
+// table.  The reference builds, per k, a networkx graph from a host copy of the true edges and walks its
+// components in Python twice (analysis/graphs.py:281-343); here the components are a lock-free
+// union-find and every figure is a count:
+//
+//   once per call   (hits)        ks_init_kernel        parent[i] = i for both component problems
+//                   (hits)        ks_particles_kernel   particle table of the masked hits (open addressing,
+//                                                       slot = first hit + 1), hits per particle c_p
+//                   (true edges)  ks_true_edges_kernel  |{t: m[t0] & m[t1]}|
+//   per k, ascending (new edges)  ks_union_kernel       the edges of rank [k_prev, k) of the table: edge counts
+//                                                       of the step, union of same-id edges in problem A (all
+//                                                       hits) and, if both ends are masked, in problem B
+//                   (hits)        ks_compress_kernel    labels A of this k (int64, smallest hit index of the
+//                                                       component); size of every B component at its root
+//                   (hits)        ks_segmax_kernel      per particle the largest B component s_p
+//                   (slots)       ks_segments_kernel    n_pids, |{2 s_p > c_p}|, |{4 s_p > 3 c_p}|, |{s_p = c_p}|
+//   once            (1 block)     ks_finish_kernel      prefix sums of the step counts into the rows of `out`
+//
+// The graphs are nested in k (the k nearest are a prefix of a query's sorted neighbours), so the forest
+// of one k is the starting point of the next larger k: every table edge is united once per call, whatever
+// the number of ks.  The label of a hit is the smallest hit index of its component: roots are only ever
+// hooked under SMALLER roots, so parent[x] <= x always holds and the root of a tree is its minimum - the
+// result is unique and does not depend on the order in which atomics land.  Every output is an integer.
+//
+// Memory-order argument of the union-find (ks_find / ks_unite): parent[] is read with relaxed
+// agent-scope atomic loads and written with compare-and-swap (hooking a root) or relaxed atomic stores
+// (path halving, which stores an ancestor of x into parent[x]).  The ancestors of a hit stay its
+// ancestors for the rest of the launch (a non-root is never re-hooked, only moved up its own path), so a
+// stale read is an older ancestor in the same component and costs extra steps, never a wrong answer.  A
+// failed compare-and-swap continues from the value it returned.  Termination: parent[x] never increases
+// and every failed compare-and-swap saw a strict decrease of one entry; the sum of all entries is
+// bounded below.
+//
+// The work is integer, atomic- and latency-bound (random 4-8 byte accesses into arrays of a few MB that
+// stay in L2 / MALL); there is no HBM roofline to quote for it.
+#include <stdio.h>
+
+#include "host_util.h"
+
+namespace gnntrk {
+namespace {
+
+constexpr int kTpb = 256;
+constexpr int kCols = GNNTRK_KSCAN_COLUMNS;
+constexpr int kMaxKs = GNNTRK_KSCAN_MAX_KS;
+
+// columns of the output table
+enum { C_EDGES = 0, C_MASKED, C_TRUE_MASKED, C_TRUE_EDGES_MASKED, C_PIDS, C_N50, C_N75, C_N100, C_BAD };
+
+// The CPU emulator build of this unit (g++, host pointers) takes the GCC builtins.
+__device__ __forceinline__ int32_t load_i32(const int32_t *p) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    return __atomic_load_n(p, __ATOMIC_RELAXED);
+#endif
+}
+__device__ __forceinline__ void store_i32(int32_t *p, int32_t v) {
+#ifdef __HIP_DEVICE_COMPILE__
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    __atomic_store_n(p, v, __ATOMIC_RELAXED);
+#endif
+}
+__device__ __forceinline__ int32_t cas_i32(int32_t *p, int32_t expect, int32_t desired) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return atomicCAS(p, expect, desired);
+#else
+    __atomic_compare_exchange_n(p, &expect, desired, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
+    return expect;
+#endif
+}
+
+__device__ __forceinline__ uint64_t mix64(uint64_t x) {   // (murmur3's finaliser)
+    x ^= x >> 33;
+    x *= 0xff51afd7ed558ccdull;
+    x ^= x >> 33;
+    x *= 0xc4ceb9fe1a85ec53ull;
+    x ^= x >> 33;
+    return x;
+}
+
+// root of x with path halving (see the argument at the top)
+__device__ __forceinline__ int32_t ks_find(int32_t *parent, int32_t x) {
+    int32_t p = load_i32(&parent[x]);
+    while (p != x) {
+        const int32_t g = load_i32(&parent[p]);
+        if (g == p) return p;
+        store_i32(&parent[x], g);
+        x = g;
+        p = load_i32(&parent[x]);
+    }
+    return x;
+}
+
+__device__ __forceinline__ void ks_unite(int32_t *parent, int32_t a, int32_t b) {
+    for (;;) {
+        a = ks_find(parent, a);
+        b = ks_find(parent, b);
+        if (a == b) return;
+        if (a < b) {
+            const int32_t t = a;
+            a = b;
+            b = t;
+        }
+        const int32_t old = cas_i32(&parent[a], a, b);   // hook the larger root under the smaller
+        if (old == a) return;
+        a = old;   // a was hooked by someone else meanwhile: go on from its new parent
+    }
+}
+
+// wave sum of an integer (every lane of the wave calls it)
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// block-wide: adds the per-thread counts v[0..NV) into dst[0..NV) with one global atomic per value
+template <int NV>
+__device__ __forceinline__ void block_add(const uint32_t (&v)[NV], unsigned long long *dst) {
+    __shared__ unsigned long long acc[NV];
+    if (threadIdx.x < NV) acc[threadIdx.x] = 0ull;
+    __syncthreads();
+    for (int k = 0; k < NV; ++k) {
+        const uint32_t s = wave_sum(v[k]);
+        if ((threadIdx.x & 63) == 0 && s) atomicAdd(&acc[k], (unsigned long long)s);
+    }
+    __syncthreads();
+    if (threadIdx.x < NV && acc[threadIdx.x]) atomicAdd(&dst[threadIdx.x], acc[threadIdx.x]);
+}
+
+// --------------------------------------------------------------------------- plain components
+__global__ __launch_bounds__(kTpb) void cc_init_kernel(int32_t *__restrict__ parent, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTpb)
+        parent[i] = (int32_t)i;
+}
+
+__device__ __forceinline__ bool keep_edge(int64_t a, int64_t b, const int64_t *pid, const uint8_t *mask) {
+    if (pid && pid[a] != pid[b]) return false;
+    if (mask && !(mask[a] && mask[b])) return false;
+    return true;
+}
+
+__global__ __launch_bounds__(kTpb) void cc_union_edges_kernel(const int64_t *__restrict__ ei, int64_t m, int64_t n,
+                                                              const int64_t *__restrict__ pid,
+                                                              const uint8_t *__restrict__ mask, int32_t *parent,
+                                                              unsigned long long *bad) {
+    uint32_t nbad[1] = {0u};
+    for (int64_t base = (int64_t)blockIdx.x * kTpb; base < m; base += (int64_t)gridDim.x * kTpb) {
+        const int64_t e = base + threadIdx.x;
+        if (e >= m) continue;
+        const int64_t a = ei[e], b = ei[m + e];
+        if (a < 0 || a >= n || b < 0 || b >= n) {
+            nbad[0] += 1u;
+            continue;
+        }
+        if (a != b && keep_edge(a, b, pid, mask)) ks_unite(parent, (int32_t)a, (int32_t)b);
+    }
+    if (bad) block_add(nbad, bad);
+}
+
+__global__ __launch_bounds__(kTpb) void cc_union_table_kernel(const int32_t *__restrict__ nbr,
+                                                              const int32_t *__restrict__ cnt, int64_t n,
+                                                              int32_t k_stride, int32_t k,
+                                                              const int64_t *__restrict__ pid,
+                                                              const uint8_t *__restrict__ mask, int32_t *parent,
+                                                              unsigned long long *bad) {
+    uint32_t nbad[1] = {0u};
+    const int64_t total = n * k;
+    for (int64_t base = (int64_t)blockIdx.x * kTpb; base < total; base += (int64_t)gridDim.x * kTpb) {
+        const int64_t idx = base + threadIdx.x;
+        if (idx >= total) continue;
+        const int64_t q = idx / k;
+        const int32_t i = (int32_t)(idx - q * k);
+        if (i >= cnt[q]) continue;
+        const int64_t j = nbr[q * k_stride + i];
+        if (j < 0 || j >= n) {
+            nbad[0] += 1u;
+            continue;
+        }
+        if (j != q && keep_edge(j, q, pid, mask)) ks_unite(parent, (int32_t)j, (int32_t)q);
+    }
+    if (bad) block_add(nbad, bad);
+}
+
+__global__ __launch_bounds__(kTpb) void cc_labels_kernel(int32_t *parent, int64_t n, int64_t *__restrict__ labels) {
+    for (int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTpb)
+        labels[i] = ks_find(parent, (int32_t)i);
+}
+
+// --------------------------------------------------------------------------- the scan
+struct Ws {
+    int32_t *parent_a;          // [n]  components of the same-id edges, all hits
+    int32_t *parent_b;          // [n]  components of the same-id edges with both ends masked
+    uint32_t *hslot;            // [n]  particle slot of every masked hit
+    uint32_t *csize;            // [n]  size of the B component rooted at the hit (cleared by its reader)
+    int32_t *ptab;              // [S]  particle table of the masked hits: first hit + 1, 0 = empty
+    uint32_t *pcnt;             // [S]  masked hits per particle c_p
+    uint32_t *smax;             // [S]  largest B component per particle s_p (cleared by its reader)
+    unsigned long long *steps;  // [n_ks][3] edge counts of every step, then [2]: true edges masked, bad
+    size_t zero_from, total;
+    uint64_t S;
+};
+
+uint64_t table_size(int64_t n) {   // power of two, at least twice the hits: load factor <= 1/2
+    uint64_t s = 64;
+    while (s < 2 * (uint64_t)n) s <<= 1;
+    return s;
+}
+
+Ws make_ws(void *base, int64_t n) {
+    Ws w{};
+    w.S = table_size(n);
+    const size_t S = w.S, N = (size_t)n;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off = align_up(off + bytes, 256);
+        return (char *)base + at;
+    };
+    w.parent_a = (int32_t *)take(4 * N);
+    w.parent_b = (int32_t *)take(4 * N);
+    w.hslot = (uint32_t *)take(4 * N);
+    w.zero_from = off;   // everything from here on is cleared
+    w.csize = (uint32_t *)take(4 * N);
+    w.ptab = (int32_t *)take(4 * S);
+    w.pcnt = (uint32_t *)take(4 * S);
+    w.smax = (uint32_t *)take(4 * S);
+    w.steps = (unsigned long long *)take(8 * (3 * (size_t)kMaxKs + 2));
+    w.total = off;
+    return w;
+}
+
+struct Plan {
+    int32_t k[kMaxKs];     // ascending
+    int32_t row[kMaxKs];   // row of `out` / `labels` of the s-th smallest k
+    int32_t n;
+};
+
+__global__ __launch_bounds__(kTpb) void ks_init_kernel(Ws w, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTpb) {
+        w.parent_a[i] = (int32_t)i;
+        w.parent_b[i] = (int32_t)i;
+    }
+}
+
+__global__ __launch_bounds__(kTpb) void ks_particles_kernel(const int64_t *__restrict__ pid,
+                                                            const uint8_t *__restrict__ mask, int64_t n, Ws w) {
+    const uint64_t smask = w.S - 1;
+    for (int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTpb) {
+        if (!mask[i]) continue;
+        const int64_t key = pid[i];
+        uint64_t s = mix64((uint64_t)key) & smask;
+        for (;;) {   // (terminates: the table has more slots than there are hits)
+            const int32_t h = cas_i32(&w.ptab[s], 0, (int32_t)(i + 1));
+            if (h == 0 || pid[h - 1] == key) break;
+            s = (s + 1) & smask;
+        }
+        w.hslot[i] = (uint32_t)s;
+        atomicAdd(&w.pcnt[s], 1u);
+    }
+}
+
+__global__ __launch_bounds__(kTpb) void ks_true_edges_kernel(const int64_t *__restrict__ te, int64_t m, int64_t n,
+                                                             const uint8_t *__restrict__ mask, Ws w) {
+    uint32_t c[2] = {0u, 0u};   // both ends masked, out of range
+    for (int64_t base = (int64_t)blockIdx.x * kTpb; base < m; base += (int64_t)gridDim.x * kTpb) {
+        const int64_t e = base + threadIdx.x;
+        if (e >= m) continue;
+        const int64_t a = te[e], b = te[m + e];
+        if (a < 0 || a >= n || b < 0 || b >= n)
+            c[1] += 1u;
+        else
+            c[0] += (mask[a] && mask[b]) ? 1u : 0u;
+    }
+    block_add(c, w.steps + 3 * kMaxKs);
+}
+
+// the table edges of rank [lo, hi): (nbr[q * k_stride + i], q) for lo <= i < min(hi, cnt[q])
+__global__ __launch_bounds__(kTpb) void ks_union_kernel(const int32_t *__restrict__ nbr,
+                                                        const int32_t *__restrict__ cnt, int64_t n,
+                                                        int32_t k_stride, int32_t lo, int32_t hi,
+                                                        const int64_t *__restrict__ pid,
+                                                        const uint8_t *__restrict__ mask, Ws w, int32_t step) {
+    uint32_t c[3] = {0u, 0u, 0u};   // edges, masked, true and masked
+    uint32_t nbad[1] = {0u};
+    const int32_t width = hi - lo;
+    const int64_t total = n * width;
+    for (int64_t base = (int64_t)blockIdx.x * kTpb; base < total; base += (int64_t)gridDim.x * kTpb) {
+        const int64_t idx = base + threadIdx.x;
+        if (idx >= total) continue;
+        const int64_t q = idx / width;
+        const int32_t i = lo + (int32_t)(idx - q * width);
+        if (i >= cnt[q]) continue;
+        const int64_t j = nbr[q * k_stride + i];
+        if (j < 0 || j >= n) {
+            nbad[0] += 1u;
+            continue;
+        }
+        const bool mj = mask[j] != 0, mq = mask[q] != 0;
+        const bool y = pid[j] == pid[q];   // (no `> 0` test: k_scanner.py:267-269)
+        c[0] += 1u;
+        c[1] += (mj || mq) ? 1u : 0u;
+        c[2] += (y && (mj || mq)) ? 1u : 0u;
+        if (y && j != q) {
+            ks_unite(w.parent_a, (int32_t)j, (int32_t)q);
+            if (mj && mq) ks_unite(w.parent_b, (int32_t)j, (int32_t)q);
+        }
+    }
+    block_add(c, w.steps + 3 * step);
+    block_add(nbad, w.steps + 3 * kMaxKs + 1);
+}
+
+__global__ __launch_bounds__(kTpb) void ks_compress_kernel(const uint8_t *__restrict__ mask, int64_t n, Ws w,
+                                                           int64_t *__restrict__ labels) {
+    for (int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTpb) {
+        labels[i] = ks_find(w.parent_a, (int32_t)i);
+        if (mask[i]) atomicAdd(&w.csize[ks_find(w.parent_b, (int32_t)i)], 1u);
+    }
+}
+
+// every B component is single-id: its root's particle slot is its particle
+__global__ __launch_bounds__(kTpb) void ks_segmax_kernel(int64_t n, Ws w) {
+    for (int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTpb) {
+        const uint32_t s = w.csize[i];
+        if (s == 0) continue;
+        w.csize[i] = 0u;   // (ready for the next k)
+        atomicMax(&w.smax[w.hslot[i]], s);
+    }
+}
+
+__global__ __launch_bounds__(kTpb) void ks_segments_kernel(Ws w, unsigned long long *__restrict__ out_row) {
+    uint32_t c[4] = {0u, 0u, 0u, 0u};   // n_pids, n50, n75, n100
+    const int64_t S = (int64_t)w.S;
+    for (int64_t base = (int64_t)blockIdx.x * kTpb; base < S; base += (int64_t)gridDim.x * kTpb) {
+        const int64_t s = base + threadIdx.x;
+        if (s >= S || w.ptab[s] == 0) continue;
+        const uint64_t cp = w.pcnt[s], sp = w.smax[s];
+        w.smax[s] = 0u;   // (ready for the next k)
+        c[0] += 1u;
+        c[1] += 2 * sp > cp ? 1u : 0u;
+        c[2] += 4 * sp > 3 * cp ? 1u : 0u;
+        c[3] += sp == cp ? 1u : 0u;
+    }
+    block_add(c, out_row + C_PIDS);
+}
+
+__global__ void ks_finish_kernel(Ws w, Plan plan, unsigned long long *__restrict__ out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    unsigned long long run[3] = {0ull, 0ull, 0ull};
+    for (int s = 0; s < plan.n; ++s) {
+        unsigned long long *row = out + (size_t)plan.row[s] * kCols;
+        for (int c = 0; c < 3; ++c) {
+            run[c] += w.steps[3 * s + c];
+            row[C_EDGES + c] = run[c];
+        }
+        row[C_TRUE_EDGES_MASKED] = w.steps[3 * kMaxKs];
+        row[C_BAD] = w.steps[3 * kMaxKs + 1];
+    }
+}
+
+int grid_for(int64_t n, int per_cu) {
+    const int64_t g = ceil_div(n, kTpb), cap = (int64_t)cu_count() * per_cu;
+    return (int)(g < 1 ? 1 : (g < cap ? g : cap));
+}
+
+}  // namespace
+
+size_t cc_labels_ws_bytes(int64_t n) { return align_up(4 * (size_t)(n < 0 ? 0 : n), 256); }
+
+int cc_labels(const int64_t *edge_index, int64_t n_edges, const int32_t *nbr, const int32_t *cnt, int32_t k_stride,
+              int32_t k, const int64_t *same_pid, const uint8_t *node_mask, int64_t n, int64_t *labels,
+              int64_t *n_bad, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+    char msg[160];
+    if (n < 0) return fail(GNNTRK_EINVAL, "cc_labels: negative node count");
+    if (n >= (int64_t(1) << 30)) {
+        snprintf(msg, sizeof(msg), "cc_labels: %lld nodes; at most 2^30-1", (long long)n);
+        return fail(GNNTRK_EUNSUPPORTED, msg);
+    }
+    const bool table = edge_index == nullptr;
+    if (table) {
+        if (k < 1 || k_stride < 1 || k > k_stride) {
+            snprintf(msg, sizeof(msg), "cc_labels: k = %d, expected 1..k_stride = %d", (int)k, (int)k_stride);
+            return fail(GNNTRK_EINVAL, msg);
+        }
+        if (n > 0 && (!nbr || !cnt)) return fail(GNNTRK_EINVAL, "cc_labels: NULL edge_index and NULL neighbour table");
+    } else if (n_edges < 0) {
+        return fail(GNNTRK_EINVAL, "cc_labels: negative edge count");
+    }
+    if (n > 0 && !labels) return fail(GNNTRK_EINVAL, "cc_labels: NULL labels");
+    if (n > 0 && (!workspace || workspace_bytes < cc_labels_ws_bytes(n))) {
+        snprintf(msg, sizeof(msg), "cc_labels: workspace of %zu bytes, need %zu (gnntrk_cc_labels_workspace_bytes)",
+                 workspace_bytes, cc_labels_ws_bytes(n));
+        return fail(GNNTRK_EINVAL, msg);
+    }
+    int rc = 0;
+    if (n_bad && (rc = check_hip(hipMemsetAsync(n_bad, 0, sizeof(int64_t), stream), "cc_labels: clear"))) return rc;
+    if (n == 0) return GNNTRK_OK;
+    auto *parent = (int32_t *)workspace;
+    auto *bad = reinterpret_cast<unsigned long long *>(n_bad);
+    hipLaunchKernelGGL(cc_init_kernel, dim3(grid_for(n, 8)), dim3(kTpb), 0, stream, parent, n);
+    if (table)
+        hipLaunchKernelGGL(cc_union_table_kernel, dim3(grid_for(n * k, 8)), dim3(kTpb), 0, stream, nbr, cnt, n,
+                           k_stride, k, same_pid, node_mask, parent, bad);
+    else if (n_edges > 0)
+        hipLaunchKernelGGL(cc_union_edges_kernel, dim3(grid_for(n_edges, 8)), dim3(kTpb), 0, stream, edge_index,
+                           n_edges, n, same_pid, node_mask, parent, bad);
+    hipLaunchKernelGGL(cc_labels_kernel, dim3(grid_for(n, 8)), dim3(kTpb), 0, stream, parent, n, labels);
+    return check_launch("cc_labels");
+}
+
+size_t kscan_counts_ws_bytes(int64_t n) { return make_ws(nullptr, n < 0 ? 0 : n).total; }
+
+int kscan_counts(const int32_t *nbr, const int32_t *cnt, int64_t n, int32_t k_stride, const int32_t *ks,
+                 int32_t n_ks, const int64_t *pid, const uint8_t *node_mask, const int64_t *true_edge_index,
+                 int64_t n_true_edges, int64_t *out, int64_t *labels, void *workspace, size_t workspace_bytes,
+                 hipStream_t stream) {
+    char msg[160];
+    if (n < 0) return fail(GNNTRK_EINVAL, "kscan_counts: negative hit count");
+    if (n >= (int64_t(1) << 30)) {
+        snprintf(msg, sizeof(msg), "kscan_counts: %lld hits; at most 2^30-1", (long long)n);
+        return fail(GNNTRK_EUNSUPPORTED, msg);
+    }
+    if (n_ks < 1 || n_ks > kMaxKs) {
+        snprintf(msg, sizeof(msg), "kscan_counts: n_ks = %d, expected 1..%d", (int)n_ks, kMaxKs);
+        return fail(GNNTRK_EINVAL, msg);
+    }
+    if (!ks) return fail(GNNTRK_EINVAL, "kscan_counts: NULL ks");
+    if (k_stride < 1) return fail(GNNTRK_EINVAL, "kscan_counts: k_stride < 1");
+    for (int s = 0; s < n_ks; ++s)
+        if (ks[s] < 1 || ks[s] > k_stride) {
+            snprintf(msg, sizeof(msg), "kscan_counts: k = %d, expected 1..k_stride = %d", (int)ks[s], (int)k_stride);
+            return fail(GNNTRK_EINVAL, msg);
+        }
+    if (n_true_edges < 0) return fail(GNNTRK_EINVAL, "kscan_counts: negative number of true edges");
+    if (n_true_edges > 0 && !true_edge_index) return fail(GNNTRK_EINVAL, "kscan_counts: NULL true_edge_index");
+    if (!out) return fail(GNNTRK_EINVAL, "kscan_counts: NULL output");
+    if (n > 0 && (!nbr || !cnt || !pid || !node_mask || !labels))
+        return fail(GNNTRK_EINVAL, "kscan_counts: NULL neighbour table, particle ids, node mask or labels");
+    const Ws need = make_ws(nullptr, n);
+    if (n > 0 && (!workspace || workspace_bytes < need.total)) {
+        snprintf(msg, sizeof(msg), "kscan_counts: workspace of %zu bytes, need %zu (gnntrk_kscan_counts_workspace_bytes)",
+                 workspace_bytes, need.total);
+        return fail(GNNTRK_EINVAL, msg);
+    }
+    int rc = check_hip(hipMemsetAsync(out, 0, sizeof(int64_t) * (size_t)n_ks * kCols, stream), "kscan_counts: clear");
+    if (rc || n == 0) return rc;
+    Plan plan{};
+    plan.n = n_ks;
+    for (int s = 0; s < n_ks; ++s) {   // insertion sort of the rows by k (stable)
+        int at = s;
+        while (at > 0 && plan.k[at - 1] > ks[s]) {
+            plan.k[at] = plan.k[at - 1];
+            plan.row[at] = plan.row[at - 1];
+            --at;
+        }
+        plan.k[at] = ks[s];
+        plan.row[at] = s;
+    }
+    const Ws w = make_ws(workspace, n);
+    if ((rc = check_hip(hipMemsetAsync((char *)workspace + w.zero_from, 0, w.total - w.zero_from, stream),
+                        "kscan_counts: clear workspace")))
+        return rc;
+    auto *o = reinterpret_cast<unsigned long long *>(out);
+    const int gn = grid_for(n, 8);
+    hipLaunchKernelGGL(ks_init_kernel, dim3(gn), dim3(kTpb), 0, stream, w, n);
+    hipLaunchKernelGGL(ks_particles_kernel, dim3(gn), dim3(kTpb), 0, stream, pid, node_mask, n, w);
+    if (n_true_edges > 0)
+        hipLaunchKernelGGL(ks_true_edges_kernel, dim3(grid_for(n_true_edges, 8)), dim3(kTpb), 0, stream,
+                           true_edge_index, n_true_edges, n, node_mask, w);
+    if ((rc = check_launch("kscan_counts: setup"))) return rc;
+    int32_t lo = 0;
+    for (int s = 0; s < n_ks; ++s) {
+        const int32_t hi = plan.k[s];
+        if (hi > lo) {
+            hipLaunchKernelGGL(ks_union_kernel, dim3(grid_for(n * (hi - lo), 8)), dim3(kTpb), 0, stream, nbr, cnt, n,
+                               k_stride, lo, hi, pid, node_mask, w, (int32_t)s);
+            lo = hi;
+        }
+        hipLaunchKernelGGL(ks_compress_kernel, dim3(gn), dim3(kTpb), 0, stream, node_mask, n, w,
+                           labels + (size_t)plan.row[s] * n);
+        hipLaunchKernelGGL(ks_segmax_kernel, dim3(gn), dim3(kTpb), 0, stream, n, w);
+        hipLaunchKernelGGL(ks_segments_kernel, dim3(grid_for((int64_t)w.S, 4)), dim3(kTpb), 0, stream, w,
+                           o + (size_t)plan.row[s] * kCols);
+        if ((rc = check_launch("kscan_counts: scan"))) return rc;
+    }
+    hipLaunchKernelGGL(ks_finish_kernel, dim3(1), dim3(64), 0, stream, w, plan, o);
+    return check_launch("kscan_counts: finish");
+}
+
+}  // namespace gnntrk

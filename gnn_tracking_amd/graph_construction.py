@@ -25,9 +25,9 @@ def knn_with_max_radius(x: Tensor, k: int, max_radius: float | None = None) -> T
 
 def knn_scan(x: Tensor, ks, max_radius: float | None = None) -> dict[int, Tensor]:
     """Edge lists of ``knn_with_max_radius(x, k, max_radius)`` for every ``k`` in ``ks`` from
-    one neighbour search at ``max(ks)``: the device part of ``GraphConstructionKNNScanner``
-    (graph_construction/k_scanner.py:203-285, which searches once per k; its figures of
-    merit are CPU tracking metrics and stay with the caller)."""
+    one neighbour search at ``max(ks)`` (graph_construction/k_scanner.py:203-285 searches once per
+    k).  The scanner itself, with its figures of merit, is ``k_scanner.GraphConstructionKNNScanner``;
+    it evaluates every k from the neighbour table and never materialises these edge lists."""
     return ops.knn_scan(x, ks, max_radius)
 
 

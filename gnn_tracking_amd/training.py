@@ -205,14 +205,15 @@ class TCModule(TrackingModule):
 
 
 class MLModule(TrackingModule):
-    """Metric-learning training (``training/ml.py:25-78``): ``model(data) -> {"H": ...}`` (e.g.
-    ``GraphConstructionFCNN``), ``loss_fct`` a ``GraphConstructionHingeEmbeddingLoss``.  The
-    scanner of the validation step (``gc_scanner``: k-scans + figures of merit) is validation-only
-    control plane; its device part is ``graph_construction.knn_scan``."""
+    """Metric-learning training and validation (``training/ml.py:25-110``): ``model(data) -> {"H": ...}``
+    (e.g. ``GraphConstructionFCNN``), ``loss_fct`` a ``GraphConstructionHingeEmbeddingLoss``,
+    ``gc_scanner`` an optional ``k_scanner.GraphConstructionKNNScanner`` run on the latent space of every
+    validation batch (k-scan and its figures of merit, on the device)."""
 
-    def __init__(self, model: nn.Module, *, loss_fct: nn.Module, **kwargs):
+    def __init__(self, model: nn.Module, *, loss_fct: nn.Module, gc_scanner=None, **kwargs):
         super().__init__(model, **kwargs)
         self.loss_fct = loss_fct
+        self.gc_scanner = gc_scanner
 
     def get_losses(self, out: dict[str, Any], data, *, metrics: bool = True):
         if not hasattr(data, "true_edge_index"):
@@ -233,3 +234,21 @@ class MLModule(TrackingModule):
         batch = self.data_preproc(batch)
         out = self(batch, _preprocessed=True)
         return self.get_losses(out, batch, metrics=metrics)
+
+    def validation_step(self, batch, batch_idx: int = 0, *, last_batch: bool = False) -> dict[str, float]:
+        """``training/ml.py:77-96``: the losses and, on the last validation batch, the k-scanner's figures
+        of merit (``on_validation_epoch_end``) - what the reference logs, as one dict.  The scanner sees
+        the latent space ``out["H"]`` of every batch (``batch_idx == 0`` resets it).  Without a Lightning
+        trainer the caller says which batch is the last one (``last_batch``)."""
+        with torch.no_grad(), bf16_storage(self.bf16):
+            batch = self.data_preproc(batch)
+            out = self(batch, _preprocessed=True)
+            _, metrics = self.get_losses(out, batch, metrics=True)
+            if self.gc_scanner is not None:
+                self.gc_scanner(batch, batch_idx, latent=out["H"])
+                if last_batch:
+                    metrics |= self.gc_scanner.get_foms()
+        return metrics
+
+    def highlight_metric(self, metric: str) -> bool:
+        return metric in ["n_edges_frac_segment50_95", "total", "attractive", "repulsive", "max_frac_segment50"]

@@ -873,6 +873,63 @@ int gnntrk_tracking_metrics(const int64_t *labels, int32_t n_trials, const int64
                             int32_t n_cuts, float max_eta, int32_t predicted_count_thld, int64_t *out,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------ k-scan (metric learning)
+ * The device part of GraphConstructionKNNScanner (graph_construction/k_scanner.py:203-285) beyond the
+ * neighbour search: connected components and the integer counts behind its records.
+ *
+ * gnntrk_cc_labels - get_cc_labels (analysis/graphs.py:331-343) and the components of
+ * get_largest_segment_fracs (analysis/graphs.py:281-328).  The undirected graph on n nodes is given
+ *   - as an edge list: edge_index != NULL, int64 [2, n_edges] (nbr, cnt, k_stride, k ignored), or
+ *   - as a prefix of a neighbour table: edge_index == NULL, edges (nbr[q * k_stride + i], q) for
+ *     i < min(k, cnt[q]) (the table of gnntrk_knn_search with k = k_stride; 1 <= k <= k_stride),
+ * with two optional filters evaluated in the kernel (no filtered edge list is materialised):
+ *   same_pid  != NULL: keep an edge only if same_pid[a] == same_pid[b] (k_scanner.py:267-269: plain
+ *             equality, two noise hits with id 0 are a true edge);
+ *   node_mask != NULL: keep an edge only if both ends pass (Data.subgraph(basic_hit_mask), graphs.py:311-315).
+ * labels[i] (int64) = the SMALLEST node index of i's component: unique, independent of the order in which
+ * atomics land, and in [0, n) as gnntrk_tracking_metrics takes labels.  (networkx numbers components in
+ * discovery order; only the partition is contract there.)  An edge with an end outside [0, n) is skipped
+ * and counted in n_bad[0] (device int64, may be NULL).  Lock-free union-find: one pass over the edges,
+ * one compression pass, no host read.  workspace: gnntrk_cc_labels_workspace_bytes(n) (4 bytes per node).
+ * GNNTRK_EINVAL for n < 0, n_edges < 0, k < 1, k > k_stride, NULL required pointers, a small workspace;
+ * GNNTRK_EUNSUPPORTED for n >= 2^30.
+ *
+ * gnntrk_kscan_counts - everything GraphConstructionKNNScanner._evaluate_graph (k_scanner.py:248-285)
+ * counts, for n_ks values of k on ONE neighbour table (nbr / cnt of a search with k = k_stride), in one
+ * call without a host read.  ks: HOST array of n_ks (1..GNNTRK_KSCAN_MAX_KS) values in 1..k_stride, any
+ * order, repeats allowed.  node_mask: the good-node mask (utils/graph_masks.py:19-28, uint8 [n]).
+ * true_edge_index: int64 [2, n_true_edges] (data.true_edge_index; may be NULL with n_true_edges == 0).
+ * With y[e] = particle_id[e0] == particle_id[e1] and m = node_mask, row r of
+ * out (int64 [n_ks][GNNTRK_KSCAN_COLUMNS], overwritten) holds for k = ks[r]:
+ *   [0] n_edges              edges of the k-graph: sum over q of min(k, cnt[q])
+ *   [1] n_masked             |{e: m[e0] | m[e1]}|            (metrics/graph_construction.py:18)
+ *   [2] n_true_masked        |{e: y[e] and (m[e0] | m[e1])}| (:23-24, numerator of efficiency and purity)
+ *   [3] n_true_edges_masked  |{t in true_edge_index: m[t0] & m[t1]}| (:19-21; the same in every row)
+ *   [4] n_pids               distinct particle ids among the masked hits (graphs.py:303-305)
+ *   [5] n50  [6] n75  [7] n100   particles with 2 s > c, 4 s > 3 c, s == c, where c is the particle's
+ *                            number of masked hits and s the size of its largest component in the graph of
+ *                            the y edges with both ends masked (graphs.py:311-327; an id without such an
+ *                            edge has s = 1, the missing_pids branch) - the integer forms of
+ *                            (lsfs > 0.5), (lsfs > 0.75), (lsfs == 1) summed;
+ *   [8] n_bad                neighbour or true-edge indices outside [0, n) (skipped; 0 for valid input).
+ * labels (int64 [n_ks][n]): row r = gnntrk_cc_labels of the y edges of k = ks[r] on ALL hits - the labels
+ * of _evaluate_tracking_metrics_upper_bounds (k_scanner.py:235-246), ready for gnntrk_tracking_metrics
+ * with n_trials = n_ks.  The graphs are nested in k: the ks are visited in ascending order and every
+ * table edge is united once per call.  workspace: gnntrk_kscan_counts_workspace_bytes(n).
+ * GNNTRK_EINVAL for n < 0, n_ks out of range, a k < 1 or > k_stride, NULL required pointers, a small
+ * workspace; GNNTRK_EUNSUPPORTED for n >= 2^30. */
+#define GNNTRK_KSCAN_COLUMNS 9
+#define GNNTRK_KSCAN_MAX_KS 64
+size_t gnntrk_cc_labels_workspace_bytes(int64_t n);
+int gnntrk_cc_labels(const int64_t *edge_index, int64_t n_edges, const int32_t *nbr, const int32_t *cnt,
+                     int32_t k_stride, int32_t k, const int64_t *same_pid, const uint8_t *node_mask, int64_t n,
+                     int64_t *labels, int64_t *n_bad, void *workspace, size_t workspace_bytes, void *stream);
+size_t gnntrk_kscan_counts_workspace_bytes(int64_t n);
+int gnntrk_kscan_counts(const int32_t *nbr, const int32_t *cnt, int64_t n, int32_t k_stride, const int32_t *ks,
+                        int32_t n_ks, const int64_t *particle_id, const uint8_t *node_mask,
+                        const int64_t *true_edge_index, int64_t n_true_edges, int64_t *out, int64_t *labels,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
