@@ -63,7 +63,7 @@ def flatten_track_metrics(custom_metrics_result: dict[float, dict[str, float]]) 
     return {denote_pt(k, pt): v for pt, results in custom_metrics_result.items() for k, v in results.items()}
 
 
-def _zdiv(a: int, b: int) -> float:
+def _zdiv(a: float, b: float) -> float:
     """``utils/math.py:zero_division_gives_nan``."""
     return float("nan") if b == 0 else a / b
 

@@ -25,6 +25,27 @@ int fail(int code, const char *msg) {
     return code;
 }
 
+int check_count_i30(const char *entry, const char *what, int64_t n) {
+    char msg[160];
+    if (n < 0) {
+        snprintf(msg, sizeof(msg), "%s: negative %s count", entry, what);
+        return fail(GNNTRK_EINVAL, msg);
+    }
+    if (n >= (int64_t(1) << 30)) {
+        snprintf(msg, sizeof(msg), "%s: %lld %ss; at most 2^30-1", entry, (long long)n, what);
+        return fail(GNNTRK_EUNSUPPORTED, msg);
+    }
+    return GNNTRK_OK;
+}
+
+int check_workspace(const char *entry, const void *workspace, size_t have, size_t need) {
+    if (workspace && have >= need) return GNNTRK_OK;
+    char msg[160];
+    snprintf(msg, sizeof(msg), "%s: workspace of %zu bytes, need %zu (gnntrk_%s_workspace_bytes)", entry, have, need,
+             entry);
+    return fail(GNNTRK_EINVAL, msg);
+}
+
 int check_hip(hipError_t e, const char *what) {
     if (e == hipSuccess) return GNNTRK_OK;
     const char *s = hipGetErrorString(e);

@@ -169,11 +169,7 @@ __global__ __launch_bounds__(kCTpb) void relabel_kernel(const int64_t *__restric
 }
 
 static int tiles_of(int64_t n) { return (int)ceil_div(n > 0 ? n : 1, kCTile); }
-static int stream_blocks(int64_t n) {
-    int64_t g = ceil_div(n > 0 ? n : 1, kCTpb);
-    const int64_t cap = (int64_t)cu_count() * 8;
-    return (int)(g > cap ? cap : g);
-}
+static int stream_blocks(int64_t n) { return blocks_for(n, 8, kCTpb); }
 
 size_t compact_ws_bytes(int64_t n) { return align_up((size_t)tiles_of(n) * sizeof(int32_t), 256); }
 

@@ -302,11 +302,7 @@ __global__ __launch_bounds__(256) void dbscan_labels_kernel(const int64_t *__res
     }
 }
 
-static int node_blocks(int64_t n) {
-    int64_t g = ceil_div(n > 0 ? n : 1, 256);
-    const int64_t cap = (int64_t)cu_count() * 16;
-    return (int)(g > cap ? cap : g);
-}
+static int node_blocks(int64_t n) { return blocks_for(n, 16); }
 
 static int check_points(const float *x, int64_t n, int dim, int stride, double radius, const char *who) {
     if (n < 0 || n > 0x7fffffff) return fail(GNNTRK_EUNSUPPORTED, "radius graph: n must fit int32");

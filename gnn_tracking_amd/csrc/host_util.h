@@ -20,6 +20,31 @@ int cu_count();
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// grid of a grid-stride kernel over n items: one workgroup of tpb threads per tpb items, at least one, at
+// most per_cu per compute unit
+inline int blocks_for(int64_t n, int per_cu, int tpb = 256) {
+    const int64_t g = ceil_div(n, tpb), cap = (int64_t)cu_count() * per_cu;
+    return (int)(g < 1 ? 1 : (g < cap ? g : cap));
+}
+
+// carves a workspace into arrays, each aligned to 256 bytes; `off` is the size carved so far (base may
+// be NULL when only the sizes are wanted)
+struct Carver {
+    char *base;
+    size_t off = 0;
+    template <class T> T *take(size_t count) {
+        const size_t at = off;
+        off = align_up(off + sizeof(T) * count, 256);
+        return (T *)(base + at);
+    }
+};
+
+// guards of the entries that index hits in int32 tables: "<entry>: negative <what> count" (EINVAL),
+// "<entry>: <n> <what>s; at most 2^30-1" (EUNSUPPORTED)
+int check_count_i30(const char *entry, const char *what, int64_t n);
+// "<entry>: workspace of <have> bytes, need <need> (gnntrk_<entry>_workspace_bytes)" if it is NULL or too small
+int check_workspace(const char *entry, const void *workspace, size_t have, size_t need);
+
 // stable LSD radix sort of (key,value) pairs on the device (sort_pairs.hip: rocPRIM)
 size_t sort_pairs_temp_bytes(int64_t n);
 int sort_pairs_u32(const uint32_t *keys_in, uint32_t *keys_out, const uint32_t *vals_in,

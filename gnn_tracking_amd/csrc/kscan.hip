@@ -36,7 +36,7 @@
 // stay in L2 / MALL); there is no HBM roofline to quote for it.
 #include <stdio.h>
 
-#include "host_util.h"
+#include "count_util.h"
 
 namespace gnntrk {
 namespace {
@@ -47,39 +47,6 @@ constexpr int kMaxKs = GNNTRK_KSCAN_MAX_KS;
 
 // columns of the output table
 enum { C_EDGES = 0, C_MASKED, C_TRUE_MASKED, C_TRUE_EDGES_MASKED, C_PIDS, C_N50, C_N75, C_N100, C_BAD };
-
-// The CPU emulator build of this unit (g++, host pointers) takes the GCC builtins.
-__device__ __forceinline__ int32_t load_i32(const int32_t *p) {
-#ifdef __HIP_DEVICE_COMPILE__
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-    return __atomic_load_n(p, __ATOMIC_RELAXED);
-#endif
-}
-__device__ __forceinline__ void store_i32(int32_t *p, int32_t v) {
-#ifdef __HIP_DEVICE_COMPILE__
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-    __atomic_store_n(p, v, __ATOMIC_RELAXED);
-#endif
-}
-__device__ __forceinline__ int32_t cas_i32(int32_t *p, int32_t expect, int32_t desired) {
-#ifdef __HIP_DEVICE_COMPILE__
-    return atomicCAS(p, expect, desired);
-#else
-    __atomic_compare_exchange_n(p, &expect, desired, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
-    return expect;
-#endif
-}
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {   // (murmur3's finaliser)
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33;
-    x *= 0xc4ceb9fe1a85ec53ull;
-    x ^= x >> 33;
-    return x;
-}
 
 // root of x with path halving (see the argument at the top)
 __device__ __forceinline__ int32_t ks_find(int32_t *parent, int32_t x) {
@@ -108,26 +75,6 @@ __device__ __forceinline__ void ks_unite(int32_t *parent, int32_t a, int32_t b) 
         if (old == a) return;
         a = old;   // a was hooked by someone else meanwhile: go on from its new parent
     }
-}
-
-// wave sum of an integer (every lane of the wave calls it)
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-// block-wide: adds the per-thread counts v[0..NV) into dst[0..NV) with one global atomic per value
-template <int NV>
-__device__ __forceinline__ void block_add(const uint32_t (&v)[NV], unsigned long long *dst) {
-    __shared__ unsigned long long acc[NV];
-    if (threadIdx.x < NV) acc[threadIdx.x] = 0ull;
-    __syncthreads();
-    for (int k = 0; k < NV; ++k) {
-        const uint32_t s = wave_sum(v[k]);
-        if ((threadIdx.x & 63) == 0 && s) atomicAdd(&acc[k], (unsigned long long)s);
-    }
-    __syncthreads();
-    if (threadIdx.x < NV && acc[threadIdx.x]) atomicAdd(&dst[threadIdx.x], acc[threadIdx.x]);
 }
 
 // --------------------------------------------------------------------------- plain components
@@ -203,32 +150,21 @@ struct Ws {
     uint64_t S;
 };
 
-uint64_t table_size(int64_t n) {   // power of two, at least twice the hits: load factor <= 1/2
-    uint64_t s = 64;
-    while (s < 2 * (uint64_t)n) s <<= 1;
-    return s;
-}
-
 Ws make_ws(void *base, int64_t n) {
     Ws w{};
     w.S = table_size(n);
     const size_t S = w.S, N = (size_t)n;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes, 256);
-        return (char *)base + at;
-    };
-    w.parent_a = (int32_t *)take(4 * N);
-    w.parent_b = (int32_t *)take(4 * N);
-    w.hslot = (uint32_t *)take(4 * N);
-    w.zero_from = off;   // everything from here on is cleared
-    w.csize = (uint32_t *)take(4 * N);
-    w.ptab = (int32_t *)take(4 * S);
-    w.pcnt = (uint32_t *)take(4 * S);
-    w.smax = (uint32_t *)take(4 * S);
-    w.steps = (unsigned long long *)take(8 * (3 * (size_t)kMaxKs + 2));
-    w.total = off;
+    Carver ws{(char *)base};
+    w.parent_a = ws.take<int32_t>(N);
+    w.parent_b = ws.take<int32_t>(N);
+    w.hslot = ws.take<uint32_t>(N);
+    w.zero_from = ws.off;   // everything from here on is cleared
+    w.csize = ws.take<uint32_t>(N);
+    w.ptab = ws.take<int32_t>(S);
+    w.pcnt = ws.take<uint32_t>(S);
+    w.smax = ws.take<uint32_t>(S);
+    w.steps = ws.take<unsigned long long>(3 * (size_t)kMaxKs + 2);
+    w.total = ws.off;
     return w;
 }
 
@@ -251,12 +187,7 @@ __global__ __launch_bounds__(kTpb) void ks_particles_kernel(const int64_t *__res
     for (int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTpb) {
         if (!mask[i]) continue;
         const int64_t key = pid[i];
-        uint64_t s = mix64((uint64_t)key) & smask;
-        for (;;) {   // (terminates: the table has more slots than there are hits)
-            const int32_t h = cas_i32(&w.ptab[s], 0, (int32_t)(i + 1));
-            if (h == 0 || pid[h - 1] == key) break;
-            s = (s + 1) & smask;
-        }
+        const uint64_t s = table_claim(w.ptab, smask, mix64((uint64_t)key), i, [&](int32_t h) { return pid[h] == key; });
         w.hslot[i] = (uint32_t)s;
         atomicAdd(&w.pcnt[s], 1u);
     }
@@ -360,11 +291,6 @@ __global__ void ks_finish_kernel(Ws w, Plan plan, unsigned long long *__restrict
     }
 }
 
-int grid_for(int64_t n, int per_cu) {
-    const int64_t g = ceil_div(n, kTpb), cap = (int64_t)cu_count() * per_cu;
-    return (int)(g < 1 ? 1 : (g < cap ? g : cap));
-}
-
 }  // namespace
 
 size_t cc_labels_ws_bytes(int64_t n) { return align_up(4 * (size_t)(n < 0 ? 0 : n), 256); }
@@ -373,11 +299,8 @@ int cc_labels(const int64_t *edge_index, int64_t n_edges, const int32_t *nbr, co
               int32_t k, const int64_t *same_pid, const uint8_t *node_mask, int64_t n, int64_t *labels,
               int64_t *n_bad, void *workspace, size_t workspace_bytes, hipStream_t stream) {
     char msg[160];
-    if (n < 0) return fail(GNNTRK_EINVAL, "cc_labels: negative node count");
-    if (n >= (int64_t(1) << 30)) {
-        snprintf(msg, sizeof(msg), "cc_labels: %lld nodes; at most 2^30-1", (long long)n);
-        return fail(GNNTRK_EUNSUPPORTED, msg);
-    }
+    int rc = check_count_i30("cc_labels", "node", n);
+    if (rc) return rc;
     const bool table = edge_index == nullptr;
     if (table) {
         if (k < 1 || k_stride < 1 || k > k_stride) {
@@ -389,24 +312,19 @@ int cc_labels(const int64_t *edge_index, int64_t n_edges, const int32_t *nbr, co
         return fail(GNNTRK_EINVAL, "cc_labels: negative edge count");
     }
     if (n > 0 && !labels) return fail(GNNTRK_EINVAL, "cc_labels: NULL labels");
-    if (n > 0 && (!workspace || workspace_bytes < cc_labels_ws_bytes(n))) {
-        snprintf(msg, sizeof(msg), "cc_labels: workspace of %zu bytes, need %zu (gnntrk_cc_labels_workspace_bytes)",
-                 workspace_bytes, cc_labels_ws_bytes(n));
-        return fail(GNNTRK_EINVAL, msg);
-    }
-    int rc = 0;
+    if (n > 0 && (rc = check_workspace("cc_labels", workspace, workspace_bytes, cc_labels_ws_bytes(n)))) return rc;
     if (n_bad && (rc = check_hip(hipMemsetAsync(n_bad, 0, sizeof(int64_t), stream), "cc_labels: clear"))) return rc;
     if (n == 0) return GNNTRK_OK;
     auto *parent = (int32_t *)workspace;
     auto *bad = reinterpret_cast<unsigned long long *>(n_bad);
-    hipLaunchKernelGGL(cc_init_kernel, dim3(grid_for(n, 8)), dim3(kTpb), 0, stream, parent, n);
+    hipLaunchKernelGGL(cc_init_kernel, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, parent, n);
     if (table)
-        hipLaunchKernelGGL(cc_union_table_kernel, dim3(grid_for(n * k, 8)), dim3(kTpb), 0, stream, nbr, cnt, n,
+        hipLaunchKernelGGL(cc_union_table_kernel, dim3(blocks_for(n * k, 8)), dim3(kTpb), 0, stream, nbr, cnt, n,
                            k_stride, k, same_pid, node_mask, parent, bad);
     else if (n_edges > 0)
-        hipLaunchKernelGGL(cc_union_edges_kernel, dim3(grid_for(n_edges, 8)), dim3(kTpb), 0, stream, edge_index,
+        hipLaunchKernelGGL(cc_union_edges_kernel, dim3(blocks_for(n_edges, 8)), dim3(kTpb), 0, stream, edge_index,
                            n_edges, n, same_pid, node_mask, parent, bad);
-    hipLaunchKernelGGL(cc_labels_kernel, dim3(grid_for(n, 8)), dim3(kTpb), 0, stream, parent, n, labels);
+    hipLaunchKernelGGL(cc_labels_kernel, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, parent, n, labels);
     return check_launch("cc_labels");
 }
 
@@ -417,11 +335,8 @@ int kscan_counts(const int32_t *nbr, const int32_t *cnt, int64_t n, int32_t k_st
                  int64_t n_true_edges, int64_t *out, int64_t *labels, void *workspace, size_t workspace_bytes,
                  hipStream_t stream) {
     char msg[160];
-    if (n < 0) return fail(GNNTRK_EINVAL, "kscan_counts: negative hit count");
-    if (n >= (int64_t(1) << 30)) {
-        snprintf(msg, sizeof(msg), "kscan_counts: %lld hits; at most 2^30-1", (long long)n);
-        return fail(GNNTRK_EUNSUPPORTED, msg);
-    }
+    int rc = check_count_i30("kscan_counts", "hit", n);
+    if (rc) return rc;
     if (n_ks < 1 || n_ks > kMaxKs) {
         snprintf(msg, sizeof(msg), "kscan_counts: n_ks = %d, expected 1..%d", (int)n_ks, kMaxKs);
         return fail(GNNTRK_EINVAL, msg);
@@ -438,13 +353,9 @@ int kscan_counts(const int32_t *nbr, const int32_t *cnt, int64_t n, int32_t k_st
     if (!out) return fail(GNNTRK_EINVAL, "kscan_counts: NULL output");
     if (n > 0 && (!nbr || !cnt || !pid || !node_mask || !labels))
         return fail(GNNTRK_EINVAL, "kscan_counts: NULL neighbour table, particle ids, node mask or labels");
-    const Ws need = make_ws(nullptr, n);
-    if (n > 0 && (!workspace || workspace_bytes < need.total)) {
-        snprintf(msg, sizeof(msg), "kscan_counts: workspace of %zu bytes, need %zu (gnntrk_kscan_counts_workspace_bytes)",
-                 workspace_bytes, need.total);
-        return fail(GNNTRK_EINVAL, msg);
-    }
-    int rc = check_hip(hipMemsetAsync(out, 0, sizeof(int64_t) * (size_t)n_ks * kCols, stream), "kscan_counts: clear");
+    if (n > 0 && (rc = check_workspace("kscan_counts", workspace, workspace_bytes, make_ws(nullptr, n).total)))
+        return rc;
+    rc = check_hip(hipMemsetAsync(out, 0, sizeof(int64_t) * (size_t)n_ks * kCols, stream), "kscan_counts: clear");
     if (rc || n == 0) return rc;
     Plan plan{};
     plan.n = n_ks;
@@ -463,25 +374,25 @@ int kscan_counts(const int32_t *nbr, const int32_t *cnt, int64_t n, int32_t k_st
                         "kscan_counts: clear workspace")))
         return rc;
     auto *o = reinterpret_cast<unsigned long long *>(out);
-    const int gn = grid_for(n, 8);
+    const int gn = blocks_for(n, 8);
     hipLaunchKernelGGL(ks_init_kernel, dim3(gn), dim3(kTpb), 0, stream, w, n);
     hipLaunchKernelGGL(ks_particles_kernel, dim3(gn), dim3(kTpb), 0, stream, pid, node_mask, n, w);
     if (n_true_edges > 0)
-        hipLaunchKernelGGL(ks_true_edges_kernel, dim3(grid_for(n_true_edges, 8)), dim3(kTpb), 0, stream,
+        hipLaunchKernelGGL(ks_true_edges_kernel, dim3(blocks_for(n_true_edges, 8)), dim3(kTpb), 0, stream,
                            true_edge_index, n_true_edges, n, node_mask, w);
     if ((rc = check_launch("kscan_counts: setup"))) return rc;
     int32_t lo = 0;
     for (int s = 0; s < n_ks; ++s) {
         const int32_t hi = plan.k[s];
         if (hi > lo) {
-            hipLaunchKernelGGL(ks_union_kernel, dim3(grid_for(n * (hi - lo), 8)), dim3(kTpb), 0, stream, nbr, cnt, n,
+            hipLaunchKernelGGL(ks_union_kernel, dim3(blocks_for(n * (hi - lo), 8)), dim3(kTpb), 0, stream, nbr, cnt, n,
                                k_stride, lo, hi, pid, node_mask, w, (int32_t)s);
             lo = hi;
         }
         hipLaunchKernelGGL(ks_compress_kernel, dim3(gn), dim3(kTpb), 0, stream, node_mask, n, w,
                            labels + (size_t)plan.row[s] * n);
         hipLaunchKernelGGL(ks_segmax_kernel, dim3(gn), dim3(kTpb), 0, stream, n, w);
-        hipLaunchKernelGGL(ks_segments_kernel, dim3(grid_for((int64_t)w.S, 4)), dim3(kTpb), 0, stream, w,
+        hipLaunchKernelGGL(ks_segments_kernel, dim3(blocks_for((int64_t)w.S, 4)), dim3(kTpb), 0, stream, w,
                            o + (size_t)plan.row[s] * kCols);
         if ((rc = check_launch("kscan_counts: scan"))) return rc;
     }

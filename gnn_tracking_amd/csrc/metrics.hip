@@ -17,7 +17,7 @@
 #include <math.h>
 #include <stdio.h>
 
-#include "host_util.h"
+#include "count_util.h"
 
 namespace gnntrk {
 namespace {
@@ -31,10 +31,6 @@ constexpr int kMaxFpr = GNNTRK_AUC_MAX_FPR;
 constexpr int kHistSmall = 4096;
 constexpr int kHistLarge = (kMaxCuts + 1) * 2 * (kMaxThr + 1);
 
-struct Cuts {
-    float v[kMaxCuts];
-    int32_t n;
-};
 struct Fprs {   // (kernel arguments by value: nothing to upload)
     double v[kMaxFpr];
 };
@@ -364,21 +360,7 @@ int check_common(const char *what, const float *w, const void *y, int32_t y_kind
     if (n > 0 && (!w || !y)) return fail(GNNTRK_EINVAL, "metrics: NULL scores or labels");
     if (pt && n > 0 && (!src || !tgt)) return fail(GNNTRK_EINVAL, "metrics: pt cuts need the NULL-free src / tgt ids");
     if (pt && !cuts) return fail(GNNTRK_EINVAL, "metrics: pt given but the cut values are NULL");
-    c.n = n_cuts;
-    for (int j = 0; j < kMaxCuts; ++j) c.v[j] = 0.f;
-    if (pt) {
-        for (int j = 0; j < n_cuts; ++j) {
-            c.v[j] = cuts[j];
-            if (!(cuts[j] == cuts[j]) || (j > 0 && !(cuts[j] >= cuts[j - 1])))
-                return fail(GNNTRK_EINVAL, "metrics: the pt cuts must be ascending numbers");
-        }
-    }
-    return GNNTRK_OK;
-}
-
-int grid_for(int64_t n, int per_cu) {
-    const int64_t g = ceil_div(n, kTpb), cap = (int64_t)cu_count() * per_cu;
-    return (int)(g < 1 ? 1 : (g < cap ? g : cap));
+    return fill_cuts(c, pt ? cuts : nullptr, n_cuts, "metrics");   // (without pt every edge passes every cut)
 }
 
 template <class ID, class Y>
@@ -386,17 +368,17 @@ void launch_counts(const float *w, const void *y, const int32_t *perm, const voi
                    const Cuts &c, const float *thr, int n_thr, int64_t n, unsigned long long *out, hipStream_t stream) {
     const int nh = (c.n + 1) * 2 * (n_thr + 1);
     if (nh <= kHistSmall)
-        hipLaunchKernelGGL((bcs_counts_kernel<ID, Y, kHistSmall>), dim3(grid_for(n, 4)), dim3(kTpb), 0, stream, w,
+        hipLaunchKernelGGL((bcs_counts_kernel<ID, Y, kHistSmall>), dim3(blocks_for(n, 4)), dim3(kTpb), 0, stream, w,
                            (const Y *)y, perm, (const ID *)src, (const ID *)tgt, pt, c, thr, n_thr, n, out);
     else
-        hipLaunchKernelGGL((bcs_counts_kernel<ID, Y, kHistLarge>), dim3(grid_for(n, 2)), dim3(kTpb), 0, stream, w,
+        hipLaunchKernelGGL((bcs_counts_kernel<ID, Y, kHistLarge>), dim3(blocks_for(n, 2)), dim3(kTpb), 0, stream, w,
                            (const Y *)y, perm, (const ID *)src, (const ID *)tgt, pt, c, thr, n_thr, n, out);
 }
 
 template <class ID, class Y>
 void launch_keys(const float *w, const void *y, const int32_t *perm, const void *src, const void *tgt, const float *pt,
                  const Cuts &c, int64_t n, uint32_t *keys, uint32_t *vals, hipStream_t stream) {
-    hipLaunchKernelGGL((auc_keys_kernel<ID, Y>), dim3(grid_for(n, 8)), dim3(kTpb), 0, stream, w, (const Y *)y, perm,
+    hipLaunchKernelGGL((auc_keys_kernel<ID, Y>), dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, w, (const Y *)y, perm,
                        (const ID *)src, (const ID *)tgt, pt, c, n, keys, vals);
 }
 
@@ -411,22 +393,18 @@ struct AucWs {
 AucWs auc_ws(void *base, int64_t n) {
     AucWs w{};
     const int64_t n_tiles = ceil_div(n, kTile) > 0 ? ceil_div(n, kTile) : 1;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes, 256);
-        return (char *)base + at;
-    };
-    w.keys_a = (uint32_t *)take(4 * (size_t)n);
-    w.keys_b = (uint32_t *)take(4 * (size_t)n);
-    w.vals_a = (uint32_t *)take(4 * (size_t)n);
-    w.vals_b = (uint32_t *)take(4 * (size_t)n);
+    const size_t N = (size_t)n;
+    Carver ws{(char *)base};
+    w.keys_a = ws.take<uint32_t>(N);
+    w.keys_b = ws.take<uint32_t>(N);
+    w.vals_a = ws.take<uint32_t>(N);
+    w.vals_b = ws.take<uint32_t>(N);
     w.temp_bytes = sort_pairs_temp_bytes(n);
-    w.temp = take(w.temp_bytes);
-    w.tile_sum = (unsigned long long *)take(8 * (size_t)n_tiles);
-    w.tile_head = (unsigned long long *)take(8 * (size_t)n_tiles);
-    w.lim = (unsigned long long *)take(8 * kMaxFpr);
-    w.total = off;
+    w.temp = ws.take<char>(w.temp_bytes);
+    w.tile_sum = ws.take<unsigned long long>((size_t)n_tiles);
+    w.tile_head = ws.take<unsigned long long>((size_t)n_tiles);
+    w.lim = ws.take<unsigned long long>(kMaxFpr);
+    w.total = ws.off;
     return w;
 }
 
@@ -472,13 +450,7 @@ int roc_auc(const float *w, const void *y, int32_t y_kind, const int32_t *perm, 
         if (!(max_fprs[m] > 0.0 && max_fprs[m] <= 1.0))
             return fail(GNNTRK_EINVAL, "roc_auc: every max_fpr must lie in (0, 1]");
     if (!out) return fail(GNNTRK_EINVAL, "roc_auc: NULL output");
-    const AucWs need = auc_ws(nullptr, n);
-    if (!workspace || workspace_bytes < need.total) {
-        char msg[128];
-        snprintf(msg, sizeof(msg), "roc_auc: workspace of %zu bytes, need %zu (gnntrk_roc_auc_workspace_bytes)",
-                 workspace_bytes, need.total);
-        return fail(GNNTRK_EINVAL, msg);
-    }
+    if ((rc = check_workspace("roc_auc", workspace, workspace_bytes, auc_ws(nullptr, n).total))) return rc;
     rc = check_hip(hipMemsetAsync(out, 0, sizeof(int64_t) * GNNTRK_AUC_STRIDE * (size_t)n_cuts, stream),
                    "roc_auc: clear");
     if (rc || n == 0) return rc;

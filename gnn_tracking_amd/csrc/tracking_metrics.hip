@@ -5,8 +5,8 @@
 //
 // The reference groups hits with pandas (value_counts of (cluster, particle), groupby means per
 // particle).  Here both groupings are open-addressing hash tables in the workspace whose slots hold
-// "first hit + 1" of their group (claimed by compare-and-swap; a probe compares the keys of the slot's
-// hit), so particle ids of any size need no sort and no densification:
+// "first hit + 1" of their group (count_util.h: claimed by compare-and-swap; a probe compares the keys of
+// the slot's hit), so particle ids of any size need no sort and no densification:
 //
 //   once per call (hits)        tm_particles_kernel   particle table; per particle its hit count, fp64
 //                                                     sums and non-NaN counts of pt / eta / reconstructable
@@ -26,7 +26,7 @@
 #include <math.h>
 #include <stdio.h>
 
-#include "host_util.h"
+#include "count_util.h"
 
 namespace gnntrk {
 namespace {
@@ -34,51 +34,6 @@ namespace {
 constexpr int kTpb = 256;
 constexpr int kMaxCuts = GNNTRK_METRICS_MAX_CUTS;
 constexpr int kProps = 3;   // pt, eta, reconstructable
-
-struct Cuts {
-    float v[kMaxCuts];
-    int32_t n;
-};
-
-// The atomics beyond the common integer set.  The CPU emulator build of this unit (g++, host
-// pointers) takes the GCC builtins.
-__device__ __forceinline__ int32_t cas_i32(int32_t *p, int32_t expect, int32_t desired) {
-#ifdef __HIP_DEVICE_COMPILE__
-    return atomicCAS(p, expect, desired);
-#else
-    __atomic_compare_exchange_n(p, &expect, desired, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
-    return expect;
-#endif
-}
-__device__ __forceinline__ void add_f64(double *p, double v) {
-#ifdef __HIP_DEVICE_COMPILE__
-    atomicAdd(p, v);
-#else
-    double old, nw;
-    __atomic_load(p, &old, __ATOMIC_RELAXED);
-    do {
-        nw = old + v;
-    } while (!__atomic_compare_exchange(p, &old, &nw, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED));
-#endif
-}
-__device__ __forceinline__ void min_u64(unsigned long long *p, unsigned long long v) {
-#ifdef __HIP_DEVICE_COMPILE__
-    atomicMin(p, v);
-#else
-    unsigned long long old = __atomic_load_n(p, __ATOMIC_RELAXED);
-    while (old > v && !__atomic_compare_exchange_n(p, &old, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {
-    }
-#endif
-}
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {   // (murmur3's finaliser)
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33;
-    x *= 0xc4ceb9fe1a85ec53ull;
-    x ^= x >> 33;
-    return x;
-}
 
 // signed particle id -> unsigned key of the same order (the tie rule's atomic minimum)
 __device__ __forceinline__ unsigned long long pid_key(int64_t pid) { return (unsigned long long)pid ^ (1ull << 63); }
@@ -92,12 +47,7 @@ __device__ __forceinline__ int cut_class(float v, const Cuts &cuts) {
 
 // the particle table's slot of pid (present: every particle id of the hits was inserted)
 __device__ __forceinline__ int64_t find_particle(const int32_t *ptab, const int64_t *pid, uint64_t mask, int64_t key) {
-    uint64_t s = mix64((uint64_t)key) & mask;
-    for (;;) {
-        const int32_t h = ptab[s];
-        if (h == 0 || pid[h - 1] == key) return (int64_t)s;
-        s = (s + 1) & mask;
-    }
+    return (int64_t)table_find(ptab, mask, mix64((uint64_t)key), [&](int32_t h) { return pid[h] == key; });
 }
 
 struct Ws {
@@ -118,36 +68,25 @@ struct Ws {
     uint64_t S;
 };
 
-uint64_t table_size(int64_t n) {   // power of two, at least twice the hits: load factor <= 1/2
-    uint64_t s = 64;
-    while (s < 2 * (uint64_t)n) s <<= 1;
-    return s;
-}
-
 Ws make_ws(void *base, int64_t n, int32_t T) {
     Ws w{};
     w.S = table_size(n);
     const size_t S = w.S, N = (size_t)n, TS = (size_t)T * S, TN = (size_t)T * N;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes, 256);
-        return (char *)base + at;
-    };
-    w.psum = (double *)take(8 * kProps * S);
-    w.ptab = (int32_t *)take(4 * S);
-    w.pcnt = (uint32_t *)take(4 * S);
-    w.phit = (uint32_t *)take(4 * S);
-    w.pcls = (uint32_t *)take(4 * S);
-    w.pnn = (uint32_t *)take(4 * kProps * S);
-    w.hslot = (uint32_t *)take(4 * N);
-    w.ttab = (int32_t *)take(4 * TS);
-    w.tcnt = (uint32_t *)take(4 * TS);
-    w.csize = (uint32_t *)take(4 * TN);
-    w.cbest = (uint32_t *)take(4 * TN);
-    w.zero_bytes = off;
-    w.cpid = (unsigned long long *)take(8 * TN);
-    w.total = off;
+    Carver ws{(char *)base};
+    w.psum = ws.take<double>(kProps * S);
+    w.ptab = ws.take<int32_t>(S);
+    w.pcnt = ws.take<uint32_t>(S);
+    w.phit = ws.take<uint32_t>(S);
+    w.pcls = ws.take<uint32_t>(S);
+    w.pnn = ws.take<uint32_t>(kProps * S);
+    w.hslot = ws.take<uint32_t>(N);
+    w.ttab = ws.take<int32_t>(TS);
+    w.tcnt = ws.take<uint32_t>(TS);
+    w.csize = ws.take<uint32_t>(TN);
+    w.cbest = ws.take<uint32_t>(TN);
+    w.zero_bytes = ws.off;
+    w.cpid = ws.take<unsigned long long>(TN);
+    w.total = ws.off;
     return w;
 }
 
@@ -160,12 +99,8 @@ __global__ __launch_bounds__(kTpb) void tm_particles_kernel(const int64_t *__res
     const uint64_t mask = w.S - 1;
     for (int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTpb) {
         const int64_t key = pid[i];
-        uint64_t s = mix64((uint64_t)key) & mask;
-        for (;;) {   // (terminates: the table has more slots than there are hits)
-            const int32_t h = cas_i32(&w.ptab[s], 0, (int32_t)(i + 1));
-            if (h == 0 || pid[h - 1] == key) break;
-            s = (s + 1) & mask;
-        }
+        const uint64_t s =
+            table_claim(w.ptab, mask, mix64((uint64_t)key), i, [&](int32_t h) { return pid[h] == key; });
         w.hslot[i] = (uint32_t)s;
         atomicAdd(&w.pcnt[s], 1u);
         const float v[kProps] = {pt[i], eta[i], reco[i]};
@@ -178,12 +113,6 @@ __global__ __launch_bounds__(kTpb) void tm_particles_kernel(const int64_t *__res
         const int hc = (v[2] != 0.f && fabsf(v[1]) < max_eta) ? cut_class(v[0], cuts) : 0;
         if (hc) atomicMax(&w.phit[s], (uint32_t)hc);
     }
-}
-
-// wave sum of an integer (every lane of the wave calls it)
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
 }
 
 __global__ __launch_bounds__(kTpb) void tm_particle_kernel(Cuts cuts, float max_eta, Ws w,
@@ -234,12 +163,8 @@ __global__ __launch_bounds__(kTpb) void tm_pairs_kernel(const int64_t *__restric
         const int64_t *lt = labels + t * n;
         int32_t *tab = w.ttab + (size_t)t * w.S;
         const uint32_t ps = w.hslot[i];
-        uint64_t s = mix64(((uint64_t)lab << 32) | ps) & mask;
-        for (;;) {
-            const int32_t h = cas_i32(&tab[s], 0, (int32_t)(i + 1));
-            if (h == 0 || (lt[h - 1] == lab && w.hslot[h - 1] == ps)) break;
-            s = (s + 1) & mask;
-        }
+        const uint64_t s = table_claim(tab, mask, mix64(((uint64_t)lab << 32) | ps), i,
+                                       [&](int32_t h) { return lt[h] == lab; }, [&](int32_t h) { return w.hslot[h] == ps; });
         atomicAdd(&w.tcnt[(size_t)t * w.S + s], 1u);
         atomicAdd(&w.csize[t * n + lab], 1u);
     }
@@ -317,11 +242,6 @@ __global__ __launch_bounds__(kTpb) void tm_clusters_kernel(const int64_t *__rest
         atomicAdd(&out[(size_t)t * cuts.n * 4 + threadIdx.x], (unsigned long long)acc[threadIdx.x]);
 }
 
-int grid_for(int64_t n, int per_cu) {
-    const int64_t g = ceil_div(n, kTpb), cap = (int64_t)cu_count() * per_cu;
-    return (int)(g < 1 ? 1 : (g < cap ? g : cap));
-}
-
 }  // namespace
 
 size_t tracking_metrics_ws_bytes(int64_t n, int32_t n_trials) {
@@ -332,11 +252,8 @@ int tracking_metrics(const int64_t *labels, int32_t n_trials, const int64_t *pid
                      const float *reco, int64_t n, const float *cuts, int32_t n_cuts, float max_eta,
                      int32_t count_thld, int64_t *out, void *workspace, size_t workspace_bytes, hipStream_t stream) {
     char msg[160];
-    if (n < 0) return fail(GNNTRK_EINVAL, "tracking_metrics: negative hit count");
-    if (n >= (int64_t(1) << 30)) {
-        snprintf(msg, sizeof(msg), "tracking_metrics: %lld hits; at most 2^30-1", (long long)n);
-        return fail(GNNTRK_EUNSUPPORTED, msg);
-    }
+    int rc = check_count_i30("tracking_metrics", "hit", n);
+    if (rc) return rc;
     if (n_trials < 1 || n_trials > GNNTRK_TRACKING_MAX_TRIALS) {
         snprintf(msg, sizeof(msg), "tracking_metrics: n_trials = %d, expected 1..%d", (int)n_trials,
                  GNNTRK_TRACKING_MAX_TRIALS);
@@ -347,25 +264,16 @@ int tracking_metrics(const int64_t *labels, int32_t n_trials, const int64_t *pid
         return fail(GNNTRK_EINVAL, msg);
     }
     if (!cuts) return fail(GNNTRK_EINVAL, "tracking_metrics: NULL cuts");
-    Cuts c{};
-    c.n = n_cuts;
-    for (int j = 0; j < n_cuts; ++j) {
-        c.v[j] = cuts[j];
-        if (!(cuts[j] == cuts[j]) || (j > 0 && !(cuts[j] >= cuts[j - 1])))
-            return fail(GNNTRK_EINVAL, "tracking_metrics: the pt cuts must be ascending numbers");
-    }
+    Cuts c;
+    if ((rc = fill_cuts(c, cuts, n_cuts, "tracking_metrics"))) return rc;
     if (!out) return fail(GNNTRK_EINVAL, "tracking_metrics: NULL output");
     if (n > 0 && (!labels || !pid || !pt || !eta || !reco))
         return fail(GNNTRK_EINVAL, "tracking_metrics: NULL labels, particle ids, pt, eta or reconstructable");
-    const Ws need = make_ws(nullptr, n, n_trials);
-    if (n > 0 && (!workspace || workspace_bytes < need.total)) {
-        snprintf(msg, sizeof(msg),
-                 "tracking_metrics: workspace of %zu bytes, need %zu (gnntrk_tracking_metrics_workspace_bytes)",
-                 workspace_bytes, need.total);
-        return fail(GNNTRK_EINVAL, msg);
-    }
+    if (n > 0 && (rc = check_workspace("tracking_metrics", workspace, workspace_bytes,
+                                       make_ws(nullptr, n, n_trials).total)))
+        return rc;
     const size_t n_out = (size_t)n_cuts + (size_t)n_trials * n_cuts * 4 + 1;
-    int rc = check_hip(hipMemsetAsync(out, 0, sizeof(int64_t) * n_out, stream), "tracking_metrics: clear");
+    rc = check_hip(hipMemsetAsync(out, 0, sizeof(int64_t) * n_out, stream), "tracking_metrics: clear");
     if (rc || n == 0) return rc;
     const Ws w = make_ws(workspace, n, n_trials);
     if ((rc = check_hip(hipMemsetAsync(workspace, 0, w.zero_bytes, stream), "tracking_metrics: clear workspace")))
@@ -375,15 +283,15 @@ int tracking_metrics(const int64_t *labels, int32_t n_trials, const int64_t *pid
         return rc;
     auto *o = reinterpret_cast<unsigned long long *>(out);
     const int64_t S = (int64_t)w.S, tn = (int64_t)n_trials * n, ts = (int64_t)n_trials * S;
-    hipLaunchKernelGGL(tm_particles_kernel, dim3(grid_for(n, 8)), dim3(kTpb), 0, stream, pid, pt, eta, reco, n, c,
+    hipLaunchKernelGGL(tm_particles_kernel, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, pid, pt, eta, reco, n, c,
                        max_eta, w);
-    hipLaunchKernelGGL(tm_particle_kernel, dim3(grid_for(S, 4)), dim3(kTpb), 0, stream, c, max_eta, w, o);
+    hipLaunchKernelGGL(tm_particle_kernel, dim3(blocks_for(S, 4)), dim3(kTpb), 0, stream, c, max_eta, w, o);
     if ((rc = check_launch("tracking_metrics: particles"))) return rc;
-    hipLaunchKernelGGL(tm_pairs_kernel, dim3(grid_for(tn, 8)), dim3(kTpb), 0, stream, labels, n, tn, w,
+    hipLaunchKernelGGL(tm_pairs_kernel, dim3(blocks_for(tn, 8)), dim3(kTpb), 0, stream, labels, n, tn, w,
                        o + n_out - 1);
-    hipLaunchKernelGGL(tm_best_count_kernel, dim3(grid_for(ts, 8)), dim3(kTpb), 0, stream, labels, n, ts, w);
-    hipLaunchKernelGGL(tm_best_pid_kernel, dim3(grid_for(ts, 8)), dim3(kTpb), 0, stream, labels, pid, n, ts, w);
-    const int gx = (int)((grid_for(n, 8) + n_trials - 1) / n_trials);
+    hipLaunchKernelGGL(tm_best_count_kernel, dim3(blocks_for(ts, 8)), dim3(kTpb), 0, stream, labels, n, ts, w);
+    hipLaunchKernelGGL(tm_best_pid_kernel, dim3(blocks_for(ts, 8)), dim3(kTpb), 0, stream, labels, pid, n, ts, w);
+    const int gx = (int)((blocks_for(n, 8) + n_trials - 1) / n_trials);
     hipLaunchKernelGGL(tm_clusters_kernel, dim3(gx < 1 ? 1 : gx, (unsigned)n_trials), dim3(kTpb), 0, stream, pid, n,
                        c, count_thld, w, o + n_cuts);
     return check_launch("tracking_metrics: clusters");

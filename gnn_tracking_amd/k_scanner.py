@@ -35,8 +35,8 @@ import torch
 from torch import Tensor
 
 from . import _capi, ops
-from .cluster_metrics import _counts as _tracking_counts, _cut_plan, _results as _tracking_results, \
-    flatten_track_metrics
+from .cluster_metrics import _counts as _tracking_counts, _cut_plan, _hits, _results as _tracking_results, \
+    _zdiv, flatten_track_metrics
 from .graph_analysis import efficiency_purity_from_counts
 from .graph_masks import get_good_node_mask
 from .hparams import HyperparametersMixin
@@ -48,10 +48,6 @@ logger = logging.getLogger("gnn_tracking_amd")
 # columns of gnntrk_kscan_counts' table (include/gnntrk.h)
 COUNT_COLUMNS = ("n_edges", "n_masked", "n_true_masked", "n_true_edges_masked", "n_pids", "n50", "n75", "n100",
                  "n_bad")
-
-
-def _zdiv(a: float, b: float) -> float:
-    return float("nan") if b == 0 else a / b
 
 
 class _NotAKnotSpline:
@@ -348,9 +344,8 @@ class GraphConstructionKNNScanner(HyperparametersMixin):
         counts, labels = kscan_counts(nbr, cnt, kmax, [min(k, kmax) for k in ks], data.particle_id, mask,
                                       getattr(data, "true_edge_index", None))
         pts, cuts, idx = _cut_plan([0.9])   # (hard-coded in the reference: k_scanner.py:243)
-        pid = data.particle_id.detach().to(device=dev, dtype=torch.int64).contiguous()
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()   # noqa: E731
-        trk = _tracking_counts(labels, pid, f32(data.pt), f32(data.reconstructable), f32(data.eta), cuts, 3, 4)
+        hits = _hits(data.particle_id, data.pt, data.reconstructable, data.eta, dev)
+        trk = _tracking_counts(labels, *hits, cuts, 3, 4)
         host = torch.cat([counts.reshape(-1), trk]).cpu().numpy()   # the batch's one host copy
         table = host[:counts.numel()].reshape(len(ks), len(COUNT_COLUMNS))
         upper = _tracking_results(host[counts.numel():], len(ks), pts, idx)

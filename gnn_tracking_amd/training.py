@@ -85,6 +85,28 @@ class TrackingModule:
     def get_losses(self, out: dict[str, Any], data):
         raise NotImplementedError
 
+    @staticmethod
+    def _loss_metrics(losses) -> dict[str, float]:
+        """The metric dict of a ``MultiLossFct`` result (the float conversions synchronise with the device)."""
+        m = dict(losses.loss_dct)
+        m.update({k + "_weighted": float(v) for k, v in losses.weighted_losses.items()})
+        m.update({k: float(v) for k, v in losses.extra_metrics.items()})
+        m["total"] = float(losses.loss)
+        return m
+
+    def _scanned_validation_step(self, data, scanner, scan, last_batch: bool) -> dict[str, float]:
+        """The validation step of ``TCModule`` / ``MLModule``: the losses' metrics, ``scan(data, out)`` if there
+        is a ``scanner`` and, on the last batch, its figures of merit."""
+        with torch.no_grad(), bf16_storage(self.bf16):
+            data = self.data_preproc(data)
+            out = self(data, _preprocessed=True)
+            _, metrics = self.get_losses(out, data, metrics=True)
+            if scanner is not None:
+                scan(data, out)
+                if last_batch:
+                    metrics |= scanner.get_foms()
+        return metrics
+
     def _loss(self, data) -> Tensor:
         r = self.training_step(data, 0)
         return r[0] if isinstance(r, tuple) else r
@@ -172,11 +194,7 @@ class TCModule(TrackingModule):
                                true_edge_index=getattr(data, "true_edges", None))
         if not metrics:  # (the float conversions below synchronise with the device)
             return losses.loss, {}
-        m = dict(losses.loss_dct)
-        m.update({k + "_weighted": float(v) for k, v in losses.weighted_losses.items()})
-        m.update({k: float(v) for k, v in losses.extra_metrics.items()})
-        m["total"] = float(losses.loss)
-        return losses.loss, m
+        return losses.loss, self._loss_metrics(losses)
 
     def training_step(self, data, batch_idx: int = 0, *, metrics: bool = False):
         data = self.data_preproc(data)
@@ -189,15 +207,8 @@ class TCModule(TrackingModule):
         dict.  The scanner sees every batch (``batch_idx == 0`` resets it).  Without a Lightning
         trainer the caller says which batch is the last one (``last_batch``, the reference's
         ``is_last_val_batch``)."""
-        with torch.no_grad(), bf16_storage(self.bf16):
-            data = self.data_preproc(data)
-            out = self(data, _preprocessed=True)
-            _, metrics = self.get_losses(out, data, metrics=True)
-            if self.cluster_scanner is not None:
-                self.cluster_scanner(data, out, batch_idx)
-                if last_batch:
-                    metrics |= self.cluster_scanner.get_foms()
-        return metrics
+        return self._scanned_validation_step(data, self.cluster_scanner,
+                                             lambda d, out: self.cluster_scanner(d, out, batch_idx), last_batch)
 
     def highlight_metric(self, metric: str) -> bool:
         return metric in ["attractive", "repulsive", "trk.lhc_pt0.9", "trk.perfect_pt0.9",
@@ -224,11 +235,7 @@ class MLModule(TrackingModule):
                                reconstructable=data.reconstructable)
         if not metrics:
             return losses.loss, {}
-        m = dict(losses.loss_dct)
-        m.update({k + "_weighted": float(v) for k, v in losses.weighted_losses.items()})
-        m.update({k: float(v) for k, v in losses.extra_metrics.items()})
-        m["total"] = float(losses.loss)
-        return losses.loss, m
+        return losses.loss, self._loss_metrics(losses)
 
     def training_step(self, batch, batch_idx: int = 0, *, metrics: bool = False):
         batch = self.data_preproc(batch)
@@ -240,15 +247,8 @@ class MLModule(TrackingModule):
         of merit (``on_validation_epoch_end``) - what the reference logs, as one dict.  The scanner sees
         the latent space ``out["H"]`` of every batch (``batch_idx == 0`` resets it).  Without a Lightning
         trainer the caller says which batch is the last one (``last_batch``)."""
-        with torch.no_grad(), bf16_storage(self.bf16):
-            batch = self.data_preproc(batch)
-            out = self(batch, _preprocessed=True)
-            _, metrics = self.get_losses(out, batch, metrics=True)
-            if self.gc_scanner is not None:
-                self.gc_scanner(batch, batch_idx, latent=out["H"])
-                if last_batch:
-                    metrics |= self.gc_scanner.get_foms()
-        return metrics
+        return self._scanned_validation_step(batch, self.gc_scanner,
+                                             lambda d, out: self.gc_scanner(d, batch_idx, latent=out["H"]), last_batch)
 
     def highlight_metric(self, metric: str) -> bool:
         return metric in ["n_edges_frac_segment50_95", "total", "attractive", "repulsive", "max_frac_segment50"]
