@@ -58,6 +58,12 @@ class GFold(C.Structure):
     _fields_ = [("ids", C.c_void_p), ("n_nodes", C.c_int64), ("seg", C.c_int32), ("_pad", C.c_int32)]
 
 
+class HeadBce(C.Structure):
+    """gnntrk_head_bce: what gnntrk_mlp_backward_bf16_bce takes beside the backward's argument block."""
+    _fields_ = [("label", C.c_void_p), ("w_out", C.c_void_p), ("gscale", C.c_float), ("_pad", C.c_int32),
+                ("n_total", C.c_int64)]
+
+
 class MlpBwdArgs(C.Structure):
     _fields_ = [("mlp", Mlp), ("n_seg", C.c_int32), ("epilogue", C.c_int32),
                 ("seg", Seg * MAX_SEGS), ("n_rows", C.c_int64), ("ca", C.c_float),
@@ -143,6 +149,10 @@ _SIGNATURES = {
     "gnntrk_mlp_backward_bf16_can_fold": (C.c_int, [C.POINTER(MlpBwdArgs)]),
     "gnntrk_fold_finish_bf16": (C.c_int, [_P, C.c_int32, C.c_int64, _P, C.c_int64, _P, C.c_int32, _P]),
     "gnntrk_mlp_backward_bf16": (C.c_int, [C.POINTER(MlpBwdArgs), _P, C.c_size_t, _P]),
+    "gnntrk_mlp_backward_bf16_bce_supported": (C.c_int, [C.POINTER(MlpBwdArgs), C.POINTER(HeadBce)]),
+    "gnntrk_mlp_backward_bf16_bce": (C.c_int, [C.POINTER(MlpBwdArgs), C.POINTER(HeadBce), _P, C.c_size_t, _P]),
+    "gnntrk_mlp_backward_bf16_bce_kernel_name": (C.c_int, [C.POINTER(MlpBwdArgs), C.POINTER(HeadBce), C.c_char_p,
+                                                           C.c_size_t]),
     "gnntrk_mlp_forward_bf16_kernel_name": (C.c_int, [C.POINTER(MlpFwdArgs), C.c_char_p, C.c_size_t]),
     "gnntrk_mlp_backward_bf16_kernel_name": (C.c_int, [C.POINTER(MlpBwdArgs), C.c_char_p, C.c_size_t]),
     "gnntrk_mlp_kernel_name": (C.c_int, [C.POINTER(Mlp), C.c_int32, C.POINTER(Seg), C.c_int32,

@@ -229,6 +229,17 @@ int gnntrk_mlp_backward_bf16(const gnntrk_mlp_bwd_args *args, void *workspace, s
                              void *stream) {
     return mlp_backward_bf16_launch(args, workspace, workspace_bytes, (hipStream_t)stream);
 }
+int gnntrk_mlp_backward_bf16_bce_supported(const gnntrk_mlp_bwd_args *args, const gnntrk_head_bce *bce) {
+    return mlp_backward_bf16_bce_supported(args, bce);
+}
+int gnntrk_mlp_backward_bf16_bce(const gnntrk_mlp_bwd_args *args, const gnntrk_head_bce *bce, void *workspace,
+                                 size_t workspace_bytes, void *stream) {
+    return mlp_backward_bf16_bce_launch(args, bce, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int gnntrk_mlp_backward_bf16_bce_kernel_name(const gnntrk_mlp_bwd_args *args, const gnntrk_head_bce *bce, char *buf,
+                                             size_t len) {
+    return mlp16_bwd_bce_kernel_name(args, bce, buf, len);
+}
 int gnntrk_mlp_forward_bf16_kernel_name(const gnntrk_mlp_fwd_args *args, char *buf, size_t len) {
     return mlp16_fwd_kernel_name(args, buf, len);
 }

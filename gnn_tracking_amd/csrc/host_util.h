@@ -92,6 +92,10 @@ size_t mlp_backward_bf16_ws_bytes(const gnntrk_mlp *m);
 int mlp_backward_bf16_launch(const gnntrk_mlp_bwd_args *a, void *ws, size_t ws_bytes, hipStream_t stream);
 int mlp_backward_bf16_max_terms(const gnntrk_mlp_bwd_args *a);
 int mlp_backward_bf16_can_fold(const gnntrk_mlp_bwd_args *a);
+int mlp_backward_bf16_bce_supported(const gnntrk_mlp_bwd_args *a, const gnntrk_head_bce *bce);
+int mlp_backward_bf16_bce_launch(const gnntrk_mlp_bwd_args *a, const gnntrk_head_bce *bce, void *ws, size_t ws_bytes,
+                                 hipStream_t stream);
+int mlp16_bwd_bce_kernel_name(const gnntrk_mlp_bwd_args *a, const gnntrk_head_bce *bce, char *buf, size_t len);
 
 
 // compact.hip

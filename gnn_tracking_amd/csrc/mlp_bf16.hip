@@ -7,7 +7,7 @@
 namespace gnntrk {
 
 int launch_bwd16_g32(const gnntrk_mlp_bwd_args *a, const SlotPlan &P, int GT, int grid, int grid_buf, int *used, float *part,
-                     uint8_t *trash, hipStream_t stream);  // mlp_bf16_g32.hip
+                     uint8_t *trash, hipStream_t stream, const gnntrk_head_bce *bce);  // mlp_bf16_g32.hip
 
 
 int mlp16_kernel_name(const gnntrk_mlp *m, int n_seg, const gnntrk_seg *seg, int backward, char *buf,
@@ -106,7 +106,60 @@ size_t mlp_backward_bf16_ws_bytes(const gnntrk_mlp *m) {
     return bwd16_partial_bytes(m) + (size_t)cu_count() * kBwd16BlocksPerCuMax * kBwd16MaxWaves * 64 * 8;
 }
 
+// the launch of gnntrk_mlp_backward_bf16_bce as the shared launcher takes it: the upstream term is a stand-in that
+// describes w_out (fp32 [n_rows]) - the buffer plan is the fp32-upstream head's, and the kernel stores W through
+// the term's descriptor
+static bool bce_args(const gnntrk_mlp_bwd_args *a, const gnntrk_head_bce *bce, gnntrk_mlp_bwd_args &b) {
+    if (!a || !bce || !bce->label || !bce->w_out || ((uintptr_t)bce->label & 3) != 0 || ((uintptr_t)bce->w_out & 3) != 0 ||
+        a->n_rows < 1 || a->n_rows > 0x7fffffff || bce->n_total < 1)
+        return false;
+    b = *a;
+    b.n_gout = 1;
+    b.gout[0].ptr = bce->w_out;
+    b.gout[0].idx = nullptr;
+    b.gout[0].stride = 1;
+    b.gout[0].rows = (int32_t)a->n_rows;
+    return true;
+}
+
+int mlp_backward_bf16_bce_supported(const gnntrk_mlp_bwd_args *a, const gnntrk_head_bce *bce) {
+    gnntrk_mlp_bwd_args b;
+    if (!bce_args(a, bce, b) || b.n_seg < 1 || b.n_seg > GNNTRK_MAX_SEGS) return 0;
+    SlotPlan P;
+    make_slot_plan(P, b.mlp, b.n_seg, b.seg, b.gseg);
+    if (!P.ok || P.KI != 1 || P.bias_init) return 0;
+    const int GT = (P.GT == 0) ? 0 : (P.GT <= 1) ? 1 : 2;
+    BufPlan B;
+    make_buf_plan(B, P, &b, GT);
+    return bwd16_bce_ht(B, P, &b, GT) != 0 ? 1 : 0;
+}
+
+int mlp16_bwd_bce_kernel_name(const gnntrk_mlp_bwd_args *a, const gnntrk_head_bce *bce, char *buf, size_t len) {
+    if (!buf || len == 0) return fail(GNNTRK_EINVAL, "mlp_kernel_name: bad argument");
+    if (!mlp_backward_bf16_bce_supported(a, bce))
+        return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16_bce: not the buffer-addressed head shape");
+    SlotPlan P;
+    make_slot_plan(P, a->mlp, a->n_seg, a->seg, a->gseg);
+    snprintf(buf, len, "mlp16_bwd_bce_kernel<%d>", P.HT);
+    return GNNTRK_OK;
+}
+
+static int bwd16_launch(const gnntrk_mlp_bwd_args *a, void *ws, size_t ws_bytes, hipStream_t stream,
+                        const gnntrk_head_bce *bce);
 int mlp_backward_bf16_launch(const gnntrk_mlp_bwd_args *a, void *ws, size_t ws_bytes, hipStream_t stream) {
+    return bwd16_launch(a, ws, ws_bytes, stream, nullptr);
+}
+int mlp_backward_bf16_bce_launch(const gnntrk_mlp_bwd_args *a, const gnntrk_head_bce *bce, void *ws, size_t ws_bytes,
+                                 hipStream_t stream) {
+    gnntrk_mlp_bwd_args b;
+    if (!bce_args(a, bce, b)) return fail(GNNTRK_EINVAL, "mlp_backward_bf16_bce: bad argument");
+    if (b.epilogue != GNNTRK_EPI_SIGMOID || b.fold.ids)
+        return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16_bce: the SIGMOID epilogue, no fold");
+    return bwd16_launch(&b, ws, ws_bytes, stream, bce);
+}
+
+static int bwd16_launch(const gnntrk_mlp_bwd_args *a, void *ws, size_t ws_bytes, hipStream_t stream,
+                        const gnntrk_head_bce *bce) {
     if (!a) return fail(GNNTRK_EINVAL, "mlp_backward_bf16: NULL args");
     int rc = check_bf16_mlp(a->mlp, a->n_seg, a->seg, "mlp_backward_bf16", a->n_rows);
     if (rc) return rc;
@@ -169,7 +222,7 @@ int mlp_backward_bf16_launch(const gnntrk_mlp_bwd_args *a, void *ws, size_t ws_b
         float *part = reinterpret_cast<float *>(ws);
         uint8_t *trash = reinterpret_cast<uint8_t *>(ws) + bwd16_partial_bytes(&a->mlp);
         rc = (a->epilogue == GNNTRK_EPI_SIGMOID)
-                 ? launch_bwd16_g32(a, P, GT, grid, grid_buf, used, part, trash, stream)
+                 ? launch_bwd16_g32(a, P, GT, grid, grid_buf, used, part, trash, stream, bce)
                  : launch_bwd16<false>(a, P, GT, grid, grid_buf, used, part, trash, stream);
         if (rc) return rc;
         grid = used[0];

@@ -1,7 +1,9 @@
 // Body of the bf16 backward kernels (mlp_bf16_kernels.h includes it once per kernel).  Expects the template
-// parameters KI, HT, GT, THREE, G32 of the enclosing kernel, constexpr int D, the type IO, constexpr bool BI
-// and the kernel arguments a, part, trash, bp by value.
+// parameters KI, HT, GT, THREE, G32 of the enclosing kernel, constexpr int D, the type IO, constexpr bool BI, kBce
+// and the kernel arguments a, part, trash, bp by value; `bce` (gnntrk_head_bce) is read where kBce is set.
     constexpr bool BUF = IO::NL > 0;
+    static_assert(!kBce || (BUF && G32 && IO::kEpi == GNNTRK_EPI_SIGMOID && IO::NG == 1),
+                  "BCE upstream gradient: the buffer-addressed one-column sigmoid head only");
     constexpr int NW = bwd16_block_waves<IO>(), NT = 64 * NW;   // waves / lanes of the workgroup
     static_assert(!BI || (!BUF && D == 1), "accumulator-initialised biases: generic one-tile form only");
     static_assert(!BUF || KI == 1, "buffer-addressed I/O: one k-step");
@@ -128,6 +130,17 @@
         ones_v = g == bp.ones_group ? bp.ones_bits : 0u;
         rmin_v[0] = g == 0 ? bp.rmin[0][0] : g == 1 ? bp.rmin[1][0] : g == 2 ? bp.rmin[2][0] : bp.rmin[3][0];
         rmin_v[1] = g == 0 ? bp.rmin[0][1] : g == 1 ? bp.rmin[1][1] : g == 2 ? bp.rmin[2][1] : bp.rmin[3][1];
+    }
+    // fused BCE (gnntrk_mlp_backward_bf16_bce): the label bytes of the tile's rows ride in the upstream term's prefetch
+    // slot - one dword per four rows, read by the lanes that own the output column; the term's own descriptor (the
+    // stand-in the launcher points at w_out) takes the W stores
+    buf_rsrc_t r_lab;
+    uint32_t v_lab = kBufOut;
+    float bce_gs = 0.f;
+    if constexpr (kBce) {
+        r_lab = buf_make(bce.label, (uint32_t)a.n_rows);
+        v_lab = g == 0 ? ((uint32_t)c & ~3u) : kBufOut;
+        bce_gs = 1.f / (float)bce.n_total;   // (as bce_csr_kernel forms it)
     }
     const bool any_relu = BUF && bp.any_relu != 0;
     const int gate_mode = BUF ? bp.gate_mode : 2;
@@ -305,7 +318,9 @@
             for (int t = 0; t < IO::NG; ++t) {
                 uint32_t voff, soff;
                 buf_addr(IO::gout[t], bp.gout[t], v_go[t], false, idv[d], r0, voff, soff);
-                if (G32) {   // fp32 upstream gradient of a one-column output (the edge-weight head)
+                if constexpr (kBce) {   // the label dword of rows r0 + (c & ~3) .. + 3 (lane group 0; zero past the end)
+                    r.v[0] = buf_load_u32(r_lab, v_lab, r0);
+                } else if (G32) {   // fp32 upstream gradient of a one-column output (the edge-weight head)
                     r.v[0] = buf_load_u32(r_go[t], voff, soff);
                 } else {
                     const u32x2 h = buf_load_u32x2(r_go[t], voff, soff);
@@ -921,7 +936,26 @@
             if (need_y) {
                 const f32x4 y = contract_hidden<HT>(wimg + F::kA3, PL(d), lane,
                                                     BI ? bias_frag(s_btab + 16 * HT, lane) : zero);
-                if (BUF && G32) {
+                if constexpr (kBce) {
+                    // the head's own output and the BCE gradient of it, in the order of the launches this replaces:
+                    // W as mlp16_fwd_kernel stores it, the unit gradient as bce_csr_one, the loss's upstream scalar
+                    // as the elementwise product behind it - then the sigmoid's derivative as below
+                    const float sg = sigmoidf_(y[0]);
+                    const float wq = a.ca + a.cb * sg;
+                    uint32_t lab = (gcur[d].v[0] >> (8 * (c & 3))) & 0xffu;
+                    if constexpr (kTail) {   // (the last label dword may be cut off by the range check: read the bytes)
+                        const int64_t row = (int64_t)row0_of(grp, d) + c;
+                        lab = bce.label[row < a.n_rows ? row : a.n_rows - 1];
+                    }
+                    const float tq = lab ? 1.f : 0.f;
+                    float gq = bce_gs * (wq - tq) / fmaxf((1.f - wq) * wq, 1e-12f);
+                    gq = gq * bce.gscale;
+                    gq = gq * a.cb * sg * (1.f - sg);
+                    const bool on = g == 0 && !(kTail && !valid[d]);
+                    gy = zero;
+                    gy[0] = on ? gq : 0.f;
+                    buf_store_u32(__float_as_uint(wq), r_go[0], on ? v_go[0] : kBufOut, row0_of(grp, d) << 2);
+                } else if (BUF && G32) {
                     // (buffer form of the fp32-gradient launch = the one-column edge-weight head: the
                     //  sigmoid's derivative for the one feature there is, not for four registers)
                     const float sg = sigmoidf_(y[0]);

@@ -665,7 +665,21 @@ __global__ __launch_bounds__(64 * bwd16_block_waves<IO_>(), HT >= 5 ? 1 : ((IO_:
                                                                            uint8_t *trash, const BufPlan bp) {
     constexpr int D = D_, OT = 1, kSkel = 0;
     using IO = IO_;
-    constexpr bool BI = false;
+    constexpr bool BI = false, kBce = false;
+    const gnntrk_head_bce bce = {};
+#include "mlp_bf16_bwd_body.inc"
+}
+// The edge-weight head's backward that forms its own upstream gradient (gnntrk_mlp_backward_bf16_bce): the
+// instantiation <1, HT, 2, true, true, D, IoHead> of the kernel above with the BCE arm of stage S1 compiled in.  A
+// kernel of its own, not a run-time branch of that instantiation: the fp32-upstream launch keeps its code object
+// (235 registers, two waves per SIMD - a second S1 arm in the same loop would have to fit beside it), and the
+// label / W traffic rides on the descriptor and prefetch slot the upstream term has there.
+template <int HT>
+__global__ __launch_bounds__(64 * bwd16_block_waves<IoHead>(), 2 * bwd16_block_waves<IoHead>() / 4) void mlp16_bwd_bce_kernel(
+    const gnntrk_mlp_bwd_args a, float *part, uint8_t *trash, const BufPlan bp, const gnntrk_head_bce bce) {
+    constexpr int KI = 1, GT = 2, D = 2, OT = 1, kSkel = 0;
+    using IO = IoHead;
+    constexpr bool THREE = true, G32 = true, BI = false, kBce = true;
 #include "mlp_bf16_bwd_body.inc"
 }
 // The I/O SKELETON of a buffer-addressed launch (debug_flags & 4096; results are NOT gradients): every load and
@@ -678,7 +692,8 @@ __global__ __launch_bounds__(64 * bwd16_block_waves<IO_>(), 2 * bwd16_block_wave
     const gnntrk_mlp_bwd_args a, float *part, uint8_t *trash, const BufPlan bp) {
     constexpr int D = D_, OT = 1, kSkel = 128;
     using IO = IO_;
-    constexpr bool BI = false;
+    constexpr bool BI = false, kBce = false;
+    const gnntrk_head_bce bce = {};
 #include "mlp_bf16_bwd_body.inc"
 }
 // outputs of 17 .. 48 features (OT output tiles) / up to four k-steps of inputs: generic I/O, one tile per
@@ -688,7 +703,8 @@ __global__ __launch_bounds__(kBlock, 1) void mlp16_bwd_ot_kernel(const gnntrk_ml
                                                                 const BufPlan bp) {
     constexpr int D = 1, OT = OT_, GT = 2 * KI, kSkel = 0;
     using IO = IoNone;
-    constexpr bool BI = false, G32 = false;
+    constexpr bool BI = false, G32 = false, kBce = false;
+    const gnntrk_head_bce bce = {};
 #include "mlp_bf16_bwd_body.inc"
 }
 // hidden width 64 with biases (SlotPlan::bias_init): generic I/O, one tile per iteration
@@ -697,7 +713,8 @@ __global__ __launch_bounds__(kBlock, (HT >= 5 || KI >= 2) ? 1 : 2) void mlp16_bw
                                                                                           uint8_t *trash, const BufPlan bp) {
     constexpr int D = 1, OT = 1, kSkel = 0;
     using IO = IoNone;
-    constexpr bool BI = true;
+    constexpr bool BI = true, kBce = false;
+    const gnntrk_head_bce bce = {};
 #include "mlp_bf16_bwd_body.inc"
 }
 
@@ -952,18 +969,45 @@ inline const char *buf_io_name(const BufPlan &B, int KI, int HT, int GT, bool th
     return "";
 }
 
+// hidden tiles (1 / 3) of the mlp16_bwd_bce_kernel instantiation the launch described by (plan, a) takes, 0: none
+inline int bwd16_bce_ht(const BufPlan &B, const SlotPlan &P, const gnntrk_mlp_bwd_args *a, int GT) {
+    if (kBwd16BufD != 2 || a->epilogue != GNNTRK_EPI_SIGMOID || a->mlp.out_dim != 1 || a->mlp.n_layers != 3 || GT != 2 ||
+        a->fold.ids || (a->debug_flags & (64 | 128 | 4096)) || (P.HT != 1 && P.HT != 3))
+        return 0;
+    return strcmp(buf_io_name(B, P.KI, P.HT, GT, true, true, a->debug_flags, a->epilogue), "IoHead") == 0 ? P.HT : 0;
+}
+
 // launches the backward instantiation for (plan, GT, three); G32 = fp32 upstream gradient
 // (grid: workgroups of kWaves waves; grid_buf: of kBwd16BufWaves waves - what the buffer-addressed kernels take;
 // *used = {workgroups, waves per workgroup} of the launch: grid * waves partial blocks unless reduced in LDS)
+// bce != NULL: the head's launch with the BCE gradient formed in the kernel (mlp16_bwd_bce_kernel) or nothing
 template <bool G32>
 int launch_bwd16(const gnntrk_mlp_bwd_args *a, const SlotPlan &P, int GT, int grid, int grid_buf, int *used,
-                 float *part, uint8_t *trash, hipStream_t stream) {
+                 float *part, uint8_t *trash, hipStream_t stream, const gnntrk_head_bce *bce = nullptr) {
     used[0] = grid;
     used[1] = kWaves;
     const bool three = a->mlp.n_layers == 3;
     bool launched = false;
     BufPlan B;
     make_buf_plan(B, P, a, GT);
+    if (bce) {
+        if constexpr (G32) {
+            if (bwd16_bce_ht(B, P, a, GT) == 0)
+                return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16_bce: not the buffer-addressed head shape "
+                                                 "(gnntrk_mlp_backward_bf16_bce_supported)");
+            if (P.HT == 3) {
+                auto kfn = mlp16_bwd_bce_kernel<3>;
+                hipLaunchKernelGGL(kfn, dim3(grid_buf), dim3(64 * kBwd16BufWaves), 0, stream, *a, part, trash, B, *bce);
+            } else {
+                auto kfn = mlp16_bwd_bce_kernel<1>;
+                hipLaunchKernelGGL(kfn, dim3(grid_buf), dim3(64 * kBwd16BufWaves), 0, stream, *a, part, trash, B, *bce);
+            }
+            used[0] = grid_buf;
+            used[1] = kBwd16BufWaves;
+            return check_launch("mlp_backward_bf16_bce");
+        }
+        return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16_bce: the SIGMOID epilogue only");
+    }
     if (a->mlp.out_dim > 16 || P.KI > 2) {   // output tiles / wide inputs (three hidden tiles; GT = 2 KI)
         if (G32 || a->epilogue == GNNTRK_EPI_RELU || a->epilogue == GNNTRK_EPI_SIGMOID)
             return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16: outputs over 16 / inputs over 64 slots take the NONE and RESIDUAL epilogues");

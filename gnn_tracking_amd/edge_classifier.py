@@ -137,9 +137,19 @@ class ECForGraphTCN(nn.Module, HyperparametersMixin):
         # W and the edge embedding stay in CSR order; they present themselves in edge_index
         # order (edge_order.EdgeOrdered: the scatter happens only if something other than
         # this package's losses looks at the values)
-        w = self.W.fused(segs, n_rows=E, epilogue=_capi.EPI_SIGMOID, ca=eps, cb=1 - 2 * eps)
+        def head():
+            return self.W.fused(segs, n_rows=E, epilogue=_capi.EPI_SIGMOID, ca=eps, cb=1 - 2 * eps).squeeze()
+
+        # inside TrackingModule.backward_step (ops.head_loss_deferral) the head does not run here: EdgeWeightBCELoss
+        # turns head + loss into one node whose backward launch forms the weights itself; any other reader of W
+        # runs head() first (edge_order.PendingEdgeWeights)
+        w = None
+        if bf16 and self.training:
+            lin = self.W.linears()
+            w = ops.deferred_head(segs, [m.weight for m in lin], [m.bias for m in lin], gi, y, n_rows=E,
+                                  ca=eps, cb=1 - 2 * eps, head=head)
         return {
-            "W": EdgeOrdered(w.squeeze(), gi),
+            "W": w if w is not None else EdgeOrdered(head(), gi),
             "node_embedding": h if nperm is None else NodeOrdered(h, gi),
             "edge_embedding": EdgeOrdered(e, gi),
         }

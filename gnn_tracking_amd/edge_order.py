@@ -101,6 +101,65 @@ class EdgeOrdered(Tensor):
         return self.in_edge_index_order().__reduce_ex__(proto)
 
 
+class PendingEdgeWeights(EdgeOrdered):
+    """``W`` of the edge classifier inside ``TrackingModule.backward_step`` (``ops.head_loss_deferral``): the head
+    has not run yet.  ``ops.bce_loss`` may take it as it is - head and loss then become one autograd node whose
+    backward launch forms the weights itself (``ops_bf16.HeadBCE16``) - and ANY other reader of the values (``csr``,
+    the ``edge_index``-ordered view, a torch function, another loss) runs the head's forward launch through its
+    ordinary autograd node first (``resolve``), after which this is an ``EdgeOrdered`` like any other.  Shape, dtype
+    and device are answered without either."""
+
+    @staticmethod
+    def __new__(cls, n_edges: int, device, gi, head, fused_args):
+        r = Tensor._make_wrapper_subclass(cls, (int(n_edges),), dtype=torch.float32, device=device,
+                                          requires_grad=False)
+        r._csr, r._gi, r._coo = None, gi, None
+        r._head, r._fused_args, r._state = head, fused_args, "pending"
+        return r
+
+    @property
+    def pending(self) -> bool:
+        return self._state == "pending"
+
+    def resolve(self) -> None:
+        """Run the head's forward launch (today's autograd node); idempotent."""
+        if self._state == "pending":
+            self._state = "resolved"
+            head, self._head, self._fused_args = self._head, None, None
+            self._csr = head()
+        elif self._state == "fused":
+            raise RuntimeError("the edge weights of a deferred head were read between the loss and its backward: "
+                               "they exist once TrackingModule.backward_step has run the backward")
+
+    def take_fused(self, w_buf: Tensor):
+        """The deferral is taken: ``w_buf`` (fp32 ``[n_edges]``) is what the backward launch fills."""
+        assert self._state == "pending"
+        args, self._head, self._fused_args = self._fused_args, None, None
+        self._csr_later, self._state = w_buf, "fused"
+        return args
+
+    def filled(self) -> None:
+        """(called by the backward) the buffer holds the weights."""
+        if self._state == "fused":
+            self._csr, self._csr_later, self._state = self._csr_later, None, "resolved"
+
+    @property
+    def csr(self) -> Tensor:
+        self.resolve()
+        return self._csr
+
+    def in_edge_index_order(self) -> Tensor:
+        self.resolve()
+        return super().in_edge_index_order()
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        name = _fname(func)
+        if name == "requires_grad" and getattr(func, "__name__", "") == "__get__" and args[0]._state != "resolved":
+            return True
+        return super().__torch_function__(func, types, args, kwargs)
+
+
 class NodeOrdered(EdgeOrdered):
     """The per-node twin (round 5): a node tensor held in the RENUMBERED node order of a graph index built with
     ``order_by`` (locality.py) that presents itself in the caller's node order - ``node_embedding`` of the edge

@@ -870,6 +870,83 @@ def fused_mlp(segs: Sequence[Seg], weights: Sequence[Tensor],
     return _FusedMLP.apply(spec, *[s.t for s in segs], *weights, *biases, res)
 
 
+# ---- the edge-weight head deferred into its backward launch (TrackingModule.backward_step) ----
+#: on: inside ``TrackingModule.backward_step`` the edge classifier's head and ``EdgeWeightBCELoss`` become one autograd
+#: node whose backward launch forms the weights and the loss's gradient itself (include/gnntrk.h:
+#: gnntrk_mlp_backward_bf16_bce) - the head's forward launch, the unit gradient's round trip and its scaling pass
+#: are gone from the step.  ``GNNTRK_FUSED_HEAD_LOSS=0``: off (A/B, bisecting).
+_FUSED_HEAD_LOSS = os.environ.get("GNNTRK_FUSED_HEAD_LOSS", "1") != "0"
+_HEAD_DEFERRAL = None
+
+
+class _HeadDeferral:
+    """State of one ``backward_step``: ``scale`` is the loss's upstream scalar, ``loss`` the tensor of the fused
+    node once ``bce_loss`` has built it (``backward_step`` then calls its ``backward()`` unscaled)."""
+
+    def __init__(self, scale: float):
+        self.scale, self.loss = float(scale), None
+
+
+@contextlib.contextmanager
+def head_loss_deferral(scale: float = 1.0, enabled: bool = True):
+    """Around forward + loss of ``TrackingModule.backward_step``: the edge classifier may hand out its weights
+    unevaluated (``edge_order.PendingEdgeWeights``).  Only for a caller that runs ``loss.backward()`` straight away
+    and lets nobody see the loss value before: it exists after the backward."""
+    global _HEAD_DEFERRAL
+    old = _HEAD_DEFERRAL
+    _HEAD_DEFERRAL = _HeadDeferral(scale) if (enabled and _FUSED_HEAD_LOSS) else None
+    try:
+        yield _HEAD_DEFERRAL
+    finally:
+        _HEAD_DEFERRAL = old
+
+
+def head_deferral_active() -> bool:
+    return _HEAD_DEFERRAL is not None and _HEAD_DEFERRAL.loss is None and torch.is_grad_enabled()
+
+
+def deferred_head(segs: Sequence[Seg], weights: Sequence[Tensor], biases, gi: "GraphIndex", y, *, n_rows: int,
+                  ca: float, cb: float, head):
+    """``PendingEdgeWeights`` for the one-column sigmoid head over ``segs`` (bf16 storage, labels carried on ``gi``,
+    inside ``head_loss_deferral``), or None: the caller runs ``head()`` itself."""
+    from .edge_order import PendingEdgeWeights
+
+    if (not head_deferral_active() or n_rows < 2 or not isinstance(y, Tensor) or carried_label(gi, y) is None
+            or not 1 <= len(segs) <= _capi.MAX_SEGS or any(s.t.dim() != 2 or s.t.dtype != torch.bfloat16 for s in segs)
+            or int(weights[-1].shape[0]) != 1 or len(weights) != 3
+            or not _fused_supported(segs, weights, biases, True, _capi.EPI_SIGMOID)
+            or not any(t is not None and t.requires_grad for t in [s.t for s in segs] + list(weights) + list(biases))):
+        return None
+    spec = _MlpSpec(len(segs), len(weights), any(b is not None for b in biases),
+                    [s.idx for s in segs], [s.relu for s in segs], [s.reduce for s in segs],
+                    _capi.EPI_SIGMOID, float(ca), float(cb), None, int(n_rows), int(n_rows))
+    return PendingEdgeWeights(n_rows, segs[0].t.device, gi, head,
+                              (spec, [s.t for s in segs], list(weights), list(biases)))
+
+
+def _fused_head_loss(w, y: Tensor, edge_index: Optional[Tensor], pt_thld: float) -> Optional[Tensor]:
+    """The loss of a pending ``W`` as the output of ONE node over the head's inputs (``ops_bf16.HeadBCE16``), or
+    None (the caller goes on with the ordinary path, whose first read of the values resolves the deferral)."""
+    from .edge_order import PendingEdgeWeights
+
+    d = _HEAD_DEFERRAL
+    if (not isinstance(w, PendingEdgeWeights) or not w.pending or d is None or d.loss is not None
+            or pt_thld > 0.0 or not torch.is_grad_enabled() or not _edge_index_is_index_source(w.graph_index, edge_index)):
+        return None
+    gi = w.graph_index
+    lab = carried_label(gi, y)
+    if lab is None:
+        return None
+    from . import ops_bf16
+
+    w_buf = torch.empty(gi.n_edges, dtype=torch.float32, device=lab.device)
+    loss = torch.empty(1, dtype=torch.float32, device=lab.device)
+    spec, seg_t, weights, biases = w.take_fused(w_buf)
+    bce = ops_bf16.HeadBce(lab, w_buf, loss, d.scale, done=w.filled)
+    d.loss = ops_bf16.HeadBCE16.apply(spec, bce, *seg_t, *weights, *biases)
+    return d.loss
+
+
 # ------------------------------------------------ MLPs beyond the fused kernels' shapes
 #: four-feature input chunks the bf16 kernels take (wide inputs: with three hidden tiles only)
 _BF16_MAX_CHUNKS = 32
@@ -1471,13 +1548,19 @@ def _csr_fast_path(w, edge_index):
     if not isinstance(w, EdgeOrdered):
         return None
     gi = w.graph_index
+    if not _edge_index_is_index_source(gi, edge_index):
+        return None
+    return w.csr.reshape(-1), gi
+
+
+def _edge_index_is_index_source(gi, edge_index) -> bool:
     if edge_index is not None:
         if int(edge_index.shape[1]) != gi.n_edges:
-            return None
+            return False
         src = getattr(gi, "_built_from", None)
         if src is not None and not (src[0]() is edge_index and src[1] == edge_index._version):
-            return None
-    return w.csr.reshape(-1), gi
+            return False
+    return True
 
 
 def focal_loss(w: Tensor, y: Tensor, edge_index: Optional[Tensor] = None, pt: Optional[Tensor] = None,
@@ -1515,6 +1598,9 @@ def bce_loss(w: Tensor, y: Tensor, edge_index: Optional[Tensor] = None,
         return w.sum() * float("nan")  # the reference's mean over no edges
     if w.dtype != torch.float32:
         raise TypeError("bce_loss: w must be fp32")
+    fused = _fused_head_loss(w, y, edge_index, float(pt_thld))
+    if fused is not None:   # (inside backward_step: head, loss and their backward are one launch + the loss pass)
+        return fused
     fast = _csr_fast_path(w, edge_index)
     if fast is not None:  # the weights are still in CSR order: labels go there, W stays put
         w_csr, gi = fast

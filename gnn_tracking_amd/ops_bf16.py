@@ -122,14 +122,18 @@ def mlp_backward_raw(segs: Sequence[Tensor], idx: Sequence[Optional[Tensor]], re
                      weights: Sequence[Tensor], biases: Sequence[Optional[Tensor]], *, n_rows: int,
                      epilogue: int, ca: float, cb: float, gout: Sequence[tuple], need_seg: Sequence[bool],
                      want_dw: bool, mlp, gidx: Optional[Sequence[Optional[Tensor]]] = None, sinks=None,
-                     fold: Optional[tuple] = None):
+                     fold: Optional[tuple] = None, bce: Optional["HeadBce"] = None):
     """One launch of gnntrk_mlp_backward_bf16.  ``gout``: 1-2 tuples (rows, idx) - padded
     bf16 rows, or one fp32 ``[*, out]`` tensor for EPI_SIGMOID.  Returns (row-aligned
     per-segment gradient slices ``[n_rows, dim]`` bf16 or None, gW list, gb list).
     ``fold = (j, n_nodes, rowptr)``: segment ``j`` is gathered through sorted ids (the CSR targets; ``rowptr``: their
     int32 row pointers ``[n_nodes + 1]``) - where the launch takes it (``gnntrk_mlp_backward_bf16_can_fold``) its
     gradient comes back ALREADY SUMMED per node as ``[n_nodes, dim]`` rows in ``slices[j]`` and ``j`` is listed in
-    the returned ``slices.folded`` set."""
+    the returned ``slices.folded`` set.
+    ``bce`` (the edge-weight head under ``EdgeWeightBCELoss``, ``gout`` empty): the launch forms the head's output
+    and the loss's gradient itself (``gnntrk_mlp_backward_bf16_bce``) and fills ``bce.w`` / ``bce.loss``; a launch
+    that is not the buffer-addressed head shape runs the forward launch, the loss pass and the ordinary backward
+    instead - the same kernels in the same order as without the deferral."""
     from . import ops
     lib = _capi.load()
     a = _capi.MlpBwdArgs()
@@ -179,8 +183,21 @@ def mlp_backward_raw(segs: Sequence[Tensor], idx: Sequence[Optional[Tensor]], re
             a.gout[t] = _capi.GTerm(rows.data_ptr(), ops._p(term_idx), rows.stride(0), min(int(rows.shape[0]), 0x7fffffff))
 
     gout = list(gout)
-    set_terms(gout[:2])
     a.debug_flags = _DEBUG_FLAGS
+    hb = None
+    if bce is not None:
+        hb = _capi.HeadBce(bce.label.data_ptr(), bce.w.data_ptr(), float(bce.gscale), 0, int(n_rows))
+        fused = (epilogue == _capi.EPI_SIGMOID and not gout and not _DEBUG_FLAGS
+                 and int(lib.gnntrk_mlp_backward_bf16_bce_supported(C.byref(a), C.byref(hb))) == 1)
+        if not fused:
+            # today's three launches, here instead of in the forward: W, loss + unit gradient, its scaling
+            hb = None
+            w = mlp_forward_raw(segs, idx, relu, weights, biases, n_rows=n_rows, epilogue=epilogue, ca=ca, cb=cb,
+                                res=None, out_idx=None, out_rows=n_rows, mlp=mlp)
+            bce.w.copy_(w.view(-1))
+            gout = [(ops._as_rows(_bce_loss_pass(bce, want_gw=True) * bce.gscale), None)]
+    if hb is None:
+        set_terms(gout[:2])
     # more terms than this launch's kernel takes (three only on the buffer-addressed shapes): the
     # surplus rows-of-the-tile terms are summed first, as autograd would have done
     limit = 2 if epilogue == _capi.EPI_SIGMOID else (int(lib.gnntrk_mlp_backward_bf16_max_terms(C.byref(a))) if len(gout) > 2 else 2)
@@ -197,8 +214,9 @@ def mlp_backward_raw(segs: Sequence[Tensor], idx: Sequence[Optional[Tensor]], re
         else:
             del gout[-1]
         gout[j] = (rows16(r1 + r2), None)
-    set_terms(gout)
-    try_fold()
+    if hb is None:
+        set_terms(gout)
+        try_fold()
     gW = [None] * len(weights)
     gb = [None] * len(weights)
     if want_dw:
@@ -220,16 +238,26 @@ def mlp_backward_raw(segs: Sequence[Tensor], idx: Sequence[Optional[Tensor]], re
     nbytes = M * (sum(2 * s.shape[1] + (4 if idx[j] is not None else 0)
                       + (2 * s.shape[1] if need_seg[j] else 0) for j, s in enumerate(segs))
                   + sum((4 if epilogue == _capi.EPI_SIGMOID else 2) * mlp.out_dim
-                        + (4 if gi is not None else 0) for _, gi in gout))
-    ref = gout[0][0]
+                        + (4 if gi is not None else 0) for _, gi in gout)
+                  + (5 if hb is not None else 0))   # (the label byte in, the weight out)
+    ref = gout[0][0] if hb is None else bce.w
     key = ""
     if ops._TIMER is not None:
         buf = C.create_string_buffer(160)
-        _capi.check(lib.gnntrk_mlp_backward_bf16_kernel_name(C.byref(a), buf, len(buf)), lib)
+        if hb is None:
+            _capi.check(lib.gnntrk_mlp_backward_bf16_kernel_name(C.byref(a), buf, len(buf)), lib)
+        else:
+            _capi.check(lib.gnntrk_mlp_backward_bf16_bce_kernel_name(C.byref(a), C.byref(hb), buf, len(buf)), lib)
         key = buf.value.decode()
     with ops._timed(ref, key, 3 * ops._mlp_flops_per_row(mlp) * M, nbytes, M):
-        _capi.check(lib.gnntrk_mlp_backward_bf16(C.byref(a), ops._p(ws), 0 if ws is None else ws.numel(),
-                                                 ops._stream(ref)), lib)
+        if hb is None:
+            _capi.check(lib.gnntrk_mlp_backward_bf16(C.byref(a), ops._p(ws), 0 if ws is None else ws.numel(),
+                                                     ops._stream(ref)), lib)
+        else:
+            _capi.check(lib.gnntrk_mlp_backward_bf16_bce(C.byref(a), C.byref(hb), ops._p(ws),
+                                                         0 if ws is None else ws.numel(), ops._stream(ref)), lib)
+    if hb is not None:
+        _bce_loss_pass(bce, want_gw=False)   # (the loss value from the W the launch wrote: the bits of the forward's)
     if fold_bufs is not None:
         j, out, rowptr, units, n_nodes = fold_bufs
         gate = segs[j] if relu[j] else None   # (relu' of the segment: once per node, by its own input row)
@@ -238,6 +266,30 @@ def mlp_backward_raw(segs: Sequence[Tensor], idx: Sequence[Optional[Tensor]], re
         slices[j] = out[:n_nodes]
         slices.folded.add(j)
     return slices, gW, gb
+
+
+class HeadBce:
+    """What the head's fused backward fills beside the gradients: ``w`` fp32 ``[n_rows]`` (the head's output, CSR
+    order), ``loss`` fp32 ``[1]``; ``label``: the carried 1-byte CSR labels, ``gscale``: the loss's upstream scalar
+    (a host constant: 1, or the weight of a micro-batch)."""
+
+    __slots__ = ("label", "w", "loss", "gscale", "done")
+
+    def __init__(self, label: Tensor, w: Tensor, loss: Tensor, gscale: float, done=None):
+        self.label, self.w, self.loss, self.gscale = label, w, loss, float(gscale)
+        self.done = done   # called once the backward has filled ``w`` and ``loss``
+
+
+def _bce_loss_pass(bce: "HeadBce", want_gw: bool) -> Optional[Tensor]:
+    """``gnntrk_bce_csr`` on ``bce.w``: fills ``bce.loss``; the unit gradient if wanted."""
+    from . import ops
+    lib = _capi.load()
+    n = bce.w.numel()
+    gw = torch.empty_like(bce.w) if want_gw else None
+    ws = ops._ws(lib.gnntrk_bce_workspace_bytes(n), bce.w)
+    _capi.check(lib.gnntrk_bce_csr(ops._p(bce.w), ops._p(bce.label), None, None, 0.0, n, ops._p(bce.loss), ops._p(gw),
+                                   ops._p(ws), ws.numel(), ops._stream(bce.w)), lib)
+    return gw
 
 
 class _Slices(list):
@@ -364,6 +416,41 @@ class FusedMLP16(torch.autograd.Function):
         return (None, *outs, g_res)
 
 
+class HeadBCE16(torch.autograd.Function):
+    """The edge-weight head AND ``EdgeWeightBCELoss`` as ONE autograd node whose forward launches nothing:
+    ``loss = f(segments, params)``.  The backward kernel recomputes the head's pre-activation anyway, so the
+    backward launch forms the weights and the loss's gradient itself (``gnntrk_mlp_backward_bf16_bce``) and fills
+    ``bce.w`` and ``bce.loss`` - both hold NOTHING until then, which is why only ``TrackingModule.backward_step``
+    (forward, loss and backward in one call, nothing in between) builds this node (``ops.head_loss_deferral``)."""
+
+    @staticmethod
+    def forward(ctx, spec, bce, *tensors):
+        from . import ops
+        ns, nl = spec.n_seg, spec.n_layers
+        segs = [rows16(t) for t in tensors[:ns]]
+        weights = [w.contiguous() for w in tensors[ns:ns + nl]]
+        biases = [None if b is None else b.contiguous() for b in tensors[ns + nl:ns + 2 * nl]]
+        _capi.require_device(*segs, *weights)
+        mlp = ops._fill_mlp(weights, biases)
+        if sum(s.shape[1] for s in segs) != mlp.in_dim:
+            raise AssertionError(
+                f"Expected feature dimension {mlp.in_dim}, got {sum(s.shape[1] for s in segs)}")
+        ctx.spec, ctx.bce = spec, bce
+        ctx.dup_of, ctx.res_same = _alias_tables(tensors[:ns])
+        ctx.save_for_backward(*segs, *weights, *[b for b in biases if b is not None])
+        ctx.bias_mask = [b is not None for b in biases]
+        return bce.loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        # (g is the 1 of a plain loss.backward(): the upstream scalar is bce.gscale, a host constant)
+        need = ctx.needs_input_grad   # [spec, bce, segs..., W..., b...]
+        outs, _ = _backward_common(ctx, [], (need[0],) + tuple(need[2:]) + (False,), None, bce=ctx.bce)
+        if ctx.bce.done is not None:
+            ctx.bce.done()
+        return (None, None, *outs)
+
+
 def _tensor_key(t: Tensor):
     return (t.data_ptr(), tuple(t.shape), t.stride(0))
 
@@ -386,7 +473,7 @@ def _alias_tables(seg_tensors, res=None):
     return dup_of, [j for j in range(len(ts)) if _same_autograd(res, ts[j])]
 
 
-def _backward_common(ctx, gout, need, g_rows, node_addend=None):
+def _backward_common(ctx, gout, need, g_rows, node_addend=None, bce=None):
     """Shared by FusedMLP16 and FusedINEdge16: one gnntrk_mlp_backward_bf16 launch for the
     upstream terms ``gout`` + the folds of the gathered input gradients.  ``need`` is laid
     out as [spec, segs..., W..., b..., res].  Returns (grads of segs/W/b, grad of res)."""
@@ -420,7 +507,8 @@ def _backward_common(ctx, gout, need, g_rows, node_addend=None):
                  and spec.idx[j] is spec.reduce[j][1].tgt), None)
     slices, gW, gb = mlp_backward_raw(segs, spec.idx, spec.relu, weights, biases, n_rows=M,
                                       epilogue=spec.epilogue, ca=spec.ca, cb=spec.cb, gout=gout,
-                                      need_seg=need_seg, want_dw=want_dw, mlp=mlp, gidx=gidx, sinks=sinks, fold=fold)
+                                      need_seg=need_seg, want_dw=want_dw, mlp=mlp, gidx=gidx, sinks=sinks,
+                                      fold=None if bce is not None else fold, bce=bce)
     seg_grads = [None] * ns
     folded: dict = {}   # (tensor identity) -> index of the segment whose fold holds its gradient so far
     # (segments the kernel folded itself come first: a later fold of the same tensor then takes the result as its

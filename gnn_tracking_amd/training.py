@@ -120,12 +120,23 @@ class TrackingModule:
     def backward_step(self, data, *, scale: float = 1.0) -> Tensor:
         """forward + loss + backward of one (micro-)batch; gradients ACCUMULATE."""
         with bf16_storage(self.bf16):
-            loss = self._loss(data)
+            # forward, loss and backward in one call and nobody in between: the edge classifier's head and its BCE
+            # loss may run inside the head's backward launch (ops.head_loss_deferral) - the loss VALUE then exists
+            # after the backward, and `scale` travels to the launch as a host constant
+            with ops.head_loss_deferral(scale, enabled=self._may_defer_head_loss()) as deferral:
+                loss = self._loss(data)
+            fused = deferral is not None and deferral.loss is not None
+            if fused and deferral.loss is not loss:
+                raise RuntimeError("backward_step: the deferred head loss was wrapped before the backward")
             # (a plain backward of this module's own loss: parameters re-homed by dist.FlatParameters may
             #  take their gradients in place from the backward launches, see ops.grad_sinks_armed)
             with ops.grad_sinks_armed():
-                (loss if scale == 1.0 else loss * scale).backward()
+                (loss if scale == 1.0 or fused else loss * scale).backward()
         return loss.detach()
+
+    def _may_defer_head_loss(self) -> bool:
+        """Nothing of this module looks at the loss value or at ``W`` between ``training_step`` and the backward."""
+        return False
 
     def optimisation_step(self, data) -> Tensor:
         """What one ``Trainer`` iteration does to the parameters (automatic optimisation):
@@ -156,6 +167,14 @@ class ECModule(TrackingModule):
         batch = self.data_preproc(batch)
         out = self(batch, _preprocessed=True)
         return self.get_losses(out, batch)
+
+    def _may_defer_head_loss(self) -> bool:
+        from .losses_ec import EdgeWeightBCELoss
+
+        # (this class's own training_step / get_losses hand the loss of exactly that loss class straight back)
+        cls = type(self)
+        return (cls.training_step is ECModule.training_step and cls.get_losses is ECModule.get_losses
+                and cls.forward is TrackingModule.forward and type(self.loss_fct) is EdgeWeightBCELoss)
 
     def validation_step(self, batch, batch_idx: int = 0) -> dict[str, float]:
         """``training/ec.py:55-84``: the loss (``total``) and, for the pt cuts 0, 0.5, 0.9 and 1.5, the ROC

@@ -356,7 +356,37 @@ size_t gnntrk_mlp_backward_bf16_workspace_bytes(const gnntrk_mlp *mlp);
 int gnntrk_mlp_backward_bf16(const gnntrk_mlp_bwd_args *args, void *workspace,
                              size_t workspace_bytes, void *stream);
 
-/* Helpers of the bf16-storage path.  All bf16 row tensors follow the padding rules of
+/* The edge-weight head's backward WITH the head's forward and the gradient of EdgeWeightBCELoss folded into it
+ * (models/edge_classifier.py:108-116, metrics/losses/ec.py:95-121): the launch recomputes the head's
+ * pre-activation y of every row anyway, so it forms the weight and its own upstream gradient from the 1-byte
+ * CSR label instead of reading an fp32 gradient that three earlier launches produced:
+ *   sg = sigmoid(y);  W = ca + cb * sg                      (w_out[k], the bits gnntrk_mlp_forward_bf16 stores)
+ *   t  = label[k] != 0
+ *   gw = ((1 / n_total) * (W - t)) / max((1 - W) * W, 1e-12)  (gnntrk_bce_csr's gw_unit, same operation order)
+ *   gw = gw * gscale                                         (the loss's upstream scalar, one fp32 product)
+ *   gy = ((gw * cb) * sg) * (1 - sg), rounded to bf16        (as gnntrk_mlp_backward_bf16 with EPI_SIGMOID)
+ * Every operation is a separate fp32 rounding in this order (no contraction): with the same inputs the launch
+ * writes the gradients gnntrk_mlp_forward_bf16 + gnntrk_bce_csr + (gw_unit * gscale) + gnntrk_mlp_backward_bf16
+ * write, bit for bit.  The loss VALUE is not formed here: run gnntrk_bce_csr on w_out with gw_unit = NULL.
+ * args: as for gnntrk_mlp_backward_bf16 with epilogue = GNNTRK_EPI_SIGMOID and out_dim = 1; n_gout / gout are
+ * ignored (the launch has no upstream tensor).  Only the buffer-addressed shape of the head takes it (h[src] |
+ * h[tgt] | four 8-byte edge tensors, every tensor's size stated, n_rows rows each below 2^31 bytes; label
+ * 4-byte aligned, w_out != NULL): gnntrk_mlp_backward_bf16_bce_supported says 1 for such a launch, anything else
+ * is GNNTRK_EUNSUPPORTED. */
+typedef struct gnntrk_head_bce {
+    const uint8_t *label; /* uint8[n_rows], CSR order (gnntrk_graph_index_carry.label_csr) */
+    float *w_out;         /* float[n_rows], written: the head's output */
+    float gscale;         /* upstream scalar of the loss (1, or the weight of a micro-batch) */
+    int32_t _pad;
+    int64_t n_total;      /* the n of the mean (= n_rows) */
+} gnntrk_head_bce;
+int gnntrk_mlp_backward_bf16_bce_supported(const gnntrk_mlp_bwd_args *args, const gnntrk_head_bce *bce);
+int gnntrk_mlp_backward_bf16_bce(const gnntrk_mlp_bwd_args *args, const gnntrk_head_bce *bce, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+int gnntrk_mlp_backward_bf16_bce_kernel_name(const gnntrk_mlp_bwd_args *args, const gnntrk_head_bce *bce, char *buf,
+                                             size_t len);
+
+/* Helpers of the bf16-storage path. All bf16 row tensors follow the padding rules of
  * gnntrk_mlp_forward_bf16 (uint16_t storage, stride in elements, multiple of 4).
  *  rows_to_bf16:      out[m] = bf16(in[idx ? idx[m] : m]) (RNE), padding written as 0: how the
  *                     dataset's fp32 x / edge_attr (graph_builder.py:440-455) enter the stack,

@@ -1,0 +1,189 @@
+"""Cases of the edge-weight head folded into its backward launch (``TrackingModule.backward_step``:
+``ops.head_loss_deferral``, ``gnntrk_mlp_backward_bf16_bce``), shared by the emulator and the GPU tests.  Every
+comparison is BIT FOR BIT (``torch.equal``) against the same step with the deferral switched off
+(``GNNTRK_FUSED_HEAD_LOSS=0``: the head's forward launch, ``gnntrk_bce_csr`` with the unit gradient, its scaling and
+the fp32-upstream backward) - the fused launch restates their arithmetic in their order (include/gnntrk.h)."""
+
+import contextlib
+
+import torch
+
+import gnn_tracking_amd as G
+from gnn_tracking_amd import _capi, ops, ops_bf16, synthetic
+from gnn_tracking_amd.training import ECModule
+
+import parity_cases as P
+
+
+@contextlib.contextmanager
+def deferral(on: bool):
+    old = ops._FUSED_HEAD_LOSS
+    ops._FUSED_HEAD_LOSS = bool(on)
+    try:
+        yield
+    finally:
+        ops._FUSED_HEAD_LOSS = old
+
+
+class LaunchCount:
+    """Counts the head's forward launches (EPI_SIGMOID) and the fused backward launches of a block."""
+
+    def __enter__(self):
+        self.head_fwd = self.fused_bwd = 0
+        self._fwd, self._bwd = ops_bf16.mlp_forward_raw, ops_bf16.mlp_backward_raw
+
+        def fwd(*a, **kw):
+            self.head_fwd += kw.get("epilogue") == _capi.EPI_SIGMOID
+            return self._fwd(*a, **kw)
+
+        def bwd(*a, **kw):
+            before = self.head_fwd
+            r = self._bwd(*a, **kw)
+            # (a fused launch ran if a BCE block came in and the head's forward was not launched for it)
+            self.fused_bwd += kw.get("bce") is not None and self.head_fwd == before
+            return r
+
+        ops_bf16.mlp_forward_raw, ops_bf16.mlp_backward_raw = fwd, bwd
+        return self
+
+    def __exit__(self, *exc):
+        ops_bf16.mlp_forward_raw, ops_bf16.mlp_backward_raw = self._fwd, self._bwd
+
+
+def testgraph_data(device):
+    """The reference's test graph (golden g1) with its labels as the dataset's bool."""
+    z = P.load("g1_ec_testgraph.npz")
+    tt = P.tt
+    return G.Data(x=tt(z["x"], device), edge_index=tt(z["edge_index"], device), edge_attr=tt(z["edge_attr"], device),
+                  y=tt(z["y"], device).bool(), pt=tt(z["pt"], device))
+
+
+def random_data(device, seed=5, n_hits=700, n_edges=4999, isolated=37):
+    """A random event whose edge count leaves a tail unit (4999 = 156 * 32 + 7: the last label dword is cut) and
+    whose last ``isolated`` hits have no edge."""
+    ev = synthetic.make_event(seed, n_hits, n_edges + n_edges % 2, "cpu")   # (the generator makes edge pairs)
+    ev.edge_index, ev.edge_attr, ev.y = (ev.edge_index[:, :n_edges].contiguous(), ev.edge_attr[:n_edges].contiguous(),
+                                         ev.y[:n_edges].contiguous())
+    if isolated:
+        g = torch.Generator().manual_seed(seed)
+        ev = G.Data(x=torch.cat([ev.x, torch.randn(isolated, ev.x.shape[1], generator=g)]), edge_index=ev.edge_index,
+                    edge_attr=ev.edge_attr, y=ev.y, pt=torch.cat([ev.pt, torch.rand(isolated, generator=g) + 0.1]))
+    d = G.Data(x=ev.x.to(device), edge_index=ev.edge_index.to(device), edge_attr=ev.edge_attr.to(device),
+               y=ev.y.to(device).bool(), pt=ev.pt.to(device))
+    assert d.edge_index.shape[1] == n_edges and n_edges % 32 != 0 and n_edges % 4 != 0
+    return d
+
+
+def make_module(device, data, *, loss_fct=None, seed=0, **model_kw):
+    torch.manual_seed(seed)
+    kw = dict(node_indim=data.x.shape[1], edge_indim=data.edge_attr.shape[1], L_ec=3, hidden_dim=40)
+    kw.update(model_kw)
+    model = G.ECForGraphTCN(**kw).to(device)
+    return ECModule(model, loss_fct=loss_fct or G.EdgeWeightBCELoss(), bf16=True)
+
+
+def run_steps(device, data_list, *, on: bool, scale=1.0, step="backward_step", hook=None, eval_mode=False,
+              module_kw=None):
+    """One ``zero_grad`` + ``backward_step`` per entry of ``data_list`` (gradients accumulate) with the deferral
+    ``on`` / off; returns (losses, W csr, node / edge embeddings of the last step, gradients, launch counts)."""
+    mod = make_module(device, data_list[0], **(module_kw or {}))
+    if eval_mode:
+        mod.model.eval()
+    got = {}
+    handle = None
+    if hook is not None:
+        handle = mod.model.register_forward_hook(lambda m, i, out: hook(out))
+    keep = {}
+    capture = mod.model.register_forward_hook(lambda m, i, out: keep.update(out=out))
+    losses = []
+    with deferral(on), LaunchCount() as n:
+        mod.zero_grad()
+        for d in data_list:
+            ops.clear_graph_index_cache()
+            if step == "backward_step":
+                losses.append(mod.backward_step(d, scale=scale).clone())
+            else:   # the Lightning shape: training_step, then somebody else's backward
+                with G.bf16_storage():
+                    loss = mod.training_step(d)
+                    (loss * scale if scale != 1.0 else loss).backward()
+                losses.append(loss.detach().clone())
+    capture.remove()
+    if handle is not None:
+        handle.remove()
+    out = keep["out"]
+    got["loss"] = torch.stack([l.reshape(()) for l in losses])
+    got["W"] = out["W"].csr.detach().clone()
+    got["W_coo"] = torch.as_tensor(out["W"]).detach().clone()
+    got["node"] = torch.as_tensor(out["node_embedding"]).detach().float().clone()
+    got["edge"] = torch.as_tensor(out["edge_embedding"]).detach().float().clone()
+    # (a parameter nothing downstream reads - the last object model of a head without node embeddings - has none)
+    got["grads"] = {k: v.grad.detach().clone() for k, v in mod.model.named_parameters() if v.grad is not None}
+    got["head_fwd"], got["fused_bwd"] = n.head_fwd, n.fused_bwd
+    return got
+
+
+def assert_same(a, b, tag):
+    for k in ("loss", "W", "W_coo", "node", "edge"):
+        assert torch.equal(a[k], b[k]), f"{tag}: {k} differs (max |d| {(a[k].double() - b[k].double()).abs().max().item():.3e})"
+    assert a["grads"].keys() == b["grads"].keys()
+    for k in a["grads"]:
+        assert torch.equal(a["grads"][k], b["grads"][k]), \
+            f"{tag}: grad {k} differs (max |d| {(a['grads'][k] - b['grads'][k]).abs().max().item():.3e})"
+    assert torch.isfinite(a["loss"]).all() and all(torch.isfinite(g).all() for g in a["grads"].values()), tag
+
+
+def case_fused_w_equals_forward_w(device, data):
+    """The premise: the W the fused backward launch writes is the W the forward launch writes, bit for bit."""
+    on = run_steps(device, [data], on=True)
+    off = run_steps(device, [data], on=False)
+    assert on["fused_bwd"] == 1 and on["head_fwd"] == 0, "the fused launch did not run"
+    assert off["fused_bwd"] == 0 and off["head_fwd"] == 1
+    diff = on["W"] != off["W"]
+    assert not diff.any(), (f"{int(diff.sum())} of {diff.numel()} weights differ, first at CSR row "
+                            f"{int(diff.nonzero()[0])}: {on['W'][diff][0].item()!r} vs {off['W'][diff][0].item()!r}")
+
+
+def case_on_off(device, data_list, *, scale=1.0, tag="", expect_fused=True, module_kw=None):
+    on = run_steps(device, data_list, on=True, scale=scale, module_kw=module_kw)
+    off = run_steps(device, data_list, on=False, scale=scale, module_kw=module_kw)
+    if expect_fused:
+        assert on["fused_bwd"] == len(data_list) and on["head_fwd"] == 0, f"{tag}: the fused launch did not run"
+    assert off["fused_bwd"] == 0 and off["head_fwd"] == len(data_list)
+    assert_same(on, off, tag)
+    return on
+
+
+def case_fallbacks(device, data):
+    """Whatever reads W's values, another loss, the pt cut, eval mode and an external backward run today's
+    launches and give today's bits."""
+    def read_w(out):
+        read_w.sum = float(torch.as_tensor(out["W"]).sum())   # (a user hook that looks at the values)
+
+    variants = {
+        "forward hook reads W": dict(hook=read_w),
+        "focal loss": dict(module_kw=dict(loss_fct=G.EdgeWeightFocalLoss())),
+        "pt_thld 0.9": dict(module_kw=dict(loss_fct=G.EdgeWeightBCELoss(pt_thld=0.9))),
+        "eval mode": dict(eval_mode=True),
+        "training_step + external backward": dict(step="training_step"),
+        "training_step + external backward, scaled": dict(step="training_step", scale=0.25),
+    }
+    for tag, kw in variants.items():
+        on = run_steps(device, [data], on=True, **kw)
+        off = run_steps(device, [data], on=False, **kw)
+        assert on["fused_bwd"] == 0 and on["head_fwd"] == 1, f"{tag}: expected today's launches"
+        assert_same(on, off, tag)
+
+
+def case_metadata_does_not_resolve(device, data):
+    """shape / dtype / device / len() of a pending W launch nothing; the values exist after the step."""
+    seen = {}
+
+    def meta(out):
+        w = out["W"]
+        seen["meta"] = (tuple(w.shape), w.dtype, w.device.type, len(w), w.dim())
+        seen["pending"] = getattr(w, "pending", False)
+
+    on = run_steps(device, [data], on=True, hook=meta)
+    E = data.edge_index.shape[1]
+    assert seen["meta"] == ((E,), torch.float32, torch.device(device).type, E, 1) and seen["pending"]
+    assert on["fused_bwd"] == 1 and on["head_fwd"] == 0
