@@ -1,11 +1,12 @@
 // Device-side helpers shared by the integer-counting units (metrics.hip, tracking_metrics.hip,
 // kscan.hip): atomics, the open-addressing table keyed by "first hit + 1", the block reduction (wave
-// sum -> LDS -> one global atomic per workgroup and value) and the pt cuts passed to kernels by value.
+// sum of wave_util.h -> LDS -> one global atomic per workgroup and value) and the pt cuts passed to kernels by value.
 #pragma once
 
 #include <stdio.h>
 
 #include "host_util.h"
+#include "wave_util.h"
 
 namespace gnntrk {
 
@@ -102,12 +103,6 @@ __device__ __forceinline__ uint64_t table_find(const int32_t *tab, uint64_t mask
 }
 
 // ------------------------------------------------------------------------ block reduction
-// wave sum of an integer (every lane of the wave calls it)
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
 // block-wide: adds the per-thread counts v[0..NV) into dst[0..NV) with one global atomic per value
 template <int NV>
 __device__ __forceinline__ void block_add(const uint32_t (&v)[NV], unsigned long long *dst) {

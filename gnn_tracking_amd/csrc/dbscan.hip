@@ -14,6 +14,7 @@
 // with pointer jumping (monotone, so races are benign and the fixpoint is unique) -> root
 // compaction -> labels.
 #include "host_util.h"
+#include "wave_util.h"
 
 namespace gnntrk {
 
@@ -207,9 +208,7 @@ __global__ __launch_bounds__(kRTpb) void radius_order_kernel(const int64_t *__re
     const bool in_lds = len <= kCap;
     if (in_lds) {
         for (int64_t i = lane; i < len; i += 64) s_v[wv][i] = nbr_in[o + i];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        wave_sync();
     }
     for (int64_t i = lane; i < len; i += 64) {
         const int v = nbr_in[o + i];
@@ -302,8 +301,6 @@ __global__ __launch_bounds__(256) void dbscan_labels_kernel(const int64_t *__res
     }
 }
 
-static int node_blocks(int64_t n) { return blocks_for(n, 16); }
-
 static int check_points(const float *x, int64_t n, int dim, int stride, double radius, const char *who) {
     if (n < 0 || n > 0x7fffffff) return fail(GNNTRK_EUNSUPPORTED, "radius graph: n must fit int32");
     if (dim < 1 || dim > 32) return fail(GNNTRK_EUNSUPPORTED, "radius graph: 1 <= dim <= 32");
@@ -313,15 +310,15 @@ static int check_points(const float *x, int64_t n, int dim, int stride, double r
     return GNNTRK_OK;
 }
 
-#define GNNTRK_RADIUS_CALL(D_, FILL_)                                                                     \
-    hipLaunchKernelGGL((radius_kernel<D_, FILL_>), dim3((unsigned)ceil_div(n, kRTpb)), dim3(kRTpb), 0, \
-                       stream, x, n, dim, stride, r2, cnt, off, nbr, dist)
-#define GNNTRK_RADIUS_DISPATCH(FILL_)        \
-    if (dim <= 2) GNNTRK_RADIUS_CALL(2, FILL_);       \
-    else if (dim <= 4) GNNTRK_RADIUS_CALL(4, FILL_);  \
-    else if (dim <= 8) GNNTRK_RADIUS_CALL(8, FILL_);  \
-    else if (dim <= 16) GNNTRK_RADIUS_CALL(16, FILL_); \
-    else GNNTRK_RADIUS_CALL(32, FILL_)
+// the N^2 kernel of either pass
+template <bool FILL>
+static void radius_launch(const float *x, int64_t n, int dim, int stride, double r2, int32_t *cnt, const int64_t *off,
+                          int32_t *nbr, double *dist, hipStream_t stream) {
+    dispatch_dp<2, 4, 8, 16, 32>(dim, [&](auto D) {
+        hipLaunchKernelGGL((radius_kernel<decltype(D)::value, FILL>), dim3((unsigned)ceil_div(n, kRTpb)), dim3(kRTpb), 0,
+                           stream, x, n, dim, stride, r2, cnt, off, nbr, dist);
+    });
+}
 
 int radius_count_launch(const float *x, int64_t n, int dim, int stride, double radius, int32_t *cnt,
                         int64_t *offsets, hipStream_t stream) {
@@ -330,11 +327,7 @@ int radius_count_launch(const float *x, int64_t n, int dim, int stride, double r
     if (!offsets) return fail(GNNTRK_EINVAL, "radius_count: NULL offsets");
     if (n == 0) return check_hip(hipMemsetAsync(offsets, 0, sizeof(int64_t), stream), "radius_count");
     if (!cnt) return fail(GNNTRK_EINVAL, "radius_count: NULL counts");
-    const double r2 = radius * radius;
-    const int64_t *off = nullptr;
-    int32_t *nbr = nullptr;
-    double *dist = nullptr;
-    GNNTRK_RADIUS_DISPATCH(false);
+    radius_launch<false>(x, n, dim, stride, radius * radius, cnt, nullptr, nullptr, nullptr, stream);
     scan_counts_launch(cnt, 0x7fffffff, n, offsets, stream);
     return check_launch("radius_count");
 }
@@ -344,35 +337,25 @@ int radius_fill_launch(const float *x, int64_t n, int dim, int stride, double ra
     int rc = check_points(x, n, dim, stride, radius, "radius_fill");
     if (rc || n == 0) return rc;
     if (!off || !nbr || !dist) return fail(GNNTRK_EINVAL, "radius_fill: NULL argument");
-    const double r2 = radius * radius;
-    int32_t *cnt = nullptr;
-    GNNTRK_RADIUS_DISPATCH(true);
+    radius_launch<true>(x, n, dim, stride, radius * radius, nullptr, off, nbr, dist, stream);
     return check_launch("radius_fill");
 }
 
 // ---- pruned graph: workspace and launchers ---------------------------------------------------
-// ws_points: [xs | sidx | box | build scratch] - filled by the count pass, read by the fill pass;
+// ws_points: the sorted chunks (host_util.h: chunks_ws) - filled by the count pass, read by the fill pass;
 // ws_edges (fill pass): staging of the unordered lists, m_edges * 12 bytes
-struct RadiusWs {
-    size_t xs, sidx, box, scratch, total;
-    int n_chunks, dp;
+struct RadiusEdgesWs {
+    int32_t *t_nbr;
+    double *t_dist;
+    size_t total;
 };
-static RadiusWs radius_ws_layout(int64_t n, int dim) {
-    RadiusWs w{};
-    w.dp = spatial_dp(dim);
-    w.n_chunks = spatial_n_chunks(n);
-    const size_t rows = (size_t)w.n_chunks * 64;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += align_up(bytes, 256);
-        return at;
-    };
-    w.xs = take(rows * w.dp * 4);
-    w.sidx = take(rows * 4);
-    w.box = take((size_t)w.n_chunks * 2 * w.dp * 4);
-    w.scratch = take(spatial_scratch_bytes(n));
-    w.total = o;
+static RadiusEdgesWs radius_edges_ws(void *base, int64_t m_edges) {
+    const size_t m = (size_t)(m_edges > 0 ? m_edges : 1);
+    RadiusEdgesWs w{};
+    Carver ws{(char *)base};
+    w.t_nbr = ws.take<int32_t>(m);
+    w.t_dist = ws.take<double>(m);
+    w.total = ws.off;
     return w;
 }
 constexpr int64_t kRadiusPrunedMinRows = 4096;
@@ -380,10 +363,22 @@ constexpr int64_t kRadiusPrunedMaxDegree = 256;  // denser graphs: nothing to pr
 
 size_t radius_points_ws_bytes(int64_t n, int dim) {
     if (n < 1 || n > 0x7fffffff || dim < 1 || dim > 16) return 0;
-    return radius_ws_layout(n, dim).total;
+    size_t total;
+    chunks_ws(nullptr, n, dim, &total);
+    return total;
 }
-size_t radius_edges_ws_bytes(int64_t m_edges) {
-    return align_up((size_t)(m_edges > 0 ? m_edges : 1) * 4, 256) + align_up((size_t)(m_edges > 0 ? m_edges : 1) * 8, 256);
+size_t radius_edges_ws_bytes(int64_t m_edges) { return radius_edges_ws(nullptr, m_edges).total; }
+
+// the pruned kernel of either pass over the chunks c
+template <bool FILL>
+static void radius_pruned_launch(const SpatialChunks &c, int64_t n, int dim, double r2, int32_t *cnt, const int64_t *off,
+                                 int32_t *nbr, double *dist, hipStream_t stream) {
+    const unsigned grid = (unsigned)ceil_div(n, (int64_t)kRWaves * radius_queries_per_wave(c.dp));
+    dispatch_dp<4, 8, 16>(dim, [&](auto D) {
+        hipLaunchKernelGGL((radius_pruned_kernel<decltype(D)::value, FILL>), dim3(grid), dim3(kRTpb), 0, stream,
+                           (const float *)c.xs, (const int32_t *)c.sidx, (const float *)c.box, n, c.n_chunks, r2, cnt, off,
+                           nbr, dist);
+    });
 }
 
 int radius_count_ws_launch(const float *x, int64_t n, int dim, int stride, double radius, int32_t *cnt,
@@ -393,24 +388,12 @@ int radius_count_ws_launch(const float *x, int64_t n, int dim, int stride, doubl
     int rc = check_points(x, n, dim, stride, radius, "radius_count");
     if (rc) return rc;
     if (!offsets || !cnt) return fail(GNNTRK_EINVAL, "radius_count: NULL argument");
-    const RadiusWs w = radius_ws_layout(n, dim);
-    if (ws_bytes < w.total) return fail(GNNTRK_EINVAL, "radius_count: workspace too small");
-    char *b = static_cast<char *>(ws_points);
-    float *xs = reinterpret_cast<float *>(b + w.xs);
-    int32_t *sidx = reinterpret_cast<int32_t *>(b + w.sidx);
-    float *box = reinterpret_cast<float *>(b + w.box);
-    rc = spatial_chunks_build(x, n, dim, stride, nullptr, 0, xs, sidx, box, b + w.scratch, w.total - w.scratch, stream);
+    size_t need;
+    const SpatialChunks c = chunks_ws(ws_points, n, dim, &need);
+    if (ws_bytes < need) return fail(GNNTRK_EINVAL, "radius_count: workspace too small");
+    rc = spatial_chunks_build(x, n, dim, stride, nullptr, 0, c, stream);
     if (rc) return rc;
-    const double r2 = radius * radius;
-    const unsigned grid = (unsigned)ceil_div(n, (int64_t)kRWaves * radius_queries_per_wave(w.dp));
-#define GNNTRK_RP_COUNT(D_)                                                                                         \
-    hipLaunchKernelGGL((radius_pruned_kernel<D_, false>), dim3(grid), dim3(kRTpb), 0, stream, (const float *)xs,     \
-                       (const int32_t *)sidx, (const float *)box, n, w.n_chunks, r2, cnt, (const int64_t *)nullptr, \
-                       (int32_t *)nullptr, (double *)nullptr)
-    if (w.dp == 4) GNNTRK_RP_COUNT(4);
-    else if (w.dp == 8) GNNTRK_RP_COUNT(8);
-    else GNNTRK_RP_COUNT(16);
-#undef GNNTRK_RP_COUNT
+    radius_pruned_launch<false>(c, n, dim, radius * radius, cnt, nullptr, nullptr, nullptr, stream);
     scan_counts_launch(cnt, 0x7fffffff, n, offsets, stream);
     return check_launch("radius_count(pruned)");
 }
@@ -424,27 +407,13 @@ int radius_fill_ws_launch(const float *x, int64_t n, int dim, int stride, double
     int rc = check_points(x, n, dim, stride, radius, "radius_fill");
     if (rc) return rc;
     if (!off || !nbr || !dist || m_edges < 0) return fail(GNNTRK_EINVAL, "radius_fill: bad argument");
-    const RadiusWs w = radius_ws_layout(n, dim);
-    if (ws_bytes < w.total || ws_edges_bytes < radius_edges_ws_bytes(m_edges))
-        return fail(GNNTRK_EINVAL, "radius_fill: workspace too small");
-    char *b = static_cast<char *>(ws_points);
-    const float *xs = reinterpret_cast<const float *>(b + w.xs);
-    const int32_t *sidx = reinterpret_cast<const int32_t *>(b + w.sidx);
-    const float *box = reinterpret_cast<const float *>(b + w.box);
-    int32_t *t_nbr = reinterpret_cast<int32_t *>(ws_edges);
-    double *t_dist = reinterpret_cast<double *>(static_cast<char *>(ws_edges) +
-                                                align_up((size_t)(m_edges > 0 ? m_edges : 1) * 4, 256));
-    const double r2 = radius * radius;
-    const unsigned grid = (unsigned)ceil_div(n, (int64_t)kRWaves * radius_queries_per_wave(w.dp));
-#define GNNTRK_RP_FILL(D_)                                                                                     \
-    hipLaunchKernelGGL((radius_pruned_kernel<D_, true>), dim3(grid), dim3(kRTpb), 0, stream, xs, sidx, box, n, \
-                       w.n_chunks, r2, (int32_t *)nullptr, off, t_nbr, t_dist)
-    if (w.dp == 4) GNNTRK_RP_FILL(4);
-    else if (w.dp == 8) GNNTRK_RP_FILL(8);
-    else GNNTRK_RP_FILL(16);
-#undef GNNTRK_RP_FILL
+    size_t need;
+    const SpatialChunks c = chunks_ws(ws_points, n, dim, &need);
+    const RadiusEdgesWs e = radius_edges_ws(ws_edges, m_edges);
+    if (ws_bytes < need || ws_edges_bytes < e.total) return fail(GNNTRK_EINVAL, "radius_fill: workspace too small");
+    radius_pruned_launch<true>(c, n, dim, radius * radius, nullptr, off, e.t_nbr, e.t_dist, stream);
     hipLaunchKernelGGL(radius_order_kernel, dim3((unsigned)ceil_div(n, kRWaves)), dim3(kRTpb), 0, stream, off, n,
-                       (const int32_t *)t_nbr, (const double *)t_dist, nbr, dist);
+                       (const int32_t *)e.t_nbr, (const double *)e.t_dist, nbr, dist);
     return check_launch("radius_fill(pruned)");
 }
 
@@ -453,7 +422,7 @@ int dbscan_init_launch(const int64_t *off, const double *dist, int64_t n, double
     if (n < 0 || n > 0x7fffffff) return fail(GNNTRK_EUNSUPPORTED, "dbscan: n must fit int32");
     if (n == 0) return GNNTRK_OK;
     if (!off || !core || !root) return fail(GNNTRK_EINVAL, "dbscan_init: NULL argument");
-    hipLaunchKernelGGL(dbscan_init_kernel, dim3(node_blocks(n)), dim3(256), 0, stream, off, dist, n, eps, min_pts,
+    hipLaunchKernelGGL(dbscan_init_kernel, dim3(blocks_for(n, 16)), dim3(256), 0, stream, off, dist, n, eps, min_pts,
                        core, root);
     return check_launch("dbscan_init");
 }
@@ -468,17 +437,30 @@ int dbscan_propagate_launch(const int64_t *off, const int32_t *nbr, const double
         // the flag reports the LAST round only: zero means the fixpoint has been reached
         int rc = check_hip(hipMemsetAsync(changed, 0, sizeof(int32_t), stream), "dbscan_propagate(memset)");
         if (rc) return rc;
-        hipLaunchKernelGGL(dbscan_propagate_kernel, dim3(node_blocks(n)), dim3(256), 0, stream, off, nbr, dist, n,
+        hipLaunchKernelGGL(dbscan_propagate_kernel, dim3(blocks_for(n, 16)), dim3(256), 0, stream, off, nbr, dist, n,
                            eps, core, root, changed);
     }
     return check_launch("dbscan_propagate");
 }
 
-size_t dbscan_ws_bytes(int64_t n) {
+struct LabelsWs {
+    uint8_t *is_root;
+    int32_t *root_list, *rank;
+    char *compact;   // compact_ws_bytes(n)
+    size_t total;
+};
+static LabelsWs labels_ws(void *base, int64_t n) {
     const size_t nn = (size_t)(n > 0 ? n : 1);
-    return align_up(nn, 256) /* is_root */ + align_up(nn * 4, 256) /* root list */ + align_up(nn * 4, 256) /* rank */ +
-           compact_ws_bytes(n);
+    LabelsWs w{};
+    Carver ws{(char *)base};
+    w.is_root = ws.take<uint8_t>(nn);
+    w.root_list = ws.take<int32_t>(nn);
+    w.rank = ws.take<int32_t>(nn);
+    w.compact = ws.take<char>(compact_ws_bytes(n));
+    w.total = ws.off;
+    return w;
 }
+size_t dbscan_ws_bytes(int64_t n) { return labels_ws(nullptr, n).total; }
 
 int dbscan_labels_launch(const int64_t *off, const int32_t *nbr, const double *dist, int64_t n, double eps,
                          const uint8_t *core, const int32_t *root, int64_t *labels, int64_t *n_clusters, void *ws,
@@ -486,19 +468,13 @@ int dbscan_labels_launch(const int64_t *off, const int32_t *nbr, const double *d
     if (!n_clusters) return fail(GNNTRK_EINVAL, "dbscan_labels: NULL count output");
     if (n == 0) return check_hip(hipMemsetAsync(n_clusters, 0, sizeof(int64_t), stream), "dbscan_labels");
     if (!off || !core || !root || !labels) return fail(GNNTRK_EINVAL, "dbscan_labels: NULL argument");
-    if (!ws || ws_bytes < dbscan_ws_bytes(n)) return fail(GNNTRK_EINVAL, "dbscan_labels: workspace too small");
-    char *p = reinterpret_cast<char *>(ws);
-    uint8_t *is_root = reinterpret_cast<uint8_t *>(p);
-    p += align_up((size_t)n, 256);
-    int32_t *root_list = reinterpret_cast<int32_t *>(p);
-    p += align_up((size_t)n * 4, 256);
-    int32_t *rank = reinterpret_cast<int32_t *>(p);
-    p += align_up((size_t)n * 4, 256);
-    hipLaunchKernelGGL(dbscan_roots_kernel, dim3(node_blocks(n)), dim3(256), 0, stream, core, root, n, is_root);
-    int rc = compact_bytes_launch(is_root, n, root_list, rank, n_clusters, p, compact_ws_bytes(n), stream);
+    const LabelsWs w = labels_ws(ws, n);
+    if (!ws || ws_bytes < w.total) return fail(GNNTRK_EINVAL, "dbscan_labels: workspace too small");
+    hipLaunchKernelGGL(dbscan_roots_kernel, dim3(blocks_for(n, 16)), dim3(256), 0, stream, core, root, n, w.is_root);
+    int rc = compact_bytes_launch(w.is_root, n, w.root_list, w.rank, n_clusters, w.compact, compact_ws_bytes(n), stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(dbscan_labels_kernel, dim3(node_blocks(n)), dim3(256), 0, stream, off, nbr, dist, n, eps,
-                       core, root, rank, labels);
+    hipLaunchKernelGGL(dbscan_labels_kernel, dim3(blocks_for(n, 16)), dim3(256), 0, stream, off, nbr, dist, n, eps,
+                       core, root, w.rank, labels);
     return check_launch("dbscan_labels");
 }
 

@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "gnntrk.h"
 
 namespace gnntrk {
@@ -39,6 +41,18 @@ struct Carver {
     }
 };
 
+// a runtime dim to a compile-time padded width: calls f(int_c<W>{}) for the first of the ascending Widths
+// with dim <= W (for the last one if there is none: the callers have refused such a dim)
+template <int V> using int_c = std::integral_constant<int, V>;
+template <int W, int... Rest, class F> void dispatch_dp(int dim, F &&f) {
+    if constexpr (sizeof...(Rest) == 0) {
+        f(int_c<W>{});
+    } else {
+        if (dim <= W) f(int_c<W>{});
+        else dispatch_dp<Rest...>(dim, f);
+    }
+}
+
 // guards of the entries that index hits in int32 tables: "<entry>: negative <what> count" (EINVAL),
 // "<entry>: <n> <what>s; at most 2^30-1" (EUNSUPPORTED)
 int check_count_i30(const char *entry, const char *what, int64_t n);
@@ -62,9 +76,40 @@ void scan_counts_launch(const int32_t *cnt, int k_take, int64_t n, int64_t *off,
 int spatial_dp(int dim);
 int spatial_n_chunks(int64_t n);
 size_t spatial_scratch_bytes(int64_t n);
+struct SpatialChunks {
+    float *xs;       // [n_chunks * 64][dp] the points in sorted order, the tail of the last chunk repeats the last point
+    int32_t *sidx;   // [n_chunks * 64] their original indices, -1 in the tail
+    float *box;      // [n_chunks][2 * dp] lo | hi of every chunk
+    void *scratch;   // of the build only
+    size_t scratch_bytes;
+    int n_chunks, dp;
+};
+// the three arrays for n points of dimension dim, then (at once, or after the regions a unit keeps in
+// between) the build's scratch
+inline SpatialChunks take_chunks(Carver &ws, int64_t n, int dim) {
+    SpatialChunks c{};
+    c.dp = spatial_dp(dim);
+    c.n_chunks = spatial_n_chunks(n);
+    const size_t rows = (size_t)c.n_chunks * 64;
+    c.xs = ws.take<float>(rows * c.dp);
+    c.sidx = ws.take<int32_t>(rows);
+    c.box = ws.take<float>((size_t)c.n_chunks * 2 * c.dp);
+    return c;
+}
+inline void take_chunks_scratch(Carver &ws, SpatialChunks &c, int64_t n) {
+    c.scratch_bytes = spatial_scratch_bytes(n);
+    c.scratch = ws.take<char>(c.scratch_bytes);
+}
+// the workspace that holds the chunks and nothing else (pruned k-NN search, radius graph): *total = its size
+inline SpatialChunks chunks_ws(void *base, int64_t n, int dim, size_t *total) {
+    Carver ws{(char *)base};
+    SpatialChunks c = take_chunks(ws, n, dim);
+    take_chunks_scratch(ws, c, n);
+    *total = ws.off;
+    return c;
+}
 int spatial_chunks_build(const float *x, int64_t n, int dim, int stride, const int64_t *seg_ptr, int n_seg,
-                         float *xs, int32_t *sidx, float *box, void *scratch, size_t scratch_bytes,
-                         hipStream_t stream);
+                         const SpatialChunks &c, hipStream_t stream);
 
 // mlp.hip
 int mlp_forward_launch(const gnntrk_mlp_fwd_args *a, hipStream_t stream);

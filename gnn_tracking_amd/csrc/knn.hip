@@ -15,6 +15,7 @@
 // in a clustered embedding almost every (query, chunk) step is 2*D VALU + compare + ballot.
 // Bound: fp32 VALU (N^2 * D fma), candidates stay L2 resident.
 #include "host_util.h"
+#include "wave_util.h"
 
 namespace gnntrk {
 
@@ -24,12 +25,6 @@ constexpr int kKnnWaves = 4;
 constexpr int kKnnLdsPerWave = 8 * 1024;  // key buffers of one wave (bytes): 20 waves per CU
 constexpr u64 kKeyMax = ~0ull;
 constexpr int kKnnGroup = 4;  // queries per step (loads of a group overlap)
-
-__device__ __forceinline__ void knn_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 // ascending bitonic sort of cap (power of two) 64-bit keys in LDS by one wave
 __device__ inline void wave_bitonic_sort(u64 *buf, int cap, int lane) {
@@ -45,7 +40,7 @@ __device__ inline void wave_bitonic_sort(u64 *buf, int cap, int lane) {
                     buf[j] = a;
                 }
             }
-            knn_wave_sync();
+            wave_sync();
         }
     }
 }
@@ -117,11 +112,11 @@ __global__ __launch_bounds__(kKnnBlock) void knn_kernel(const float *__restrict_
             qlo[lane] = (int)seg_ptr[sg];
             qhi[lane] = (int)seg_ptr[sg + 1];
         }
-        knn_wave_sync();
+        wave_sync();
         c_begin = qlo[0];
         c_end = qhi[nq - 1];
     }
-    knn_wave_sync();
+    wave_sync();
 
     // candidate rows: every lane loads unconditionally (row index clamped, `d < dim` is a
     // uniform condition) - a load inside a divergent branch forces s_waitcnt vmcnt(0) on each
@@ -206,18 +201,18 @@ __global__ __launch_bounds__(kKnnBlock) void knn_kernel(const float *__restrict_
                     const int base = cnt[q];
                     if (pass) keys[q * cap + base + __popcll(mask & ((1ull << lane) - 1ull))] = key;
                     int nc = base + __popcll(mask);
-                    knn_wave_sync();
+                    wave_sync();
                     if (nc > cap - 64) {  // no room for another full chunk: keep the k best
                         u64 *b = keys + q * cap;
                         for (int i = nc + lane; i < cap; i += 64) b[i] = kKeyMax;
-                        knn_wave_sync();
+                        wave_sync();
                         wave_bitonic_sort(b, cap, lane);
                         nc = k;
                         if (QW > 0) tau_hi[(qb + u) < kQ ? (qb + u) : kQ - 1] = (uint32_t)(b[k - 1] >> 32);
                         if (lane == 0) tau[q] = b[k - 1];
                     }
                     if (lane == 0) cnt[q] = nc;
-                    knn_wave_sync();
+                    wave_sync();
                 }
             }
         }
@@ -230,7 +225,7 @@ __global__ __launch_bounds__(kKnnBlock) void knn_kernel(const float *__restrict_
         u64 *b = keys + q * cap;
         const int nc = cnt[q];
         for (int i = nc + lane; i < cap; i += 64) b[i] = kKeyMax;
-        knn_wave_sync();
+        wave_sync();
         wave_bitonic_sort(b, cap, lane);
         const int m = nc < k ? nc : k;
         int out = 0;
@@ -248,7 +243,7 @@ __global__ __launch_bounds__(kKnnBlock) void knn_kernel(const float *__restrict_
             out += __popcll(__ballot(ok));
         }
         if (lane == 0) cnt_out[q0 + q] = out;
-        knn_wave_sync();
+        wave_sync();
     }
 }
 
@@ -430,7 +425,7 @@ __global__ __launch_bounds__(kKnnBlock) void knn_pruned_kernel(const float *__re
             qhi[lane] = (int)seg_ptr[sg + 1];
         }
     }
-    knn_wave_sync();
+    wave_sync();
     // chunks the wave has to look at: the events of its queries occupy the same positions in the
     // sorted order as in the original one (the event is the top of the sort key)
     int c_lo = 0, c_hi = n_chunks;
@@ -473,7 +468,7 @@ __global__ __launch_bounds__(kKnnBlock) void knn_pruned_kernel(const float *__re
             s_gbox[wv][DP + d] = hi;
         }
     }
-    knn_wave_sync();
+    wave_sync();
 
     auto load_chunk = [&](int c, float (&v)[DP], int &id) {
         const int64_t p = (int64_t)c * 64 + lane;
@@ -557,11 +552,11 @@ __global__ __launch_bounds__(kKnnBlock) void knn_pruned_kernel(const float *__re
                         if (pass) keys[u * cap + base + __popcll(mask & ((1ull << lane) - 1ull))] = key;
                         int nc = base + __popcll(mask);
                         dirty |= 1 << u;
-                        knn_wave_sync();
+                        wave_sync();
                         if (nc > cap - 64) {  // no room for another full chunk: keep the k best
                             u64 *bq = keys + u * cap;
                             for (int i = nc + lane; i < cap; i += 64) bq[i] = kKeyMax;
-                            knn_wave_sync();
+                            wave_sync();
                             wave_bitonic_sort(bq, cap, lane);
                             nc = k;
                             tau_hi[u] = (uint32_t)(bq[k - 1] >> 32);
@@ -569,7 +564,7 @@ __global__ __launch_bounds__(kKnnBlock) void knn_pruned_kernel(const float *__re
                             dirty &= ~(1 << u);
                         }
                         if (lane == 0) cnt[u] = nc;
-                        knn_wave_sync();
+                        wave_sync();
                     }
                 }
 #pragma unroll
@@ -592,14 +587,14 @@ __global__ __launch_bounds__(kKnnBlock) void knn_pruned_kernel(const float *__re
                 if (nc < k) continue;
                 u64 *bq = keys + u * cap;
                 for (int i = nc + lane; i < cap; i += 64) bq[i] = kKeyMax;
-                knn_wave_sync();
+                wave_sync();
                 wave_bitonic_sort(bq, cap, lane);
                 tau_hi[u] = (uint32_t)(bq[k - 1] >> 32);
                 if (lane == 0) {
                     tau[u] = bq[k - 1];
                     cnt[u] = k;
                 }
-                knn_wave_sync();
+                wave_sync();
             }
         }
     }
@@ -611,7 +606,7 @@ __global__ __launch_bounds__(kKnnBlock) void knn_pruned_kernel(const float *__re
         const int nc = cnt[q];
         const int64_t row = oq[q];
         for (int i = nc + lane; i < cap; i += 64) bq[i] = kKeyMax;
-        knn_wave_sync();
+        wave_sync();
         wave_bitonic_sort(bq, cap, lane);
         const int mm = nc < k ? nc : k;
         int out = 0;
@@ -629,7 +624,7 @@ __global__ __launch_bounds__(kKnnBlock) void knn_pruned_kernel(const float *__re
             out += __popcll(__ballot(ok));
         }
         if (lane == 0) cnt_out[row] = out;
-        knn_wave_sync();
+        wave_sync();
     }
 }
 
@@ -747,13 +742,6 @@ __global__ __launch_bounds__(256) void edge_labels_kernel(const int64_t *__restr
     }
 }
 
-static int stream_grid(int64_t n) {
-    int64_t g = ceil_div(n, 256);
-    const int64_t cap = (int64_t)cu_count() * 8;
-    if (g > cap) g = cap;
-    return (int)(g < 1 ? 1 : g);
-}
-
 int knn_search_launch(const float *x, int64_t n, int dim, int stride, int k, float max_radius,
                       const int64_t *seg_ptr, int n_seg, int32_t *nbr, int32_t *cnt, hipStream_t stream) {
     if (!x || !nbr || !cnt || n < 0 || dim < 1 || stride < dim || k < 1)
@@ -768,31 +756,27 @@ int knn_search_launch(const float *x, int64_t n, int dim, int stride, int k, flo
     int qw = kKnnLdsPerWave / (cap * 8);
     if (qw > 32) qw = 32;
     const int64_t grid = ceil_div(n, (int64_t)qw * kKnnWaves);
-#define KNN_LAUNCH_Q(DP, FULL_, BATCH_, QW_)                                                        \
-    hipLaunchKernelGGL((knn_kernel<DP, FULL_, BATCH_, QW_>), dim3((unsigned)grid), dim3(kKnnBlock), 0, stream, x, n, \
-                       dim, stride, k, cap, qw, max_radius, seg_ptr, n_seg, nbr, cnt)
-#define KNN_LAUNCH(DP, FULL_, BATCH_)                                                               \
-    if (DP <= 8 && qw == 8) KNN_LAUNCH_Q(DP, FULL_, BATCH_, (DP <= 8 ? 8 : 0));                     \
-    else if (DP <= 8 && qw == 4) KNN_LAUNCH_Q(DP, FULL_, BATCH_, (DP <= 8 ? 4 : 0));                \
-    else KNN_LAUNCH_Q(DP, FULL_, BATCH_, 0)
-#define KNN_CALL(DP)                                                                               \
-    if (seg_ptr) {                                                                                 \
-        if (dim == DP) KNN_LAUNCH(DP, true, true); else KNN_LAUNCH(DP, false, true);               \
-    } else {                                                                                       \
-        if (dim == DP) KNN_LAUNCH(DP, true, false); else KNN_LAUNCH(DP, false, false);             \
-    }
-    if (dim <= 4) {
-        KNN_CALL(4);
-    } else if (dim <= 8) {
-        KNN_CALL(8);
-    } else if (dim <= 16) {
-        KNN_CALL(16);
-    } else {
-        KNN_CALL(32);
-    }
-#undef KNN_CALL
-#undef KNN_LAUNCH
-#undef KNN_LAUNCH_Q
+    dispatch_dp<4, 8, 16, 32>(dim, [&](auto DP) {
+        constexpr int dp = decltype(DP)::value;
+        auto launch = [&](auto FULL, auto BATCH) {
+            auto with = [&](auto QW) {
+                hipLaunchKernelGGL((knn_kernel<dp, decltype(FULL)::value, decltype(BATCH)::value, decltype(QW)::value>),
+                                   dim3((unsigned)grid), dim3(kKnnBlock), 0, stream, x, n, dim, stride, k, cap, qw,
+                                   max_radius, seg_ptr, n_seg, nbr, cnt);
+            };
+            // (the queries' coordinates stay in registers up to 8 dimensions only)
+            if constexpr (dp <= 8) {
+                if (qw == 8) return with(int_c<8>{});
+                if (qw == 4) return with(int_c<4>{});
+            }
+            with(int_c<0>{});
+        };
+        if (seg_ptr) {
+            if (dim == dp) launch(std::true_type{}, std::true_type{}); else launch(std::false_type{}, std::true_type{});
+        } else {
+            if (dim == dp) launch(std::true_type{}, std::false_type{}); else launch(std::false_type{}, std::false_type{});
+        }
+    });
     return check_launch("knn_search");
 }
 
@@ -802,89 +786,54 @@ int spatial_dp(int dim) { return dim <= 4 ? 4 : dim <= 8 ? 8 : 16; }
 int spatial_n_chunks(int64_t n) { return (int)ceil_div(n, 64); }
 // scratch of the build: [box partials | keys a | keys b | vals a | vals b | radix-sort temp]
 struct SpatialScratch {
-    size_t part, keys_a, keys_b, vals_a, vals_b, temp, total;
+    float *part;
+    u64 *keys_a, *keys_b;
+    uint32_t *vals_a, *vals_b;
+    char *temp;
+    size_t temp_bytes, total;
 };
-static SpatialScratch spatial_scratch_layout(int64_t n) {
+static SpatialScratch spatial_scratch(void *base, int64_t n) {
     SpatialScratch w{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += align_up(bytes, 256);
-        return at;
-    };
-    w.part = take((size_t)kKnnBoxParts * 2 * kSpMaxDim * sizeof(float));
-    w.keys_a = take((size_t)n * 8);
-    w.keys_b = take((size_t)n * 8);
-    w.vals_a = take((size_t)n * 4);
-    w.vals_b = take((size_t)n * 4);
-    w.temp = take(sort_pairs_u64_temp_bytes(n));
-    w.total = o;
+    Carver ws{(char *)base};
+    w.part = ws.take<float>((size_t)kKnnBoxParts * 2 * kSpMaxDim);
+    w.keys_a = ws.take<u64>((size_t)n);
+    w.keys_b = ws.take<u64>((size_t)n);
+    w.vals_a = ws.take<uint32_t>((size_t)n);
+    w.vals_b = ws.take<uint32_t>((size_t)n);
+    w.temp_bytes = sort_pairs_u64_temp_bytes(n);
+    w.temp = ws.take<char>(w.temp_bytes);
+    w.total = ws.off;
     return w;
 }
-size_t spatial_scratch_bytes(int64_t n) { return spatial_scratch_layout(n).total; }
+size_t spatial_scratch_bytes(int64_t n) { return spatial_scratch(nullptr, n).total; }
 
-// xs[n_chunks * 64][DP]: the points in (event, Morton) order, the tail of the last chunk repeats the
-// last point; sidx[n_chunks * 64]: their original indices (-1 in the tail); box[n_chunks][2 * DP]
+// fills c (host_util.h: SpatialChunks, carved for the same n and dim) with the points in (event, Morton) order
 int spatial_chunks_build(const float *x, int64_t n, int dim, int stride, const int64_t *seg_ptr, int n_seg,
-                         float *xs, int32_t *sidx, float *box, void *scratch, size_t scratch_bytes,
-                         hipStream_t stream) {
-    if (!x || n < 1 || dim < 1 || dim > kSpMaxDim || stride < dim || !xs || !sidx || !box || !scratch)
+                         const SpatialChunks &c, hipStream_t stream) {
+    if (!x || n < 1 || dim < 1 || dim > kSpMaxDim || stride < dim || !c.xs || !c.sidx || !c.box || !c.scratch)
         return fail(GNNTRK_EINVAL, "spatial_chunks: bad argument");
-    const SpatialScratch w = spatial_scratch_layout(n);
-    if (scratch_bytes < w.total) return fail(GNNTRK_EINVAL, "spatial_chunks: scratch too small");
-    char *base = static_cast<char *>(scratch);
-    float *part = reinterpret_cast<float *>(base + w.part);
-    u64 *keys_a = reinterpret_cast<u64 *>(base + w.keys_a), *keys_b = reinterpret_cast<u64 *>(base + w.keys_b);
-    uint32_t *vals_a = reinterpret_cast<uint32_t *>(base + w.vals_a), *vals_b = reinterpret_cast<uint32_t *>(base + w.vals_b);
+    const SpatialScratch w = spatial_scratch(c.scratch, n);
+    if (c.scratch_bytes < w.total) return fail(GNNTRK_EINVAL, "spatial_chunks: scratch too small");
     int seg_bits = 0;
     if (seg_ptr)
         while ((1 << seg_bits) < n_seg) ++seg_bits;
     const int n_part = (int)(ceil_div(n, 1024) < kKnnBoxParts ? ceil_div(n, 1024) : kKnnBoxParts);
-    hipLaunchKernelGGL(knn_bbox_partial_kernel, dim3(n_part), dim3(256), 0, stream, x, n, dim, stride, part);
+    hipLaunchKernelGGL(knn_bbox_partial_kernel, dim3(n_part), dim3(256), 0, stream, x, n, dim, stride, w.part);
     hipLaunchKernelGGL(knn_morton_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, stream, x, n, dim, stride,
-                       (const float *)part, n_part, seg_ptr, n_seg, seg_bits, keys_a, vals_a);
+                       (const float *)w.part, n_part, seg_ptr, n_seg, seg_bits, w.keys_a, w.vals_a);
     int rc = check_launch("spatial_chunks(sort keys)");
     if (rc != GNNTRK_OK) return rc;
-    rc = sort_pairs_u64(keys_a, keys_b, vals_a, vals_b, n, base + w.temp, sort_pairs_u64_temp_bytes(n), stream);
+    rc = sort_pairs_u64(w.keys_a, w.keys_b, w.vals_a, w.vals_b, n, w.temp, w.temp_bytes, stream);
     if (rc != GNNTRK_OK) return rc;
-    const int n_chunks = spatial_n_chunks(n);
-    const unsigned gb = (unsigned)ceil_div(n_chunks, 4);
-    if (spatial_dp(dim) == 4)
-        hipLaunchKernelGGL((knn_gather_box_kernel<4>), dim3(gb), dim3(256), 0, stream, x, n, dim, stride,
-                           (const uint32_t *)vals_b, n_chunks, xs, sidx, box);
-    else if (spatial_dp(dim) == 8)
-        hipLaunchKernelGGL((knn_gather_box_kernel<8>), dim3(gb), dim3(256), 0, stream, x, n, dim, stride,
-                           (const uint32_t *)vals_b, n_chunks, xs, sidx, box);
-    else
-        hipLaunchKernelGGL((knn_gather_box_kernel<16>), dim3(gb), dim3(256), 0, stream, x, n, dim, stride,
-                           (const uint32_t *)vals_b, n_chunks, xs, sidx, box);
+    const unsigned gb = (unsigned)ceil_div(c.n_chunks, 4);
+    dispatch_dp<4, 8, 16>(dim, [&](auto DP) {
+        hipLaunchKernelGGL((knn_gather_box_kernel<decltype(DP)::value>), dim3(gb), dim3(256), 0, stream, x, n, dim, stride,
+                           (const uint32_t *)w.vals_b, c.n_chunks, c.xs, c.sidx, c.box);
+    });
     return check_launch("spatial_chunks(gather)");
 }
 
-// ---- pruned search: workspace layout and launch -------------------------------------------
-struct KnnWs {
-    size_t xs, sidx, box, scratch, total;
-    int n_chunks, dp;
-};
-static KnnWs knn_ws_layout(int64_t n, int dim) {
-    KnnWs w{};
-    w.dp = spatial_dp(dim);
-    w.n_chunks = spatial_n_chunks(n);
-    const size_t rows = (size_t)w.n_chunks * 64;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += align_up(bytes, 256);
-        return at;
-    };
-    w.xs = take(rows * w.dp * sizeof(float));
-    w.sidx = take(rows * 4);
-    w.box = take((size_t)w.n_chunks * 2 * w.dp * sizeof(float));
-    w.scratch = take(spatial_scratch_bytes(n));
-    w.total = o;
-    return w;
-}
-
+// ---- pruned search: launch (its workspace is the chunks alone: host_util.h chunks_ws) ---------
 // queries per wave of the pruned kernel for this k (0: not covered, use the brute-force kernel)
 static int knn_pruned_qw(int dim, int k, int *cap_out) {
     int cap = 128;
@@ -898,7 +847,9 @@ static int knn_pruned_qw(int dim, int k, int *cap_out) {
 size_t knn_workspace_bytes(int64_t n, int dim, int k) {
     int cap;
     if (n <= 0 || dim < 1 || k < 1 || n > 0x7fffffff || knn_pruned_qw(dim, k, &cap) == 0) return 0;
-    return knn_ws_layout(n, dim).total;
+    size_t total;
+    chunks_ws(nullptr, n, dim, &total);
+    return total;
 }
 
 constexpr int64_t kKnnPrunedMinRows = 8192;  // below this the sort + boxes cost more than they save
@@ -914,33 +865,32 @@ int knn_search_ws_launch(const float *x, int64_t n, int dim, int stride, int k, 
     if (!pruned) return knn_search_launch(x, n, dim, stride, k, max_radius, seg_ptr, n_seg, nbr, cnt, stream);
     if (!x || !nbr || !cnt || stride < dim) return fail(GNNTRK_EINVAL, "knn_search: bad argument");
     if (seg_ptr && n_seg < 1) return fail(GNNTRK_EINVAL, "knn_search: seg_ptr needs n_seg >= 1");
-    const KnnWs w = knn_ws_layout(n, dim);
-    if (ws_bytes < w.total) return fail(GNNTRK_EINVAL, "knn_search: workspace too small (gnntrk_knn_workspace_bytes)");
-    char *base = static_cast<char *>(ws);
-    float *xs = reinterpret_cast<float *>(base + w.xs);
-    int32_t *sidx = reinterpret_cast<int32_t *>(base + w.sidx);
-    float *box = reinterpret_cast<float *>(base + w.box);
-    const int rc = spatial_chunks_build(x, n, dim, stride, seg_ptr, n_seg, xs, sidx, box, base + w.scratch,
-                                        w.total - w.scratch, stream);
+    size_t need;
+    const SpatialChunks c = chunks_ws(ws, n, dim, &need);
+    if (ws_bytes < need) return fail(GNNTRK_EINVAL, "knn_search: workspace too small (gnntrk_knn_workspace_bytes)");
+    const int rc = spatial_chunks_build(x, n, dim, stride, seg_ptr, n_seg, c, stream);
     if (rc != GNNTRK_OK) return rc;
     const unsigned grid = (unsigned)ceil_div(n, (int64_t)qw * kKnnWaves);
-#define KNN_PRUNED(DP, QW_)                                                                                  \
-    if (seg_ptr)                                                                                             \
-        hipLaunchKernelGGL((knn_pruned_kernel<DP, true, QW_>), dim3(grid), dim3(kKnnBlock), 0, stream,       \
-                           (const float *)xs, (const int32_t *)sidx, (const float *)box, n, w.n_chunks, k,   \
-                           cap, max_radius, seg_ptr, n_seg, nbr, cnt);                                       \
-    else                                                                                                     \
-        hipLaunchKernelGGL((knn_pruned_kernel<DP, false, QW_>), dim3(grid), dim3(kKnnBlock), 0, stream,      \
-                           (const float *)xs, (const int32_t *)sidx, (const float *)box, n, w.n_chunks, k,   \
-                           cap, max_radius, seg_ptr, n_seg, nbr, cnt)
-    if (w.dp == 4) {
-        if (qw == 8) { KNN_PRUNED(4, 8); } else if (qw == 4) { KNN_PRUNED(4, 4); } else { KNN_PRUNED(4, 2); }
-    } else if (w.dp == 8) {
-        if (qw == 8) { KNN_PRUNED(8, 8); } else if (qw == 4) { KNN_PRUNED(8, 4); } else { KNN_PRUNED(8, 2); }
-    } else {
-        if (qw == 4) { KNN_PRUNED(16, 4); } else { KNN_PRUNED(16, 2); }
-    }
-#undef KNN_PRUNED
+    dispatch_dp<4, 8, 16>(dim, [&](auto DP) {
+        constexpr int dp = decltype(DP)::value;
+        auto with = [&](auto QW) {
+            constexpr int q = decltype(QW)::value;
+            if (seg_ptr)
+                hipLaunchKernelGGL((knn_pruned_kernel<dp, true, q>), dim3(grid), dim3(kKnnBlock), 0, stream,
+                                   (const float *)c.xs, (const int32_t *)c.sidx, (const float *)c.box, n, c.n_chunks, k,
+                                   cap, max_radius, seg_ptr, n_seg, nbr, cnt);
+            else
+                hipLaunchKernelGGL((knn_pruned_kernel<dp, false, q>), dim3(grid), dim3(kKnnBlock), 0, stream,
+                                   (const float *)c.xs, (const int32_t *)c.sidx, (const float *)c.box, n, c.n_chunks, k,
+                                   cap, max_radius, seg_ptr, n_seg, nbr, cnt);
+        };
+        // (knn_pruned_qw: beyond 8 dimensions four queries fill the registers)
+        if constexpr (dp <= 8) {
+            if (qw == 8) return with(int_c<8>{});
+        }
+        if (qw == 4) return with(int_c<4>{});
+        with(int_c<2>{});
+    });
     return check_launch("knn_search(pruned)");
 }
 
@@ -963,7 +913,7 @@ int knn_emit_launch(const int32_t *nbr, const int32_t *cnt, int64_t n, int k_str
         return check_launch("knn_emit(scan)");
     }
     if (m_total > 0)
-        hipLaunchKernelGGL(knn_emit_kernel, dim3(stream_grid(n * k)), dim3(256), 0, stream, nbr, cnt,
+        hipLaunchKernelGGL(knn_emit_kernel, dim3(blocks_for(n * k, 8)), dim3(256), 0, stream, nbr, cnt,
                            (const int64_t *)offsets, n, k_stride, k, m_total, edge_index);
     return check_launch("knn_emit");
 }
@@ -973,7 +923,7 @@ int edge_features_launch(const float *x, int dim, int stride, const int64_t *ei,
     if (!x || dim < 1 || stride < dim || m < 0) return fail(GNNTRK_EINVAL, "edge_features: bad argument");
     if (m == 0) return GNNTRK_OK;
     if (!ei || !out) return fail(GNNTRK_EINVAL, "edge_features: NULL pointer");
-    hipLaunchKernelGGL(edge_features_kernel, dim3(stream_grid(m * dim)), dim3(256), 0, stream, x, dim,
+    hipLaunchKernelGGL(edge_features_kernel, dim3(blocks_for(m * dim, 8)), dim3(256), 0, stream, x, dim,
                        stride, ei, m, out);
     return check_launch("edge_features");
 }
@@ -983,7 +933,7 @@ int edge_labels_launch(const int64_t *pid, const int64_t *ei, int64_t m, int64_t
     if (m < 0) return fail(GNNTRK_EINVAL, "edge_labels: bad argument");
     if (m == 0) return GNNTRK_OK;
     if (!pid || !ei || !y) return fail(GNNTRK_EINVAL, "edge_labels: NULL pointer");
-    hipLaunchKernelGGL(edge_labels_kernel, dim3(stream_grid(m)), dim3(256), 0, stream, pid, ei, m, y);
+    hipLaunchKernelGGL(edge_labels_kernel, dim3(blocks_for(m, 8)), dim3(256), 0, stream, pid, ei, m, y);
     return check_launch("edge_labels");
 }
 

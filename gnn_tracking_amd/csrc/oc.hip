@@ -15,6 +15,7 @@
 // implementation-defined subset when a hit has more neighbours than the cap; the reference
 // tests never reach it) - see DESIGN.md.
 #include "host_util.h"
+#include "wave_util.h"
 
 namespace gnntrk {
 
@@ -30,7 +31,7 @@ static int oc_grid(int64_t n) {
 
 __device__ __forceinline__ double oc_block_sum(double v, double *sh) {
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);   // (wave_sum here would reorder the callers' instructions)
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
     double s = 0.0;
@@ -612,22 +613,6 @@ __global__ __launch_bounds__(kOcTpb) void oc_cp_records_kernel(const OcParams p,
     cpid[k] = p.pid[a];
 }
 
-__device__ __forceinline__ void oc_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-__device__ __forceinline__ double oc_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-__device__ __forceinline__ float oc_wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 // hit pass: workgroup = chunk of 64 sorted hits, its four waves take every fourth round of 64
 // condensation points (the rounds are latency bound: more of them in flight) and their per-hit
 // sums are added in wave order through LDS.  BWD = false: part[chunk][8] = {attractive, repulsive,
@@ -702,13 +687,13 @@ __global__ __launch_bounds__(kOcTpb) void oc_hits_spatial_kernel(const OcParams 
         }
         unsigned long long near = __ballot(k < K && lb <= r2m);
         if (near != 0ull) {
-            oc_wave_sync();  // (the previous round's readers are done)
+            wave_sync();  // (the previous round's readers are done)
 #pragma unroll
             for (int d = 0; d < DP; ++d) s_x[wv][lane][d] = ck[d];
             s_q[wv][lane] = sp.cq[kc];
             s_pid[wv][lane] = sp.cpid[kc];
             s_hit[wv][lane] = p.alphas[kc];
-            oc_wave_sync();
+            wave_sync();
             while (near != 0ull) {
                 const int i = __ffsll(near) - 1;
                 near &= near - 1ull;
@@ -789,9 +774,9 @@ __global__ __launch_bounds__(kOcTpb) void oc_hits_spatial_kernel(const OcParams 
     }
     const bool is_noise = live && ((p.mode == 1) ? !(pj > 0) : (pj == 0));
     if (!BWD) {
-        const double a = oc_wave_sum(va), rr = oc_wave_sum(vr), cc = oc_wave_sum(nrep);
-        const double ns = oc_wave_sum(is_noise ? (double)bj : 0.0), nn = oc_wave_sum(is_noise ? 1.0 : 0.0),
-                     no = oc_wave_sum(mj ? 1.0 : 0.0);
+        const double a = wave_sum(va), rr = wave_sum(vr), cc = wave_sum(nrep);
+        const double ns = wave_sum(is_noise ? (double)bj : 0.0), nn = wave_sum(is_noise ? 1.0 : 0.0),
+                     no = wave_sum(mj ? 1.0 : 0.0);
         if (lane == 0) {
             double *o = part + (int64_t)c * 8;
             o[0] = a; o[1] = rr; o[2] = cc; o[3] = ns; o[4] = nn; o[5] = no; o[6] = 0.0; o[7] = 0.0;
@@ -963,8 +948,8 @@ __global__ __launch_bounds__(kOcTpb) void oc_cps_spatial_kernel(const OcParams p
         }
     }
 #pragma unroll
-    for (int d = 0; d < DP; ++d) gxk[d] = oc_wave_sum(gxk[d]);
-    gqk = oc_wave_sum(gqk);
+    for (int d = 0; d < DP; ++d) gxk[d] = wave_sum(gxk[d]);
+    gqk = wave_sum(gqk);
     if (lane == 0) {
 #pragma unroll
         for (int d = 0; d < DP; ++d) s_acc[wv][d] = gxk[d];
@@ -982,10 +967,6 @@ __global__ __launch_bounds__(kOcTpb) void oc_cps_spatial_kernel(const OcParams p
 }
 
 // ---- launchers -----------------------------------------------------------------------
-size_t sort_pairs_u64_temp_bytes(int64_t n);
-int sort_pairs_u64(const u64 *keys_in, u64 *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
-                   int64_t n, void *temp, size_t temp_bytes, hipStream_t stream);
-
 int good_node_mask_launch(const float *pt, const int64_t *pid, const float *reco, const float *eta,
                           int64_t n, float pt_thld, float max_eta, uint8_t *mask,
                           hipStream_t stream) {
@@ -997,12 +978,31 @@ int good_node_mask_launch(const float *pt, const int64_t *pid, const float *reco
     return check_launch("good_node_mask");
 }
 
-size_t oc_select_ws_bytes(int64_t n) {
-    const size_t a8 = align_up((size_t)(n > 0 ? n : 1) * 8, 256);
-    const size_t a4 = align_up((size_t)(n > 0 ? n : 1) * 4, 256);
-    return 2 * a8 /*keys*/ + 2 * a4 /*vals*/ + 2 * a4 /*flag,best*/ + align_up((size_t)(n + 1) * 8, 256) +
-           align_up(sort_pairs_u64_temp_bytes(n), 256);
+struct SelectWs {
+    u64 *keys_a, *keys_b;
+    uint32_t *vals_a, *vals_b;
+    int32_t *flag, *best;
+    int64_t *off;   // [n + 1]
+    char *temp;
+    size_t temp_bytes, total;
+};
+static SelectWs select_ws(void *base, int64_t n) {
+    const size_t nn = (size_t)(n > 0 ? n : 1);
+    SelectWs w{};
+    Carver ws{(char *)base};
+    w.keys_a = ws.take<u64>(nn);
+    w.keys_b = ws.take<u64>(nn);
+    w.vals_a = ws.take<uint32_t>(nn);
+    w.vals_b = ws.take<uint32_t>(nn);
+    w.flag = ws.take<int32_t>(nn);
+    w.best = ws.take<int32_t>(nn);
+    w.off = ws.take<int64_t>((size_t)(n + 1));
+    w.temp_bytes = sort_pairs_u64_temp_bytes(n);
+    w.temp = ws.take<char>(w.temp_bytes);
+    w.total = ws.off;
+    return w;
 }
+size_t oc_select_ws_bytes(int64_t n) { return select_ws(nullptr, n).total; }
 
 int oc_select_launch(const float *score, const int64_t *pid, const uint8_t *mask, int64_t n, int mode,
                      int32_t *alphas, int32_t *gid, int32_t *n_cp, void *ws, size_t ws_bytes,
@@ -1010,29 +1010,20 @@ int oc_select_launch(const float *score, const int64_t *pid, const uint8_t *mask
     if (!score || !pid || !mask || !alphas || !gid || !n_cp || n < 1 || (mode != 0 && mode != 1))
         return fail(GNNTRK_EINVAL, "oc_select_cps: bad argument");
     if (n > 0x7fffffff) return fail(GNNTRK_EUNSUPPORTED, "oc_select_cps: n must fit int32");
-    if (!ws || ws_bytes < oc_select_ws_bytes(n)) return fail(GNNTRK_EINVAL, "oc_select_cps: workspace too small");
-    char *w = reinterpret_cast<char *>(ws);
-    const size_t a8 = align_up((size_t)n * 8, 256), a4 = align_up((size_t)n * 4, 256);
-    u64 *keys_a = (u64 *)w; w += a8;
-    u64 *keys_b = (u64 *)w; w += a8;
-    uint32_t *vals_a = (uint32_t *)w; w += a4;
-    uint32_t *vals_b = (uint32_t *)w; w += a4;
-    int32_t *flag = (int32_t *)w; w += a4;
-    int32_t *best = (int32_t *)w; w += a4;
-    int64_t *off = (int64_t *)w; w += align_up((size_t)(n + 1) * 8, 256);
-    void *temp = w;
+    const SelectWs w = select_ws(ws, n);
+    if (!ws || ws_bytes < w.total) return fail(GNNTRK_EINVAL, "oc_select_cps: workspace too small");
     const int grid = oc_grid(n);
-    hipLaunchKernelGGL(oc_keys_kernel, dim3(grid), dim3(kOcTpb), 0, stream, pid, n, keys_a, vals_a);
-    int rc = sort_pairs_u64(keys_a, keys_b, vals_a, vals_b, n, temp, sort_pairs_u64_temp_bytes(n), stream);
+    hipLaunchKernelGGL(oc_keys_kernel, dim3(grid), dim3(kOcTpb), 0, stream, pid, n, w.keys_a, w.vals_a);
+    int rc = sort_pairs_u64(w.keys_a, w.keys_b, w.vals_a, w.vals_b, n, w.temp, w.temp_bytes, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(oc_segment_best_kernel, dim3(grid), dim3(kOcTpb), 0, stream,
-                       (const u64 *)keys_b, (const uint32_t *)vals_b, score, mask, n, mode, flag, best);
-    scan_counts_launch(flag, 0x7fffffff, n, off, stream);
+                       (const u64 *)w.keys_b, (const uint32_t *)w.vals_b, score, mask, n, mode, w.flag, w.best);
+    scan_counts_launch(w.flag, 0x7fffffff, n, w.off, stream);
     rc = check_hip(hipMemsetAsync(gid, 0xff, (size_t)n * sizeof(int32_t), stream), "oc_select_cps(memset)");
     if (rc) return rc;
-    hipLaunchKernelGGL(oc_assign_kernel, dim3(grid), dim3(kOcTpb), 0, stream, (const u64 *)keys_b,
-                       (const uint32_t *)vals_b, (const int32_t *)flag, (const int32_t *)best,
-                       (const int64_t *)off, n, alphas, gid, n_cp);
+    hipLaunchKernelGGL(oc_assign_kernel, dim3(grid), dim3(kOcTpb), 0, stream, (const u64 *)w.keys_b,
+                       (const uint32_t *)w.vals_b, (const int32_t *)w.flag, (const int32_t *)w.best,
+                       (const int64_t *)w.off, n, alphas, gid, n_cp);
     return check_launch("oc_select_cps");
 }
 
@@ -1058,13 +1049,6 @@ static OcParams oc_params(const gnntrk_oc_args *a) {
 
 size_t oc_forward_ws_bytes(int64_t n) { return (size_t)oc_grid(n) * 4 * sizeof(double); }
 
-#define OC_DISPATCH(CALL)                \
-    if (a->dim <= 2) { CALL(2); }        \
-    else if (a->dim <= 4) { CALL(4); }   \
-    else if (a->dim <= 8) { CALL(8); }   \
-    else if (a->dim <= 16) { CALL(16); } \
-    else { CALL(32); }
-
 int oc_forward_launch(const gnntrk_oc_args *a, float *out, void *ws, size_t ws_bytes, hipStream_t stream) {
     int rc = oc_check(a);
     if (rc) return rc;
@@ -1072,9 +1056,9 @@ int oc_forward_launch(const gnntrk_oc_args *a, float *out, void *ws, size_t ws_b
     const OcParams p = oc_params(a);
     const int grid = oc_grid(a->n);
     double *part = reinterpret_cast<double *>(ws);
-#define CALL_F(DP) hipLaunchKernelGGL(oc_forward_kernel<DP>, dim3(grid), dim3(kOcTpb), 0, stream, p, part)
-    OC_DISPATCH(CALL_F)
-#undef CALL_F
+    dispatch_dp<2, 4, 8, 16, 32>(a->dim, [&](auto DP) {
+        hipLaunchKernelGGL(oc_forward_kernel<decltype(DP)::value>, dim3(grid), dim3(kOcTpb), 0, stream, p, part);
+    });
     hipLaunchKernelGGL(oc_finalize_kernel, dim3(1), dim3(kOcTpb), 0, stream, p, (const double *)part, grid, out);
     return check_launch("oc_forward");
 }
@@ -1094,9 +1078,10 @@ int oc_backward_launch(const gnntrk_oc_args *a, const float *g, const float *fwd
     if (!ws || ws_bytes < oc_backward_ws_bytes(a->n, a->dim)) return fail(GNNTRK_EINVAL, "oc_backward: workspace too small");
     const OcParams p = oc_params(a);
     const int grid = oc_grid(a->n);
-#define CALL_BH(DP) hipLaunchKernelGGL(oc_backward_hits_kernel<DP>, dim3(grid), dim3(kOcTpb), 0, stream, p, g, fwd, gx, gbeta)
-    OC_DISPATCH(CALL_BH)
-#undef CALL_BH
+    dispatch_dp<2, 4, 8, 16, 32>(a->dim, [&](auto DP) {
+        hipLaunchKernelGGL(oc_backward_hits_kernel<decltype(DP)::value>, dim3(grid), dim3(kOcTpb), 0, stream, p, g, fwd, gx,
+                           gbeta);
+    });
     // condensation-point side in batches of kOcCpBatch (the count K lives on the device: batches
     // past it exit at once), each batch cut into hit slices
     int64_t n_chunks = (a->n + kOcChunk - 1) / kOcChunk;
@@ -1105,106 +1090,81 @@ int oc_backward_launch(const gnntrk_oc_args *a, const float *g, const float *fwd
     for (int64_t kb = 0; kb < max_cps; kb += kOcCpBatch) {
         const int64_t in_batch = (max_cps - kb < kOcCpBatch) ? (max_cps - kb) : kOcCpBatch;
         const int kgrid = oc_grid(in_batch);
-#define CALL_BC(DP)                                                                                          \
-    hipLaunchKernelGGL(oc_backward_cps_kernel<DP>, dim3(kgrid, slices), dim3(kOcTpb), 0, stream, p, g, fwd,    \
-                       (int)kb, part);                                                                        \
-    hipLaunchKernelGGL(oc_backward_cps_reduce_kernel<DP>, dim3(kgrid), dim3(kOcTpb), 0, stream, p, g, fwd,     \
-                       (int)kb, slices, (const float *)part, gx, gbeta)
-        OC_DISPATCH(CALL_BC)
-#undef CALL_BC
+        dispatch_dp<2, 4, 8, 16, 32>(a->dim, [&](auto DP) {
+            constexpr int dp = decltype(DP)::value;
+            hipLaunchKernelGGL(oc_backward_cps_kernel<dp>, dim3(kgrid, slices), dim3(kOcTpb), 0, stream, p, g, fwd,
+                               (int)kb, part);
+            hipLaunchKernelGGL(oc_backward_cps_reduce_kernel<dp>, dim3(kgrid), dim3(kOcTpb), 0, stream, p, g, fwd,
+                               (int)kb, slices, (const float *)part, gx, gbeta);
+        });
     }
     return check_launch("oc_backward");
 }
 
 // ---- spatial passes: workspace layout and launchers ------------------------------------------
+// the chunks, the view `sp` the kernels read, and the arrays of it that the launchers fill
 struct OcSpatialWs {
-    size_t xs, sidx, box, hq, hpid, hcap, hcapd2, cx, cq, cpid, part, gkeys_a, gkeys_b, gvals_a, gvals_b, gstart,
-        gtemp, scratch, total;
-    int n_chunks, dp;
+    SpatialChunks c;
+    OcSpatial sp;
+    float *hq, *hcapd2, *cx, *cq;
+    long long *hpid, *cpid;
+    int32_t *hcap, *gstart;
+    double *part;   // [n_chunks][8] of the forward
+    uint32_t *gkeys_a, *gkeys_b, *gvals_a, *gvals_b;
+    char *gtemp;
+    size_t gtemp_bytes, total;
 };
-static OcSpatialWs oc_spatial_layout(int64_t n, int dim) {
+static OcSpatialWs oc_spatial_ws(void *base, int64_t n, int dim) {
     OcSpatialWs w{};
-    w.dp = spatial_dp(dim);
-    w.n_chunks = spatial_n_chunks(n);
-    const size_t rows = (size_t)w.n_chunks * 64;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += align_up(bytes, 256);
-        return at;
-    };
-    w.xs = take(rows * w.dp * 4);
-    w.sidx = take(rows * 4);
-    w.box = take((size_t)w.n_chunks * 2 * w.dp * 4);
-    w.hq = take(rows * 4);
-    w.hpid = take(rows * 8);
-    w.hcap = take(rows * 4);
-    w.hcapd2 = take(rows * 4);
-    w.cx = take((size_t)n * w.dp * 4);
-    w.cq = take((size_t)n * 4);
-    w.cpid = take((size_t)n * 8);
-    w.part = take((size_t)w.n_chunks * 8 * sizeof(double));
-    w.gkeys_a = take((size_t)n * 4);
-    w.gkeys_b = take((size_t)n * 4);
-    w.gvals_a = take((size_t)n * 4);
-    w.gvals_b = take((size_t)n * 4);
-    w.gstart = take((size_t)n * 4);
-    w.gtemp = take(sort_pairs_temp_bytes(n));
-    w.scratch = take(spatial_scratch_bytes(n));
-    w.total = o;
+    Carver ws{(char *)base};
+    w.c = take_chunks(ws, n, dim);
+    const size_t rows = (size_t)w.c.n_chunks * 64, N = (size_t)n;
+    w.hq = ws.take<float>(rows);
+    w.hpid = ws.take<long long>(rows);
+    w.hcap = ws.take<int32_t>(rows);
+    w.hcapd2 = ws.take<float>(rows);
+    w.cx = ws.take<float>(N * w.c.dp);
+    w.cq = ws.take<float>(N);
+    w.cpid = ws.take<long long>(N);
+    w.part = ws.take<double>((size_t)w.c.n_chunks * 8);
+    w.gkeys_a = ws.take<uint32_t>(N);
+    w.gkeys_b = ws.take<uint32_t>(N);
+    w.gvals_a = ws.take<uint32_t>(N);
+    w.gvals_b = ws.take<uint32_t>(N);
+    w.gstart = ws.take<int32_t>(N);
+    w.gtemp_bytes = sort_pairs_temp_bytes(n);
+    w.gtemp = ws.take<char>(w.gtemp_bytes);
+    take_chunks_scratch(ws, w.c, n);
+    w.total = ws.off;
+    w.sp = OcSpatial{w.c.xs, w.c.sidx, w.c.box, w.hq, w.hpid, w.hcap, w.hcapd2, w.cx, w.cq, w.cpid,
+                     w.gvals_b /* gorder */, w.gkeys_b /* gkeys */, w.gstart, w.c.n_chunks};
     return w;
 }
 size_t oc_spatial_ws_bytes(int64_t n, int dim) {
     if (n < 1 || n > 0x7fffffff || dim < 1 || dim > 16) return 0;
-    return oc_spatial_layout(n, dim).total;
-}
-static OcSpatial oc_spatial_view(const OcSpatialWs &w, void *ws) {
-    char *b = static_cast<char *>(ws);
-    OcSpatial sp{};
-    sp.xs = reinterpret_cast<const float *>(b + w.xs);
-    sp.sidx = reinterpret_cast<const int32_t *>(b + w.sidx);
-    sp.box = reinterpret_cast<const float *>(b + w.box);
-    sp.hq = reinterpret_cast<const float *>(b + w.hq);
-    sp.hpid = reinterpret_cast<const long long *>(b + w.hpid);
-    sp.hcap = reinterpret_cast<const int32_t *>(b + w.hcap);
-    sp.hcapd2 = reinterpret_cast<const float *>(b + w.hcapd2);
-    sp.cx = reinterpret_cast<const float *>(b + w.cx);
-    sp.cq = reinterpret_cast<const float *>(b + w.cq);
-    sp.cpid = reinterpret_cast<const long long *>(b + w.cpid);
-    sp.gorder = reinterpret_cast<const uint32_t *>(b + w.gvals_b);
-    sp.gkeys = reinterpret_cast<const uint32_t *>(b + w.gkeys_b);
-    sp.gstart = reinterpret_cast<const int32_t *>(b + w.gstart);
-    sp.n_chunks = w.n_chunks;
-    return sp;
+    return oc_spatial_ws(nullptr, n, dim).total;
 }
 
 int oc_forward_spatial_launch(const gnntrk_oc_args *a, float *out, void *ws, size_t ws_bytes, hipStream_t stream) {
     int rc = oc_check(a);
     if (rc) return rc;
     if (a->dim > 16) return fail(GNNTRK_EUNSUPPORTED, "oc_forward_spatial: dim > 16 (use gnntrk_oc_forward)");
-    const OcSpatialWs w = oc_spatial_layout(a->n, a->dim);
+    const OcSpatialWs w = oc_spatial_ws(ws, a->n, a->dim);
     if (!out || !ws || ws_bytes < w.total) return fail(GNNTRK_EINVAL, "oc_forward_spatial: workspace too small");
     const OcParams p = oc_params(a);
-    char *b = static_cast<char *>(ws);
-    rc = spatial_chunks_build(a->x, a->n, a->dim, a->stride, nullptr, 0, reinterpret_cast<float *>(b + w.xs),
-                              reinterpret_cast<int32_t *>(b + w.sidx), reinterpret_cast<float *>(b + w.box),
-                              b + w.scratch, w.total - w.scratch, stream);
+    rc = spatial_chunks_build(a->x, a->n, a->dim, a->stride, nullptr, 0, w.c, stream);
     if (rc) return rc;
-    const OcSpatial sp = oc_spatial_view(w, ws);
-    const int rgrid = oc_grid((int64_t)w.n_chunks * 64), kgrid = oc_grid(a->n), hgrid = w.n_chunks;
-    double *part = reinterpret_cast<double *>(b + w.part);
-#define CALL_FS(DP)                                                                                              \
-    hipLaunchKernelGGL(oc_hit_records_kernel<DP>, dim3(rgrid), dim3(kOcTpb), 0, stream, p, sp,                    \
-                       reinterpret_cast<float *>(b + w.hq), reinterpret_cast<long long *>(b + w.hpid),            \
-                       reinterpret_cast<int32_t *>(b + w.hcap), reinterpret_cast<float *>(b + w.hcapd2));         \
-    hipLaunchKernelGGL(oc_cp_records_kernel<DP>, dim3(kgrid), dim3(kOcTpb), 0, stream, p,                         \
-                       reinterpret_cast<float *>(b + w.cx), reinterpret_cast<float *>(b + w.cq),                  \
-                       reinterpret_cast<long long *>(b + w.cpid));                                                \
-    hipLaunchKernelGGL((oc_hits_spatial_kernel<DP, false>), dim3(hgrid), dim3(kOcTpb), 0, stream, p, sp,          \
-                       (const float *)nullptr, (const float *)nullptr, part, (float *)nullptr, (float *)nullptr)
-    if (w.dp == 4) { CALL_FS(4); } else if (w.dp == 8) { CALL_FS(8); } else { CALL_FS(16); }
-#undef CALL_FS
-    hipLaunchKernelGGL(oc_finalize_spatial_kernel, dim3(1), dim3(kOcTpb), 0, stream, p, (const double *)part, w.n_chunks, out);
+    const int rgrid = oc_grid((int64_t)w.c.n_chunks * 64), kgrid = oc_grid(a->n), hgrid = w.c.n_chunks;
+    dispatch_dp<4, 8, 16>(a->dim, [&](auto DP) {
+        constexpr int dp = decltype(DP)::value;
+        hipLaunchKernelGGL(oc_hit_records_kernel<dp>, dim3(rgrid), dim3(kOcTpb), 0, stream, p, w.sp, w.hq, w.hpid, w.hcap,
+                           w.hcapd2);
+        hipLaunchKernelGGL(oc_cp_records_kernel<dp>, dim3(kgrid), dim3(kOcTpb), 0, stream, p, w.cx, w.cq, w.cpid);
+        hipLaunchKernelGGL((oc_hits_spatial_kernel<dp, false>), dim3(hgrid), dim3(kOcTpb), 0, stream, p, w.sp,
+                           (const float *)nullptr, (const float *)nullptr, w.part, (float *)nullptr, (float *)nullptr);
+    });
+    hipLaunchKernelGGL(oc_finalize_spatial_kernel, dim3(1), dim3(kOcTpb), 0, stream, p, (const double *)w.part,
+                       w.c.n_chunks, out);
     return check_launch("oc_forward_spatial");
 }
 
@@ -1214,27 +1174,23 @@ int oc_backward_spatial_launch(const gnntrk_oc_args *a, const float *g, const fl
     if (rc) return rc;
     if (a->dim > 16) return fail(GNNTRK_EUNSUPPORTED, "oc_backward_spatial: dim > 16 (use gnntrk_oc_backward)");
     if (!g || !fwd || !gx || !gbeta || max_cps < 1) return fail(GNNTRK_EINVAL, "oc_backward_spatial: bad argument");
-    const OcSpatialWs w = oc_spatial_layout(a->n, a->dim);
+    const OcSpatialWs w = oc_spatial_ws(ws, a->n, a->dim);
     if (!ws || ws_bytes < w.total) return fail(GNNTRK_EINVAL, "oc_backward_spatial: workspace too small");
     const OcParams p = oc_params(a);
-    const OcSpatial sp = oc_spatial_view(w, ws);
-    char *b = static_cast<char *>(ws);
-    const int hgrid = w.n_chunks, ngrid = oc_grid(a->n);
+    const int hgrid = w.c.n_chunks, ngrid = oc_grid(a->n);
     // the by-gid ordering of the hits (for the points' attractive share)
-    uint32_t *gka = reinterpret_cast<uint32_t *>(b + w.gkeys_a), *gkb = reinterpret_cast<uint32_t *>(b + w.gkeys_b);
-    uint32_t *gva = reinterpret_cast<uint32_t *>(b + w.gvals_a), *gvb = reinterpret_cast<uint32_t *>(b + w.gvals_b);
-    hipLaunchKernelGGL(oc_gid_keys_kernel, dim3(ngrid), dim3(kOcTpb), 0, stream, a->gid, a->n, gka, gva);
-    rc = sort_pairs_u32(gka, gkb, gva, gvb, a->n, 32, b + w.gtemp, sort_pairs_temp_bytes(a->n), stream);
+    hipLaunchKernelGGL(oc_gid_keys_kernel, dim3(ngrid), dim3(kOcTpb), 0, stream, a->gid, a->n, w.gkeys_a, w.gvals_a);
+    rc = sort_pairs_u32(w.gkeys_a, w.gkeys_b, w.gvals_a, w.gvals_b, a->n, 32, w.gtemp, w.gtemp_bytes, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(oc_gid_starts_kernel, dim3(ngrid), dim3(kOcTpb), 0, stream, (const uint32_t *)gkb, a->n,
-                       reinterpret_cast<int32_t *>(b + w.gstart));
+    hipLaunchKernelGGL(oc_gid_starts_kernel, dim3(ngrid), dim3(kOcTpb), 0, stream, (const uint32_t *)w.gkeys_b, a->n,
+                       w.gstart);
     const int cgrid = (int)(max_cps < a->n ? max_cps : a->n);
-#define CALL_BS(DP)                                                                                              \
-    hipLaunchKernelGGL((oc_hits_spatial_kernel<DP, true>), dim3(hgrid), dim3(kOcTpb), 0, stream, p, sp, g, fwd,   \
-                       (double *)nullptr, gx, gbeta);                                                             \
-    hipLaunchKernelGGL(oc_cps_spatial_kernel<DP>, dim3(cgrid), dim3(kOcTpb), 0, stream, p, sp, g, fwd, gx, gbeta)
-    if (w.dp == 4) { CALL_BS(4); } else if (w.dp == 8) { CALL_BS(8); } else { CALL_BS(16); }
-#undef CALL_BS
+    dispatch_dp<4, 8, 16>(a->dim, [&](auto DP) {
+        constexpr int dp = decltype(DP)::value;
+        hipLaunchKernelGGL((oc_hits_spatial_kernel<dp, true>), dim3(hgrid), dim3(kOcTpb), 0, stream, p, w.sp, g, fwd,
+                           (double *)nullptr, gx, gbeta);
+        hipLaunchKernelGGL(oc_cps_spatial_kernel<dp>, dim3(cgrid), dim3(kOcTpb), 0, stream, p, w.sp, g, fwd, gx, gbeta);
+    });
     return check_launch("oc_backward_spatial");
 }
 

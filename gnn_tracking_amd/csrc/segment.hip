@@ -6,13 +6,6 @@ namespace gnntrk {
 
 constexpr int kTpb = 256;
 
-static int stream_grid(int64_t n) {
-    int64_t g = ceil_div(n, kTpb);
-    const int64_t cap = (int64_t)cu_count() * 8;
-    if (g > cap) g = cap;
-    return (int)(g < 1 ? 1 : g);
-}
-
 // thread <-> (segment n, feature f); consecutive threads read consecutive floats of
 // the same CSR row, consecutive segments read adjacent row ranges: coalesced when
 // pos == NULL, L2-resident gathers otherwise.  Summation in CSR order.
@@ -156,7 +149,7 @@ __device__ __forceinline__ float bce_target(const float *y, const int64_t *src_n
 
 __device__ __forceinline__ double block_sum(double v, double *sh) {
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);   // (as wave_util.h: wave_sum, kept in place)
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) sh[w] = v;
     __syncthreads();
@@ -359,18 +352,18 @@ int segment_sum_launch(const float *rows, int dim, int row_stride, const int32_t
     if (!rowptr || !out || dim < 1 || row_stride < dim || out_stride < dim || n_seg < 0)
         return fail(GNNTRK_EINVAL, "segment_sum: bad argument");
     if (rows && dim == 4 && row_stride == 4 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0) {
-        hipLaunchKernelGGL(segment_sum4_kernel, dim3(stream_grid(n_seg)), dim3(kTpb), 0, stream, rows,
+        hipLaunchKernelGGL(segment_sum4_kernel, dim3(blocks_for(n_seg, 8)), dim3(kTpb), 0, stream, rows,
                            rowptr, pos, n_seg, out, out_stride, accumulate);
         return check_launch("segment_sum");
     }
     if (rows && dim % 4 == 0 && row_stride % 4 == 0 && out_stride % 4 == 0 &&
         ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(out)) & 15) == 0) {
-        hipLaunchKernelGGL(segment_sum_v4_kernel, dim3(stream_grid(n_seg * (dim / 4))), dim3(kTpb), 0, stream,
+        hipLaunchKernelGGL(segment_sum_v4_kernel, dim3(blocks_for(n_seg * (dim / 4), 8)), dim3(kTpb), 0, stream,
                            reinterpret_cast<const float4 *>(rows), dim / 4, row_stride / 4, rowptr, pos, n_seg,
                            reinterpret_cast<float4 *>(out), out_stride / 4, accumulate);
         return check_launch("segment_sum");
     }
-    hipLaunchKernelGGL(segment_sum_kernel, dim3(stream_grid(n_seg * dim)), dim3(kTpb), 0, stream,
+    hipLaunchKernelGGL(segment_sum_kernel, dim3(blocks_for(n_seg * dim, 8)), dim3(kTpb), 0, stream,
                        rows, dim, row_stride, rowptr, pos, n_seg, out, out_stride, accumulate);
     return check_launch("segment_sum");
 }
@@ -380,7 +373,7 @@ int permute_rows_launch(const float *in, int dim, int in_stride, const int32_t *
     if (n_rows == 0) return GNNTRK_OK;  // empty tensors may carry NULL pointers
     if (!in || !idx || !out || dim < 1 || in_stride < dim || out_stride < dim || n_rows < 0)
         return fail(GNNTRK_EINVAL, "permute_rows: bad argument");
-    hipLaunchKernelGGL(permute_rows_kernel, dim3(stream_grid(n_rows * dim)), dim3(kTpb), 0, stream,
+    hipLaunchKernelGGL(permute_rows_kernel, dim3(blocks_for(n_rows * dim, 8)), dim3(kTpb), 0, stream,
                        in, dim, in_stride, idx, n_rows, out, out_stride, scatter);
     return check_launch("permute_rows");
 }
@@ -389,13 +382,13 @@ int axpby_launch(float a, const float *x, float b, const float *y, const float *
                  int64_t n, hipStream_t stream) {
     if (n == 0) return GNNTRK_OK;
     if (!x || !out || n < 0) return fail(GNNTRK_EINVAL, "axpby: bad argument");
-    hipLaunchKernelGGL(axpby_kernel, dim3(stream_grid(n)), dim3(kTpb), 0, stream, a, x, b, y, mask,
+    hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, a, x, b, y, mask,
                        out, n);
     return check_launch("axpby");
 }
 
 static int bce_grid(int64_t n) {
-    int g = stream_grid(n);
+    int g = blocks_for(n, 8);
     return g > 1024 ? 1024 : g;
 }
 
@@ -425,7 +418,7 @@ int bce_backward_launch(const float *w, const float *y, const int64_t *src_node,
     if (!w || !y || !gscale || !gw || n < 1) return fail(GNNTRK_EINVAL, "bce_backward: bad argument");
     if (thld > 0.f && (!src_node || !pt))
         return fail(GNNTRK_EINVAL, "bce_backward: pt threshold needs edge_index and pt");
-    hipLaunchKernelGGL(bce_bwd_kernel, dim3(stream_grid(n)), dim3(kTpb), 0, stream, w, y, src_node,
+    hipLaunchKernelGGL(bce_bwd_kernel, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, w, y, src_node,
                        pt, thld, n, gscale, gw);
     return check_launch("bce_backward");
 }
@@ -452,10 +445,10 @@ int edge_targets_csr_launch(const void *y, int y_is_u8, const int32_t *perm, con
     if (thld > 0.f && (!src_csr || !pt))
         return fail(GNNTRK_EINVAL, "edge_targets_csr: pt threshold needs the CSR source ids and pt");
     if (y_is_u8)
-        hipLaunchKernelGGL(edge_targets_csr_kernel<uint8_t>, dim3(stream_grid(n)), dim3(kTpb), 0, stream,
+        hipLaunchKernelGGL(edge_targets_csr_kernel<uint8_t>, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream,
                            reinterpret_cast<const uint8_t *>(y), perm, src_csr, pt, thld, n, out);
     else
-        hipLaunchKernelGGL(edge_targets_csr_kernel<float>, dim3(stream_grid(n)), dim3(kTpb), 0, stream,
+        hipLaunchKernelGGL(edge_targets_csr_kernel<float>, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream,
                            reinterpret_cast<const float *>(y), perm, src_csr, pt, thld, n, out);
     return check_launch("edge_targets_csr");
 }
@@ -483,7 +476,7 @@ int focal_backward_launch(const float *w, const float *y, const int64_t *src_nod
     if (!w || !y || !gscale || !gw || n < 1) return fail(GNNTRK_EINVAL, "focal_backward: bad argument");
     if (thld > 0.f && (!src_node || !pt))
         return fail(GNNTRK_EINVAL, "focal_backward: pt threshold needs edge_index and pt");
-    hipLaunchKernelGGL(focal_bwd_kernel, dim3(stream_grid(n)), dim3(kTpb), 0, stream, w, y, src_node, pt, thld, alpha,
+    hipLaunchKernelGGL(focal_bwd_kernel, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, w, y, src_node, pt, thld, alpha,
                        gamma, pos_weight, haughty, n, gscale, gw);
     return check_launch("focal_backward");
 }

@@ -2318,6 +2318,162 @@ def case_dbscan_pruned(device, clouds=("d2", "d3", "d8"), trials=DBSCAN_TRIALS, 
         postprocessing.RADIUS_FLAGS = old
 
 
+def case_workspace_exact(device):
+    """Every workspace of the sorted-chunk units (csrc/knn.hip, dbscan.hip, oc.hip) at exactly the size its
+    gnntrk_*_workspace_bytes function states, through the raw C entries: the results equal those of a call with a
+    megabyte to spare bit for bit, 4096 guard bytes behind the stated size stay as they were, and one byte less is
+    refused with GNNTRK_EINVAL before anything is launched (the outputs keep their fill).  Shapes: the smallest with
+    more than one chunk of 64 and a partial last one, one per padded width."""
+    import ctypes as C
+
+    lib = _capi.load()
+    EINVAL, GUARD, ROOM = 1, 4096, 1 << 20
+    gen = torch.Generator().manual_seed(11)
+
+    def fresh(shape, dtype):   # an output no kernel has written: every byte 0xEE
+        numel = int(np.prod(shape)) if shape else 1
+        return torch.full((numel * torch.empty((), dtype=dtype).element_size(),), 0xEE, dtype=torch.uint8,
+                          device=device).view(dtype).reshape(shape)
+
+    def raw(t):
+        return t.contiguous().view(torch.uint8).cpu()
+
+    def check(what, sizes, run):
+        """run([(buffer, stated bytes), ...]) -> (return code, outputs made by fresh())"""
+        assert all(s > 0 for s in sizes), f"{what}: workspace sizes {sizes}"
+
+        def buffers(extra, short=None):
+            return [(torch.full((s + extra,), 0xA5, dtype=torch.uint8, device=device), s - (1 if i == short else 0))
+                    for i, s in enumerate(sizes)]
+
+        rc, want = run([(t, t.numel()) for t, _ in buffers(ROOM)])
+        assert rc == 0, f"{what} (roomy): {lib.gnntrk_last_error()}"
+        exact = buffers(GUARD)
+        rc, got = run(exact)
+        assert rc == 0, f"{what} (exact): {lib.gnntrk_last_error()}"
+        for i, (a, b) in enumerate(zip(got, want)):
+            assert torch.equal(raw(a), raw(b)), f"{what}: output {i} differs between the exact and the roomy workspace"
+        for (t, s) in exact:
+            assert bool((t[s:] == 0xA5).all()), f"{what}: wrote behind its {s} bytes"
+        for i in range(len(sizes)):
+            rc, outs = run(buffers(GUARD, short=i))
+            assert rc == EINVAL, f"{what}: workspace {i} one byte short returned {rc}"
+            for o in outs:
+                assert bool((raw(o) == 0xEE).all()), f"{what}: an output was written although the call was refused"
+        return want
+
+    # ---- pruned k-NN search (flag 1: pruned form forced)
+    n = 130
+    for dim, k in ((3, 4), (8, 16), (12, 4)):
+        x = torch.randn(n, dim, generator=gen).to(device)
+        st = ops._stream(x)
+
+        def run_knn(ws):
+            nbr, cnt = fresh((n, k), torch.int32), fresh((n,), torch.int32)
+            return lib.gnntrk_knn_search_ws(ops._p(x), n, dim, dim, k, 0.0, None, 0, ops._p(nbr), ops._p(cnt),
+                                            ops._p(ws[0][0]), ws[0][1], 1, st), (nbr, cnt)
+
+        _, cnt = check(f"knn_search_ws dim={dim} k={k}", [int(lib.gnntrk_knn_workspace_bytes(n, dim, k))], run_knn)
+        assert int(cnt.min()) == k, "fewer than k neighbours found"
+
+    # ---- pruned radius graph (points and edges workspaces) and the DBSCAN labels on it
+    for dim in (3, 8, 12):
+        x = (0.5 * torch.randn(n, dim, generator=gen)).to(device)
+        st = ops._stream(x)
+        radius = 0.5 * math.sqrt(dim)   # (about 0.7 of the typical distance of two points: a few neighbours each)
+        nbp = int(lib.gnntrk_radius_points_workspace_bytes(n, dim))
+
+        def count(ws_p, stated, cnt, off):
+            return lib.gnntrk_radius_count_ws(ops._p(x), n, dim, dim, radius, ops._p(cnt), ops._p(off), ops._p(ws_p),
+                                              stated, 1, st)
+
+        def run_count(ws):
+            cnt, off = fresh((n,), torch.int32), fresh((n + 1,), torch.int64)
+            return count(ws[0][0], ws[0][1], cnt, off), (cnt, off)
+
+        _, off = check(f"radius_count_ws dim={dim}", [nbp], run_count)
+        m = int(off[n])
+        assert m > n, "the radius graph has no edges beside the points themselves"
+
+        def run_fill(ws):   # (the count pass, which fills the chunks the fill pass reads, always gets the full size)
+            nbr, dist = fresh((m,), torch.int32), fresh((m,), torch.float64)
+            cnt2, off2 = fresh((n,), torch.int32), fresh((n + 1,), torch.int64)
+            rc = count(ws[0][0], nbp, cnt2, off2)
+            assert rc == 0, lib.gnntrk_last_error()
+            return lib.gnntrk_radius_fill_ws(ops._p(x), n, dim, dim, radius, ops._p(off), m, ops._p(nbr), ops._p(dist),
+                                             ops._p(ws[0][0]), ws[0][1], ops._p(ws[1][0]), ws[1][1], 1, st), (nbr, dist)
+
+        nbr, dist = check(f"radius_fill_ws dim={dim}", [nbp, int(lib.gnntrk_radius_edges_workspace_bytes(m))], run_fill)
+        assert bool((nbr >= 0).all()) and bool((nbr < n).all())
+
+        eps, min_pts = 0.9 * radius, 3
+        core, root = fresh((n,), torch.uint8), fresh((n,), torch.int32)
+        changed = torch.ones(1, dtype=torch.int32, device=device)
+        _capi.check(lib.gnntrk_dbscan_init(ops._p(off), ops._p(dist), n, eps, min_pts, ops._p(core), ops._p(root), st), lib)
+        for _ in range(n):
+            _capi.check(lib.gnntrk_dbscan_propagate(ops._p(off), ops._p(nbr), ops._p(dist), n, eps, ops._p(core),
+                                                    ops._p(root), 8, ops._p(changed), st), lib)
+            if int(changed.item()) == 0:
+                break
+        assert int(changed.item()) == 0
+
+        def run_labels(ws):
+            labels, n_clusters = fresh((n,), torch.int64), fresh((1,), torch.int64)
+            return lib.gnntrk_dbscan_labels(ops._p(off), ops._p(nbr), ops._p(dist), n, eps, ops._p(core), ops._p(root),
+                                            ops._p(labels), ops._p(n_clusters), ops._p(ws[0][0]), ws[0][1], st), \
+                (labels, n_clusters)
+
+        labels, n_clusters = check(f"dbscan_labels dim={dim}", [int(lib.gnntrk_dbscan_workspace_bytes(n))], run_labels)
+        assert int(n_clusters) >= 1 and int(labels.max()) == int(n_clusters) - 1
+
+    # ---- condensation losses: point selection, spatial forward and backward
+    def oc_inputs(n, dim):
+        x = (0.5 * torch.randn(n, dim, generator=gen)).to(device)
+        beta = (0.01 + 0.98 * torch.rand(n, generator=gen)).to(device)
+        pid = torch.randint(0, 12, (n,), generator=gen).to(device)   # (0: noise)
+        mask = ((pid > 0).cpu() & (torch.rand(n, generator=gen) < 0.8)).to(torch.uint8).to(device)
+        return x, beta, pid, mask
+
+    def select(ws, n, beta, pid, mask):
+        alphas, gid, n_cp = fresh((n,), torch.int32), fresh((n,), torch.int32), fresh((1,), torch.int32)
+        return lib.gnntrk_oc_select_cps(ops._p(beta), ops._p(pid), ops._p(mask), n, 0, ops._p(alphas), ops._p(gid),
+                                        ops._p(n_cp), ops._p(ws[0][0]), ws[0][1], ops._stream(beta)), (alphas, gid, n_cp)
+
+    n = 65
+    x, beta, pid, mask = oc_inputs(n, 3)
+    check("oc_select_cps", [int(lib.gnntrk_oc_select_workspace_bytes(n))], lambda ws: select(ws, n, beta, pid, mask))
+
+    n = 200
+    for dim in (3, 8):
+        x, beta, pid, mask = oc_inputs(n, dim)
+        st = ops._stream(x)
+        sel = torch.empty(int(lib.gnntrk_oc_select_workspace_bytes(n)), dtype=torch.uint8, device=device)
+        rc, (alphas, gid, n_cp) = select([(sel, sel.numel())], n, beta, pid, mask)
+        assert rc == 0 and int(n_cp) > 1
+        a = _capi.OcArgs(ops._p(x), ops._p(beta), ops._p(pid), ops._p(mask), ops._p(gid), ops._p(alphas), ops._p(n_cp),
+                         n, dim, dim, 0.01, 1.0, 1e-9, 0, 1.0, 0, 0, None)
+        nbs = int(lib.gnntrk_oc_spatial_workspace_bytes(n, dim))
+
+        def run_forward(ws):
+            out = fresh((9,), torch.float32)
+            return lib.gnntrk_oc_forward_spatial(C.byref(a), ops._p(out), ops._p(ws[0][0]), ws[0][1], st), (out,)
+
+        (fwd,) = check(f"oc_forward_spatial dim={dim}", [nbs], run_forward)
+        assert float(fwd[7]) > 0, "no repulsive pairs: the comparison is vacuous"
+        g = torch.tensor([1.0, 2.0, 0.25, 0.5], device=device)
+
+        def run_backward(ws):   # (the forward, which fills the buffer the backward reads, always gets the full size)
+            out = fresh((9,), torch.float32)
+            rc = lib.gnntrk_oc_forward_spatial(C.byref(a), ops._p(out), ops._p(ws[0][0]), nbs, st)
+            assert rc == 0, lib.gnntrk_last_error()
+            gx, gbeta = fresh((n, dim), torch.float32), fresh((n,), torch.float32)
+            return lib.gnntrk_oc_backward_spatial(C.byref(a), ops._p(g), ops._p(fwd), ops._p(gx), ops._p(gbeta), n,
+                                                  ops._p(ws[0][0]), ws[0][1], st), (gx, gbeta)
+
+        gx, gbeta = check(f"oc_backward_spatial dim={dim}", [nbs], run_backward)
+        assert bool(torch.isfinite(gx).all()) and bool(torch.isfinite(gbeta).all()) and float(gx.abs().max()) > 0
+
+
 def case_full_size_properties(device, n_events=32, n_nodes=150_000, n_edges=2_000_000, n_hits=200_000):
     """BASELINE.json's full sizes (cfg3: 32 events x 150 k hits x 2 M edges collated; cfg5:
     200 k hits), checked through properties that do not need an oracle run of that size:

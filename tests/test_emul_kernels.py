@@ -147,6 +147,11 @@ def test_graph_cut_emulated():
         P.case_graph_cut("cpu")
 
 
+def test_workspace_exact_emulated():
+    with emulated():
+        P.case_workspace_exact("cpu")
+
+
 def test_dbscan_emulated():
     with emulated():
         P.case_dbscan("cpu")

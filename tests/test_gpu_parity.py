@@ -211,6 +211,10 @@ def test_graph_cut(dev):
     P.case_graph_cut(dev, big=3_000_000)
 
 
+def test_workspace_exact(dev):
+    P.case_workspace_exact(dev)
+
+
 def test_dbscan(dev):
     P.case_dbscan(dev)
     P.case_dbscan_pruned(dev, n_big=30000)
