@@ -53,6 +53,26 @@ template <int W, int... Rest, class F> void dispatch_dp(int dim, F &&f) {
     }
 }
 
+// The same for the instantiation lists of the fused-MLP launchers.  tag<T>: a type as a value, what a visitor of a
+// class list hands to its callback.  lift_*: a run-time value to a compile-time constant over an EXPLICIT list of
+// allowed values - f(int_c<V>{}) for the V equal to v; false if v is not in the list (no instantiation).
+template <class T> struct tag { using type = T; };
+template <int... Vs, class F> bool lift_int(int v, F &&f) { return ((v == Vs && (f(int_c<Vs>{}), true)) || ...); }
+template <int A, int B> struct int2_c { static constexpr int a = A, b = B; };
+template <class... Ps, class F> bool lift_int2(int a, int b, F &&f) {
+    return ((a == Ps::a && b == Ps::b && (f(Ps{}), true)) || ...);
+}
+// f(c1, c2, ...) with every run-time flag as std::true_type / std::false_type
+template <class F> void lift_bools(F &&f) { f(); }
+template <class F, class... B> void lift_bools(F &&f, bool b, B... rest) {
+    if (b) lift_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else lift_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+// one kernel launch without dynamic LDS (the arguments are copied into the kernel's parameter types)
+template <class K, class... A> void launch(K kfn, int grid, int block, hipStream_t stream, const A &...args) {
+    hipLaunchKernelGGL(kfn, dim3(grid), dim3(block), 0, stream, args...);
+}
+
 // guards of the entries that index hits in int32 tables: "<entry>: negative <what> count" (EINVAL),
 // "<entry>: <n> <what>s; at most 2^30-1" (EUNSUPPORTED)
 int check_count_i30(const char *entry, const char *what, int64_t n);
@@ -131,8 +151,8 @@ int mlp_forward_bf16_launch(const gnntrk_mlp_fwd_args *a, hipStream_t stream);
 // hidden width 128 with biases (eight hidden tiles, accumulator-initialised biases): mlp_bf16_bi8.hip
 struct SlotPlan;
 int launch_fwd16_bi8(const gnntrk_mlp_fwd_args *a, const SlotPlan &P, int grid, hipStream_t stream);
-int launch_bwd16_bi8(const gnntrk_mlp_bwd_args *a, const SlotPlan &P, int GT, int g32, int grid, float *part,
-                     uint8_t *trash, hipStream_t stream);
+int launch_bwd16_bi8(const gnntrk_mlp_bwd_args *a, const SlotPlan &P, int GT, int grid, float *part, uint8_t *trash,
+                     hipStream_t stream);
 size_t mlp_backward_bf16_ws_bytes(const gnntrk_mlp *m);
 int mlp_backward_bf16_launch(const gnntrk_mlp_bwd_args *a, void *ws, size_t ws_bytes, hipStream_t stream);
 int mlp_backward_bf16_max_terms(const gnntrk_mlp_bwd_args *a);

@@ -15,7 +15,6 @@
 //
 // Weights are packed once per workgroup into LDS as ready-to-use A fragments.
 // Bound: fp32 matrix pipe (157 TF) for hidden width 40; see DESIGN.md.
-#include <atomic>
 #include "tile_mlp.h"
 
 #include "host_util.h"
@@ -753,16 +752,6 @@ static int count_items(int n_seg, const gnntrk_seg *seg) {
     return n;
 }
 
-static int grid_for(int64_t n_rows, int blocks_per_cu, int waves = kWaves) {
-    const int64_t tiles = (n_rows + kTileRows - 1) / kTileRows;
-    int64_t g = (tiles + waves - 1) / waves;
-    const int64_t cap = (int64_t)cu_count() * blocks_per_cu;
-    if (g > cap) g = cap;
-    if (g >= 8) g -= g % 8;  // XCD-aware schedule wants a multiple of 8
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 constexpr int kBwdWavesPerCu = 8;  // static: 1 block of 8 waves; generic: 2 blocks of 4
 constexpr int kFwdBlocksPerCu = 4;
 
@@ -849,46 +838,26 @@ int mlp_forward_launch(const gnntrk_mlp_fwd_args *a, hipStream_t stream) {
     int kt = (a->mlp.in_dim + 15) / 16;
     const int ht = (a->mlp.hidden + 15) / 16;
     while (4 * kt + 4 < n_items) ++kt;  // the load list of an instantiation holds 4*KT+4 items
-    int grid = grid_for(a->n_rows, kFwdBlocksPerCu);
-    // (the persistent grid of an instantiation = its resident workgroups, asked of the runtime once per instantiation:
-    //  the static shapes hold 124-156 registers = three, not four, workgroups per CU - see mlp_bf16_fwd.hip)
-#define GNNTRK_FWD32_GRID(kfn_)  /* (occupancy cached per DEVICE ordinal, atomically: launch threads race, devices differ) */ \
-    {                                                                                   \
-        static std::atomic<int> occ_dev_[16];                                           \
-        int dev_ = 0;                                                                   \
-        (void)hipGetDevice(&dev_);                                                      \
-        std::atomic<int>& slot_ = occ_dev_[dev_ & 15];                                  \
-        int occ_ = slot_.load(std::memory_order_relaxed);                               \
-        if (occ_ <= 0) {                                                                \
-            int o_ = 0;                                                                 \
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o_, kfn_, kBlock, 0) != hipSuccess || o_ < 1) \
-                o_ = kFwdBlocksPerCu;                                                 \
-            occ_ = o_ > 8 ? 8 : o_;                                                     \
-            slot_.store(occ_, std::memory_order_relaxed);                               \
-        }                                                                               \
-        grid = grid_for(a->n_rows, occ_);                                                       \
-    }
+    // (the persistent grid of an instantiation = its resident workgroups, tile_mlp.h: the static shapes hold 124-156
+    //  registers = three, not four, workgroups per CU)
     const int ksh = make_dimmap(a->mlp.hidden).ks, kso = make_dimmap(a->mlp.out_dim).ks;
     const bool three = a->mlp.n_layers == 3;
     // static instantiations need their own load-list capacity
     const int ksi = (n_items <= 4 * ((a->mlp.in_dim + 15) / 16) + 4) ? make_dimmap(a->mlp.in_dim).ks : -1;
 #define CALL_FWD_S(KSI, KSH, KSO, THREE, NIT)                                                  \
     if (!done_ && ksi == KSI && ksh == KSH && kso == KSO && three == THREE && n_items <= NIT) { \
-        auto kfn = mlp_fwd_kernel<(KSI + 3) / 4, (KSH + 3) / 4, StaticDims<KSI, KSH, KSO, THREE, NIT>>; \
-        GNNTRK_FWD32_GRID(kfn)                                                                  \
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a);                       \
+        constexpr auto kfn = mlp_fwd_kernel<(KSI + 3) / 4, (KSH + 3) / 4, StaticDims<KSI, KSH, KSO, THREE, NIT>>; \
+        launch(kfn, tile_grid(a->n_rows, resident_blocks<kfn>(kFwdBlocksPerCu)), kBlock, stream, *a); \
         done_ = true;                                                                           \
     }
 #define CALL_FWD_D(K, H)                                                                \
     {                                                                                   \
-        auto kfn = mlp_fwd_kernel<K, H, DynDims>;                                       \
-        GNNTRK_FWD32_GRID(kfn)                                                          \
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a);               \
+        constexpr auto kfn = mlp_fwd_kernel<K, H, DynDims>;                             \
+        launch(kfn, tile_grid(a->n_rows, resident_blocks<kfn>(kFwdBlocksPerCu)), kBlock, stream, *a); \
     }
     GNNTRK_DISPATCH(CALL_FWD_S, CALL_FWD_D)
 #undef CALL_FWD_S
 #undef CALL_FWD_D
-#undef GNNTRK_FWD32_GRID
     return check_launch("mlp_forward");
 }
 
@@ -934,7 +903,7 @@ int mlp_backward_launch(const gnntrk_mlp_bwd_args *a, void *ws, size_t ws_bytes,
         while (4 * kt + 4 < n_items) ++kt;
         const bool is_static = static_shape(ksi0, ksh0, kso0, a->mlp.n_layers == 3, n_items);
         wpb = is_static ? 8 : 4;
-        grid = grid_for(a->n_rows, is_static ? 1 : 2, wpb);
+        grid = tile_grid(a->n_rows, is_static ? 1 : 2, wpb);
         float *part = reinterpret_cast<float *>(ws);
         const int ksi = ksi0, ksh = ksh0, kso = kso0;
         const bool three = a->mlp.n_layers == 3;

@@ -6,8 +6,8 @@
 
 namespace gnntrk {
 
-int launch_bwd16_g32(const gnntrk_mlp_bwd_args *a, const SlotPlan &P, int GT, int grid, int grid_buf, int *used, float *part,
-                     uint8_t *trash, hipStream_t stream, const gnntrk_head_bce *bce);  // mlp_bf16_g32.hip
+int launch_bwd16_g32(const gnntrk_mlp_bwd_args *a, const SlotPlan &P, float *part, uint8_t *trash, hipStream_t stream,
+                     const gnntrk_head_bce *bce, int *grid_out);  // mlp_bf16_g32.hip
 
 
 int mlp16_kernel_name(const gnntrk_mlp *m, int n_seg, const gnntrk_seg *seg, int backward, char *buf,
@@ -22,40 +22,21 @@ int mlp16_kernel_name(const gnntrk_mlp *m, int n_seg, const gnntrk_seg *seg, int
     return GNNTRK_OK;
 }
 
-// exact backward instantiation (needs the gradient slices and the epilogue)
+// exact backward instantiation (needs the gradient slices and the epilogue): the selection of the launcher, printed
 int mlp16_bwd_kernel_name(const gnntrk_mlp_bwd_args *a, char *buf, size_t len) {
     if (!a || !buf || len == 0) return fail(GNNTRK_EINVAL, "mlp_kernel_name: bad argument");
     SlotPlan P;
     make_slot_plan(P, a->mlp, a->n_seg, a->seg, a->gseg);
-    const int GT = (P.GT == 0 && P.KI == 1) ? 0 : (P.GT <= 1) ? 1 : 2 * P.KI;  // 0: no input gradient wanted
-    const int D = (P.KI == 1 && P.HT <= 3 && !(a->debug_flags & 64)) ? 2 : 1;  // as launch_bwd16 dispatches
-    const bool g32 = a->epilogue == GNNTRK_EPI_SIGMOID;
-    if (a->mlp.out_dim > 16 || P.KI > 2) {
-        snprintf(buf, len, "mlp16_bwd_ot_kernel<%d, %d, %d, %s>", P.KI, P.HT, (a->mlp.out_dim + 15) / 16,
-                 a->mlp.n_layers == 3 ? "true" : "false");
-        return GNNTRK_OK;
-    }
-    if (P.bias_init) {
-        snprintf(buf, len, "mlp16_bwd_bi_kernel<%d, %d, %d, %s, %s>", P.KI, P.HT, GT,
-                 a->mlp.n_layers == 3 ? "true" : "false", g32 ? "true" : "false");
-        return GNNTRK_OK;
-    }
     BufPlan B;
-    make_buf_plan(B, P, a, GT);
-    const char *io = buf_io_name(B, P.KI, P.HT, GT, a->mlp.n_layers == 3, g32, a->debug_flags, a->epilogue);
-    // (as rocprofv3 prints the instantiation: a template argument that itself ends in '>' is followed by a space)
-    // (as rocprofv3 prints the class: the fold flag is a template argument, the launch tables use comma-free aliases)
-    const char *ion = !io[0] ? "IoNone"
-                      : !strcmp(io, "IoRelational<2>") ? "IoRelational<2, false>"
-                      : !strcmp(io, "IoRelational<3>") ? "IoRelational<3, false>"
-                      : !strcmp(io, "IoRelationalF2") ? "IoRelational<2, true>"
-                      : !strcmp(io, "IoRelationalF3") ? "IoRelational<3, true>"
-                      : !strcmp(io, "IoHead") ? "IoHeadT<false>"
-                      : !strcmp(io, "IoHeadF") ? "IoHeadT<true>"
-                      : io;
-    snprintf(buf, len, "mlp16_bwd_kernel<%d, %d, %d, %s, %s, %d, %s%s>", P.KI, P.HT, GT,
-             a->mlp.n_layers == 3 ? "true" : "false", g32 ? "true" : "false", D, ion,
-             ion[strlen(ion) - 1] == '>' ? " " : "");
+    const Bwd16Sel S = bwd16_select(a, P, B);
+    const char *three = S.three ? "true" : "false", *g32 = S.g32 ? "true" : "false";
+    if (S.kind == Bwd16Sel::kOt)
+        snprintf(buf, len, "mlp16_bwd_ot_kernel<%d, %d, %d, %s>", S.KI, S.HT, S.OT, three);
+    else if (S.kind == Bwd16Sel::kBi8 || S.kind == Bwd16Sel::kBi)
+        snprintf(buf, len, "mlp16_bwd_bi_kernel<%d, %d, %d, %s, %s>", S.KI, S.HT, S.GT, three, g32);
+    else   // (as rocprofv3 prints the instantiation: a template argument that itself ends in '>' is followed by a space)
+        snprintf(buf, len, "mlp16_bwd_kernel<%d, %d, %d, %s, %s, %d, %s%s>", S.KI, S.HT, S.GT, three, g32, S.D, S.io_name,
+                 S.io_name[strlen(S.io_name) - 1] == '>' ? " " : "");
     return GNNTRK_OK;
 }
 
@@ -66,7 +47,6 @@ int mlp_backward_bf16_max_terms(const gnntrk_mlp_bwd_args *a) {
     SlotPlan P;
     make_slot_plan(P, a->mlp, a->n_seg, a->seg, a->gseg);
     if (!P.ok || P.KI != 1) return 2;
-    const int GT = (P.GT == 0) ? 0 : (P.GT <= 1) ? 1 : 2;
     gnntrk_mlp_bwd_args b = *a;
     while (b.n_gout < 3) {   // probe with stand-in terms: rows of the tile, sized like the first term
         b.gout[b.n_gout] = b.gout[0];
@@ -75,35 +55,30 @@ int mlp_backward_bf16_max_terms(const gnntrk_mlp_bwd_args *a) {
         b.n_gout += 1;
     }
     BufPlan B;
-    make_buf_plan(B, P, &b, GT);
-    const char *io = buf_io_name(B, P.KI, P.HT, GT, a->mlp.n_layers == 3, false, a->debug_flags, a->epilogue);
-    return (io[0] && B.n_gout == 3) ? 3 : 2;
+    const Bwd16Sel S = bwd16_select(&b, P, B);
+    return (S.kind == Bwd16Sel::kBuf && S.terms == 3) ? 3 : 2;
 }
 
 // 1 if the launch described by `a` (fold block filled in) runs on an instantiation that folds inside the kernel
 int mlp_backward_bf16_can_fold(const gnntrk_mlp_bwd_args *a) {
     if (!a || !a->fold.ids || a->fold.seg < 0 || a->fold.seg >= a->n_seg || a->n_rows <= 0 || a->n_rows > 0x7fffffff ||
-        a->n_gout < 1 || a->n_gout > 3 || (a->debug_flags & (64 | 128)))
+        a->n_gout < 1 || a->n_gout > 3)
         return 0;
     SlotPlan P;
     make_slot_plan(P, a->mlp, a->n_seg, a->seg, a->gseg);
-    if (!P.ok || P.KI != 1 || P.bias_init || a->mlp.out_dim > 16) return 0;
-    const int GT = (P.GT == 0) ? 0 : (P.GT <= 1) ? 1 : 2;
+    if (!P.ok) return 0;
     BufPlan B;
-    make_buf_plan(B, P, a, GT);
-    const char *io = buf_io_name(B, P.KI, P.HT, GT, a->mlp.n_layers == 3, a->epilogue == GNNTRK_EPI_SIGMOID, a->debug_flags,
-                                 a->epilogue);
-    return (io[0] && B.fold_on) ? 1 : 0;
+    const Bwd16Sel S = bwd16_select(a, P, B);
+    return (S.kind == Bwd16Sel::kBuf && S.fold) ? 1 : 0;
 }
 
 // workspace = one partial block per wave | one 8-byte trash slot per lane
-constexpr int kBwd16MaxWaves = kBwd16BufWaves > kWaves ? kBwd16BufWaves : kWaves;
 static size_t bwd16_partial_bytes(const gnntrk_mlp *m) {
-    return align_up((size_t)cu_count() * kBwd16BlocksPerCuMax * kBwd16MaxWaves * (size_t)part_total(*m) * sizeof(float), 256);
+    return align_up((size_t)cu_count() * kBwd16BlocksPerCuMax * kWaves * (size_t)part_total(*m) * sizeof(float), 256);
 }
 size_t mlp_backward_bf16_ws_bytes(const gnntrk_mlp *m) {
     if (!m) return 0;
-    return bwd16_partial_bytes(m) + (size_t)cu_count() * kBwd16BlocksPerCuMax * kBwd16MaxWaves * 64 * 8;
+    return bwd16_partial_bytes(m) + (size_t)cu_count() * kBwd16BlocksPerCuMax * kWaves * 64 * 8;
 }
 
 // the launch of gnntrk_mlp_backward_bf16_bce as the shared launcher takes it: the upstream term is a stand-in that
@@ -127,11 +102,9 @@ int mlp_backward_bf16_bce_supported(const gnntrk_mlp_bwd_args *a, const gnntrk_h
     if (!bce_args(a, bce, b) || b.n_seg < 1 || b.n_seg > GNNTRK_MAX_SEGS) return 0;
     SlotPlan P;
     make_slot_plan(P, b.mlp, b.n_seg, b.seg, b.gseg);
-    if (!P.ok || P.KI != 1 || P.bias_init) return 0;
-    const int GT = (P.GT == 0) ? 0 : (P.GT <= 1) ? 1 : 2;
+    if (!P.ok) return 0;
     BufPlan B;
-    make_buf_plan(B, P, &b, GT);
-    return bwd16_bce_ht(B, P, &b, GT) != 0 ? 1 : 0;
+    return bwd16_select(&b, P, B).bce ? 1 : 0;
 }
 
 int mlp16_bwd_bce_kernel_name(const gnntrk_mlp_bwd_args *a, const gnntrk_head_bce *bce, char *buf, size_t len) {
@@ -208,30 +181,19 @@ static int bwd16_launch(const gnntrk_mlp_bwd_args *a, void *ws, size_t ws_bytes,
     make_slot_plan(P, a->mlp, a->n_seg, a->seg, a->gseg);
     if (!P.ok || P.KI > kMaxChunks16 / 8)
         return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16: shape outside the instantiations (include/gnntrk.h)");
-    const bool three = a->mlp.n_layers == 3;
-    // gradient M tiles: 1 or the maximum of the k-step count (keeps the instantiation list short)
-    const bool wide_io = a->mlp.out_dim > 16 || P.KI > 2;   // output tiles / wide inputs: every gradient tile
-    const int GT = wide_io ? 2 * P.KI : (P.GT == 0 && P.KI == 1) ? 0 : (P.GT <= 1) ? 1 : 2 * P.KI;  // 0: no input gradient wanted
-    int grid = 0, waves = kWaves, used[2] = {0, kWaves};
+    int grid = 0;
     if (a->n_rows > 0) {
-        // (five / six hidden tiles: one workgroup per CU is resident - its share of the rows is simply larger)
-        const int per_cu = (P.HT >= 5 || wide_io || (P.bias_init && P.KI >= 2)) ? 1 : (GT == 0 && P.HT <= 3 && !(a->debug_flags & 1024)) ? kBwd16BlocksPerCuLight : kBwd16BlocksPerCu;
-        grid = grid16(a->n_rows, per_cu, kWaves);
-        // (the buffer-addressed kernels: workgroups of kBwd16BufWaves waves, two resident per CU)
-        const int grid_buf = grid16(a->n_rows, (kBwd16BufD == 1 && per_cu == kBwd16BlocksPerCu) ? 3 : (kBwd16BufWaves == kWaves || per_cu < kBwd16BlocksPerCu) ? per_cu : kBwd16BlocksPerCu, kBwd16BufWaves);
         float *part = reinterpret_cast<float *>(ws);
         uint8_t *trash = reinterpret_cast<uint8_t *>(ws) + bwd16_partial_bytes(&a->mlp);
-        rc = (a->epilogue == GNNTRK_EPI_SIGMOID)
-                 ? launch_bwd16_g32(a, P, GT, grid, grid_buf, used, part, trash, stream, bce)
-                 : launch_bwd16<false>(a, P, GT, grid, grid_buf, used, part, trash, stream);
+        rc = (a->epilogue == GNNTRK_EPI_SIGMOID) ? launch_bwd16_g32(a, P, part, trash, stream, bce, &grid)
+                                                 : launch_bwd16<false>(a, P, part, trash, stream, nullptr, &grid);
         if (rc) return rc;
-        grid = used[0];
-        waves = used[1];
     }
     if (want_dw) {
         // one partial block per workgroup when the parameters fit the kernel's LDS image
-        const bool via_lds = part_total(a->mlp) <= bwd16_img_dwords(P.KI, P.HT, GT, three) && P.HT <= 4 && !(a->debug_flags & 2048);
-        rc = reduce_partials_launch(reinterpret_cast<const float *>(ws), via_lds ? grid : grid * waves, &a->mlp,
+        const bool via_lds = part_total(a->mlp) <= bwd16_img_dwords(P.KI, P.HT, bwd16_gt(a, P), a->mlp.n_layers == 3) &&
+                             P.HT <= 4 && !(a->debug_flags & 2048);
+        rc = reduce_partials_launch(reinterpret_cast<const float *>(ws), via_lds ? grid : grid * kWaves, &a->mlp,
                                     a->gW, a->gb, a->accumulate_params, stream);
     }
     return rc;

@@ -4,7 +4,7 @@
     constexpr bool BUF = IO::NL > 0;
     static_assert(!kBce || (BUF && G32 && IO::kEpi == GNNTRK_EPI_SIGMOID && IO::NG == 1),
                   "BCE upstream gradient: the buffer-addressed one-column sigmoid head only");
-    constexpr int NW = bwd16_block_waves<IO>(), NT = 64 * NW;   // waves / lanes of the workgroup
+    constexpr int NW = kWaves, NT = kBlock;   // waves / lanes of the workgroup
     static_assert(!BI || (!BUF && D == 1), "accumulator-initialised biases: generic one-tile form only");
     static_assert(!BUF || KI == 1, "buffer-addressed I/O: one k-step");
     using I = BwdImg<KI, HT, GT, THREE>;

@@ -1,123 +1,71 @@
 // Forward launchers of the bf16-storage fused MLP kernels (mlp_bf16_kernels.h).  Own translation
 // unit: the forward kernels are compiled with -amdgpu-sched-strategy=max-ilp (_build.py), which
 // suits their load-heavy tile loop (edge-weight head 1.58 -> 1.39 ms) but not the backward.
-#include <atomic>
 #include "mlp_bf16_kernels.h"
 
 namespace gnntrk {
 
-// The persistent grid of an instantiation = the workgroups of it that are RESIDENT at once (asked of the runtime once
-// per instantiation: registers and LDS decide), not a fixed five per CU: a larger grid runs in rounds whose last one
-// leaves CUs idle (round 5: the hot instantiations hold 164-230 registers = two, not five, workgroups per CU).
-#define GNNTRK_FWD16_GRID(kfn_)  /* (occupancy cached per DEVICE ordinal, atomically: launch threads race, devices differ) */ \
-    {                                                                                   \
-        static std::atomic<int> occ_dev_[16];                                           \
-        int dev_ = 0;                                                                   \
-        (void)hipGetDevice(&dev_);                                                      \
-        std::atomic<int>& slot_ = occ_dev_[dev_ & 15];                                  \
-        int occ_ = slot_.load(std::memory_order_relaxed);                               \
-        if (occ_ <= 0) {                                                                \
-            int o_ = 0;                                                                 \
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o_, kfn_, kBlock, 0) != hipSuccess || o_ < 1) \
-                o_ = kFwd16BlocksPerCu;                                                 \
-            occ_ = o_ > 8 ? 8 : o_;                                                     \
-            slot_.store(occ_, std::memory_order_relaxed);                               \
-        }                                                                               \
-        grid = grid16(a->n_rows, occ_, kWaves);                                         \
-        if (grid > kFwdMaxBlocks) grid = kFwdMaxBlocks - kFwdMaxBlocks % 8;             \
+// The instantiation a forward launch takes, resolved ONCE: the launcher below lifts these values over its
+// instantiation lists, the name entry point prints them.
+struct Fwd16Sel {
+    enum Kind { kOt, kBi8, kBi, kMain } kind;   // output tiles / wide inputs | hidden 128 with biases | hidden 64 with biases | the rest
+    int KI, HT, OT, R;   // R: tiles sharing one output tile (4 / 1)
+    bool three, sig, wide;
+    int per_cu;          // workgroups per CU the grid is sized for (kMain with up to four hidden tiles: what is resident)
+};
+static Fwd16Sel fwd16_select(const gnntrk_mlp_fwd_args *a, const SlotPlan &P) {
+    Fwd16Sel S{};
+    S.KI = P.KI;
+    S.HT = P.HT;
+    S.OT = (a->mlp.out_dim + 15) / 16;
+    S.R = 1;
+    S.three = a->mlp.n_layers == 3;
+    S.sig = a->epilogue == GNNTRK_EPI_SIGMOID;
+    if (a->mlp.out_dim > 16 || P.KI > 2) {
+        S.kind = Fwd16Sel::kOt;
+        S.per_cu = P.KI > 2 ? 1 : 2;
+    } else if (P.bias_init) {
+        S.kind = P.HT == 8 ? Fwd16Sel::kBi8 : Fwd16Sel::kBi;
+        S.per_cu = P.HT == 8 ? 1 : 3;
+    } else {
+        // hidden widths 64 .. 127 (five to eight hidden tiles): the plain forms only (own output tile per tile, 8-byte
+        // loads) - four instantiations per shape instead of sixteen
+        const bool plain = P.HT >= 5;
+        S.kind = Fwd16Sel::kMain;
+        S.R = (a->mlp.out_dim <= 4 && !plain) ? 4 : 1;       // four tiles share one output tile and one store
+        S.wide = !plain && wide_ok(P, a->seg, a->n_rows);   // one 16-byte load per lane and k-step
+        // (five / six hidden tiles: 230 .. 330 registers per lane - two workgroups per CU are resident with one
+        //  k-step, one with two; the grid of the persistent tile schedule matches what is resident)
+        S.per_cu = plain ? ((P.KI == 1 && P.HT <= 6) ? 2 : 1) : kFwd16BlocksPerCu;
     }
-#define GNNTRK_FWD16_LAUNCH(KI_, HT_, T_, S_, R_)                                       \
-    {                                                                                   \
-        if (wide) {                                                                     \
-            auto kfn = mlp16_fwd_kernel<KI_, HT_, T_, S_, R_, true>;                    \
-            GNNTRK_FWD16_GRID(kfn)                                                      \
-            hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a);           \
-        } else {                                                                        \
-            auto kfn = mlp16_fwd_kernel<KI_, HT_, T_, S_, R_, false>;                   \
-            GNNTRK_FWD16_GRID(kfn)                                                      \
-            hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a);           \
-        }                                                                               \
-    }
-// the I/O skeleton of the two large forward shapes (three hidden tiles, shared output tile): debug_flags & 4096
-#define GNNTRK_FWD16_SKEL(S_, W_)                                                       \
-    if (!launched && (a->debug_flags & 4096) && P.KI == 1 && P.HT == 3 && three && share && sig == S_ && wide == W_) { \
-        auto kfn = mlp16_fwd_skel_kernel<1, 3, true, S_, 4, W_>;                        \
-        GNNTRK_FWD16_GRID(kfn)                                                          \
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a);               \
-        launched = true;                                                                \
-    }
-#define GNNTRK_FWD16_CASE(KI_, HT_)                                                     \
-    if (!launched && P.KI == KI_ && P.HT == HT_) {                                      \
-        if (three && sig && share) GNNTRK_FWD16_LAUNCH(KI_, HT_, true, true, 4)         \
-        else if (three && sig) GNNTRK_FWD16_LAUNCH(KI_, HT_, true, true, 1)             \
-        else if (three && share) GNNTRK_FWD16_LAUNCH(KI_, HT_, true, false, 4)          \
-        else if (three) GNNTRK_FWD16_LAUNCH(KI_, HT_, true, false, 1)                   \
-        else if (sig && share) GNNTRK_FWD16_LAUNCH(KI_, HT_, false, true, 4)            \
-        else if (sig) GNNTRK_FWD16_LAUNCH(KI_, HT_, false, true, 1)                     \
-        else if (share) GNNTRK_FWD16_LAUNCH(KI_, HT_, false, false, 4)                  \
-        else GNNTRK_FWD16_LAUNCH(KI_, HT_, false, false, 1)                             \
-        launched = true;                                                                \
-    }
-
-// hidden widths 64 .. 95 (five / six hidden tiles): the plain forms only (own output tile per tile,
-// 8-byte loads) - four instantiations per shape instead of sixteen
-#define GNNTRK_FWD16_CASE_PLAIN(KI_, HT_)                                                   \
-    if (P.KI == KI_ && P.HT == HT_) {                                                       \
-        if (three && sig) { auto kfn = mlp16_fwd_kernel<KI_, HT_, true, true, 1, false>;    \
-            hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a); }             \
-        else if (three) { auto kfn = mlp16_fwd_kernel<KI_, HT_, true, false, 1, false>;     \
-            hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a); }             \
-        else if (sig) { auto kfn = mlp16_fwd_kernel<KI_, HT_, false, true, 1, false>;       \
-            hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a); }             \
-        else { auto kfn = mlp16_fwd_kernel<KI_, HT_, false, false, 1, false>;               \
-            hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a); }             \
-        launched = true;                                                                    \
-    }
-
-// hidden width 64 with biases (SlotPlan::bias_init): plain forms of the accumulator-initialised kernels
-#define GNNTRK_FWD16_CASE_BI(KI_, HT_)                                                      \
-    if (P.KI == KI_ && P.HT == HT_) {                                                       \
-        if (three && sig) { auto kfn = mlp16_fwd_bi_kernel<KI_, HT_, true, true>;           \
-            hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a); }             \
-        else if (three) { auto kfn = mlp16_fwd_bi_kernel<KI_, HT_, true, false>;            \
-            hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a); }             \
-        else if (sig) { auto kfn = mlp16_fwd_bi_kernel<KI_, HT_, false, true>;              \
-            hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a); }             \
-        else { auto kfn = mlp16_fwd_bi_kernel<KI_, HT_, false, false>;                      \
-            hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a); }             \
-        launched = true;                                                                    \
-    }
-
-// outputs of 17 .. 48 features / inputs of 65 .. 128 slots (three hidden tiles): the plain output-tile kernels
-#define GNNTRK_FWD16_CASE_OT(KI_, OT_)                                                      \
-    if (P.KI == KI_ && ot == OT_) {                                                         \
-        if (three) { auto kfn = mlp16_fwd_ot_kernel<KI_, 3, OT_, true>;                     \
-            hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a); }             \
-        else { auto kfn = mlp16_fwd_ot_kernel<KI_, 3, OT_, false>;                          \
-            hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a); }             \
-        launched = true;                                                                    \
-    }
+    return S;
+}
 
 // exact forward instantiation
 int mlp16_fwd_kernel_name(const gnntrk_mlp_fwd_args *a, char *buf, size_t len) {
     if (!a || !buf || len == 0) return fail(GNNTRK_EINVAL, "mlp_kernel_name: bad argument");
     SlotPlan P;
     make_slot_plan(P, a->mlp, a->n_seg, a->seg, nullptr);
-    const bool plain = P.HT >= 5;
-    if (a->mlp.out_dim > 16 || P.KI > 2) {
-        snprintf(buf, len, "mlp16_fwd_ot_kernel<%d, %d, %d, %s>", P.KI, P.HT, (a->mlp.out_dim + 15) / 16,
-                 a->mlp.n_layers == 3 ? "true" : "false");
-        return GNNTRK_OK;
-    }
-    if (P.bias_init) {
-        snprintf(buf, len, "mlp16_fwd_bi_kernel<%d, %d, %s, %s>", P.KI, P.HT, a->mlp.n_layers == 3 ? "true" : "false",
-                 a->epilogue == GNNTRK_EPI_SIGMOID ? "true" : "false");
-        return GNNTRK_OK;
-    }
-    snprintf(buf, len, "mlp16_fwd_kernel<%d, %d, %s, %s, %d, %s>", P.KI, P.HT, a->mlp.n_layers == 3 ? "true" : "false",
-             a->epilogue == GNNTRK_EPI_SIGMOID ? "true" : "false", (a->mlp.out_dim <= 4 && !plain) ? 4 : 1,
-             (!plain && wide_ok(P, a->seg, a->n_rows)) ? "true" : "false");
+    const Fwd16Sel S = fwd16_select(a, P);
+    const char *three = S.three ? "true" : "false", *sig = S.sig ? "true" : "false";
+    if (S.kind == Fwd16Sel::kOt)
+        snprintf(buf, len, "mlp16_fwd_ot_kernel<%d, %d, %d, %s>", S.KI, S.HT, S.OT, three);
+    else if (S.kind != Fwd16Sel::kMain)
+        snprintf(buf, len, "mlp16_fwd_bi_kernel<%d, %d, %s, %s>", S.KI, S.HT, three, sig);
+    else
+        snprintf(buf, len, "mlp16_fwd_kernel<%d, %d, %s, %s, %d, %s>", S.KI, S.HT, three, sig, S.R, S.wide ? "true" : "false");
     return GNNTRK_OK;
+}
+
+static int fwd16_grid(int64_t n_rows, int per_cu) {
+    const int grid = tile_grid(n_rows, per_cu);
+    return grid > kFwdMaxBlocks ? kFwdMaxBlocks - kFwdMaxBlocks % 8 : grid;   // (the store-redirect slots: g_fwd_trash)
+}
+// The persistent grid of an instantiation of up to four hidden tiles = the workgroups of it that are RESIDENT at once
+// (tile_mlp.h: resident_blocks), not a fixed five per CU: a larger grid runs in rounds whose last one leaves CUs idle
+// (round 5: the hot instantiations hold 164-230 registers = two, not five, workgroups per CU).
+template <auto Kfn> static void fwd16_launch_resident(const gnntrk_mlp_fwd_args *a, hipStream_t stream) {
+    launch(Kfn, fwd16_grid(a->n_rows, resident_blocks<Kfn>(kFwd16BlocksPerCu)), kBlock, stream, *a);
 }
 
 int mlp_forward_bf16_launch(const gnntrk_mlp_fwd_args *a, hipStream_t stream) {
@@ -144,50 +92,56 @@ int mlp_forward_bf16_launch(const gnntrk_mlp_fwd_args *a, hipStream_t stream) {
     make_slot_plan(P, a->mlp, a->n_seg, a->seg, nullptr);
     if (!P.ok || P.KI > kMaxChunks16 / 8)
         return fail(GNNTRK_EUNSUPPORTED, "mlp_forward_bf16: shape outside the instantiations (include/gnntrk.h)");
-    const bool three = a->mlp.n_layers == 3, sig = a->epilogue == GNNTRK_EPI_SIGMOID;
-    const bool share = a->mlp.out_dim <= 4;  // four tiles share one output tile and one store
-    const bool wide = wide_ok(P, a->seg, a->n_rows);  // one 16-byte load per lane and k-step
-    // (five / six hidden tiles: 230 .. 330 registers per lane - two workgroups per CU are resident with one
-    //  k-step, one with two; the grid of the persistent tile schedule matches what is resident)
-    int grid = grid16(a->n_rows, P.HT >= 5 ? ((P.KI == 1 && P.HT <= 6) ? 2 : 1) : kFwd16BlocksPerCu, kWaves);
-    if (grid > kFwdMaxBlocks) grid = kFwdMaxBlocks - kFwdMaxBlocks % 8;
-    bool launched = false;
-    if (a->mlp.out_dim > 16 || P.KI > 2) {
-        if (sig) return fail(GNNTRK_EUNSUPPORTED, "mlp_forward_bf16: SIGMOID epilogue with a wide input / output");
-        const int ot = (a->mlp.out_dim + 15) / 16;
-        grid = grid16(a->n_rows, P.KI > 2 ? 1 : 2, kWaves);
-        GNNTRK_FWD16_CASE_OT(1, 2) GNNTRK_FWD16_CASE_OT(1, 3)
-        GNNTRK_FWD16_CASE_OT(2, 2) GNNTRK_FWD16_CASE_OT(2, 3)
-        GNNTRK_FWD16_CASE_OT(3, 1) GNNTRK_FWD16_CASE_OT(3, 2) GNNTRK_FWD16_CASE_OT(3, 3)
-        GNNTRK_FWD16_CASE_OT(4, 1) GNNTRK_FWD16_CASE_OT(4, 2) GNNTRK_FWD16_CASE_OT(4, 3)
-        if (!launched) return fail(GNNTRK_EUNSUPPORTED, "mlp_forward_bf16: no instantiation (output tiles)");
-        return check_launch("mlp_forward_bf16");
+    const Fwd16Sel S = fwd16_select(a, P);
+    const int grid = fwd16_grid(a->n_rows, S.per_cu);
+    bool found = false;
+    switch (S.kind) {
+    case Fwd16Sel::kOt:   // outputs of 17 .. 48 features / inputs of 65 .. 128 slots (three hidden tiles): the plain output-tile kernels
+        if (S.sig) return fail(GNNTRK_EUNSUPPORTED, "mlp_forward_bf16: SIGMOID epilogue with a wide input / output");
+        found = S.HT == 3 &&
+                lift_int2<int2_c<1, 2>, int2_c<1, 3>, int2_c<2, 2>, int2_c<2, 3>, int2_c<3, 1>, int2_c<3, 2>, int2_c<3, 3>,
+                          int2_c<4, 1>, int2_c<4, 2>, int2_c<4, 3>>(S.KI, S.OT, [&](auto p) {
+                    lift_bools([&](auto three) {
+                        launch(mlp16_fwd_ot_kernel<decltype(p)::a, 3, decltype(p)::b, decltype(three)::value>, grid, kBlock, stream, *a);
+                    }, S.three);
+                });
+        if (!found) return fail(GNNTRK_EUNSUPPORTED, "mlp_forward_bf16: no instantiation (output tiles)");
+        break;
+    case Fwd16Sel::kBi8:
+        return launch_fwd16_bi8(a, P, grid, stream);
+    case Fwd16Sel::kBi:   // hidden width 64 with biases (SlotPlan::bias_init): plain forms of the accumulator-initialised kernels
+        found = lift_int2<int2_c<1, 4>, int2_c<2, 4>>(S.KI, S.HT, [&](auto p) {
+            lift_bools([&](auto three, auto sig) {
+                launch(mlp16_fwd_bi_kernel<decltype(p)::a, decltype(p)::b, decltype(three)::value, decltype(sig)::value>, grid,
+                       kBlock, stream, *a);
+            }, S.three, S.sig);
+        });
+        if (!found) return fail(GNNTRK_EUNSUPPORTED, "mlp_forward_bf16: no instantiation (bias_init)");
+        break;
+    case Fwd16Sel::kMain:
+        // the I/O skeleton of the two large forward shapes (three hidden tiles, shared output tile): debug_flags & 4096
+        if ((a->debug_flags & 4096) && S.KI == 1 && S.HT == 3 && S.three && S.R == 4 && S.sig != S.wide) {
+            if (S.wide) fwd16_launch_resident<mlp16_fwd_skel_kernel<1, 3, true, false, 4, true>>(a, stream);   // relational / object-shaped: bf16 output, 16-byte loads
+            else fwd16_launch_resident<mlp16_fwd_skel_kernel<1, 3, true, true, 4, false>>(a, stream);          // the edge-weight head: fp32 sigmoid output, 8-byte loads
+            break;
+        }
+        found = lift_int2<int2_c<1, 1>, int2_c<1, 2>, int2_c<1, 3>, int2_c<1, 4>, int2_c<2, 1>, int2_c<2, 2>, int2_c<2, 3>,
+                          int2_c<2, 4>>(S.KI, S.HT, [&](auto p) {
+            lift_bools([&](auto three, auto sig, auto share, auto wide) {
+                fwd16_launch_resident<mlp16_fwd_kernel<decltype(p)::a, decltype(p)::b, decltype(three)::value, decltype(sig)::value,
+                                                       decltype(share)::value ? 4 : 1, decltype(wide)::value>>(a, stream);
+            }, S.three, S.sig, S.R == 4, S.wide);
+        });
+        found = found || lift_int2<int2_c<1, 5>, int2_c<1, 6>, int2_c<2, 5>, int2_c<2, 6>, int2_c<1, 7>, int2_c<1, 8>>(
+                             S.KI, S.HT, [&](auto p) {
+            lift_bools([&](auto three, auto sig) {
+                launch(mlp16_fwd_kernel<decltype(p)::a, decltype(p)::b, decltype(three)::value, decltype(sig)::value, 1, false>, grid,
+                       kBlock, stream, *a);
+            }, S.three, S.sig);
+        });
+        if (!found) return fail(GNNTRK_EUNSUPPORTED, "mlp_forward_bf16: no instantiation");
+        break;
     }
-    if (P.bias_init && P.HT == 8) return launch_fwd16_bi8(a, P, grid16(a->n_rows, 1, kWaves), stream);
-    if (P.bias_init) {
-        grid = grid16(a->n_rows, 3, kWaves);
-        GNNTRK_FWD16_CASE_BI(1, 4)
-        GNNTRK_FWD16_CASE_BI(2, 4)
-        if (!launched) return fail(GNNTRK_EUNSUPPORTED, "mlp_forward_bf16: no instantiation (bias_init)");
-        return check_launch("mlp_forward_bf16");
-    }
-    GNNTRK_FWD16_SKEL(false, true)    // relational / object-shaped: bf16 output, 16-byte loads
-    GNNTRK_FWD16_SKEL(true, false)    // the edge-weight head: fp32 sigmoid output, 8-byte loads
-    GNNTRK_FWD16_CASE(1, 1)
-    GNNTRK_FWD16_CASE(1, 2)
-    GNNTRK_FWD16_CASE(1, 3)
-    GNNTRK_FWD16_CASE(1, 4)
-    GNNTRK_FWD16_CASE(2, 1)
-    GNNTRK_FWD16_CASE(2, 2)
-    GNNTRK_FWD16_CASE(2, 3)
-    GNNTRK_FWD16_CASE(2, 4)
-    GNNTRK_FWD16_CASE_PLAIN(1, 5)
-    GNNTRK_FWD16_CASE_PLAIN(1, 6)
-    GNNTRK_FWD16_CASE_PLAIN(2, 5)
-    GNNTRK_FWD16_CASE_PLAIN(2, 6)
-    GNNTRK_FWD16_CASE_PLAIN(1, 7)
-    GNNTRK_FWD16_CASE_PLAIN(1, 8)
-    if (!launched) return fail(GNNTRK_EUNSUPPORTED, "mlp_forward_bf16: no instantiation");
     return check_launch("mlp_forward_bf16");
 }
 

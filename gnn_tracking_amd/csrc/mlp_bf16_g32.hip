@@ -6,9 +6,9 @@
 
 namespace gnntrk {
 
-int launch_bwd16_g32(const gnntrk_mlp_bwd_args *a, const SlotPlan &P, int GT, int grid, int grid_buf, int *used,
-                     float *part, uint8_t *trash, hipStream_t stream, const gnntrk_head_bce *bce) {
-    return launch_bwd16<true>(a, P, GT, grid, grid_buf, used, part, trash, stream, bce);
+int launch_bwd16_g32(const gnntrk_mlp_bwd_args *a, const SlotPlan &P, float *part, uint8_t *trash, hipStream_t stream,
+                     const gnntrk_head_bce *bce, int *grid_out) {
+    return launch_bwd16<true>(a, P, part, trash, stream, bce, grid_out);
 }
 
 }  // namespace gnntrk

@@ -348,12 +348,7 @@ __device__ uint8_t g_fwd_trash[(size_t)kFwdMaxBlocks * kBlock * 16];
 // persistent grid is sized for (the two have to agree: a grid larger than what is resident runs in rounds, the last
 // one part empty).  Round 5 found the hot instantiations at 216 registers = TWO waves per SIMD under a grid of five
 // workgroups per CU (the max-ilp scheduling strategy of mlp_bf16_fwd.hip had doubled the 108 of round 1).
-#ifndef GNNTRK_FWD16_WAVES_PER_SIMD
-#define GNNTRK_FWD16_WAVES_PER_SIMD 0   // (0: no bound stated)
-#endif
-#ifndef GNNTRK_FWD16_BLOCKS_PER_CU
-#define GNNTRK_FWD16_BLOCKS_PER_CU 5
-#endif
+constexpr int kFwd16BlocksPerCu = 5;
 // (measured per instantiation, same box, alternating - tools/ab_step.sh: the two-layer encoders are fastest at four
 //  waves per SIMD (126 registers, no spill: edge encoder 0.58 -> 0.48 ms per 64 M rows), the three-layer bf16-output
 //  shapes at three (154-165 registers: relational 0.77 -> 0.76, object 0.131 -> 0.118), the edge-weight head without a
@@ -361,7 +356,6 @@ __device__ uint8_t g_fwd_trash[(size_t)kFwdMaxBlocks * kBlock * 16];
 //  and run at half speed)
 template <int KI, int HT, bool THREE, bool SIG, int R, bool WIDE>
 __host__ __device__ constexpr int fwd16_waves_per_simd() {
-    if (GNNTRK_FWD16_WAVES_PER_SIMD > 0) return HT <= 4 ? GNNTRK_FWD16_WAVES_PER_SIMD : 1;
     if (KI != 1 || HT > 3) return 1;
     if (!THREE) return (R == 4 && WIDE && !SIG) ? 4 : 3;   // (the other two-layer forms spill 4-12 registers at four)
     return SIG ? 1 : 3;
@@ -553,12 +547,12 @@ struct BufPlan {
 #ifndef GNNTRK_BWD_STATIC_GATE
 #define GNNTRK_BWD_STATIC_GATE 1   // (0: the input ReLU / relu' pattern of the buffer-addressed shapes stays a run-time value - A/B builds)
 #endif
-#ifndef GNNTRK_BWD_STATIC_EPI
-#define GNNTRK_BWD_STATIC_EPI 1   // (0: the epilogue of the buffer-addressed shapes stays a run-time value - A/B builds)
-#endif
-constexpr int kEpiOf(int e) { return GNNTRK_BWD_STATIC_EPI ? e : -1; }
+// An I/O class states, next to the shape of its accesses, the one instantiation family it stands for: kName (as a
+// profiler prints the class in a kernel name), the epilogue it is compiled for (kEpi; a run-time value of the generic
+// I/O only), the gradient tiles and layer count of its kernels (kGT, kThree: mlp16_bwd_kernel<1, HT, kGT, kThree, .., 2, IO>).
 
 struct IoNone {   // the generic per-lane I/O
+    static constexpr const char *kName = "IoNone";
     static constexpr bool kFold = false;
     static constexpr uint32_t kFoldPart = 0;
     static constexpr int kFoldStream = 0;
@@ -573,7 +567,10 @@ struct IoNone {   // the generic per-lane I/O
 // FOLD_ (round 6, gnntrk_gfold): g_x_i leaves the kernel summed per target node - its per-row store is gone
 template <int NG_, bool FOLD_ = false>   // NG_ = 3: a third upstream term on the tile's rows (the edge-weight head's share, see ops_bf16.grad_tap)
 struct IoRelational {
-    static constexpr int kEpi = kEpiOf(GNNTRK_EPI_NONE);
+    static constexpr const char *kName = NG_ == 3 ? (FOLD_ ? "IoRelational<3, true>" : "IoRelational<3, false>")
+                                                  : (FOLD_ ? "IoRelational<2, true>" : "IoRelational<2, false>");
+    static constexpr int kEpi = GNNTRK_EPI_NONE, kGT = 2;
+    static constexpr bool kThree = true;
     static constexpr bool kFold = FOLD_;
     static constexpr uint32_t kFoldPart = 0b0011;
     static constexpr int kFoldStream = 0;   // x_i is gathered through the first id stream (the CSR targets)
@@ -585,15 +582,15 @@ struct IoRelational {
                                 kE = {0, 0, -1, -1, 0b0001, 0, 1, 0};
     static constexpr BufOpShape store[3] = {FOLD_ ? kXj : kXi, FOLD_ ? kE : kXj, FOLD_ ? BufOpShape{} : kE};
 };
-using IoRelationalF2 = IoRelational<2, true>;   // (names without a comma: the launch macros take them as one argument)
-using IoRelationalF3 = IoRelational<3, true>;
 // object model (interaction_network.py:92-103): x (16-byte rows) | aggr (8-byte rows), all rows of
 // the tile; one upstream term; gradient slices g_x, g_aggr
 struct IoObject {
+    static constexpr const char *kName = "IoObject";
     static constexpr bool kFold = false;
     static constexpr uint32_t kFoldPart = 0;
     static constexpr int kFoldStream = 0;
-    static constexpr int kEpi = kEpiOf(GNNTRK_EPI_RESIDUAL);
+    static constexpr int kEpi = GNNTRK_EPI_RESIDUAL, kGT = 1;
+    static constexpr bool kThree = true;
     static constexpr int NL = 2, NI = 0, NSI = 0, NS = 2, NG = 1, kOnesDword = 2;
     static constexpr BufOpShape load[2] = {{1, 0, -1, -1, 0b0001, 0, 0, 0}, {0, 0, -1, -1, 0b0010, 0, 0, 0}};
     static constexpr BufOpShape gout[1] = {{0, 0, -1, -1, 0b0011, 0, 0, 0}};
@@ -605,7 +602,9 @@ struct IoObject {
 // g_e0 .. g_e3
 template <bool FOLD_ = false>   // FOLD_: g_h[tgt] leaves the kernel summed per target node (gnntrk_gfold)
 struct IoHeadT {
-    static constexpr int kEpi = kEpiOf(GNNTRK_EPI_SIGMOID);
+    static constexpr const char *kName = FOLD_ ? "IoHeadT<true>" : "IoHeadT<false>";
+    static constexpr int kEpi = GNNTRK_EPI_SIGMOID, kGT = 2;
+    static constexpr bool kThree = true;
     static constexpr bool kFold = FOLD_;
     static constexpr uint32_t kFoldPart = 0b1100;
     static constexpr int kFoldStream = 1;   // h[src] | h[tgt]: the targets are the second id stream
@@ -620,48 +619,36 @@ struct IoHeadT {
     static constexpr BufOpShape store[6] = {kHs, FOLD_ ? kE0 : kHt, FOLD_ ? kE1 : kE0, FOLD_ ? kE2 : kE1,
                                             FOLD_ ? kE3 : kE2, FOLD_ ? BufOpShape{} : kE3};
 };
-using IoHead = IoHeadT<false>;
-using IoHeadF = IoHeadT<true>;
 // bias-free encoder of 8-byte rows (edge_classifier.py:66-69 on the four edge features): one tensor,
 // rows of the tile, weight gradients only
 template <int NG_>
 struct IoEncoder8 {
+    static constexpr const char *kName = NG_ == 2 ? "IoEncoder8<2>" : "IoEncoder8<1>";
     static constexpr bool kFold = false;
     static constexpr uint32_t kFoldPart = 0;
     static constexpr int kFoldStream = 0;
-    static constexpr int kEpi = kEpiOf(GNNTRK_EPI_RELU);
+    static constexpr int kEpi = GNNTRK_EPI_RELU, kGT = 0;
+    static constexpr bool kThree = false;
     static constexpr int NL = 1, NI = 0, NSI = 0, NS = 0, NG = NG_, kOnesDword = -1;
     static constexpr BufOpShape load[1] = {{0, 0, -1, -1, 0b0001, 0, 0, 0}};
     static constexpr BufOpShape gout[2] = {{0, 0, -1, -1, 0b0001, 0, 0, 0}, {0, 0, -1, -1, 0b0001, 0, 0, 0}};
     static constexpr BufOpShape store[1] = {};
 };
 
-// Waves per workgroup of the buffer-addressed backward kernels (the hot shapes).  A workgroup is one fragment image
-// + one staging image per wave (9.2 KB with D = 2): four waves (60 KB) give two workgroups = 2 waves per SIMD on
-// a CU; six waves (79 KB) would still be two workgroups = 3 waves per SIMD - but the kernels hold 202 - 206
-// registers, and at the 168 of three waves per SIMD they spill 33 (relational) / 83 (head)
-// registers into the tile loop: measured 6.76 against 2.88 ms and 9.88 against 3.67 ms per 64 M rows (round 4,
-// tools/bench_bwd_io.py).  The occupancy of these kernels is set by registers AND LDS; the switch stays for A/B.
-#ifndef GNNTRK_BWD16_BUF_WAVES
-#define GNNTRK_BWD16_BUF_WAVES 4
-#endif
-constexpr int kBwd16BufWaves = GNNTRK_BWD16_BUF_WAVES;
-// Tiles per iteration of the buffer-addressed kernels (2: K = 32 weight-gradient contractions over two 16-row
-// halves; 1: half the per-wave state and staging - 162 registers, 42 KB: three workgroups per CU = 3 waves per
-// SIMD without a spill.  Measured SLOWER, round 4: relational 2.83-2.89 against 2.71 ms, head 3.57 against 3.30 per
-// 64 M rows on one box, alternating - a third wave does not pay for half-used weight-gradient MFMAs and the
-// per-tile overheads no longer shared by two tiles.  A/B switch.)
-#ifndef GNNTRK_BWD16_BUF_D
-#define GNNTRK_BWD16_BUF_D 2
-#endif
-constexpr int kBwd16BufD = GNNTRK_BWD16_BUF_D;
-template <class IO>
-__host__ __device__ constexpr int bwd16_block_waves() {
-    return IO::NL > 0 ? kBwd16BufWaves : kWaves;
-}
+// Waves per workgroup of the buffer-addressed backward kernels (the hot shapes): kWaves, like the rest.  A workgroup
+// is one fragment image + one staging image per wave (9.2 KB with D = 2): four waves (60 KB) give two workgroups = 2
+// waves per SIMD on a CU; six waves (79 KB) would still be two workgroups = 3 waves per SIMD - but the kernels hold
+// 202 - 206 registers, and at the 168 of three waves per SIMD they spill 33 (relational) / 83 (head) registers into
+// the tile loop: measured 6.76 against 2.88 ms and 9.88 against 3.67 ms per 64 M rows (round 4,
+// tools/bench_bwd_io.py).  The occupancy of these kernels is set by registers AND LDS.
+// Tiles per iteration of the buffer-addressed kernels: D = 2 (K = 32 weight-gradient contractions over two 16-row
+// halves).  D = 1 is half the per-wave state and staging - 162 registers, 42 KB: three workgroups per CU = 3 waves
+// per SIMD without a spill - and was measured SLOWER, round 4: relational 2.83-2.89 against 2.71 ms, head 3.57
+// against 3.30 per 64 M rows on one box, alternating - a third wave does not pay for half-used weight-gradient MFMAs
+// and the per-tile overheads no longer shared by two tiles.
 
 template <int KI, int HT, int GT, bool THREE, bool G32, int D_, class IO_ = IoNone>
-__global__ __launch_bounds__(64 * bwd16_block_waves<IO_>(), HT >= 5 ? 1 : ((IO_::NL > 0 && D_ == 1) ? 3 : 2) * bwd16_block_waves<IO_>() / 4) void mlp16_bwd_kernel(const gnntrk_mlp_bwd_args a, float *part,
+__global__ __launch_bounds__(kBlock, HT >= 5 ? 1 : 2) void mlp16_bwd_kernel(const gnntrk_mlp_bwd_args a, float *part,
                                                                            uint8_t *trash, const BufPlan bp) {
     constexpr int D = D_, OT = 1, kSkel = 0;
     using IO = IO_;
@@ -670,15 +657,15 @@ __global__ __launch_bounds__(64 * bwd16_block_waves<IO_>(), HT >= 5 ? 1 : ((IO_:
 #include "mlp_bf16_bwd_body.inc"
 }
 // The edge-weight head's backward that forms its own upstream gradient (gnntrk_mlp_backward_bf16_bce): the
-// instantiation <1, HT, 2, true, true, D, IoHead> of the kernel above with the BCE arm of stage S1 compiled in.  A
+// instantiation <1, HT, 2, true, true, D, IoHeadT<false>> of the kernel above with the BCE arm of stage S1 compiled in.  A
 // kernel of its own, not a run-time branch of that instantiation: the fp32-upstream launch keeps its code object
 // (235 registers, two waves per SIMD - a second S1 arm in the same loop would have to fit beside it), and the
 // label / W traffic rides on the descriptor and prefetch slot the upstream term has there.
 template <int HT>
-__global__ __launch_bounds__(64 * bwd16_block_waves<IoHead>(), 2 * bwd16_block_waves<IoHead>() / 4) void mlp16_bwd_bce_kernel(
+__global__ __launch_bounds__(kBlock, 2) void mlp16_bwd_bce_kernel(
     const gnntrk_mlp_bwd_args a, float *part, uint8_t *trash, const BufPlan bp, const gnntrk_head_bce bce) {
     constexpr int KI = 1, GT = 2, D = 2, OT = 1, kSkel = 0;
-    using IO = IoHead;
+    using IO = IoHeadT<false>;
     constexpr bool THREE = true, G32 = true, BI = false, kBce = true;
 #include "mlp_bf16_bwd_body.inc"
 }
@@ -688,7 +675,7 @@ __global__ __launch_bounds__(64 * bwd16_block_waves<IoHead>(), 2 * bwd16_block_w
 // kernel at its occupancy, whatever the instruction stream does (bench.py: roofline.access_floor; round 5
 // measured 2.52 of 2.75 ms for the relational shape on shuffled node ids, 1.35 ms on sequential ones).
 template <int KI, int HT, int GT, bool THREE, bool G32, int D_, class IO_>
-__global__ __launch_bounds__(64 * bwd16_block_waves<IO_>(), 2 * bwd16_block_waves<IO_>() / 4) void mlp16_bwd_skel_kernel(
+__global__ __launch_bounds__(kBlock, 2) void mlp16_bwd_skel_kernel(
     const gnntrk_mlp_bwd_args a, float *part, uint8_t *trash, const BufPlan bp) {
     constexpr int D = D_, OT = 1, kSkel = 128;
     using IO = IO_;
@@ -740,16 +727,6 @@ int check_bf16_mlp(const gnntrk_mlp &m, int n_seg, const gnntrk_seg *seg, const 
         if (!m.W[i]) return fail(GNNTRK_EINVAL, "mlp(bf16): NULL weight pointer");
     (void)who;
     return GNNTRK_OK;
-}
-
-int grid16(int64_t n_rows, int blocks_per_cu, int waves) {
-    const int64_t tiles = (n_rows + kTileRows - 1) / kTileRows;
-    int64_t g = (tiles + waves - 1) / waves;
-    const int64_t cap = (int64_t)cu_count() * blocks_per_cu;
-    if (g > cap) g = cap;
-    if (g >= 8) g -= g % 8;
-    if (g < 1) g = 1;
-    return (int)g;
 }
 
 // ---- host: the buffer-addressed form of a backward launch (see BufPlan) ------------------------
@@ -943,7 +920,6 @@ inline bool buf_plan_is(const BufPlan &B) {
     return true;
 }
 
-constexpr int kFwd16BlocksPerCu = GNNTRK_FWD16_BLOCKS_PER_CU;
 constexpr int kBwd16BlocksPerCu = 2;
 // weight-gradient-only launches (GT = 0: the encoders of raw dataset features) need 50 KB of LDS and
 // under 100 registers: three workgroups per CU are resident, and the latency-bound tile loop takes them
@@ -951,191 +927,186 @@ constexpr int kBwd16BlocksPerCuLight = 3;
 constexpr int kBwd16BlocksPerCuMax = 3;   // (sizes the workspace)
 
 
-// the buffer-addressed instantiation of a launch, by name ("" = the generic per-lane I/O)
-inline const char *buf_io_name(const BufPlan &B, int KI, int HT, int GT, bool three, bool g32, int debug_flags,
-                               int epilogue) {
-    if (!B.ok || (debug_flags & (64 | 128)) || KI != 1 || (HT != 1 && HT != 3)) return "";
-    auto epi_ok = [&](int k) { return k < 0 || k == epilogue; };   // (a class with a static epilogue only takes that one)
-    if (g32)
-        return (GT == 2 && three && epi_ok(IoHead::kEpi) && buf_plan_is<IoHead>(B)) ? "IoHead"
-               : (GT == 2 && three && HT == 3 && kBwd16BufD == 2 && epi_ok(IoHeadF::kEpi) && buf_plan_is<IoHeadF>(B)) ? "IoHeadF" : "";
-    if (GT == 2 && three && epi_ok(IoRelational<2>::kEpi) && buf_plan_is<IoRelational<2>>(B)) return "IoRelational<2>";
-    if (GT == 2 && three && epi_ok(IoRelational<3>::kEpi) && buf_plan_is<IoRelational<3>>(B)) return "IoRelational<3>";
-    if (GT == 2 && three && HT == 3 && kBwd16BufD == 2 && epi_ok(IoRelationalF2::kEpi) && buf_plan_is<IoRelationalF2>(B)) return "IoRelationalF2";
-    if (GT == 2 && three && HT == 3 && kBwd16BufD == 2 && epi_ok(IoRelationalF3::kEpi) && buf_plan_is<IoRelationalF3>(B)) return "IoRelationalF3";
-    if (GT == 1 && three && epi_ok(IoObject::kEpi) && buf_plan_is<IoObject>(B)) return "IoObject";
-    if (GT == 0 && !three && epi_ok(IoEncoder8<1>::kEpi) && buf_plan_is<IoEncoder8<1>>(B)) return "IoEncoder8<1>";
-    if (GT == 0 && !three && epi_ok(IoEncoder8<2>::kEpi) && buf_plan_is<IoEncoder8<2>>(B)) return "IoEncoder8<2>";
-    return "";
+// ---- host: ONE selection of the backward instantiation ----------------------------------------------------------
+// The buffer-addressed I/O classes in matching order, one list per upstream format (G32: the fp32 gradient of the
+// edge-weight head).  find: the position (from 1) of the first class pred(tag<IO>{}) accepts, 0: none.  visit:
+// f(tag<IO>{}) for the class at that position.  A translation unit instantiates the kernels of the list it visits
+// only (mlp_bf16_g32.hip / mlp_bf16.hip); matching a launch against either list instantiates none.
+template <class... IO>
+struct io_list {
+    template <class F> static int find(F &&pred) {
+        int n = 0;
+        return ((++n, pred(tag<IO>{})) || ...) ? n : 0;
+    }
+    template <class F> static bool visit(int io, F &&f) {
+        int n = 0;
+        return ((++n == io && (f(tag<IO>{}), true)) || ...);
+    }
+};
+template <bool G32>
+using buf_io_list = std::conditional_t<G32, io_list<IoHeadT<false>, IoHeadT<true>>,
+                                       io_list<IoRelational<2, false>, IoRelational<3, false>, IoRelational<2, true>,
+                                               IoRelational<3, true>, IoObject, IoEncoder8<1>, IoEncoder8<2>>>;
+
+// What a backward launch runs.  The launcher lifts these values over its instantiation lists, the name entry points
+// print them, the capability probes (max_terms, can_fold, bce_supported) read them.
+struct Bwd16Sel {
+    enum Kind { kOt, kBi8, kBi, kBuf, kGeneric } kind;   // output tiles / wide inputs | hidden 128 with biases | hidden 64
+                                                         // with biases | buffer-addressed | generic per-lane I/O
+    int KI, HT, GT, OT, D;   // GT: input-gradient tiles; D: 16-row tiles per iteration
+    bool three, g32;
+    int io;                  // kBuf: position of the class in buf_io_list<g32>; 0: the generic per-lane I/O
+    const char *io_name;
+    bool fold;               // kBuf: the class folds a gathered segment's gradient inside the kernel
+    int terms;               // kBuf: upstream terms the class takes
+    bool bce;                // the launch can run as mlp16_bwd_bce_kernel<HT> (the head's shape, no fold, no debug form)
+    int per_cu;              // workgroups per CU the grid is sized for
+};
+// gradient M tiles: 1 or the maximum of the k-step count (keeps the instantiation list short); 0: no input gradient wanted
+inline int bwd16_gt(const gnntrk_mlp_bwd_args *a, const SlotPlan &P) {
+    if (a->mlp.out_dim > 16 || P.KI > 2) return 2 * P.KI;   // output tiles / wide inputs: every gradient tile
+    return (P.GT == 0 && P.KI == 1) ? 0 : (P.GT <= 1) ? 1 : 2 * P.KI;
+}
+// fills B (the buffer plan of the launch) and resolves the instantiation
+inline Bwd16Sel bwd16_select(const gnntrk_mlp_bwd_args *a, const SlotPlan &P, BufPlan &B) {
+    Bwd16Sel S{};
+    const bool wide_io = a->mlp.out_dim > 16 || P.KI > 2;
+    S.KI = P.KI;
+    S.HT = P.HT;
+    S.GT = bwd16_gt(a, P);
+    S.OT = (a->mlp.out_dim + 15) / 16;
+    S.D = 1;
+    S.three = a->mlp.n_layers == 3;
+    S.g32 = a->epilogue == GNNTRK_EPI_SIGMOID;
+    S.io_name = IoNone::kName;
+    // (five / six hidden tiles: one workgroup per CU is resident - its share of the rows is simply larger)
+    S.per_cu = (P.HT >= 5 || wide_io || (P.bias_init && P.KI >= 2)) ? 1
+               : (S.GT == 0 && P.HT <= 3 && !(a->debug_flags & 1024)) ? kBwd16BlocksPerCuLight : kBwd16BlocksPerCu;
+    make_buf_plan(B, P, a, S.GT);
+    if (wide_io) {
+        S.kind = Bwd16Sel::kOt;
+    } else if (P.bias_init) {
+        S.kind = P.HT == 8 ? Bwd16Sel::kBi8 : Bwd16Sel::kBi;
+    } else {
+        // the shapes of the default models go through buffer descriptors (debug_flags & 128: generic I/O); a class
+        // takes the launch whose gradient tiles, layer count, epilogue and buffer plan are its own (the fold classes:
+        // three hidden tiles only)
+        if (B.ok && !(a->debug_flags & (64 | 128)) && P.KI == 1 && (P.HT == 1 || P.HT == 3)) {
+            auto takes = [&](auto t) {
+                using IO = typename decltype(t)::type;
+                if (S.GT != IO::kGT || S.three != IO::kThree || (IO::kFold && P.HT != 3) || a->epilogue != IO::kEpi ||
+                    !buf_plan_is<IO>(B))
+                    return false;
+                S.io_name = IO::kName;
+                S.fold = IO::kFold;
+                S.terms = IO::NG;
+                S.bce = std::is_same_v<IO, IoHeadT<false>> && a->mlp.out_dim == 1 && !(a->debug_flags & 4096);
+                return true;
+            };
+            S.io = S.g32 ? buf_io_list<true>::find(takes) : buf_io_list<false>::find(takes);
+        }
+        S.kind = S.io ? Bwd16Sel::kBuf : Bwd16Sel::kGeneric;
+        // D = 2 (two 16-row halves per iteration, K = 32 weight-gradient contractions) wherever the doubled staging
+        // images fit the workgroup's LDS budget: one k-step, up to three hidden tiles - every shape of the
+        // reference's default models.  debug_flags & 64 forces D = 1 (A/B timing).
+        S.D = (P.KI == 1 && P.HT <= 3 && !(a->debug_flags & 64)) ? 2 : 1;
+    }
+    return S;
 }
 
-// hidden tiles (1 / 3) of the mlp16_bwd_bce_kernel instantiation the launch described by (plan, a) takes, 0: none
-inline int bwd16_bce_ht(const BufPlan &B, const SlotPlan &P, const gnntrk_mlp_bwd_args *a, int GT) {
-    if (kBwd16BufD != 2 || a->epilogue != GNNTRK_EPI_SIGMOID || a->mlp.out_dim != 1 || a->mlp.n_layers != 3 || GT != 2 ||
-        a->fold.ids || (a->debug_flags & (64 | 128 | 4096)) || (P.HT != 1 && P.HT != 3))
-        return 0;
-    return strcmp(buf_io_name(B, P.KI, P.HT, GT, true, true, a->debug_flags, a->epilogue), "IoHead") == 0 ? P.HT : 0;
-}
-
-// launches the backward instantiation for (plan, GT, three); G32 = fp32 upstream gradient
-// (grid: workgroups of kWaves waves; grid_buf: of kBwd16BufWaves waves - what the buffer-addressed kernels take;
-// *used = {workgroups, waves per workgroup} of the launch: grid * waves partial blocks unless reduced in LDS)
+// selects and launches the backward instantiation of (a, P); G32 = fp32 upstream gradient.  *grid_out: the workgroups
+// launched (of kWaves waves: grid * kWaves partial blocks unless reduced in LDS).
 // bce != NULL: the head's launch with the BCE gradient formed in the kernel (mlp16_bwd_bce_kernel) or nothing
 template <bool G32>
-int launch_bwd16(const gnntrk_mlp_bwd_args *a, const SlotPlan &P, int GT, int grid, int grid_buf, int *used,
-                 float *part, uint8_t *trash, hipStream_t stream, const gnntrk_head_bce *bce = nullptr) {
-    used[0] = grid;
-    used[1] = kWaves;
-    const bool three = a->mlp.n_layers == 3;
-    bool launched = false;
+int launch_bwd16(const gnntrk_mlp_bwd_args *a, const SlotPlan &P, float *part, uint8_t *trash, hipStream_t stream,
+                 const gnntrk_head_bce *bce, int *grid_out) {
     BufPlan B;
-    make_buf_plan(B, P, a, GT);
+    const Bwd16Sel S = bwd16_select(a, P, B);
+    const int grid = *grid_out = tile_grid(a->n_rows, S.per_cu);
+    auto run = [&](auto kfn) { launch(kfn, grid, kBlock, stream, *a, part, trash, B); };
+    using P10 = int2_c<1, 0>;   // (k-steps, gradient tiles) of the generic and the bias_init kernels
+    using P11 = int2_c<1, 1>;
+    using P12 = int2_c<1, 2>;
+    using P21 = int2_c<2, 1>;
+    using P24 = int2_c<2, 4>;
+    bool found = false;
     if (bce) {
         if constexpr (G32) {
-            if (bwd16_bce_ht(B, P, a, GT) == 0)
+            if (!S.bce)
                 return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16_bce: not the buffer-addressed head shape "
                                                  "(gnntrk_mlp_backward_bf16_bce_supported)");
-            if (P.HT == 3) {
-                auto kfn = mlp16_bwd_bce_kernel<3>;
-                hipLaunchKernelGGL(kfn, dim3(grid_buf), dim3(64 * kBwd16BufWaves), 0, stream, *a, part, trash, B, *bce);
-            } else {
-                auto kfn = mlp16_bwd_bce_kernel<1>;
-                hipLaunchKernelGGL(kfn, dim3(grid_buf), dim3(64 * kBwd16BufWaves), 0, stream, *a, part, trash, B, *bce);
-            }
-            used[0] = grid_buf;
-            used[1] = kBwd16BufWaves;
+            lift_int<3, 1>(S.HT, [&](auto ht) {
+                launch(mlp16_bwd_bce_kernel<decltype(ht)::value>, grid, kBlock, stream, *a, part, trash, B, *bce);
+            });
             return check_launch("mlp_backward_bf16_bce");
         }
         return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16_bce: the SIGMOID epilogue only");
     }
-    if (a->mlp.out_dim > 16 || P.KI > 2) {   // output tiles / wide inputs (three hidden tiles; GT = 2 KI)
+    if ((a->debug_flags & 256) && (S.kind == Bwd16Sel::kBuf || S.kind == Bwd16Sel::kGeneric))   // (diagnostics: which I/O form a launch takes)
+        fprintf(stderr, "mlp_backward_bf16: KI %d HT %d GT %d three %d rows %lld plan ok %d (loads %d ids %d+%d gout %d stores %d ones %d) -> %s\n",
+                S.KI, S.HT, S.GT, (int)S.three, (long long)a->n_rows, B.ok, B.n_load, B.n_ids, B.n_sids, B.n_gout, B.n_store,
+                B.ones_dword, S.io ? S.io_name : "generic");
+    switch (S.kind) {
+    case Bwd16Sel::kOt:   // output tiles / wide inputs (three hidden tiles; GT = 2 KI)
         if (G32 || a->epilogue == GNNTRK_EPI_RELU || a->epilogue == GNNTRK_EPI_SIGMOID)
             return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16: outputs over 16 / inputs over 64 slots take the NONE and RESIDUAL epilogues");
-        const int ot = (a->mlp.out_dim + 15) / 16;
-#define GNNTRK_BWD16_OT(KI_, OT_)                                                              \
-    if (!launched && P.KI == KI_ && ot == OT_ && P.HT == 3 && GT == 2 * KI_) {                 \
-        if (three) { auto kfn = mlp16_bwd_ot_kernel<KI_, 3, OT_, true>;                        \
-            hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a, part, trash, B); } \
-        else { auto kfn = mlp16_bwd_ot_kernel<KI_, 3, OT_, false>;                             \
-            hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a, part, trash, B); } \
-        launched = true;                                                                       \
+        if constexpr (!G32)
+            found = S.HT == 3 && S.GT == 2 * S.KI &&
+                    lift_int2<int2_c<1, 2>, int2_c<1, 3>, int2_c<2, 2>, int2_c<2, 3>, int2_c<3, 1>, int2_c<3, 2>, int2_c<3, 3>,
+                              int2_c<4, 1>, int2_c<4, 2>, int2_c<4, 3>>(S.KI, S.OT, [&](auto p) {
+                        lift_bools([&](auto three) {
+                            run(mlp16_bwd_ot_kernel<decltype(p)::a, 3, decltype(p)::b, decltype(three)::value>);
+                        }, S.three);
+                    });
+        if (!found) return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16: no instantiation (output tiles)");
+        break;
+    case Bwd16Sel::kBi8:   // hidden width 128: own translation unit (mlp_bf16_bi8.hip says why)
+        return launch_bwd16_bi8(a, P, S.GT, grid, part, trash, stream);
+    case Bwd16Sel::kBi:   // hidden width 64 with biases: the accumulator-initialised kernels
+        found = S.HT == 4 && lift_int2<P10, P11, P12, P21, P24>(S.KI, S.GT, [&](auto p) {
+            lift_bools([&](auto three) {
+                run(mlp16_bwd_bi_kernel<decltype(p)::a, 4, decltype(p)::b, decltype(three)::value, G32>);
+            }, S.three);
+        });
+        if (!found) return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16: no instantiation (bias_init)");
+        break;
+    case Bwd16Sel::kBuf:
+        buf_io_list<G32>::visit(S.io, [&](auto t) {
+            using IO = typename decltype(t)::type;
+            // (debug_flags & 4096: the I/O skeleton - of the classes with two gradient tiles, three hidden tiles)
+            if constexpr (IO::kGT == 2)
+                if ((a->debug_flags & 4096) && S.HT == 3) {
+                    run(mlp16_bwd_skel_kernel<1, 3, 2, true, G32, 2, IO>);
+                    return;
+                }
+            auto go = [&](auto ht) { run(mlp16_bwd_kernel<1, decltype(ht)::value, IO::kGT, IO::kThree, G32, 2, IO>); };
+            if constexpr (IO::kFold) lift_int<3>(S.HT, go);
+            else lift_int<3, 1>(S.HT, go);
+        });
+        break;
+    case Bwd16Sel::kGeneric:
+        if (a->fold.ids) return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16: this launch does not take a fold (gnntrk_mlp_backward_bf16_can_fold)");
+        // (one k-step: up to eight hidden tiles, GT = 0 are the weight-gradient-only launches of the encoders of raw
+        //  dataset features; two k-steps: up to six)
+        lift_int2<P10, P11, P12, P21, P24>(S.KI, S.GT, [&](auto p) {
+            constexpr int KI = decltype(p)::a, GT = decltype(p)::b;
+            auto go = [&](auto ht) {
+                constexpr int HT = decltype(ht)::value;
+                lift_bools([&](auto three) {
+                    if constexpr (KI == 1 && HT <= 3)
+                        if (S.D == 2) {
+                            run(mlp16_bwd_kernel<KI, HT, GT, decltype(three)::value, G32, 2>);
+                            return;
+                        }
+                    run(mlp16_bwd_kernel<KI, HT, GT, decltype(three)::value, G32, 1>);
+                }, S.three);
+            };
+            if constexpr (KI == 1) found = lift_int<1, 2, 3, 4, 5, 6, 7, 8>(S.HT, go);
+            else found = lift_int<1, 2, 3, 4, 5, 6>(S.HT, go);
+        });
+        if (!found) return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16: no instantiation");
+        break;
     }
-        if constexpr (!G32) {
-            GNNTRK_BWD16_OT(1, 2) GNNTRK_BWD16_OT(1, 3) GNNTRK_BWD16_OT(2, 2) GNNTRK_BWD16_OT(2, 3)
-            GNNTRK_BWD16_OT(3, 1) GNNTRK_BWD16_OT(3, 2) GNNTRK_BWD16_OT(3, 3)
-            GNNTRK_BWD16_OT(4, 1) GNNTRK_BWD16_OT(4, 2) GNNTRK_BWD16_OT(4, 3)
-        }
-#undef GNNTRK_BWD16_OT
-        if (!launched) return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16: no instantiation (output tiles)");
-        return check_launch("mlp_backward_bf16");
-    }
-    if (P.bias_init && P.HT == 8)   // hidden width 128: own translation unit (mlp_bf16_bi8.hip says why)
-        return launch_bwd16_bi8(a, P, GT, G32 ? 1 : 0, grid, part, trash, stream);
-    if (P.bias_init) {   // hidden width 64 with biases: the accumulator-initialised kernels
-#define GNNTRK_BWD16_BI(KI_, HT_, GT_)                                                         \
-    if (!launched && P.KI == KI_ && P.HT == HT_ && GT == GT_) {                                \
-        if (three) { auto kfn = mlp16_bwd_bi_kernel<KI_, HT_, GT_, true, G32>;                 \
-            hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a, part, trash, B); } \
-        else { auto kfn = mlp16_bwd_bi_kernel<KI_, HT_, GT_, false, G32>;                      \
-            hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a, part, trash, B); } \
-        launched = true;                                                                       \
-    }
-        GNNTRK_BWD16_BI(1, 4, 0) GNNTRK_BWD16_BI(1, 4, 1) GNNTRK_BWD16_BI(1, 4, 2)
-        GNNTRK_BWD16_BI(2, 4, 1) GNNTRK_BWD16_BI(2, 4, 4)
-#undef GNNTRK_BWD16_BI
-        if (!launched) return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16: no instantiation (bias_init)");
-        return check_launch("mlp_backward_bf16");
-    }
-    // the shapes of the default models go through buffer descriptors (debug_flags & 128: generic I/O)
-    {
-        const char *io = buf_io_name(B, P.KI, P.HT, GT, three, G32, a->debug_flags, a->epilogue);
-        if (a->debug_flags & 256)   // (diagnostics: which I/O form a launch takes)
-            fprintf(stderr, "mlp_backward_bf16: KI %d HT %d GT %d three %d rows %lld plan ok %d (loads %d ids %d+%d gout %d stores %d ones %d) -> %s\n",
-                    P.KI, P.HT, GT, (int)three, (long long)a->n_rows, B.ok, B.n_load, B.n_ids, B.n_sids, B.n_gout,
-                    B.n_store, B.ones_dword, io[0] ? io : "generic");
-#define GNNTRK_BWD16_SKEL(IO_)                                                                        \
-    if (!launched && (a->debug_flags & 4096) && P.HT == 3 && kBwd16BufD == 2 && strcmp(io, #IO_) == 0) { \
-        auto kfn = mlp16_bwd_skel_kernel<1, 3, 2, true, G32, 2, IO_>;                                 \
-        hipLaunchKernelGGL(kfn, dim3(grid_buf), dim3(64 * kBwd16BufWaves), 0, stream, *a, part, trash, B); \
-        used[0] = grid_buf;                                                                           \
-        used[1] = kBwd16BufWaves;                                                                     \
-        launched = true;                                                                              \
-    }
-        if constexpr (G32) {
-            GNNTRK_BWD16_SKEL(IoHead)
-            GNNTRK_BWD16_SKEL(IoHeadF)
-        } else {
-            GNNTRK_BWD16_SKEL(IoRelational<2>)
-            GNNTRK_BWD16_SKEL(IoRelational<3>)
-            GNNTRK_BWD16_SKEL(IoRelationalF2)
-            GNNTRK_BWD16_SKEL(IoRelationalF3)
-        }
-#undef GNNTRK_BWD16_SKEL
-#define GNNTRK_BWD16_BUF(HT_, GT_, T_, IO_)                                                           \
-    if (!launched && P.HT == HT_ && strcmp(io, #IO_) == 0) {                                          \
-        auto kfn = mlp16_bwd_kernel<1, HT_, GT_, T_, G32, kBwd16BufD, IO_>;                           \
-        hipLaunchKernelGGL(kfn, dim3(grid_buf), dim3(64 * kBwd16BufWaves), 0, stream, *a, part, trash, B); \
-        used[0] = grid_buf;                                                                           \
-        used[1] = kBwd16BufWaves;                                                                     \
-        launched = true;                                                                              \
-    }
-        if constexpr (G32) {
-            GNNTRK_BWD16_BUF(3, 2, true, IoHead)
-            GNNTRK_BWD16_BUF(1, 2, true, IoHead)
-            GNNTRK_BWD16_BUF(3, 2, true, IoHeadF)
-        } else {
-            GNNTRK_BWD16_BUF(3, 2, true, IoRelational<2>)
-            GNNTRK_BWD16_BUF(3, 2, true, IoRelational<3>)
-            GNNTRK_BWD16_BUF(3, 2, true, IoRelationalF2)
-            GNNTRK_BWD16_BUF(3, 2, true, IoRelationalF3)
-            GNNTRK_BWD16_BUF(1, 2, true, IoRelational<2>)
-            GNNTRK_BWD16_BUF(1, 2, true, IoRelational<3>)
-            GNNTRK_BWD16_BUF(3, 1, true, IoObject)
-            GNNTRK_BWD16_BUF(1, 1, true, IoObject)
-            GNNTRK_BWD16_BUF(3, 0, false, IoEncoder8<1>)
-            GNNTRK_BWD16_BUF(3, 0, false, IoEncoder8<2>)
-            GNNTRK_BWD16_BUF(1, 0, false, IoEncoder8<1>)
-            GNNTRK_BWD16_BUF(1, 0, false, IoEncoder8<2>)
-        }
-#undef GNNTRK_BWD16_BUF
-        if (launched) return check_launch("mlp_backward_bf16");
-    }
-    if (a->fold.ids) return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16: this launch does not take a fold (gnntrk_mlp_backward_bf16_can_fold)");
-// D = 2 (two 16-row halves per iteration, K = 32 weight-gradient contractions) wherever the
-// doubled staging images fit the workgroup's LDS budget: one k-step, up to three hidden tiles -
-// every shape of the reference's default models.  debug_flags & 64 forces D = 1 (A/B timing).
-#define GNNTRK_BWD16_LAUNCH(KI_, HT_, GT_, T_, D_)                                             \
-    {                                                                                          \
-        auto kfn = mlp16_bwd_kernel<KI_, HT_, GT_, T_, G32, D_>;                               \
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(kBlock), 0, stream, *a, part, trash, B);      \
-    }
-#define GNNTRK_BWD16_CASE(KI_, HT_, GT_)                                                       \
-    if (P.KI == KI_ && P.HT == HT_ && GT == GT_) {                                             \
-        constexpr bool kTwo = (KI_ == 1 && HT_ <= 3);                                          \
-        if (kTwo && !(a->debug_flags & 64)) {                                                  \
-            if (three) GNNTRK_BWD16_LAUNCH(KI_, HT_, GT_, true, (kTwo ? 2 : 1))                \
-            else GNNTRK_BWD16_LAUNCH(KI_, HT_, GT_, false, (kTwo ? 2 : 1))                     \
-        } else {                                                                               \
-            if (three) GNNTRK_BWD16_LAUNCH(KI_, HT_, GT_, true, 1)                             \
-            else GNNTRK_BWD16_LAUNCH(KI_, HT_, GT_, false, 1)                                  \
-        }                                                                                      \
-        launched = true;                                                                       \
-    }
-#define GNNTRK_BWD16_HT(KI_, GT_) \
-    GNNTRK_BWD16_CASE(KI_, 1, GT_) GNNTRK_BWD16_CASE(KI_, 2, GT_) GNNTRK_BWD16_CASE(KI_, 3, GT_) \
-        GNNTRK_BWD16_CASE(KI_, 4, GT_) GNNTRK_BWD16_CASE(KI_, 5, GT_) GNNTRK_BWD16_CASE(KI_, 6, GT_)
-    GNNTRK_BWD16_HT(1, 0)   // weight gradients only (the encoders of raw dataset features)
-    GNNTRK_BWD16_HT(1, 1)
-    GNNTRK_BWD16_HT(1, 2)
-    GNNTRK_BWD16_CASE(1, 7, 0) GNNTRK_BWD16_CASE(1, 8, 0)   // hidden widths 96 .. 127: one k-step of inputs
-    GNNTRK_BWD16_CASE(1, 7, 1) GNNTRK_BWD16_CASE(1, 8, 1)
-    GNNTRK_BWD16_CASE(1, 7, 2) GNNTRK_BWD16_CASE(1, 8, 2)
-    GNNTRK_BWD16_HT(2, 1)
-    GNNTRK_BWD16_HT(2, 4)
-#undef GNNTRK_BWD16_HT
-#undef GNNTRK_BWD16_CASE
-#undef GNNTRK_BWD16_LAUNCH
-    if (!launched) return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16: no instantiation");
     return check_launch("mlp_backward_bf16");
 }
 

@@ -24,6 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "gnntrk.h"
 
 namespace gnntrk {
@@ -46,6 +48,38 @@ constexpr int kTbLd = 20;      // leading dim (floats) of a transpose buffer
 constexpr int kTbRows = 64;    // max features staged at once (+1 garbage row for padding)
 constexpr int kTbBufs = 3;     // rotating transpose buffers per wave
 constexpr int kTbSize = (kTbRows + 1) * kTbLd;
+
+// ---- host: the persistent grid of a tile kernel ---------------------------------------------------------------
+int cu_count();   // (host_util.h)
+// workgroups of `waves` waves for n_rows rows, one tile per wave and step: at most blocks_per_cu per compute
+// unit, a multiple of 8 (the XCD-aware schedule), at least one
+inline int tile_grid(int64_t n_rows, int blocks_per_cu, int waves = kWaves) {
+    const int64_t tiles = (n_rows + kTileRows - 1) / kTileRows;
+    int64_t g = (tiles + waves - 1) / waves;
+    const int64_t cap = (int64_t)cu_count() * blocks_per_cu;
+    if (g > cap) g = cap;
+    if (g >= 8) g -= g % 8;
+    if (g < 1) g = 1;
+    return (int)g;
+}
+// Workgroups (of kBlock threads) of the instantiation Kfn that are RESIDENT on a CU at once - registers and LDS
+// decide; `fallback` if the runtime does not say, at most 8.  A persistent grid larger than that runs in rounds
+// whose last one leaves CUs idle.  Asked once per instantiation and device ordinal (cached atomically: launch
+// threads race, devices differ); an ordinal past the cache is asked every time rather than sharing a slot.
+template <auto Kfn> int resident_blocks(int fallback) {
+    static std::atomic<int> cached[16];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::atomic<int> *slot = (dev >= 0 && dev < 16) ? &cached[dev] : nullptr;
+    int occ = slot ? slot->load(std::memory_order_relaxed) : 0;
+    if (occ <= 0) {
+        int o = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, Kfn, kBlock, 0) != hipSuccess || o < 1) o = fallback;
+        occ = o > 8 ? 8 : o;
+        if (slot) slot->store(occ, std::memory_order_relaxed);
+    }
+    return occ;
+}
 
 struct DimMap {
     int D;   // features

@@ -1158,6 +1158,273 @@ def case_mlp_bf16_fold(device, seed=5, sizes=(1, 31, 32, 33, 75, 640, 2050)):
     return checked
 
 
+# ---- the instantiations of the bf16 launchers: names, probes, launches ------------------------------------------
+# (shape, segment dims, hidden, out, L, bias, epilogue, upstream terms, wanted gradients, debug_flags, mode) ->
+# per row count (33, 1): kernel name, then max_terms, can_fold, bce_supported.  Shapes: "plain" own tensor per
+# segment; "rel" x[tgt] | x[src] | e of one node tensor (the relational model), "obj" x | aggr, "head" h[src] |
+# h[tgt] | four edge tensors with an fp32 upstream gradient, "enc" one tensor of the tile's rows - what the
+# buffer-addressed classes take.  mode: "" / "fold" (in-kernel fold of the target-gathered segment) / "bce".
+# THE LITERALS ARE THE PARENT COMMIT'S ANSWERS (recorded on the emulator build of the commit before the launchers
+# were rewritten; names and probes are host code) - consumers key timers and profiles on the names.
+BF16_FWD_INSTANTIATIONS = [
+    # shared output tile (R = 4), wide and not, with and without the sigmoid; two and three layers
+    (("rel", (5, 5, 4), 40, 4, 3, True, "none"), ("mlp16_fwd_kernel<1, 3, true, false, 4, true>", "mlp16_fwd_kernel<1, 3, true, false, 4, false>")),
+    (("gath", (4,), 40, 4, 2, False, "relu"), ("mlp16_fwd_kernel<1, 3, false, false, 4, false>",) * 2),
+    (("enc", (4,), 40, 4, 2, False, "relu"), ("mlp16_fwd_kernel<1, 3, false, false, 4, true>", "mlp16_fwd_kernel<1, 3, false, false, 4, false>")),
+    (("head", (5, 5, 4, 4, 4, 4), 40, 1, 3, True, "sigmoid"), ("mlp16_fwd_kernel<1, 3, true, true, 4, false>",) * 2),
+    (("enc", (8,), 40, 1, 2, True, "sigmoid"), ("mlp16_fwd_kernel<1, 3, false, true, 4, true>",) * 2),
+    (("obj", (5, 4), 40, 5, 3, True, "residual"), ("mlp16_fwd_kernel<1, 3, true, false, 1, true>", "mlp16_fwd_kernel<1, 3, true, false, 1, false>")),
+    (("plain", (8, 8, 8, 8, 3), 62, 9, 3, True, "none"), ("mlp16_fwd_kernel<2, 4, true, false, 1, true>", "mlp16_fwd_kernel<2, 4, true, false, 1, false>")),
+    # plain forms, five to eight hidden tiles
+    (("rel", (5, 5, 4), 70, 4, 3, True, "none"), ("mlp16_fwd_kernel<1, 5, true, false, 1, false>",) * 2),
+    (("obj", (5, 4), 90, 5, 2, True, "residual"), ("mlp16_fwd_kernel<1, 6, false, false, 1, false>",) * 2),
+    (("head", (5, 5, 4, 4, 4, 4), 100, 1, 3, True, "sigmoid"), ("mlp16_fwd_kernel<1, 7, true, true, 1, false>",) * 2),
+    (("enc", (14,), 120, 5, 3, True, "relu"), ("mlp16_fwd_kernel<1, 8, true, false, 1, false>",) * 2),
+    # bias_init: hidden 64 / 128 with biases
+    (("rel", (5, 5, 4), 64, 4, 3, True, "none"), ("mlp16_fwd_bi_kernel<1, 4, true, false>",) * 2),
+    (("head", (5, 5, 4, 4, 4, 4), 128, 1, 3, True, "sigmoid"), ("mlp16_fwd_bi_kernel<1, 8, true, true>",) * 2),
+    # output tiles / wide inputs, one to four k-steps
+    (("rel", (5, 5, 4), 40, 40, 3, True, "none"), ("mlp16_fwd_ot_kernel<1, 3, 3, true>",) * 2),
+    (("plain", (8, 8, 8, 8, 3), 40, 33, 3, True, "residual"), ("mlp16_fwd_ot_kernel<2, 3, 3, true>",) * 2),
+    (("plain", (40, 40), 40, 40, 3, True, "residual"), ("mlp16_fwd_ot_kernel<3, 3, 3, true>",) * 2),
+    (("plain", (40, 31, 30), 37, 5, 2, False, "relu"), ("mlp16_fwd_ot_kernel<4, 3, 1, false>",) * 2),
+]
+BF16_BWD_INSTANTIATIONS = [
+    # generic I/O: no / one / two input-gradient tiles, two tiles per iteration and one, the two A/B flags
+    (("plain", (14,), 40, 5, 2, False, "relu", 1, (False,), 0, ""),
+     (("mlp16_bwd_kernel<1, 3, 0, false, false, 2, IoNone>", 2, 0, 0),) * 2),
+    (("plain", (3,), 7, 2, 3, True, "none", 1, (True,), 0, ""),
+     (("mlp16_bwd_kernel<1, 1, 1, true, false, 2, IoNone>", 2, 0, 0),) * 2),
+    (("plain", (8, 8, 8, 8), 16, 16, 3, True, "none", 1, (True, False, True, False), 0, ""),
+     (("mlp16_bwd_kernel<2, 2, 1, true, false, 1, IoNone>", 2, 0, 0),) * 2),
+    (("plain", (5, 4), 64, 5, 3, False, "residual", 1, (True, True), 0, ""),
+     (("mlp16_bwd_kernel<1, 4, 1, true, false, 1, IoNone>", 2, 0, 0),) * 2),
+    (("plain", (8, 8, 8, 8, 3), 30, 9, 3, True, "none", 1, (True,) * 5, 0, ""),
+     (("mlp16_bwd_kernel<2, 2, 4, true, false, 1, IoNone>", 2, 0, 0),) * 2),
+    (("rel", (5, 5, 4), 40, 4, 3, True, "none", 2, (True,) * 3, 64, ""),
+     (("mlp16_bwd_kernel<1, 3, 2, true, false, 1, IoNone>", 2, 0, 0),) * 2),
+    (("rel", (5, 5, 4), 40, 4, 3, True, "none", 2, (True,) * 3, 128, ""),
+     (("mlp16_bwd_kernel<1, 3, 2, true, false, 2, IoNone>", 2, 0, 0),) * 2),
+    # output tiles / wide inputs, bias_init (hidden 64 / 128 with biases)
+    (("rel", (5, 5, 4), 40, 40, 3, True, "none", 2, (True,) * 3, 0, ""),
+     (("mlp16_bwd_ot_kernel<1, 3, 3, true>", 2, 0, 0),) * 2),
+    (("plain", (40, 40), 40, 40, 3, True, "residual", 1, (True, True), 0, ""),
+     (("mlp16_bwd_ot_kernel<3, 3, 3, true>", 2, 0, 0),) * 2),
+    (("rel", (5, 5, 4), 64, 4, 3, True, "none", 2, (True,) * 3, 0, ""),
+     (("mlp16_bwd_bi_kernel<1, 4, 2, true, false>", 2, 0, 0),) * 2),
+    (("head", (5, 5, 4, 4, 4, 4), 128, 1, 3, True, "sigmoid", 1, (True,) * 6, 0, ""),
+     (("mlp16_bwd_bi_kernel<1, 8, 2, true, true>", 2, 0, 0),) * 2),
+    # the buffer-addressed classes
+    (("rel", (5, 5, 4), 40, 4, 3, True, "none", 2, (True,) * 3, 0, ""),
+     (("mlp16_bwd_kernel<1, 3, 2, true, false, 2, IoRelational<2, false> >", 3, 0, 0),) * 2),
+    (("rel", (5, 5, 4), 40, 4, 3, True, "none", 3, (True,) * 3, 0, ""),
+     (("mlp16_bwd_kernel<1, 3, 2, true, false, 2, IoRelational<3, false> >", 3, 0, 0),) * 2),
+    (("rel", (5, 5, 4), 12, 4, 3, True, "none", 2, (True,) * 3, 0, ""),
+     (("mlp16_bwd_kernel<1, 1, 2, true, false, 2, IoRelational<2, false> >", 3, 0, 0),) * 2),
+    (("obj", (5, 4), 40, 5, 3, True, "residual", 1, (True, True), 0, ""),
+     (("mlp16_bwd_kernel<1, 3, 1, true, false, 2, IoObject>", 2, 0, 0),) * 2),
+    (("head", (5, 5, 4, 4, 4, 4), 40, 1, 3, True, "sigmoid", 1, (True,) * 6, 0, ""),
+     (("mlp16_bwd_kernel<1, 3, 2, true, true, 2, IoHeadT<false> >", 2, 0, 1),) * 2),
+    (("enc", (4,), 40, 4, 2, False, "relu", 1, (False,), 0, ""),
+     (("mlp16_bwd_kernel<1, 3, 0, false, false, 2, IoEncoder8<1> >", 2, 0, 0),) * 2),
+    (("enc", (4,), 40, 4, 2, False, "relu", 2, (False,), 0, ""),
+     (("mlp16_bwd_kernel<1, 3, 0, false, false, 2, IoEncoder8<2> >", 2, 0, 0),) * 2),
+    # both fold classes, the BCE head with three hidden tiles and one
+    (("rel", (5, 5, 4), 40, 4, 3, True, "none", 2, (True,) * 3, 0, "fold"),
+     (("mlp16_bwd_kernel<1, 3, 2, true, false, 2, IoRelational<2, true> >", 3, 1, 0),) * 2),
+    (("rel", (5, 5, 4), 40, 4, 3, True, "none", 3, (True,) * 3, 0, "fold"),
+     (("mlp16_bwd_kernel<1, 3, 2, true, false, 2, IoRelational<3, true> >", 3, 1, 0),) * 2),
+    (("head", (5, 5, 4, 4, 4, 4), 40, 1, 3, True, "sigmoid", 1, (True,) * 6, 0, "fold"),
+     (("mlp16_bwd_kernel<1, 3, 2, true, true, 2, IoHeadT<true> >", 2, 1, 0),) * 2),
+    (("head", (5, 5, 4, 4, 4, 4), 40, 1, 3, True, "sigmoid", 1, (True,) * 6, 0, "bce"),
+     (("mlp16_bwd_bce_kernel<3>", 2, 0, 1),) * 2),
+    (("head", (5, 5, 4, 4, 4, 4), 10, 1, 3, True, "sigmoid", 1, (True,) * 6, 0, "bce"),
+     (("mlp16_bwd_bce_kernel<1>", 2, 0, 1),) * 2),
+]
+
+
+def _rows16_on(device, n, d, gen, poison):
+    """Kernel-ready random rows on ``device`` with the WHOLE padded buffer behind them: a device copy of the [1, d]
+    view of a single row keeps the row stride but drops the padding after the row, which the buffer-addressed
+    shapes read as stored."""
+    from gnn_tracking_amd import ops_bf16 as B
+    t = _rand_rows16(n, d, "cpu", gen, poison=poison)
+    full = t.as_strided((n, B.pad4(d)), (B.pad4(d), 1))
+    return B.rows16((full if device == "cpu" else full.to(device))[:, :d])
+
+
+def _inst_inputs(shape, dims, rows, out, epi, n_gout, device, gen):
+    """Segments, their id streams, the upstream terms and the gradient row permutations of one table entry."""
+    from gnn_tracking_amd import ops_bf16 as B
+    n_src = 31
+    buf = shape != "plain" and shape != "gath"
+
+    node = lambda d: _rows16_on(device, n_src, d, gen, not buf)
+    tile = lambda d: _rows16_on(device, rows, d, gen, not buf)
+    ids = lambda: torch.randint(0, n_src, (rows,), generator=gen).int().to(device)
+    perm = lambda: torch.randperm(rows, generator=gen).int().to(device)
+    segs, idxs, gidx = [], [], [None] * len(dims)
+    if shape in ("rel", "head"):       # two gathers of ONE node tensor, then tensors of the tile's rows
+        x = node(dims[0])
+        tgt_first = shape == "rel"
+        tgt = torch.sort(torch.randint(0, n_src, (rows,), generator=gen)).values.int().to(device)   # (CSR order)
+        src = ids()
+        segs, idxs = [x, x], ([tgt, src] if tgt_first else [src, tgt])
+        for d in dims[2:]:
+            segs.append(tile(d))
+            idxs.append(None)
+        gidx[1 if tgt_first else 0] = perm()    # the source-gathered slice leaves through a row permutation
+    elif shape == "gath":
+        segs, idxs = [node(d) for d in dims], [ids() for _ in dims]
+    else:                              # "obj", "enc", "plain": rows of the tile
+        segs, idxs = [tile(d) for d in dims], [None] * len(dims)
+        if shape == "plain" and len(dims) > 1:
+            gidx[1] = perm()
+    gout = []
+    if epi == "sigmoid":
+        gout.append((torch.randn(rows, out, generator=gen).to(device), None))
+    else:
+        for t in range(n_gout):
+            if t == 1 and shape == "rel":     # the aggregation's share, gathered through the target ids
+                gout.append((_rows16_on(device, n_src, out, gen, False), idxs[0]))
+            else:
+                gout.append((_rows16_on(device, rows, out, gen, False), None))
+    return segs, idxs, gidx, gout, n_src
+
+
+class _LaunchSpy:
+    """Stands in for the loaded library: every bf16 MLP launch is also asked for its kernel name and its probes,
+    with exactly the arguments of the launch."""
+
+    def __init__(self, lib, device):
+        import ctypes as C
+        from gnn_tracking_amd import _capi
+        self._lib, self.seen = lib, []
+        self._label = torch.zeros(64, dtype=torch.uint8, device=device)
+        self._w = torch.zeros(64, dtype=torch.float32, device=device)
+
+        def name(fn, *args):
+            buf = C.create_string_buffer(160)
+            _capi.check(fn(*args, buf, len(buf)), lib)
+            return buf.value.decode()
+
+        def fwd(a, stream):
+            rc = lib.gnntrk_mlp_forward_bf16(a, stream)
+            self.seen.append(("fwd", name(lib.gnntrk_mlp_forward_bf16_kernel_name, a), rc))
+            return rc
+
+        def probes(a, hb):
+            return (int(lib.gnntrk_mlp_backward_bf16_max_terms(a)), int(lib.gnntrk_mlp_backward_bf16_can_fold(a)),
+                    int(lib.gnntrk_mlp_backward_bf16_bce_supported(a, hb)))
+
+        def bwd(a, ws, ws_bytes, stream):
+            rc = lib.gnntrk_mlp_backward_bf16(a, ws, ws_bytes, stream)
+            # (bce_supported is asked with a stand-in loss block: whether the SHAPE is the fused head's)
+            hb = _capi.HeadBce(self._label.data_ptr(), self._w.data_ptr(), 1.0, 0, int(a._obj.n_rows))
+            self.seen.append(("bwd", name(lib.gnntrk_mlp_backward_bf16_kernel_name, a), rc) + probes(a, C.byref(hb)))
+            return rc
+
+        def bwd_bce(a, hb, ws, ws_bytes, stream):
+            rc = lib.gnntrk_mlp_backward_bf16_bce(a, hb, ws, ws_bytes, stream)
+            self.seen.append(("bwd", name(lib.gnntrk_mlp_backward_bf16_bce_kernel_name, a, hb), rc) + probes(a, hb))
+            return rc
+
+        self._over = {"gnntrk_mlp_forward_bf16": fwd, "gnntrk_mlp_backward_bf16": bwd,
+                      "gnntrk_mlp_backward_bf16_bce": bwd_bce}
+
+    def __getattr__(self, key):
+        return self._over.get(key) or getattr(self._lib, key)
+
+
+def bf16_instantiation_answers(device, direction, spec, rows):
+    """Runs one table entry; returns what the library answered (forward: the kernel name; backward: name, max_terms,
+    can_fold, bce_supported).  The launch must succeed, and a backward launch's results must equal those of the same
+    launch on the generic I/O (debug_flags = 128) by the rule of case_mlp_bf16_backward: rows within TOL16."""
+    from gnn_tracking_amd import _capi, ops_bf16 as B
+    epi_code = {"none": _capi.EPI_NONE, "relu": _capi.EPI_RELU, "residual": _capi.EPI_RESIDUAL,
+                "sigmoid": _capi.EPI_SIGMOID}
+    gen = torch.Generator().manual_seed(11)
+    torch.manual_seed(11)
+    if direction == "fwd":
+        shape, dims, hid, out, L, bias, epi = spec
+        n_gout, need, flags, mode = 1, None, 0, ""
+    else:
+        shape, dims, hid, out, L, bias, epi, n_gout, need, flags, mode = spec
+    segs, idxs, gidx, gout, n_src = _inst_inputs(shape, dims, rows, out, epi, n_gout, device, gen)
+    relu = [shape == "rel"] * len(dims)
+    m = G.MLP(sum(dims), out, hid, L=L, bias=bias)
+    W = [l.weight.detach().to(device).contiguous() for l in m.linears()]
+    b = [l.bias.detach().to(device).contiguous() if bias else None for l in m.linears()]
+    ca, cb = (0.6, 0.8) if epi == "residual" else ((0.001, 0.998) if epi == "sigmoid" else (0.0, 1.0))
+    spy = _LaunchSpy(_capi.load(), device)
+    saved = (_capi.load, B._DEBUG_FLAGS, B.FOLD_IN_KERNEL)
+    _capi.load = lambda: spy
+    try:
+        if direction == "fwd":
+            res = _rows16_on(device, rows, out, gen, True) if epi == "residual" else None
+            B.mlp_forward_raw(segs, idxs, relu, W, b, n_rows=rows, epilogue=epi_code[epi], ca=ca, cb=cb, res=res,
+                              out_idx=None, out_rows=rows, mlp=ops._fill_mlp(W, b))
+            (_, name, rc), = spy.seen
+            assert rc == 0, (spec, rows, rc)
+            return name
+
+        label = (torch.rand(rows + 8, generator=gen) < 0.5).to(torch.uint8).to(device)[:rows]
+
+        def launch(flags_, fold_):
+            B._DEBUG_FLAGS, B.FOLD_IN_KERNEL = flags_, fold_
+            del spy.seen[:]
+            kw, bce = {}, None
+            if fold_:
+                jf = 0 if shape == "rel" else 1
+                rowptr = torch.searchsorted(idxs[jf].cpu().long(), torch.arange(n_src + 1)).int().to(device)
+                kw["fold"] = (jf, n_src, rowptr)
+            if mode == "bce":
+                bce = kw["bce"] = B.HeadBce(label, torch.zeros(rows, dtype=torch.float32, device=device),
+                                            torch.zeros(1, dtype=torch.float32, device=device), 0.5)
+            sl, gW, gb = B.mlp_backward_raw(segs, idxs, relu, W, b, n_rows=rows, epilogue=epi_code[epi], ca=ca, cb=cb,
+                                            gout=[] if mode == "bce" else gout, need_seg=need, want_dw=True,
+                                            mlp=ops._fill_mlp(W, b), gidx=gidx, **kw)
+            seen = [s for s in spy.seen if s[0] == "bwd"]
+            assert len(seen) == 1 and seen[0][2] == 0, (spec, rows, spy.seen)
+            return seen[0][1:2] + seen[0][3:], sl, [g.clone() for g in gW], [None if g is None else g.clone() for g in gb], bce
+
+        got, sl, gW, gb, bce = launch(flags, mode == "fold")
+        ref, sl_g, gW_g, gb_g, bce_g = launch(128, False)
+        tag = f"bf16 instantiation {spec} rows={rows}"
+        assert "IoNone" in ref[0] or "_ot_" in ref[0] or "_bi_" in ref[0], (tag, ref[0])
+        for j in range(len(dims)):
+            if sl[j] is None or j in sl.folded:   # (a folded slice is one row per node: case_mlp_bf16_fold checks it)
+                continue
+            assert_rows_close(sl[j].float(), sl_g[j].float().cpu(), TOL16, f"{tag} gseg{j} vs generic I/O")
+        for i in range(L):
+            assert_close(gW[i], gW_g[i].cpu(), TOL16, f"{tag} gW{i} vs generic I/O")
+            if bias:
+                assert_close(gb[i], gb_g[i].cpu(), TOL16, f"{tag} gb{i} vs generic I/O")
+        if bce is not None:
+            assert_close(bce.w, bce_g.w.cpu(), TOL16_SIG, f"{tag} W vs the forward launch")
+        return got
+    finally:
+        _capi.load, B._DEBUG_FLAGS, B.FOLD_IN_KERNEL = saved
+
+
+def case_bf16_instantiations(device, rows=(33, 1)):
+    """Every branch of the bf16 launchers' selection (forward, generic / output-tile / bias_init backward, every
+    buffer-addressed class, both fold classes, the BCE head): the name entry points and the probes answer the
+    literals of the tables above, the launch runs, and its results are those of the generic I/O."""
+    n = 0
+    for spec, names in BF16_FWD_INSTANTIATIONS:
+        for r, want in zip(rows, names):
+            got = bf16_instantiation_answers(device, "fwd", spec, r)
+            assert got == want, f"forward {spec} rows={r}: {got!r}, the table says {want!r}"
+            n += 1
+    for spec, answers in BF16_BWD_INSTANTIATIONS:
+        for r, want in zip(rows, answers):
+            got = bf16_instantiation_answers(device, "bwd", spec, r)
+            assert got == want, f"backward {spec} rows={r}: {got!r}, the table says {want!r}"
+            n += 1
+    return n
+
+
 def case_bf16_shape_rules_agree(device, hiddens=(1, 16, 31, 32, 33, 40, 47, 48, 63, 64, 65, 95, 96, 97, 112, 127, 128, 129),
                                 outs=(1, 4, 16, 17, 40, 48, 49), min_ran=300):
     """What ``ops._fused_supported`` accepts in bf16 storage, the C launchers run - forward and backward - over a

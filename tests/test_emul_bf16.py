@@ -85,3 +85,10 @@ def test_mlp_bf16_in_kernel_fold_emulated():
     nodes, the tail unit - relational and head shapes."""
     with emulated():
         assert P.case_mlp_bf16_fold("cpu", sizes=(1, 31, 33, 75, 640)) == 3 * 5 * 4
+
+
+def test_bf16_instantiations_emulated():
+    """Names, probes and launches of every branch of the bf16 launchers' selection (names and probes are host code:
+    the emulator build answers what the GPU build answers)."""
+    with emulated():
+        assert P.case_bf16_instantiations("cpu") == 2 * (17 + 23)

@@ -367,6 +367,12 @@ def test_mlp_bf16_in_kernel_fold(dev):
     assert P.case_mlp_bf16_fold(dev) == 3 * 7 * 4
 
 
+def test_bf16_instantiations(dev):
+    """Every branch of the bf16 launchers' selection: kernel names and probe answers are the recorded literals, the
+    launches run and agree with the generic I/O (17 forward + 23 backward entries, 33 rows and 1)."""
+    assert P.case_bf16_instantiations(dev) == 2 * (17 + 23)
+
+
 def test_cfg3_full_size_event_against_oracle(dev):
     rep = P.case_cfg3_event(dev)
     print("cfg3 event:", rep)
