@@ -13,6 +13,7 @@ no CPU fallback.
 from .data import Data, collate
 from .io import GraphDataset, PrefetchLoader, ResidentDataset, load_graph, renumber_nodes
 from .edge_classifier import ECForGraphTCN, PerfectEdgeClassification
+from .edge_filter import EFMLP, EFDeepSet, GeometricEF
 from .interaction_network import InteractionNetwork
 from .graph_construction import MLGraphConstruction, MLPCTransformer, knn_scan, knn_with_max_radius
 from .graph_masks import get_good_node_mask, get_good_node_mask_tensors
@@ -52,4 +53,4 @@ __all__ = ["Data", "collate", "MLP", "InteractionNetwork", "ResIN", "ECForGraphT
            "tracking_metrics_trials", "flatten_track_metrics", "ClusterScanner", "CombinedClusterScanner",
            "DBSCANHyperParamScanner", "DBSCANHyperParamScannerFixed", "OCScanResults", "get_cc_labels",
            "get_largest_segment_fracs", "get_efficiency_purity_edges", "GraphConstructionKNNScanner",
-           "KScanResults"]
+           "KScanResults", "EFMLP", "EFDeepSet", "GeometricEF"]

@@ -111,6 +111,21 @@ class ResFcnnGrads(C.Structure):
                 ("out_scale", C.c_void_p)]
 
 
+class EfMlp(C.Structure):
+    _fields_ = [("W_enc", C.c_void_p), ("W_hid", C.c_void_p * RESFCNN_MAX_HIDDEN), ("W_dec", C.c_void_p),
+                ("node_dim", C.c_int32), ("edge_dim", C.c_int32), ("hidden", C.c_int32), ("n_hidden", C.c_int32),
+                ("beta", C.c_float), ("derived", C.c_int32)]
+
+
+class EfMlpGrads(C.Structure):
+    _fields_ = [("W_enc", C.c_void_p), ("W_hid", C.c_void_p * RESFCNN_MAX_HIDDEN), ("W_dec", C.c_void_p)]
+
+
+class EdgeRows(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("edge_index", C.c_void_p), ("edge_attr", C.c_void_p), ("n_nodes", C.c_int64),
+                ("n_edges", C.c_int64), ("edge_stride", C.c_int64), ("x_stride", C.c_int32), ("ea_stride", C.c_int32)]
+
+
 class HingeArgs(C.Structure):
     _fields_ = [("x", C.c_void_p), ("dim", C.c_int32), ("x_stride", C.c_int32), ("n_nodes", C.c_int64),
                 ("node_mask", C.c_void_p), ("particle_id", C.c_void_p), ("r_emb", C.c_float), ("p", C.c_float),
@@ -222,6 +237,15 @@ _SIGNATURES = {
     "gnntrk_resfcnn_backward": (C.c_int, [C.POINTER(ResFcnn), _P, C.c_int32, C.c_int64, _P, _P, C.c_int32, _P,
                                           C.c_int32, _P, C.c_int32, C.POINTER(ResFcnnGrads), C.c_int32, _P,
                                           C.c_size_t, _P]),
+    "gnntrk_efmlp_forward_workspace_bytes": (C.c_size_t, [C.POINTER(EfMlp)]),
+    "gnntrk_efmlp_forward": (C.c_int, [C.POINTER(EfMlp), C.POINTER(EdgeRows), _P, _P, C.c_size_t, _P]),
+    "gnntrk_efmlp_backward_chunk_rows": (C.c_int64, [C.POINTER(EfMlp), C.c_int64, C.c_size_t]),
+    "gnntrk_efmlp_backward_workspace_bytes": (C.c_size_t, [C.POINTER(EfMlp), C.c_int64, C.c_size_t]),
+    "gnntrk_efmlp_backward": (C.c_int, [C.POINTER(EfMlp), C.POINTER(EdgeRows), _P, C.POINTER(EfMlpGrads), C.c_int32,
+                                        C.c_size_t, _P, C.c_size_t, _P]),
+    "gnntrk_pair_invariants_forward": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P]),
+    "gnntrk_pair_invariants_backward": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P,
+                                                  _P, _P]),
     "gnntrk_hinge_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gnntrk_hinge_forward": (C.c_int, [C.POINTER(HingeArgs), _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_size_t, _P]),
     "gnntrk_hinge_backward": (C.c_int, [C.POINTER(HingeArgs), C.POINTER(GraphIndex), _P, _P, _P, C.c_int32,

@@ -3,17 +3,27 @@
 Reference: models/graph_construction.py:222-413 (``knn_with_max_radius``,
 ``MLGraphConstruction``).  The kNN search replaces ``torch_cluster.knn_graph``; edge
 labels and edge features are built by two small gather kernels.  The optional embedding
-network ``ml`` and edge filter ``ec`` are ordinary modules supplied by the caller.
+network ``ml`` and edge filter ``ec`` are modules supplied by the caller.  With
+``GNNTRK_EF_FUSED_CUT=1`` an ``edge_filter.EFMLP`` on ``[x_i, x_j, edge features]`` that runs on its
+kernel scores the kNN edges BEFORE their features are written (the kernel derives them in registers)
+and only the kept edges get an ``edge_attr`` row; ``0`` (the default until that order is measured
+faster): features first, as for every other filter.  The ``Data`` is the same bits.
 """
 
 from __future__ import annotations
 
+import os
+
 import torch
 from torch import Tensor, nn
 
-from . import ops
+from . import graph_cut, ops
 from .data import Data
+from .edge_filter import EFMLP
 from .hparams import HyperparametersMixin, obj_from_or_to_hparams
+
+
+_EF_FUSED_CUT = os.environ.get("GNNTRK_EF_FUSED_CUT", "0") != "0"
 
 
 def knn_with_max_radius(x: Tensor, k: int, max_radius: float | None = None) -> Tensor:
@@ -78,6 +88,13 @@ class MLGraphConstruction(nn.Module, HyperparametersMixin):
             node_dim += self._ml.out_dim
         return node_dim, (2 * node_dim if self.hparams.build_edge_features else 0)
 
+    def _score_before_features(self, x: Tensor) -> bool:
+        ef = self._ef
+        return (_EF_FUSED_CUT and isinstance(ef, EFMLP) and bool(self.hparams.build_edge_features)
+                and ef.hparams.node_indim == x.shape[1] and ef.hparams.edge_indim == 2 * x.shape[1]
+                and ef.kernel_supported() and x.dtype == torch.float32
+                and not (torch.is_grad_enabled() and x.requires_grad))
+
     def forward(self, data) -> Data:
         if not hasattr(data, "true_edge_index"):
             data.true_edge_index = data.edge_index
@@ -103,14 +120,24 @@ class MLGraphConstruction(nn.Module, HyperparametersMixin):
             y = torch.cat((torch.zeros(false_edges.shape[1], dtype=y.dtype, device=y.device),
                            torch.ones(true_edges.shape[1], dtype=y.dtype, device=y.device)))
         edge_attr = None
-        if self.hparams.build_edge_features:
+        if self._score_before_features(x):
+            # the filter's third input segment IS ops.edge_features(x, edge_index): scored from x alone, then the
+            # features of the kept edges only (the same kernel on the same hits: the same bits)
+            w = self._ef.score(x, edge_index, None, derived=True)
+            _mask, idx = graph_cut.threshold_compact(w, self.hparams.ec_threshold)
+            idx = idx.long()
+            edge_index = edge_index.index_select(1, idx)
+            y = y.index_select(0, idx)
             edge_attr = ops.edge_features(x, edge_index)
-        if self._ef is not None:
-            w = self._ef(Data(x=x, edge_index=edge_index, edge_attr=edge_attr))["W"]
-            mask = w > self.hparams.ec_threshold
-            edge_index = edge_index[:, mask].contiguous()
-            y = y[mask]
-            edge_attr = edge_attr[mask]
+        else:
+            if self.hparams.build_edge_features:
+                edge_attr = ops.edge_features(x, edge_index)
+            if self._ef is not None:
+                w = self._ef(Data(x=x, edge_index=edge_index, edge_attr=edge_attr))["W"]
+                mask = w > self.hparams.ec_threshold
+                edge_index = edge_index[:, mask].contiguous()
+                y = y[mask]
+                edge_attr = edge_attr[mask]
         return Data(x=x, edge_index=edge_index, true_edges=data.true_edge_index, y=y.long(),
                     pt=data.pt, particle_id=data.particle_id,
                     sector=getattr(data, "sector", None),

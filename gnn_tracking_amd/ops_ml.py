@@ -6,6 +6,10 @@
   (``metrics/losses/metric_learning.py:14-55``) with the reference's edge selection applied inside the
   kernels (``gnntrk_hinge_forward`` / ``_backward``, csrc/hinge.hip).
 
+* ``ef_mlp``: the ``EFMLP`` edge filter (``models/edge_filter.py:68-141``) on gathered edge rows, one forward
+  launch and a chunked backward that keeps no edge-sized state (``gnntrk_efmlp_*``, csrc/edge_filter.hip);
+  ``pair_invariants``: the per-edge invariants of ``EFDeepSet`` (``gnntrk_pair_invariants_*``).
+
 No CPU path: the tensors must live on the GPU (``_capi.require_device``).
 """
 
@@ -106,6 +110,150 @@ def res_fcnn(x: Tensor, weights: Sequence[Tensor], biases: Sequence[Optional[Ten
     None).  ``scale``: one-element parameter multiplied onto the output (``_latent_normalization``)."""
     return _ResFCNN.apply(x, scale, float(alpha), bool(normalize), bool(out_relu), len(weights), torch.is_grad_enabled(),
                           *weights, *biases)
+
+
+# ----------------------------------------------------------------------------------- edge filters
+#: bytes of per-edge state a backward chunk of ``ef_mlp`` may hold (DESIGN.md section 4.15)
+EF_WORKSPACE_CAP = 1 << 30
+
+
+def ef_mlp_supported(node_dim: int, edge_dim: int, hidden: int, depth: int) -> bool:
+    """Shapes ``gnntrk_efmlp_*`` instantiates (include/gnntrk.h)."""
+    return (node_dim >= 1 and edge_dim >= 0 and 2 * node_dim + edge_dim <= _capi.RESFCNN_MAX_IN
+            and 1 <= hidden <= _capi.RESFCNN_MAX_WIDTH and 1 <= depth <= _capi.RESFCNN_MAX_HIDDEN + 1)
+
+
+def _edge_rows(x: Tensor, edge_index: Tensor, edge_attr: Optional[Tensor]):
+    """``(gnntrk_edge_rows, tensors to keep alive)``; ``edge_index`` rows may be any distance apart."""
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype != torch.int64:
+        raise ValueError("edge filter: edge_index must be int64 [2, E]")
+    n_e = int(edge_index.shape[1])
+    e = edge_index if n_e > 1 and edge_index.stride(1) == 1 and edge_index.stride(0) >= n_e else edge_index.contiguous()
+    if ops._VALIDATE and n_e > 0:   # (a host synchronisation, off by default: unchecked ids out of range are clamped)
+        lo, hi = int(e.min()), int(e.max())
+        if lo < 0 or hi >= int(x.shape[0]):
+            raise IndexError(f"edge filter: node ids in [{lo}, {hi}] outside [0, {int(x.shape[0])})")
+    d = _capi.EdgeRows()
+    d.x, d.edge_index, d.edge_attr = _p(x), _p(e), _p(edge_attr)
+    d.n_nodes, d.n_edges, d.edge_stride = int(x.shape[0]), n_e, int(e.stride(0)) if n_e > 1 else max(n_e, 1)
+    d.x_stride = int(x.shape[1])
+    d.ea_stride = 0 if edge_attr is None else int(edge_attr.shape[1])
+    return d, (x, e, edge_attr)
+
+
+def _ef_model(weights: Sequence[Tensor], node_dim: int, beta: float, derived: bool) -> _capi.EfMlp:
+    m = _capi.EfMlp()
+    m.W_enc, m.W_dec = _p(weights[0]), _p(weights[-1])
+    for i in range(len(weights) - 2):
+        m.W_hid[i] = _p(weights[1 + i])
+    m.node_dim, m.edge_dim = node_dim, int(weights[0].shape[1]) - 2 * node_dim
+    m.hidden, m.n_hidden = int(weights[0].shape[0]), len(weights) - 2
+    m.beta, m.derived = float(beta), int(derived)
+    return m
+
+
+class _EFMLP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, edge_index, edge_attr, beta: float, derived: bool, cap: int, *weights):
+        weights = [w.contiguous() for w in weights]
+        _capi.require_device(x, edge_index, edge_attr, *weights)
+        lib = _capi.load()
+        if x.dtype != torch.float32 or any(w.dtype != torch.float32 for w in weights) or \
+                (edge_attr is not None and edge_attr.dtype != torch.float32):
+            raise TypeError("ef_mlp: fp32 rows and parameters expected")
+        x = x.contiguous()
+        edge_attr = None if edge_attr is None else edge_attr.contiguous()
+        node_dim = int(x.shape[1])
+        edge_dim = int(weights[0].shape[1]) - 2 * node_dim
+        have = 2 * node_dim if derived else (0 if edge_attr is None else int(edge_attr.shape[1]))
+        if edge_dim < 0 or have != edge_dim:
+            raise AssertionError(f"Expected feature dimension {edge_dim}, got {have}")
+        if edge_attr is not None and edge_attr.shape[0] != edge_index.shape[1]:
+            raise ValueError("ef_mlp: one edge_attr row per edge expected")
+        m = _ef_model(weights, node_dim, beta, derived)
+        d, keep = _edge_rows(x, edge_index, edge_attr)
+        out = torch.empty(d.n_edges, dtype=torch.float32, device=x.device)
+        ws = _ws(lib.gnntrk_efmlp_forward_workspace_bytes(C.byref(m)), x)
+        _capi.check(lib.gnntrk_efmlp_forward(C.byref(m), C.byref(d), _p(out), _p(ws), ws.numel(), _stream(x)), lib)
+        # (nothing edge-sized but the inputs is kept: the backward re-runs the forward chunk by chunk)
+        ctx.cfg = (float(beta), bool(derived), int(cap), edge_attr is not None)
+        ctx.save_for_backward(keep[0], keep[1], *([edge_attr] if edge_attr is not None else []), *weights)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _capi.load()
+        beta, derived, cap, has_attr = ctx.cfg
+        x, e = ctx.saved_tensors[:2]
+        edge_attr = ctx.saved_tensors[2] if has_attr else None
+        weights = list(ctx.saved_tensors[2 + int(has_attr):])
+        m = _ef_model(weights, int(x.shape[1]), beta, derived)
+        d, _keep = _edge_rows(x, e, edge_attr)
+        g = g.contiguous().to(torch.float32)
+        gW = [torch.empty_like(w) for w in weights]
+        gr = _capi.EfMlpGrads()
+        gr.W_enc, gr.W_dec = _p(gW[0]), _p(gW[-1])
+        for i in range(len(weights) - 2):
+            gr.W_hid[i] = _p(gW[1 + i])
+        ws = _ws(lib.gnntrk_efmlp_backward_workspace_bytes(C.byref(m), d.n_edges, cap), x)
+        _capi.check(lib.gnntrk_efmlp_backward(C.byref(m), C.byref(d), _p(g), C.byref(gr), 0, cap, _p(ws), ws.numel(),
+                                              _stream(x)), lib)
+        return (None, None, None, None, None, None, *gW)
+
+
+def ef_mlp(x: Tensor, edge_index: Tensor, edge_attr: Optional[Tensor], weights: Sequence[Tensor], *, beta: float,
+           derived: bool = False, workspace_cap: Optional[int] = None) -> Tensor:
+    """``W`` [E] of ``EFMLP``: ``weights = [W_enc, W_hidden_1 .., W_dec]`` (``nn.Linear`` storage, no biases).
+
+    ``derived``: ``edge_attr`` is None and stands for ``ops.edge_features(x, edge_index)``, formed inside the
+    kernel (bit for bit the same ``W``).  ``workspace_cap``: bytes of per-edge state one chunk of the backward
+    may hold (default ``EF_WORKSPACE_CAP``); the weight gradients are deterministic for a given cap.  No gradient
+    reaches ``x`` or ``edge_attr``."""
+    cap = EF_WORKSPACE_CAP if workspace_cap is None else int(workspace_cap)
+    return _EFMLP.apply(x, edge_index, edge_attr, float(beta), bool(derived), cap, *weights)
+
+
+class _PairInvariants(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, edge_index):
+        _capi.require_device(h, edge_index)
+        lib = _capi.load()
+        if h.dtype != torch.float32:
+            raise TypeError("pair_invariants: fp32 rows expected")
+        h = h.contiguous()
+        d, keep = _edge_rows(h, edge_index, None)
+        f = int(h.shape[1])
+        out = torch.empty(d.n_edges, 2 * f, dtype=torch.float32, device=h.device)
+        _capi.check(lib.gnntrk_pair_invariants_forward(_p(h), f, f, d.n_nodes, d.edge_index, d.edge_stride, d.n_edges,
+                                                       _p(out), _stream(h)), lib)
+        ctx.save_for_backward(h, keep[1])
+        ctx.ei = edge_index
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _capi.load()
+        h, e = ctx.saved_tensors
+        n, f, n_e = int(h.shape[0]), int(h.shape[1]), int(e.shape[1])
+        if n_e == 0:
+            return torch.zeros_like(h), None
+        d, _keep = _edge_rows(h, e, None)
+        g = g.contiguous().to(torch.float32)
+        gi_, gj_ = (torch.empty(n_e, f, dtype=torch.float32, device=h.device) for _ in range(2))
+        _capi.check(lib.gnntrk_pair_invariants_backward(_p(h), f, f, d.n_nodes, d.edge_index, d.edge_stride, d.n_edges,
+                                                        _p(g), _p(gi_), _p(gj_), _stream(h)), lib)
+        # per hit: the edges it ends (edge_index[1]) and the edges it starts - two deterministic segment sums
+        # over the graph index of the edge list, as the backward of ops.edge_features
+        gi = ops.graph_index(ctx.ei, n)
+        gh = ops._segment_sum_raw(ops._permute_raw(gj_, gi.perm, scatter=False), gi.rowptr_t, None, n)
+        ops._segment_sum_raw(ops._permute_raw(gi_, gi.perm, scatter=False), gi.rowptr_s, gi.spos, n, out=gh, accumulate=True)
+        return gh, None
+
+
+def pair_invariants(h: Tensor, edge_index: Tensor) -> Tensor:
+    """``cat[|h[i] - h[j]|, h[i] + h[j]]`` -> ``[E, 2F]`` with ``i, j = edge_index`` (``EFDeepSet``,
+    models/edge_filter.py:53-60); differentiable w.r.t. ``h``."""
+    return _PairInvariants.apply(h, edge_index)
 
 
 # ----------------------------------------------------------------------------------- hinge loss

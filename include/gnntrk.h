@@ -779,6 +779,72 @@ int gnntrk_resfcnn_backward(const gnntrk_resfcnn *m, const float *x, int32_t x_s
                             int32_t gout_stride, float *gx, int32_t gx_stride, const gnntrk_resfcnn_grads *grads,
                             int32_t accumulate, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ edge filters
+ * models/edge_filter.py.  EFMLP (:68-141) is the residual network above on EDGE rows, without biases and
+ * without normalisation, with one logit per edge:
+ *
+ *   v  <- [x[i], x[j], edge_attr[e]]      i = edge_index[0][e], j = edge_index[1][e]      (:124-132)
+ *   h  <- W_enc v                                                                         (:133)
+ *   h  <- sqrt(beta) W_l relu(h) + sqrt(1 - beta) h,   l = 1 .. n_hidden                  (:134-138)
+ *   W  <- 0.001 + 0.998 sigmoid(w_dec . relu(h))                                          (:139)
+ *
+ * derived != 0: there is no edge_attr array; the third segment is [x[i] - x[j], x[i] + x[j]] (edge_dim =
+ * 2 node_dim), formed in registers with the arithmetic of gnntrk_edge_features - bit for bit the W of the
+ * materialised features.  Limits: 2 node_dim + edge_dim <= 64, hidden <= 128, n_hidden <=
+ * GNNTRK_RESFCNN_MAX_HIDDEN.  Node ids outside [0, n_nodes) are clamped.
+ *
+ * The forward writes W and nothing else.  The backward produces the weight gradients from dL/dW [n_edges]
+ * and keeps no edge-sized state between the two calls: it walks the edges in chunks of
+ * gnntrk_efmlp_backward_chunk_rows(m, n_edges, cap_bytes) rows (what fits into cap_bytes of per-row state,
+ * a multiple of 64, at least 64), re-runs the forward of a chunk into the workspace, runs the layer-outer
+ * backward of gnntrk_resfcnn_backward on it and adds the chunk's reduced partial sums to the gradients in
+ * chunk order: deterministic for a given cap, no atomics.  Gradient pointers may be NULL; accumulate != 0
+ * adds into them.  No gradient with respect to x or edge_attr.
+ */
+typedef struct gnntrk_efmlp {
+    const float *W_enc;                              /* [hidden, 2 node_dim + edge_dim] */
+    const float *W_hid[GNNTRK_RESFCNN_MAX_HIDDEN];   /* [hidden, hidden]                */
+    const float *W_dec;                              /* [1, hidden]                     */
+    int32_t node_dim, edge_dim, hidden, n_hidden;
+    float beta;
+    int32_t derived;
+} gnntrk_efmlp;
+
+typedef struct gnntrk_efmlp_grads {
+    float *W_enc;
+    float *W_hid[GNNTRK_RESFCNN_MAX_HIDDEN];
+    float *W_dec;
+} gnntrk_efmlp_grads;
+
+typedef struct gnntrk_edge_rows {
+    const float *x;            /* [n_nodes, x_stride]                                           */
+    const int64_t *edge_index; /* [2, n_edges], the two rows edge_stride elements apart         */
+    const float *edge_attr;    /* [n_edges, ea_stride], or NULL (edge_dim = 0 or derived)       */
+    int64_t n_nodes, n_edges, edge_stride;
+    int32_t x_stride, ea_stride;
+} gnntrk_edge_rows;
+
+size_t gnntrk_efmlp_forward_workspace_bytes(const gnntrk_efmlp *m);
+int gnntrk_efmlp_forward(const gnntrk_efmlp *m, const gnntrk_edge_rows *rows, float *W /* [n_edges] */, void *workspace,
+                         size_t workspace_bytes, void *stream);
+int64_t gnntrk_efmlp_backward_chunk_rows(const gnntrk_efmlp *m, int64_t n_edges, size_t cap_bytes);
+size_t gnntrk_efmlp_backward_workspace_bytes(const gnntrk_efmlp *m, int64_t n_edges, size_t cap_bytes);
+int gnntrk_efmlp_backward(const gnntrk_efmlp *m, const gnntrk_edge_rows *rows, const float *gW /* dL/dW [n_edges] */,
+                          const gnntrk_efmlp_grads *grads, int32_t accumulate, size_t cap_bytes, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
+/* EFDeepSet (:22-65), between its node encoder and its aggregator:
+ *   out[e] = [|h[i] - h[j]|, h[i] + h[j]]                              ([n_edges, 2 dim], :56-60)
+ * backward: the per-edge gradients at the two ends, for the caller's per-hit segment sums
+ *   gi[e] = sign(h[i] - h[j]) g_abs[e] + g_sum[e],  gj[e] = g_sum[e] - sign(h[i] - h[j]) g_abs[e]   (sign(0) = 0)
+ */
+int gnntrk_pair_invariants_forward(const float *h, int32_t dim, int32_t h_stride, int64_t n_nodes,
+                                   const int64_t *edge_index, int64_t edge_stride, int64_t n_edges, float *out,
+                                   void *stream);
+int gnntrk_pair_invariants_backward(const float *h, int32_t dim, int32_t h_stride, int64_t n_nodes,
+                                    const int64_t *edge_index, int64_t edge_stride, int64_t n_edges, const float *gout,
+                                    float *gi /* [n_edges, dim] */, float *gj /* [n_edges, dim] */, void *stream);
+
 /* ------------------------------------------------------------------ hinge embedding loss
  * The two edge-list reductions of GraphConstructionHingeEmbeddingLoss
  * (metrics/losses/metric_learning.py:14-55, `_hinge_loss_components`; edge selection :88-110):
