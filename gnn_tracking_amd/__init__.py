@@ -23,8 +23,9 @@ from .losses_ml import GraphConstructionHingeEmbeddingLoss
 from .losses_oc import CondensationLossRG, CondensationLossTiger, MultiLossFctReturn
 from .metrics import (BinaryClassificationStats, ec_validation_metrics, get_maximized_bcs, get_roc_auc_scores,
                       roc_auc_score)
-from .cluster_metrics import (TrackingMetrics, flatten_track_metrics, tracking_metrics, tracking_metrics_data,
-                              tracking_metrics_trials)
+from .cluster_metrics import (TrackingMetrics, flatten_track_metrics, tracking_metric_table, tracking_metrics,
+                              tracking_metrics_data, tracking_metrics_trials, tracking_metrics_vs_eta,
+                              tracking_metrics_vs_pt)
 from .graph_analysis import get_cc_labels, get_efficiency_purity_edges, get_largest_segment_fracs
 from .k_scanner import GraphConstructionKNNScanner, KScanResults
 from .mlp import MLP
@@ -32,7 +33,7 @@ from .locality import node_order
 from .precision import bf16_storage
 from .resin import ResIN
 from .postprocessing import (ClusterScanner, CombinedClusterScanner, DBSCANFastRescan, DBSCANHyperParamScanner,
-                             DBSCANHyperParamScannerFixed, OCScanResults, dbscan)
+                             DBSCANHyperParamScannerFixed, DBSCANPerformanceDetails, OCScanResults, dbscan)
 from .track_condensation_networks import (GraphConstructionFCNN, GraphConstructionHeteroEncResFCNN,
                                             GraphConstructionHeteroResFCNN, GraphConstructionResIN, GraphTCN,
                                             GraphTCNForMLGCPipeline, PerfectECGraphTCN,
@@ -53,4 +54,5 @@ __all__ = ["Data", "collate", "MLP", "InteractionNetwork", "ResIN", "ECForGraphT
            "tracking_metrics_trials", "flatten_track_metrics", "ClusterScanner", "CombinedClusterScanner",
            "DBSCANHyperParamScanner", "DBSCANHyperParamScannerFixed", "OCScanResults", "get_cc_labels",
            "get_largest_segment_fracs", "get_efficiency_purity_edges", "GraphConstructionKNNScanner",
-           "KScanResults", "EFMLP", "EFDeepSet", "GeometricEF"]
+           "KScanResults", "EFMLP", "EFDeepSet", "GeometricEF", "tracking_metric_table", "tracking_metrics_vs_pt",
+           "tracking_metrics_vs_eta", "DBSCANPerformanceDetails"]

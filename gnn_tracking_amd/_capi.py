@@ -20,6 +20,7 @@ MAX_IN_BF16, MAX_HIDDEN_BF16 = 128, 128             # bf16 storage: 16 four-feat
 EPI_NONE, EPI_RELU, EPI_RESIDUAL, EPI_SIGMOID = 0, 1, 2, 3
 METRICS_MAX_CUTS, METRICS_MAX_THR, AUC_MAX_FPR, AUC_STRIDE = 8, 1024, 4, 28   # gnntrk_bcs_counts / gnntrk_roc_auc
 TRACKING_MAX_TRIALS = 4096                                                      # gnntrk_tracking_metrics
+TRACKING_MAX_WINDOWS = 32                                                       # gnntrk_tracking_metrics_windows
 KSCAN_COLUMNS, KSCAN_MAX_KS = 9, 64                                             # gnntrk_kscan_counts
 
 _PKG = pathlib.Path(__file__).resolve().parent
@@ -258,6 +259,12 @@ _SIGNATURES = {
     "gnntrk_tracking_metrics_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "gnntrk_tracking_metrics": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_float), C.c_int32,
                                           C.c_float, C.c_int32, _P, _P, C.c_size_t, _P]),
+    "gnntrk_tracking_metrics_windows_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "gnntrk_tracking_metrics_windows": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_float),
+                                                  C.c_int32, C.c_int32, _P, _P, C.c_size_t, _P]),
+    "gnntrk_cluster_table_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gnntrk_cluster_table": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t,
+                                       _P]),
     "gnntrk_cc_labels_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gnntrk_cc_labels": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P, _P, _P,
                                    C.c_size_t, _P]),

@@ -14,11 +14,18 @@ Semantics are the reference's with pandas 2 / numpy 2 (``include/gnntrk.h``), wi
 the reference has none: when two particles have the same number of hits in a cluster, the smallest
 particle id is the cluster's majority particle (pandas leaves the choice to an unstable sort).  Cut
 and ``max_eta`` comparisons are in fp32, as numpy 2 compares float32 columns with Python scalars.
+
+The binned views of a study's end (``cluster_metrics.py:76-149, 292-384``) are here too, without
+pandas: ``tracking_metric_table`` is ``tracking_metric_df`` as a dict of numpy columns
+(``gnntrk_cluster_table``), ``tracking_metrics_vs_pt`` / ``tracking_metrics_vs_eta`` return one dict
+per bin; their counts come from ``gnntrk_tracking_metrics_windows``, one call per batch and 32 bins.
 """
 
 from __future__ import annotations
 
 import ctypes as C
+import itertools
+import math
 from typing import Iterable, TypedDict
 
 import numpy as np
@@ -29,7 +36,8 @@ from . import _capi, ops
 from .metrics import denote_pt
 
 __all__ = ["TrackingMetrics", "tracking_metrics", "tracking_metrics_data", "tracking_metrics_trials",
-           "flatten_track_metrics", "denote_pt"]
+           "flatten_track_metrics", "denote_pt", "tracking_metric_table", "tracking_metrics_vs_pt",
+           "tracking_metrics_vs_eta"]
 
 
 class TrackingMetrics(TypedDict):
@@ -82,6 +90,16 @@ def _from_counts(n_particles: int, c: np.ndarray) -> TrackingMetrics:
         "fake_double_majority": _zdiv(n_clusters - n_dm, n_clusters),
         "fake_lhc": _zdiv(n_clusters - n_lhc, n_clusters),
     }
+
+
+def _nanmean(v: np.ndarray) -> float:
+    v = v[~np.isnan(v)]
+    return float(v.mean()) if v.size else float("nan")
+
+
+def _nanstd(v: np.ndarray) -> float:   # (ddof = 1, as pandas)
+    v = v[~np.isnan(v)]
+    return float(v.std(ddof=1)) if v.size > 1 else float("nan")
 
 
 def _device_of(*xs):
@@ -193,3 +211,151 @@ def tracking_metrics_data(data, labels, pt_thlds: Iterable[float], predicted_cou
     return tracking_metrics(truth=data.particle_id, predicted=labels, pts=data.pt,
                             reconstructable=data.reconstructable, eta=data.eta, pt_thlds=pt_thlds,
                             max_eta=max_eta, predicted_count_thld=predicted_count_thld)
+
+
+# ------------------------------------------------------------------ cluster table, binned metrics
+TABLE_COLUMNS = ("maj_pid", "maj_hits", "cluster_size", "valid_cluster", "maj_reconstructable", "maj_eta", "maj_pt",
+                 "maj_pid_hits", "maj_frac", "maj_pid_frac", "perfect_match", "double_majority", "lhc_match")
+
+
+def _dense_labels(lab: Tensor) -> tuple[Tensor, Tensor]:
+    """Labels of any integers -> (labels in [-1, n): negatives -1, the rest their rank; the ascending
+    distinct labels).  No host sync."""
+    uniq, inv = torch.unique(lab, return_inverse=True)
+    return torch.where(lab < 0, torch.full_like(lab, -1), inv), uniq
+
+
+def _table(lab: Tensor, uniq: Tensor | None, t: Tensor, p: Tensor, r: Tensor, e: Tensor,
+           predicted_count_thld: int) -> dict[str, np.ndarray]:
+    """``gnntrk_cluster_table`` of dense labels [n] in [-1, n), its rows with a cluster selected on the
+    device, one host copy; ``uniq``: the label value of every dense label (None: itself)."""
+    lib = _capi.load()
+    _capi.require_device(lab, t, p, r, e)
+    n = int(lab.shape[0])
+    dev = lab.device
+    ints = torch.empty((5, max(n, 1)), dtype=torch.int64, device=dev)   # size, maj_hits, maj_pid, maj_pid_hits | bad
+    flts = torch.empty((3, max(n, 1)), dtype=torch.float32, device=dev)
+    ws = ops._ws(lib.gnntrk_cluster_table_workspace_bytes(n), lab)
+    q = ops._p
+    _capi.check(lib.gnntrk_cluster_table(q(lab), q(t), q(p), q(e), q(r), n, q(ints[0]), q(ints[1]), q(ints[2]),
+                                         q(ints[3]), q(flts[0]), q(flts[1]), q(flts[2]), q(ints[4]), q(ws), ws.numel(),
+                                         ops._stream(lab)), lib)
+    rows = torch.nonzero(ints[0, :n] > 0).view(-1)
+    c = rows if uniq is None else uniq[rows]
+    # (one copy: the label, four integer columns, three fp32 columns as their bits, then the bad-label count)
+    packed = torch.cat([c.view(1, -1), ints[:4, rows], flts[:, rows].view(torch.int32).to(torch.int64)]).view(-1)
+    host = torch.cat([packed, ints[4, :1]]).cpu().numpy()
+    if host[-1] != 0:
+        raise ValueError(f"tracking_metric_table: {int(host[-1])} labels are >= the number of hits")
+    m = int(rows.shape[0])
+    col = host[:-1].reshape(8, m)
+    size, maj_hits, maj_pid, pid_hits = col[1], col[2], col[3], col[4]
+    mpt, meta, mreco = (col[5 + k].astype(np.int32).view(np.float32) for k in range(3))
+    valid = size >= predicted_count_thld
+    # (fp64 ratios; the reference's fillna(0) never applies: a cluster and its majority particle have hits)
+    frac = maj_hits / size
+    pid_frac = maj_hits / pid_hits
+    return {
+        "c": col[0].copy(), "maj_pid": maj_pid.copy(), "maj_hits": maj_hits.copy(), "cluster_size": size.copy(),
+        "valid_cluster": valid, "maj_reconstructable": mreco, "maj_eta": meta, "maj_pt": mpt,
+        "maj_pid_hits": pid_hits.copy(), "maj_frac": frac, "maj_pid_frac": pid_frac,
+        "perfect_match": (pid_hits == maj_hits) & (frac > 0.99) & valid,
+        "double_majority": (pid_frac > 0.5) & (frac > 0.5) & valid,
+        "lhc_match": (frac > 0.75) & valid,
+    }
+
+
+def tracking_metric_table(labels, *, truth, pts, reconstructable, eta, predicted_count_thld=3) -> dict[str, np.ndarray]:
+    """``tracking_metric_df`` (cluster_metrics.py:76-149) of one labelling as a dict of numpy columns:
+    the index ``c`` (ascending cluster labels) and the reference's 13 columns in its order and dtypes.
+    Inputs as ``tracking_metrics`` takes them.  Differences from the reference: only clusters (labels
+    >= 0) have rows - the reference also lists its negative labels, as rows that are never valid - and
+    ties for the majority particle go to the smallest id."""
+    if not torch.is_tensor(labels):
+        labels = torch.as_tensor(np.asarray(labels))
+    if labels.dim() != 1:
+        raise ValueError("tracking_metric_table: labels must be [n]")
+    dev = _device_of(labels, truth, pts, reconstructable, eta)
+    t, p, r, e = _hits(truth, pts, reconstructable, eta, dev)
+    if int(t.shape[0]) != int(labels.shape[0]):
+        raise ValueError("tracking_metric_table: labels and truth differ in the number of hits")
+    lab, uniq = _dense_labels(_on(labels, torch.int64, dev))
+    return _table(lab, uniq, t, p, r, e, predicted_count_thld)
+
+
+def _window_counts(h: dict, windows: np.ndarray, predicted_count_thld: int) -> tuple[np.ndarray, np.ndarray]:
+    """One batch's hit record and fp32 windows [n, 4] -> (n_particles [n], counts [n, 4]); one
+    ``gnntrk_tracking_metrics_windows`` call and one host copy per 32 windows."""
+    lib = _capi.load()
+    dev = _device_of(h["c"], h["id"], h["pt"], h["reconstructable"], h["eta"])
+    t, p, r, e = _hits(h["id"], h["pt"], h["reconstructable"], h["eta"], dev)
+    lab, _ = _dense_labels(_on(h["c"], torch.int64, dev).view(-1))
+    n = int(lab.shape[0])
+    if int(t.shape[0]) != n:
+        raise ValueError("tracking_metrics_vs: a hit record's columns differ in length")
+    n_part = np.zeros(len(windows), dtype=np.int64)
+    counts = np.zeros((len(windows), 4), dtype=np.int64)
+    if n == 0:
+        return n_part, counts
+    _capi.require_device(lab, t, p, r, e)
+    ws = ops._ws(lib.gnntrk_tracking_metrics_windows_workspace_bytes(n, 1), lab)
+    q = ops._p
+    for lo in range(0, len(windows), _capi.TRACKING_MAX_WINDOWS):
+        win = np.ascontiguousarray(windows[lo:lo + _capi.TRACKING_MAX_WINDOWS], dtype=np.float32)
+        nw = len(win)
+        out = torch.empty(nw * 5 + 1, dtype=torch.int64, device=dev)
+        _capi.check(lib.gnntrk_tracking_metrics_windows(q(lab), 1, q(t), q(p), q(e), q(r), n,
+                                                        win.ctypes.data_as(C.POINTER(C.c_float)), nw,
+                                                        int(predicted_count_thld), q(out), q(ws), ws.numel(),
+                                                        ops._stream(lab)), lib)
+        host = out.cpu().numpy()
+        if host[-1] != 0:
+            raise ValueError(f"tracking_metrics_vs: {int(host[-1])} labels are >= the number of hits")
+        n_part[lo:lo + nw] = host[:nw]
+        counts[lo:lo + nw] = host[nw:nw * 5].reshape(nw, 4)
+    return n_part, counts
+
+
+def _binned(h_dfs, c_dfs, edges, window_of, names: tuple[str, str], predicted_count_thld: int) -> list[dict]:
+    h_dfs, edges = list(h_dfs), list(edges)
+    if len(list(c_dfs)) != len(h_dfs):
+        raise ValueError("tracking_metrics_vs: h_dfs and c_dfs differ in length")
+    bins = list(itertools.pairwise(edges))
+    if not bins:
+        return []
+    # (edges rounded to fp32: numpy 2 compares float32 columns with Python scalars in fp32)
+    windows = np.array([window_of(lo, hi) for lo, hi in bins], dtype=np.float32).reshape(len(bins), 4)
+    per_batch = [_window_counts(h, windows, predicted_count_thld) for h in h_dfs]
+    rows = []
+    for j, (lo, hi) in enumerate(bins):
+        ms = [_from_counts(int(n_part[j]), counts[j]) for n_part, counts in per_batch]
+        keys = list(ms[0]) if ms else list(_from_counts(0, np.zeros(4, np.int64)))
+        vals = {k: np.array([float(m[k]) for m in ms], dtype=np.float64) for k in keys}
+        row = {k: _nanmean(v) for k, v in vals.items()}
+        norm = math.sqrt(len(ms)) if ms else float("nan")
+        row.update({k + "_err": _nanstd(v) / norm for k, v in vals.items()})
+        row[names[0]], row[names[1]] = lo, hi
+        rows.append(row)
+    return rows
+
+
+def tracking_metrics_vs_pt(h_dfs, c_dfs, pts, *, max_eta: float = 4.0, predicted_count_thld=3) -> list[dict[str, float]]:
+    """``cluster_metrics.py:292-337``: the tracking metrics per pt slice ``[pts[i], pts[i + 1])``, one
+    dict per slice with the eight ``TrackingMetrics`` keys (NaN-skipping mean over the batches), their
+    ``_err`` (ddof = 1 std over the batches / sqrt(number of batches); NaN for one batch), ``pt_min``
+    and ``pt_max``.  ``h_dfs``: per batch a hit record - a mapping with ``c`` (labels), ``id``,
+    ``reconstructable``, ``pt``, ``eta`` as device tensors or arrays, as ``DBSCANPerformanceDetails``
+    keeps them.  ``c_dfs`` is accepted for the reference's signature and checked for its length only:
+    the clusters are rebuilt on the device with ``predicted_count_thld``.  As in the reference, eta is
+    tested as ``eta < max_eta``, signed."""
+    nan = float("nan")
+    return _binned(h_dfs, c_dfs, pts, lambda lo, hi: (lo, hi, nan, max_eta), ("pt_min", "pt_max"),
+                   predicted_count_thld)
+
+
+def tracking_metrics_vs_eta(h_dfs, c_dfs, etas, pt_thld: float = 0.9, *, predicted_count_thld=3) -> list[dict[str, float]]:
+    """``cluster_metrics.py:340-384``: the same per eta slice ``[etas[i], etas[i + 1])`` for
+    ``pt >= pt_thld``, with ``eta_min`` and ``eta_max``."""
+    nan = float("nan")
+    return _binned(h_dfs, c_dfs, etas, lambda lo, hi: (pt_thld, nan, lo, hi), ("eta_min", "eta_max"),
+                   predicted_count_thld)

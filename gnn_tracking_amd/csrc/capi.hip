@@ -137,6 +137,10 @@ int roc_auc(const float *, const void *, int32_t, const int32_t *, const void *,
 size_t tracking_metrics_ws_bytes(int64_t, int32_t);
 int tracking_metrics(const int64_t *, int32_t, const int64_t *, const float *, const float *, const float *, int64_t,
                      const float *, int32_t, float, int32_t, int64_t *, void *, size_t, hipStream_t);
+int tracking_metrics_windows(const int64_t *, int32_t, const int64_t *, const float *, const float *, const float *,
+                             int64_t, const float *, int32_t, int32_t, int64_t *, void *, size_t, hipStream_t);
+int cluster_table(const int64_t *, const int64_t *, const float *, const float *, const float *, int64_t, int64_t *,
+                  int64_t *, int64_t *, int64_t *, float *, float *, float *, int64_t *, void *, size_t, hipStream_t);
 
 // kscan.hip
 size_t cc_labels_ws_bytes(int64_t);
@@ -450,6 +454,28 @@ int gnntrk_tracking_metrics(const int64_t *labels, int32_t n_trials, const int64
                             void *workspace, size_t workspace_bytes, void *stream) {
     return tracking_metrics(labels, n_trials, particle_id, pt, eta, reconstructable, n, cuts, n_cuts, max_eta,
                             predicted_count_thld, out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t gnntrk_tracking_metrics_windows_workspace_bytes(int64_t n, int32_t n_trials) {
+    return tracking_metrics_ws_bytes(n, n_trials);
+}
+int gnntrk_tracking_metrics_windows(const int64_t *labels, int32_t n_trials, const int64_t *particle_id,
+                                    const float *pt, const float *eta, const float *reconstructable, int64_t n,
+                                    const float *windows, int32_t n_win, int32_t predicted_count_thld, int64_t *out,
+                                    void *workspace, size_t workspace_bytes, void *stream) {
+    return tracking_metrics_windows(labels, n_trials, particle_id, pt, eta, reconstructable, n, windows, n_win,
+                                    predicted_count_thld, out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t gnntrk_cluster_table_workspace_bytes(int64_t n) { return tracking_metrics_ws_bytes(n, 1); }
+int gnntrk_cluster_table(const int64_t *labels, const int64_t *particle_id, const float *pt, const float *eta,
+                         const float *reconstructable, int64_t n, int64_t *cluster_size, int64_t *maj_hits,
+                         int64_t *maj_pid, int64_t *maj_pid_hits, float *maj_pt, float *maj_eta,
+                         float *maj_reconstructable, int64_t *n_bad, void *workspace, size_t workspace_bytes,
+                         void *stream) {
+    return cluster_table(labels, particle_id, pt, eta, reconstructable, n, cluster_size, maj_hits, maj_pid,
+                         maj_pid_hits, maj_pt, maj_eta, maj_reconstructable, n_bad, workspace, workspace_bytes,
+                         (hipStream_t)stream);
 }
 
 size_t gnntrk_cc_labels_workspace_bytes(int64_t n) { return cc_labels_ws_bytes(n); }

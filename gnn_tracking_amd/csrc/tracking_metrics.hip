@@ -21,6 +21,15 @@
 //                                                     sums, LDS, one int64 atomic per workgroup and value
 //
 // Every output is an integer count, so the result does not depend on the order in which atomics land.
+//
+// Two more entries share the tables, the pair kernels and the tie rule:
+//   tracking_metrics_windows    the same counts for up to 32 two-sided (pt, eta) windows that may overlap
+//                               (tracking_metrics_vs_pt / _vs_eta, cluster_metrics.py:292-384).  Windows
+//                               are not nested, so the "highest cut class" becomes a bit mask per particle:
+//                               tm_particles_kernel<WinSel> ORs the windows of its hits, tmw_particle_kernel
+//                               stores the windows of its means, tmw_clusters_kernel walks the set bits
+//   cluster_table               one labelling's per-cluster rows (tracking_metric_df, :76-149) as dense
+//                               per-label columns: tm_table_kernel
 // Tie rule: the majority particle of a cluster is the one with the most hits in it and, among equals,
 // the smallest particle id (pandas' value_counts leaves ties to an unstable sort).
 #include <math.h>
@@ -34,6 +43,7 @@ namespace {
 constexpr int kTpb = 256;
 constexpr int kMaxCuts = GNNTRK_METRICS_MAX_CUTS;
 constexpr int kProps = 3;   // pt, eta, reconstructable
+constexpr int kMaxWin = GNNTRK_TRACKING_MAX_WINDOWS;
 
 // signed particle id -> unsigned key of the same order (the tie rule's atomic minimum)
 __device__ __forceinline__ unsigned long long pid_key(int64_t pid) { return (unsigned long long)pid ^ (1ull << 63); }
@@ -45,6 +55,44 @@ __device__ __forceinline__ int cut_class(float v, const Cuts &cuts) {
     return k;
 }
 
+// up to kMaxWin windows (pt_lo, pt_hi, eta_lo, eta_hi), passed to kernels by value
+struct Windows {
+    float v[kMaxWin][4];
+    int32_t n;
+};
+
+// bit j: lo <= value < hi of window j for pt and (signed) eta; a NaN bound is not tested, a NaN value
+// fails every test that is
+__device__ __forceinline__ uint32_t window_mask(float pt, float eta, const Windows &w) {
+    uint32_t m = 0u;
+    for (int j = 0; j < w.n; ++j) {
+        const float *b = w.v[j];
+        const bool in = (b[0] != b[0] || pt >= b[0]) && (b[1] != b[1] || pt < b[1]) &&
+                        (b[2] != b[2] || eta >= b[2]) && (b[3] != b[3] || eta < b[3]);
+        m |= in ? (1u << j) : 0u;
+    }
+    return m;
+}
+
+// What a hit contributes to its particle's phit word.  CutSel: the highest cut class, nested cuts
+// (tracking_metrics).  WinSel: the mask of the windows it lies in (n = 0: nothing, cluster_table).
+struct CutSel {
+    Cuts cuts;
+    float max_eta;
+    // hit mask: pt >= cut, reconstructable truthy (NaN is), |eta| < max_eta (NaN is not)
+    __device__ __forceinline__ uint32_t hit(float pt, float eta, float reco) const {
+        return (reco != 0.f && fabsf(eta) < max_eta) ? (uint32_t)cut_class(pt, cuts) : 0u;
+    }
+    __device__ __forceinline__ static void merge(uint32_t *p, uint32_t c) { atomicMax(p, c); }
+};
+struct WinSel {
+    Windows win;
+    __device__ __forceinline__ uint32_t hit(float pt, float eta, float reco) const {
+        return reco != 0.f ? window_mask(pt, eta, win) : 0u;
+    }
+    __device__ __forceinline__ static void merge(uint32_t *p, uint32_t c) { atomicOr(p, c); }
+};
+
 // the particle table's slot of pid (present: every particle id of the hits was inserted)
 __device__ __forceinline__ int64_t find_particle(const int32_t *ptab, const int64_t *pid, uint64_t mask, int64_t key) {
     return (int64_t)table_find(ptab, mask, mix64((uint64_t)key), [&](int32_t h) { return pid[h] == key; });
@@ -53,8 +101,8 @@ __device__ __forceinline__ int64_t find_particle(const int32_t *ptab, const int6
 struct Ws {
     int32_t *ptab;            // [S]  particle table: first hit + 1, 0 = empty
     uint32_t *pcnt;           // [S]  hits per particle
-    uint32_t *phit;           // [S]  highest hit cut class of the particle (n_particles)
-    uint32_t *pcls;           // [S]  cut class of the particle's means (cluster mask)
+    uint32_t *phit;           // [S]  highest hit cut class of the particle (n_particles); windows: mask of its hits
+    uint32_t *pcls;           // [S]  cut class of the particle's means (cluster mask); windows: their mask
     uint32_t *pnn;            // [3][S] non-NaN values per property
     double *psum;             // [3][S] fp64 sums of the non-NaN values
     uint32_t *hslot;          // [n]  particle slot of every hit
@@ -91,11 +139,11 @@ Ws make_ws(void *base, int64_t n, int32_t T) {
 }
 
 // ------------------------------------------------------------------ once per call
+template <class Sel>
 __global__ __launch_bounds__(kTpb) void tm_particles_kernel(const int64_t *__restrict__ pid,
                                                             const float *__restrict__ pt,
                                                             const float *__restrict__ eta,
-                                                            const float *__restrict__ reco, int64_t n, Cuts cuts,
-                                                            float max_eta, Ws w) {
+                                                            const float *__restrict__ reco, int64_t n, Sel sel, Ws w) {
     const uint64_t mask = w.S - 1;
     for (int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTpb) {
         const int64_t key = pid[i];
@@ -109,10 +157,16 @@ __global__ __launch_bounds__(kTpb) void tm_particles_kernel(const int64_t *__res
             add_f64(&w.psum[(size_t)k * w.S + s], (double)v[k]);
             atomicAdd(&w.pnn[(size_t)k * w.S + s], 1u);
         }
-        // hit mask: pt >= cut, reconstructable truthy (NaN is), |eta| < max_eta (NaN is not)
-        const int hc = (v[2] != 0.f && fabsf(v[1]) < max_eta) ? cut_class(v[0], cuts) : 0;
-        if (hc) atomicMax(&w.phit[s], (uint32_t)hc);
+        const uint32_t hc = sel.hit(v[0], v[1], v[2]);
+        if (hc) Sel::merge(&w.phit[s], hc);
     }
+}
+
+// fp64 mean of property k of the particle in slot s, rounded once to fp32 (groupby().mean() keeps a
+// float32 column's dtype); NaN where every value was
+__device__ __forceinline__ float particle_mean(const Ws &w, int k, int64_t s) {
+    const uint32_t c = w.pnn[(size_t)k * w.S + s];
+    return c ? (float)(w.psum[(size_t)k * w.S + s] / (double)c) : NAN;
 }
 
 __global__ __launch_bounds__(kTpb) void tm_particle_kernel(Cuts cuts, float max_eta, Ws w,
@@ -126,11 +180,7 @@ __global__ __launch_bounds__(kTpb) void tm_particle_kernel(Cuts cuts, float max_
         const int64_t s = base + threadIdx.x;
         if (s >= S || w.ptab[s] == 0) continue;
         float mean[kProps];
-        for (int k = 0; k < kProps; ++k) {
-            const uint32_t c = w.pnn[(size_t)k * S + s];
-            // fp64 mean rounded once to fp32 (groupby().mean() keeps a float32 column's dtype)
-            mean[k] = c ? (float)(w.psum[(size_t)k * S + s] / (double)c) : NAN;
-        }
+        for (int k = 0; k < kProps; ++k) mean[k] = particle_mean(w, k, s);
         // cluster mask of a cluster with this majority particle: maj_pt >= cut, maj_reconstructable
         // truthy (non-zero and not NaN), |maj_eta| < max_eta
         const bool ok = mean[2] != 0.f && mean[2] == mean[2] && fabsf(mean[1]) < max_eta;
@@ -242,6 +292,137 @@ __global__ __launch_bounds__(kTpb) void tm_clusters_kernel(const int64_t *__rest
         atomicAdd(&out[(size_t)t * cuts.n * 4 + threadIdx.x], (unsigned long long)acc[threadIdx.x]);
 }
 
+// ---------------------------------------------------------------------- windows
+// per particle the windows of its means (cluster mask: maj_reconstructable non-zero and not NaN) and
+// n_particles per window: the set bits of the hit mask into LDS, one int64 atomic per workgroup and window
+__global__ __launch_bounds__(kTpb) void tmw_particle_kernel(Windows win, Ws w,
+                                                            unsigned long long *__restrict__ n_particles) {
+    __shared__ uint32_t acc[kMaxWin];
+    if (threadIdx.x < kMaxWin) acc[threadIdx.x] = 0u;
+    __syncthreads();
+    const int64_t S = (int64_t)w.S;
+    for (int64_t s = (int64_t)blockIdx.x * kTpb + threadIdx.x; s < S; s += (int64_t)gridDim.x * kTpb) {
+        if (w.ptab[s] == 0) continue;
+        const float reco = particle_mean(w, 2, s);
+        const bool ok = reco != 0.f && reco == reco;
+        w.pcls[s] = ok ? window_mask(particle_mean(w, 0, s), particle_mean(w, 1, s), win) : 0u;
+        for (uint32_t m = w.phit[s]; m; m &= m - 1u) atomicAdd(&acc[__ffsll((unsigned long long)m) - 1], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < win.n && acc[threadIdx.x])
+        atomicAdd(&n_particles[threadIdx.x], (unsigned long long)acc[threadIdx.x]);
+}
+
+// what the tables hold about the cluster of label lab in trial t
+struct Majority {
+    uint32_t size, hits, pid_hits;   // cluster size, hits of the majority particle in it and anywhere
+    int64_t pid, slot;               // the majority particle and its slot in the particle table
+};
+__device__ __forceinline__ Majority majority_of(const int64_t *pid, int64_t n, const Ws &w, int64_t t, int64_t lab) {
+    Majority m;
+    m.size = w.csize[t * n + lab];
+    m.hits = w.cbest[t * n + lab];
+    m.pid = (int64_t)(w.cpid[t * n + lab] ^ (1ull << 63));
+    m.slot = find_particle(w.ptab, pid, w.S - 1, m.pid);
+    m.pid_hits = w.pcnt[m.slot];
+    return m;
+}
+
+// one trial per blockIdx.y; per valid cluster its flags into the LDS counters of the windows of its
+// majority particle's means (windows are mostly disjoint: one or two set bits)
+__global__ __launch_bounds__(kTpb) void tmw_clusters_kernel(const int64_t *__restrict__ pid, int64_t n, int32_t n_win,
+                                                            int32_t count_thld, Ws w,
+                                                            unsigned long long *__restrict__ out) {
+    __shared__ uint32_t acc[kMaxWin * 4];
+    if (threadIdx.x < kMaxWin * 4) acc[threadIdx.x] = 0u;
+    __syncthreads();
+    const int64_t t = blockIdx.y;
+    for (int64_t lab = (int64_t)blockIdx.x * kTpb + threadIdx.x; lab < n; lab += (int64_t)gridDim.x * kTpb) {
+        const uint32_t size = w.csize[t * n + lab];
+        if (size == 0 || (int64_t)size < (int64_t)count_thld) continue;   // not a valid cluster
+        const Majority c = majority_of(pid, n, w, t, lab);
+        uint32_t m = w.pcls[c.slot];
+        if (m == 0) continue;
+        // (fp64 ratios as the reference evaluates them)
+        const double frac = (double)c.hits / (double)size, pid_frac = (double)c.hits / (double)c.pid_hits;
+        const bool perfect = c.pid_hits == c.hits && frac > 0.99;
+        const bool dm = pid_frac > 0.5 && frac > 0.5;
+        const bool lhc = frac > 0.75;
+        for (; m; m &= m - 1u) {
+            uint32_t *a = &acc[(__ffsll((unsigned long long)m) - 1) * 4];
+            atomicAdd(&a[0], 1u);
+            if (perfect) atomicAdd(&a[1], 1u);
+            if (dm) atomicAdd(&a[2], 1u);
+            if (lhc) atomicAdd(&a[3], 1u);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < n_win * 4 && acc[threadIdx.x])
+        atomicAdd(&out[(size_t)t * n_win * 4 + threadIdx.x], (unsigned long long)acc[threadIdx.x]);
+}
+
+// ----------------------------------------------------------------- cluster table
+// the rows of tracking_metric_df of one labelling, one per label (cluster_size 0: no such cluster)
+__global__ __launch_bounds__(kTpb) void tm_table_kernel(const int64_t *__restrict__ pid, int64_t n, Ws w,
+                                                        int64_t *__restrict__ cluster_size,
+                                                        int64_t *__restrict__ maj_hits, int64_t *__restrict__ maj_pid,
+                                                        int64_t *__restrict__ maj_pid_hits, float *__restrict__ maj_pt,
+                                                        float *__restrict__ maj_eta, float *__restrict__ maj_reco) {
+    for (int64_t lab = (int64_t)blockIdx.x * kTpb + threadIdx.x; lab < n; lab += (int64_t)gridDim.x * kTpb) {
+        Majority c{};
+        float mean[kProps] = {0.f, 0.f, 0.f};
+        if (w.csize[lab]) {
+            c = majority_of(pid, n, w, 0, lab);
+            for (int k = 0; k < kProps; ++k) mean[k] = particle_mean(w, k, c.slot);
+        }
+        cluster_size[lab] = (int64_t)c.size;
+        maj_hits[lab] = (int64_t)c.hits;
+        maj_pid[lab] = c.pid;
+        maj_pid_hits[lab] = (int64_t)c.pid_hits;
+        maj_pt[lab] = mean[0];
+        maj_eta[lab] = mean[1];
+        maj_reco[lab] = mean[2];
+    }
+}
+
+// clears the tables and fills them: the particle table with sel's hit words, then per trial the pair
+// table, cluster sizes, best counts and best particle ids; *bad counts the labels >= n
+template <class Sel>
+int fill_tables(const char *what, const int64_t *labels, int32_t n_trials, const int64_t *pid, const float *pt,
+                const float *eta, const float *reco, int64_t n, const Sel &sel, const Ws &w, unsigned long long *bad,
+                hipStream_t stream) {
+    char msg[96];
+    snprintf(msg, sizeof(msg), "%s: clear workspace", what);
+    int rc;
+    if ((rc = check_hip(hipMemsetAsync(w.psum, 0, w.zero_bytes, stream), msg))) return rc;
+    if ((rc = check_hip(hipMemsetAsync(w.cpid, 0xFF, 8 * (size_t)n_trials * n, stream), msg))) return rc;
+    const int64_t S = (int64_t)w.S, tn = (int64_t)n_trials * n, ts = (int64_t)n_trials * S;
+    hipLaunchKernelGGL(tm_particles_kernel<Sel>, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, pid, pt, eta, reco, n,
+                       sel, w);
+    hipLaunchKernelGGL(tm_pairs_kernel, dim3(blocks_for(tn, 8)), dim3(kTpb), 0, stream, labels, n, tn, w, bad);
+    hipLaunchKernelGGL(tm_best_count_kernel, dim3(blocks_for(ts, 8)), dim3(kTpb), 0, stream, labels, n, ts, w);
+    hipLaunchKernelGGL(tm_best_pid_kernel, dim3(blocks_for(ts, 8)), dim3(kTpb), 0, stream, labels, pid, n, ts, w);
+    snprintf(msg, sizeof(msg), "%s: tables", what);
+    return check_launch(msg);
+}
+
+// the checks the three entries share, before any launch
+int check_hits(const char *entry, int64_t n, int32_t n_trials, const void *labels, const void *pid, const void *pt,
+               const void *eta, const void *reco, const void *workspace, size_t workspace_bytes) {
+    char msg[160];
+    if (n_trials < 1 || n_trials > GNNTRK_TRACKING_MAX_TRIALS) {
+        snprintf(msg, sizeof(msg), "%s: n_trials = %d, expected 1..%d", entry, (int)n_trials,
+                 GNNTRK_TRACKING_MAX_TRIALS);
+        return fail(GNNTRK_EINVAL, msg);
+    }
+    if (n > 0 && (!labels || !pid || !pt || !eta || !reco)) {
+        snprintf(msg, sizeof(msg), "%s: NULL labels, particle ids, pt, eta or reconstructable", entry);
+        return fail(GNNTRK_EINVAL, msg);
+    }
+    if (n > 0) return check_workspace(entry, workspace, workspace_bytes, make_ws(nullptr, n, n_trials).total);
+    return GNNTRK_OK;
+}
+
 }  // namespace
 
 size_t tracking_metrics_ws_bytes(int64_t n, int32_t n_trials) {
@@ -254,47 +435,87 @@ int tracking_metrics(const int64_t *labels, int32_t n_trials, const int64_t *pid
     char msg[160];
     int rc = check_count_i30("tracking_metrics", "hit", n);
     if (rc) return rc;
-    if (n_trials < 1 || n_trials > GNNTRK_TRACKING_MAX_TRIALS) {
-        snprintf(msg, sizeof(msg), "tracking_metrics: n_trials = %d, expected 1..%d", (int)n_trials,
-                 GNNTRK_TRACKING_MAX_TRIALS);
-        return fail(GNNTRK_EINVAL, msg);
-    }
     if (n_cuts < 1 || n_cuts > kMaxCuts) {
         snprintf(msg, sizeof(msg), "tracking_metrics: n_cuts = %d, expected 1..%d", (int)n_cuts, kMaxCuts);
         return fail(GNNTRK_EINVAL, msg);
     }
     if (!cuts) return fail(GNNTRK_EINVAL, "tracking_metrics: NULL cuts");
-    Cuts c;
-    if ((rc = fill_cuts(c, cuts, n_cuts, "tracking_metrics"))) return rc;
+    CutSel sel{};
+    sel.max_eta = max_eta;
+    if ((rc = fill_cuts(sel.cuts, cuts, n_cuts, "tracking_metrics"))) return rc;
     if (!out) return fail(GNNTRK_EINVAL, "tracking_metrics: NULL output");
-    if (n > 0 && (!labels || !pid || !pt || !eta || !reco))
-        return fail(GNNTRK_EINVAL, "tracking_metrics: NULL labels, particle ids, pt, eta or reconstructable");
-    if (n > 0 && (rc = check_workspace("tracking_metrics", workspace, workspace_bytes,
-                                       make_ws(nullptr, n, n_trials).total)))
+    if ((rc = check_hits("tracking_metrics", n, n_trials, labels, pid, pt, eta, reco, workspace, workspace_bytes)))
         return rc;
     const size_t n_out = (size_t)n_cuts + (size_t)n_trials * n_cuts * 4 + 1;
     rc = check_hip(hipMemsetAsync(out, 0, sizeof(int64_t) * n_out, stream), "tracking_metrics: clear");
     if (rc || n == 0) return rc;
     const Ws w = make_ws(workspace, n, n_trials);
-    if ((rc = check_hip(hipMemsetAsync(workspace, 0, w.zero_bytes, stream), "tracking_metrics: clear workspace")))
-        return rc;
-    if ((rc = check_hip(hipMemsetAsync(w.cpid, 0xFF, 8 * (size_t)n_trials * n, stream),
-                        "tracking_metrics: clear workspace")))
-        return rc;
     auto *o = reinterpret_cast<unsigned long long *>(out);
-    const int64_t S = (int64_t)w.S, tn = (int64_t)n_trials * n, ts = (int64_t)n_trials * S;
-    hipLaunchKernelGGL(tm_particles_kernel, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, pid, pt, eta, reco, n, c,
-                       max_eta, w);
-    hipLaunchKernelGGL(tm_particle_kernel, dim3(blocks_for(S, 4)), dim3(kTpb), 0, stream, c, max_eta, w, o);
-    if ((rc = check_launch("tracking_metrics: particles"))) return rc;
-    hipLaunchKernelGGL(tm_pairs_kernel, dim3(blocks_for(tn, 8)), dim3(kTpb), 0, stream, labels, n, tn, w,
-                       o + n_out - 1);
-    hipLaunchKernelGGL(tm_best_count_kernel, dim3(blocks_for(ts, 8)), dim3(kTpb), 0, stream, labels, n, ts, w);
-    hipLaunchKernelGGL(tm_best_pid_kernel, dim3(blocks_for(ts, 8)), dim3(kTpb), 0, stream, labels, pid, n, ts, w);
+    if ((rc = fill_tables("tracking_metrics", labels, n_trials, pid, pt, eta, reco, n, sel, w, o + n_out - 1, stream)))
+        return rc;
+    hipLaunchKernelGGL(tm_particle_kernel, dim3(blocks_for((int64_t)w.S, 4)), dim3(kTpb), 0, stream, sel.cuts, max_eta,
+                       w, o);
     const int gx = (int)((blocks_for(n, 8) + n_trials - 1) / n_trials);
     hipLaunchKernelGGL(tm_clusters_kernel, dim3(gx < 1 ? 1 : gx, (unsigned)n_trials), dim3(kTpb), 0, stream, pid, n,
-                       c, count_thld, w, o + n_cuts);
+                       sel.cuts, count_thld, w, o + n_cuts);
     return check_launch("tracking_metrics: clusters");
+}
+
+int tracking_metrics_windows(const int64_t *labels, int32_t n_trials, const int64_t *pid, const float *pt,
+                             const float *eta, const float *reco, int64_t n, const float *windows, int32_t n_win,
+                             int32_t count_thld, int64_t *out, void *workspace, size_t workspace_bytes,
+                             hipStream_t stream) {
+    char msg[160];
+    int rc = check_count_i30("tracking_metrics_windows", "hit", n);
+    if (rc) return rc;
+    if (n_win < 1 || n_win > kMaxWin) {
+        snprintf(msg, sizeof(msg), "tracking_metrics_windows: n_win = %d, expected 1..%d", (int)n_win, kMaxWin);
+        return fail(GNNTRK_EINVAL, msg);
+    }
+    if (!windows) return fail(GNNTRK_EINVAL, "tracking_metrics_windows: NULL windows");
+    if (!out) return fail(GNNTRK_EINVAL, "tracking_metrics_windows: NULL output");
+    if ((rc = check_hits("tracking_metrics_windows", n, n_trials, labels, pid, pt, eta, reco, workspace,
+                         workspace_bytes)))
+        return rc;
+    WinSel sel{};
+    sel.win.n = n_win;
+    for (int j = 0; j < n_win; ++j)
+        for (int k = 0; k < 4; ++k) sel.win.v[j][k] = windows[4 * j + k];
+    const size_t n_out = (size_t)n_win + (size_t)n_trials * n_win * 4 + 1;
+    rc = check_hip(hipMemsetAsync(out, 0, sizeof(int64_t) * n_out, stream), "tracking_metrics_windows: clear");
+    if (rc || n == 0) return rc;
+    const Ws w = make_ws(workspace, n, n_trials);
+    auto *o = reinterpret_cast<unsigned long long *>(out);
+    if ((rc = fill_tables("tracking_metrics_windows", labels, n_trials, pid, pt, eta, reco, n, sel, w, o + n_out - 1,
+                          stream)))
+        return rc;
+    hipLaunchKernelGGL(tmw_particle_kernel, dim3(blocks_for((int64_t)w.S, 4)), dim3(kTpb), 0, stream, sel.win, w, o);
+    const int gx = (int)((blocks_for(n, 8) + n_trials - 1) / n_trials);
+    hipLaunchKernelGGL(tmw_clusters_kernel, dim3(gx < 1 ? 1 : gx, (unsigned)n_trials), dim3(kTpb), 0, stream, pid, n,
+                       n_win, count_thld, w, o + n_win);
+    return check_launch("tracking_metrics_windows: clusters");
+}
+
+int cluster_table(const int64_t *labels, const int64_t *pid, const float *pt, const float *eta, const float *reco,
+                  int64_t n, int64_t *cluster_size, int64_t *maj_hits, int64_t *maj_pid, int64_t *maj_pid_hits,
+                  float *maj_pt, float *maj_eta, float *maj_reco, int64_t *n_bad, void *workspace,
+                  size_t workspace_bytes, hipStream_t stream) {
+    int rc = check_count_i30("cluster_table", "hit", n);
+    if (rc) return rc;
+    if (!n_bad) return fail(GNNTRK_EINVAL, "cluster_table: NULL n_bad");
+    if (n > 0 && (!cluster_size || !maj_hits || !maj_pid || !maj_pid_hits || !maj_pt || !maj_eta || !maj_reco))
+        return fail(GNNTRK_EINVAL, "cluster_table: NULL output column");
+    if ((rc = check_hits("cluster_table", n, 1, labels, pid, pt, eta, reco, workspace, workspace_bytes))) return rc;
+    rc = check_hip(hipMemsetAsync(n_bad, 0, sizeof(int64_t), stream), "cluster_table: clear");
+    if (rc || n == 0) return rc;
+    const Ws w = make_ws(workspace, n, 1);
+    // (no windows: the hits leave no mask, only the particle table and its sums are wanted)
+    if ((rc = fill_tables("cluster_table", labels, 1, pid, pt, eta, reco, n, WinSel{}, w,
+                          reinterpret_cast<unsigned long long *>(n_bad), stream)))
+        return rc;
+    hipLaunchKernelGGL(tm_table_kernel, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, pid, n, w, cluster_size,
+                       maj_hits, maj_pid, maj_pid_hits, maj_pt, maj_eta, maj_reco);
+    return check_launch("cluster_table: rows");
 }
 
 }  // namespace gnntrk

@@ -10,7 +10,9 @@ array like the reference (``cluster_device`` the device tensor).
 The DBSCAN hyperparameter scanners of the object-condensation validation
 (postprocessing/clusterscanner.py, dbscanscanner.py:29-187) are here too: per batch one radius graph,
 every trial's labels into one device buffer, and the tracking metrics of all trials from one C call
-(``cluster_metrics.tracking_metrics_trials``) and one host copy.
+(``cluster_metrics.tracking_metrics_trials``) and one host copy.  ``DBSCANPerformanceDetails``
+(dbscanscanner.py:215-264) keeps per batch the hit record on the device and the cluster table, the
+inputs of ``cluster_metrics.tracking_metrics_vs_pt`` / ``_vs_eta``.
 """
 
 from __future__ import annotations
@@ -25,6 +27,7 @@ import torch
 from torch import Tensor
 
 from . import _capi, ops
+from .cluster_metrics import _nanmean, _nanstd
 from .hparams import HyperparametersMixin
 
 
@@ -160,16 +163,6 @@ class CombinedClusterScanner(ClusterScanner):
         return foms
 
 
-def _nanmean(v: np.ndarray) -> float:
-    v = v[~np.isnan(v)]
-    return float(v.mean()) if v.size else float("nan")
-
-
-def _nanstd(v: np.ndarray) -> float:   # (ddof = 1, as pandas)
-    v = v[~np.isnan(v)]
-    return float(v.std(ddof=1)) if v.size > 1 else float("nan")
-
-
 class OCScanResults:
     """``dbscanscanner.py:29-73`` without pandas.  ``records``: one dict per (batch, trial) with
     ``i_batch``, ``eps``, ``min_samples`` and the flattened tracking metrics.  Grouped by (eps,
@@ -303,3 +296,35 @@ class DBSCANHyperParamScannerFixed(DBSCANHyperParamScanner):
 
     def _reset_trials(self) -> None:
         pass
+
+
+class DBSCANPerformanceDetails(DBSCANHyperParamScanner):
+    def __init__(self, eps: float, min_samples: int):
+        """``dbscanscanner.py:215-264``: the detailed performance of fixed DBSCAN parameters.  Per batch
+        the device DBSCAN of ``out["H"]``, then the hit record (``c``, ``id``, ``reconstructable``,
+        ``pt``, ``eta`` as device tensors) and the cluster table
+        (``cluster_metrics.tracking_metric_table``: numpy columns) are kept; see ``get_results``.  As
+        the reference, it neither resets on ``i_batch == 0`` nor looks at ``ec_hit_mask``."""
+        super().__init__()
+        self.save_hyperparameters()
+        self._h_dfs: list[dict[str, Tensor]] = []
+        self._c_dfs: list[dict[str, np.ndarray]] = []
+
+    def __call__(self, data, out: dict[str, Tensor], i_batch: int) -> None:
+        from . import cluster_metrics as CM
+
+        fr = DBSCANFastRescan(out["H"].detach(), max_eps=self.hparams.eps)
+        labels = fr.cluster_device(eps=self.hparams.eps, min_pts=self.hparams.min_samples)
+        dev = labels.device
+        pid, pt, reco, eta = CM._hits(data.particle_id, data.pt, data.reconstructable, data.eta, dev)
+        self._h_dfs.append({"c": labels, "id": pid, "reconstructable": reco, "pt": pt, "eta": eta})
+        # (DBSCAN's labels are in [-1, n) already: no ranking pass)
+        self._c_dfs.append(CM._table(labels, None, pid, pt, reco, eta, 3))
+
+    def get_results(self) -> tuple[list[dict[str, Tensor]], list[dict[str, np.ndarray]]]:
+        """(h_dfs, c_dfs): per batch the hit record and the cluster table, as
+        ``tracking_metrics_vs_pt`` / ``tracking_metrics_vs_eta`` take them."""
+        return self._h_dfs, self._c_dfs
+
+    def get_foms(self) -> dict[str, float]:
+        return {}

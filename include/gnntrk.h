@@ -969,6 +969,44 @@ int gnntrk_tracking_metrics(const int64_t *labels, int32_t n_trials, const int64
                             int32_t n_cuts, float max_eta, int32_t predicted_count_thld, int64_t *out,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/* The same counts for two-sided windows instead of nested cuts (tracking_metrics_vs_pt / _vs_eta,
+ * metrics/cluster_metrics.py:292-384), arguments as gnntrk_tracking_metrics except:
+ *   windows         HOST array of n_win (1..GNNTRK_TRACKING_MAX_WINDOWS) windows, four fp32 each:
+ *                   (pt_lo, pt_hi, eta_lo, eta_hi).  A NaN bound means that side is not tested.
+ *                   Windows may overlap and need no order.
+ *   - a hit is in a window iff pt >= pt_lo, pt < pt_hi, eta >= eta_lo, eta < eta_hi (a NaN value
+ *     fails every test that is applied; eta is compared SIGNED, as the reference does there) and
+ *     reconstructable != 0 (NaN counts);
+ *   - a valid cluster is in a window iff the means of its majority particle pass the same tests and
+ *     its mean reconstructable is non-zero and not NaN.  Means, validity, tie rule and flags as above.
+ * out (int64, n_win + n_trials * n_win * 4 + 1 values, overwritten): as above with windows for cuts; a
+ * particle whose hits lie in several windows counts in each of them.
+ * workspace: gnntrk_tracking_metrics_windows_workspace_bytes(n, n_trials).  No host synchronisation.
+ * GNNTRK_EINVAL for n_win or n_trials out of range, NULL required pointers, a small workspace;
+ * GNNTRK_EUNSUPPORTED for n >= 2^30. */
+#define GNNTRK_TRACKING_MAX_WINDOWS 32
+size_t gnntrk_tracking_metrics_windows_workspace_bytes(int64_t n, int32_t n_trials);
+int gnntrk_tracking_metrics_windows(const int64_t *labels, int32_t n_trials, const int64_t *particle_id,
+                                    const float *pt, const float *eta, const float *reconstructable, int64_t n,
+                                    const float *windows, int32_t n_win, int32_t predicted_count_thld, int64_t *out,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+
+/* The per-cluster rows of tracking_metric_df (metrics/cluster_metrics.py:76-149) of ONE labelling
+ * (labels [n], as above) as dense columns of length n indexed by label (device pointers):
+ *   cluster_size [n] int64   hits with this label; 0: there is no such cluster (the other columns are 0);
+ *   maj_hits     [n] int64   hits of the majority particle in the cluster (tie rule as above);
+ *   maj_pid      [n] int64   its id;   maj_pid_hits [n] int64  its hits anywhere;
+ *   maj_pt, maj_eta, maj_reconstructable [n] fp32  its means (NaN skipped, fp64 sum rounded once);
+ *   n_bad        [1] int64   number of labels >= n (ignored; 0 for valid input).
+ * workspace: gnntrk_cluster_table_workspace_bytes(n).  No host synchronisation.
+ * GNNTRK_EINVAL for NULL required pointers or a small workspace; GNNTRK_EUNSUPPORTED for n >= 2^30. */
+size_t gnntrk_cluster_table_workspace_bytes(int64_t n);
+int gnntrk_cluster_table(const int64_t *labels, const int64_t *particle_id, const float *pt, const float *eta,
+                         const float *reconstructable, int64_t n, int64_t *cluster_size, int64_t *maj_hits,
+                         int64_t *maj_pid, int64_t *maj_pid_hits, float *maj_pt, float *maj_eta,
+                         float *maj_reconstructable, int64_t *n_bad, void *workspace, size_t workspace_bytes,
+                         void *stream);
+
 /* ------------------------------------------------------------ k-scan (metric learning)
  * The device part of GraphConstructionKNNScanner (graph_construction/k_scanner.py:203-285) beyond the
  * neighbour search: connected components and the integer counts behind its records.
