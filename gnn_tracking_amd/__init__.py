@@ -23,9 +23,10 @@ from .losses_ml import GraphConstructionHingeEmbeddingLoss
 from .losses_oc import CondensationLossRG, CondensationLossTiger, MultiLossFctReturn
 from .metrics import (BinaryClassificationStats, ec_validation_metrics, get_maximized_bcs, get_roc_auc_scores,
                       roc_auc_score)
-from .cluster_metrics import (TrackingMetrics, flatten_track_metrics, tracking_metric_table, tracking_metrics,
-                              tracking_metrics_data, tracking_metrics_trials, tracking_metrics_vs_eta,
-                              tracking_metrics_vs_pt)
+from .cluster_metrics import (TrackingMetrics, clustering_scores_trials, clustering_spectra, common_metrics,
+                              count_hits_per_cluster, flatten_track_metrics, hits_per_cluster_count_to_flat_dict,
+                              tracking_metric_table, tracking_metrics, tracking_metrics_data, tracking_metrics_trials,
+                              tracking_metrics_vs_eta, tracking_metrics_vs_pt)
 from .graph_analysis import get_cc_labels, get_efficiency_purity_edges, get_largest_segment_fracs
 from .k_scanner import GraphConstructionKNNScanner, KScanResults
 from .mlp import MLP
@@ -55,4 +56,5 @@ __all__ = ["Data", "collate", "MLP", "InteractionNetwork", "ResIN", "ECForGraphT
            "DBSCANHyperParamScanner", "DBSCANHyperParamScannerFixed", "OCScanResults", "get_cc_labels",
            "get_largest_segment_fracs", "get_efficiency_purity_edges", "GraphConstructionKNNScanner",
            "KScanResults", "EFMLP", "EFDeepSet", "GeometricEF", "tracking_metric_table", "tracking_metrics_vs_pt",
-           "tracking_metrics_vs_eta", "DBSCANPerformanceDetails"]
+           "tracking_metrics_vs_eta", "DBSCANPerformanceDetails", "clustering_spectra", "clustering_scores_trials",
+           "count_hits_per_cluster", "hits_per_cluster_count_to_flat_dict", "common_metrics"]

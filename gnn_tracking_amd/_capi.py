@@ -265,6 +265,9 @@ _SIGNATURES = {
     "gnntrk_cluster_table_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gnntrk_cluster_table": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t,
                                        _P]),
+    "gnntrk_cluster_spectra_capacity": (C.c_int64, [C.c_int64]),
+    "gnntrk_cluster_spectra_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "gnntrk_cluster_spectra": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, _P, C.c_size_t, _P]),
     "gnntrk_cc_labels_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gnntrk_cc_labels": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P, _P, _P,
                                    C.c_size_t, _P]),

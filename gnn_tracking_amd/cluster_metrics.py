@@ -19,6 +19,17 @@ The binned views of a study's end (``cluster_metrics.py:76-149, 292-384``) are h
 pandas: ``tracking_metric_table`` is ``tracking_metric_df`` as a dict of numpy columns
 (``gnntrk_cluster_table``), ``tracking_metrics_vs_pt`` / ``tracking_metrics_vs_eta`` return one dict
 per bin; their counts come from ``gnntrk_tracking_metrics_windows``, one call per batch and 32 bins.
+
+The module's registry closes it (``cluster_metrics.py:400-456``): ``common_metrics`` with the reference's
+six keys, ``count_hits_per_cluster`` and ``hits_per_cluster_count_to_flat_dict``.  The reference hands
+host copies of one trial's labels to sklearn; here ``gnntrk_cluster_spectra``
+(``csrc/cluster_scores.hip``) counts on the device, for all trials of a call, the *size spectra* of the
+truth classes, the predicted clusters and the cells of their contingency table - the distinct sizes and
+how many classes / clusters / cells have each, at most ``floor((sqrt(8n + 1) - 1) / 2)`` entries each - and
+the host finishes v-measure, homogeneity, completeness, the adjusted Rand index and the Fowlkes-Mallows
+index from those few hundred integers (``clustering_scores_trials``: one C call and one host copy for all
+trials).  For these scores labels and truth ids are categories of any integer value, as for sklearn: the
+noise label -1 is ONE cluster and truth id 0 an ordinary class, unlike in the tracking metrics.
 """
 
 from __future__ import annotations
@@ -26,7 +37,7 @@ from __future__ import annotations
 import ctypes as C
 import itertools
 import math
-from typing import Iterable, TypedDict
+from typing import Callable, Iterable, TypedDict
 
 import numpy as np
 import torch
@@ -37,7 +48,8 @@ from .metrics import denote_pt
 
 __all__ = ["TrackingMetrics", "tracking_metrics", "tracking_metrics_data", "tracking_metrics_trials",
            "flatten_track_metrics", "denote_pt", "tracking_metric_table", "tracking_metrics_vs_pt",
-           "tracking_metrics_vs_eta"]
+           "tracking_metrics_vs_eta", "clustering_spectra", "clustering_scores_trials", "count_hits_per_cluster",
+           "hits_per_cluster_count_to_flat_dict", "common_metrics"]
 
 
 class TrackingMetrics(TypedDict):
@@ -359,3 +371,161 @@ def tracking_metrics_vs_eta(h_dfs, c_dfs, etas, pt_thld: float = 0.9, *, predict
     nan = float("nan")
     return _binned(h_dfs, c_dfs, etas, lambda lo, hi: (pt_thld, nan, lo, hi), ("eta_min", "eta_max"),
                    predicted_count_thld)
+
+
+# ------------------------------------------------------------------ clustering scores, common_metrics
+SCORE_KEYS = ("v_measure", "homogeneity", "completeness", "adjusted_rand", "fowlkes_mallows")
+_EMPTY = (np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64))
+
+
+def _spectra_host(labels: Tensor, truth: Tensor | None) -> tuple[np.ndarray, int]:
+    """``gnntrk_cluster_spectra`` of ``labels`` [T, n] (1 <= T, 1 <= n): its output on the host, one copy,
+    as rows of 1 + 2 D(n) values, and D(n)."""
+    lib = _capi.load()
+    _capi.require_device(labels, truth)
+    n_trials, n = int(labels.shape[0]), int(labels.shape[1])
+    if n_trials > _capi.TRACKING_MAX_TRIALS:
+        raise ValueError(f"clustering_spectra: at most {_capi.TRACKING_MAX_TRIALS} trials per call")
+    cap = int(lib.gnntrk_cluster_spectra_capacity(n))
+    out = torch.empty((1 + 2 * n_trials, 1 + 2 * cap), dtype=torch.int64, device=labels.device)
+    ws = ops._ws(lib.gnntrk_cluster_spectra_workspace_bytes(n, n_trials), labels)
+    p = ops._p
+    _capi.check(lib.gnntrk_cluster_spectra(p(labels), n_trials, p(truth) if truth is not None else None, n, p(out),
+                                           p(ws), ws.numel(), ops._stream(labels)), lib)
+    return out.cpu().numpy(), cap
+
+
+def _spectrum(row: np.ndarray, cap: int) -> tuple[np.ndarray, np.ndarray]:
+    d = int(row[0])
+    if not 0 <= d <= cap:
+        raise RuntimeError(f"clustering_spectra: a spectrum of {d} entries, at most {cap} are possible")
+    pairs = row[1:1 + 2 * d].reshape(d, 2)
+    pairs = pairs[np.argsort(pairs[:, 0], kind="stable")]
+    return pairs[:, 0].copy(), pairs[:, 1].copy()
+
+
+def clustering_spectra(labels, truth=None) -> list[dict[str, tuple[np.ndarray, np.ndarray]]]:
+    """The size spectra of ``labels`` ([n] or [n_trials, n]) against ``truth`` ([n], optional): one dict per
+    trial with ``classes`` (truth classes; the same for every trial), ``clusters`` and ``cells`` (non-zero
+    cells of the contingency table), each a pair of ascending int64 arrays ``(sizes, multiplicities)``.
+    Labels and ids are categories of any integer value (-1 is one cluster).  Without ``truth``, ``classes``
+    and ``cells`` are empty.  One C call and one host copy."""
+    if not torch.is_tensor(labels):
+        labels = torch.as_tensor(np.asarray(labels))
+    if labels.dim() == 1:
+        labels = labels.view(1, -1)
+    if labels.dim() != 2:
+        raise ValueError("clustering_spectra: labels must be [n] or [n_trials, n]")
+    n_trials, n = int(labels.shape[0]), int(labels.shape[1])
+    if truth is not None and int(np.shape(truth)[0] if not torch.is_tensor(truth) else truth.shape[0]) != n:
+        raise ValueError("clustering_spectra: labels and truth differ in the number of hits")
+    if n == 0 or n_trials == 0:
+        return [{"classes": _EMPTY, "clusters": _EMPTY, "cells": _EMPTY} for _ in range(n_trials)]
+    dev = _device_of(labels, truth)
+    lab = _on(labels, torch.int64, dev)
+    tru = _on(truth, torch.int64, dev).view(-1) if truth is not None else None
+    host, cap = _spectra_host(lab, tru)
+    classes = _spectrum(host[0], cap)
+    return [{"classes": classes, "clusters": _spectrum(host[1 + 2 * t], cap), "cells": _spectrum(host[2 + 2 * t], cap)}
+            for t in range(n_trials)]
+
+
+def _xlogx(s: tuple[np.ndarray, np.ndarray]) -> float:
+    """X(s) = sum of m v ln v over a spectrum."""
+    return math.fsum(int(m) * int(v) * math.log(int(v)) for v, m in zip(*s))
+
+
+def _squares(s: tuple[np.ndarray, np.ndarray]) -> int:
+    """Q(s) = sum of m v^2 over a spectrum, as a Python int."""
+    return sum(int(m) * int(v) * int(v) for v, m in zip(*s))
+
+
+def _scores_from_spectra(sp: dict[str, tuple[np.ndarray, np.ndarray]]) -> dict[str, float]:
+    """sklearn's v_measure / homogeneity / completeness / adjusted_rand / fowlkes_mallows scores from the
+    three spectra of one trial.  With X, Q as above and L = ln n: H(C) = L - X(a) / n, H(K) = L - X(b) / n,
+    MI = (X(c) - X(a) - X(b)) / n + L (0 where either labelling has one group, as in sklearn); the pair
+    counts are integers: tp = Q(c) - n, fp = Q(b) - Q(c), fn = Q(a) - Q(c), tn = n^2 - fp - fn - Q(c)."""
+    a, b, c = sp["classes"], sp["clusters"], sp["cells"]
+    n = sum(int(m) * int(v) for v, m in zip(*b))
+    if n == 0:
+        return dict(zip(SCORE_KEYS, (1.0, 1.0, 1.0, 1.0, 0.0)))
+    one_class, one_cluster = int(a[1].sum()) == 1, int(b[1].sum()) == 1
+    log_n = math.log(n)
+    xa, xb, xc = _xlogx(a), _xlogx(b), _xlogx(c)
+    h_c = 0.0 if one_class else log_n - xa / n
+    h_k = 0.0 if one_cluster else log_n - xb / n
+    mi = 0.0 if one_class or one_cluster else max(0.0, (xc - xa - xb) / n + log_n)
+    hom = mi / h_c if h_c else 1.0
+    com = mi / h_k if h_k else 1.0
+    v = 0.0 if hom + com == 0.0 else 2 * hom * com / (hom + com)
+    qa, qb, s = _squares(a), _squares(b), _squares(c)
+    tp, fp, fn = s - n, qb - s, qa - s
+    tn = n * n - fp - fn - s
+    # (Python ints up to the one floating expression, which is sklearn's: the products pass 2^63)
+    ari = 1.0 if fn == 0 and fp == 0 else 2.0 * (tp * tn - fn * fp) / ((tp + fn) * (fn + tn) + (tp + fp) * (fp + tn))
+    tk, pk, qk = s - n, qb - n, qa - n
+    fmi = math.sqrt(tk / pk) * math.sqrt(tk / qk) if tk != 0 else 0.0
+    return dict(zip(SCORE_KEYS, (v, hom, com, ari, fmi)))
+
+
+def clustering_scores_trials(labels, *, truth) -> list[dict[str, float]]:
+    """sklearn's clustering scores of many labellings of the same hits (``labels`` [n_trials, n] or [n]) from
+    one C call and one host copy: per trial a dict with ``v_measure``, ``homogeneity``, ``completeness``,
+    ``adjusted_rand`` and ``fowlkes_mallows``, as the reference's ``common_metrics`` give them one by one.
+    The sibling of ``tracking_metrics_trials`` for a scanner that ranks DBSCAN trials by such a score."""
+    if truth is None:
+        raise ValueError("clustering_scores_trials: truth is required")
+    return [_scores_from_spectra(sp) for sp in clustering_spectra(labels, truth)]
+
+
+def count_hits_per_cluster(predicted) -> np.ndarray:
+    """``cluster_metrics.py:400-404``: ``out[v - 1]`` = the number of clusters with exactly ``v`` hits, for
+    ``v`` = 1 ... the largest cluster size (every distinct label is a cluster, -1 included)."""
+    if not torch.is_tensor(predicted):
+        predicted = torch.as_tensor(np.asarray(predicted))
+    if predicted.dim() != 1:
+        raise ValueError("count_hits_per_cluster: predicted must be [n]")
+    if int(predicted.shape[0]) == 0:   # (the reference fails on counts.max() of nothing)
+        raise ValueError("count_hits_per_cluster: no hits")
+    sizes, mult = clustering_spectra(predicted)[0]["clusters"]
+    out = np.zeros(int(sizes[-1]), dtype=np.int64)
+    out[sizes - 1] = mult
+    return out
+
+
+def hits_per_cluster_count_to_flat_dict(counts: np.ndarray, min_max=10) -> dict[str, float]:
+    """``cluster_metrics.py:407-424``: the result of ``count_hits_per_cluster``, padded with zeros to at
+    least ``min_max`` sizes, as cumulative fractions (keys ``hitcountgeq_0001`` ... enumerate the cumulative
+    sums from the last one down, as the reference does)."""
+    cumulative = np.cumsum(np.pad(counts, (0, max(0, min_max - len(counts))), "constant"))
+    total = cumulative[-1]
+    return {f"hitcountgeq_{i:04}": cumulative / total for i, cumulative in enumerate(reversed(cumulative), start=1)}
+
+
+def _score_metric(key: str) -> Callable[..., float]:
+    def metric(*, truth, predicted, **_ignored) -> float:
+        return clustering_scores_trials(predicted, truth=truth)[0][key]
+
+    metric.__name__ = metric.__qualname__ = f"{key}_score"
+    metric.__doc__ = f"sklearn's ``{key}_score(truth, predicted)`` from the device's size spectra."
+    return metric
+
+
+def _trk_metric(*, truth, predicted, pts, reconstructable, eta, pt_thlds, predicted_count_thld=3, max_eta=4,
+                **_ignored) -> dict[str, float]:
+    return flatten_track_metrics(tracking_metrics(truth=truth, predicted=predicted, pts=pts,
+                                                  reconstructable=reconstructable, eta=eta, pt_thlds=pt_thlds,
+                                                  predicted_count_thld=predicted_count_thld, max_eta=max_eta))
+
+
+#: ``cluster_metrics.py:440-456``: the metrics a ``ClusterMetricType`` consumer looks up by name, in the
+#: reference's order.  Every value takes ``truth=`` and ``predicted=`` (``trk`` also the hit properties and
+#: ``pt_thlds`` of ``tracking_metrics``) and ignores further keyword arguments.
+common_metrics: dict[str, Callable] = {
+    "v_measure": _score_metric("v_measure"),
+    "homogeneity": _score_metric("homogeneity"),
+    "completeness": _score_metric("completeness"),
+    "trk": _trk_metric,
+    "adjusted_rand": _score_metric("adjusted_rand"),
+    "fowlkes_mallows": _score_metric("fowlkes_mallows"),
+}

@@ -142,6 +142,11 @@ int tracking_metrics_windows(const int64_t *, int32_t, const int64_t *, const fl
 int cluster_table(const int64_t *, const int64_t *, const float *, const float *, const float *, int64_t, int64_t *,
                   int64_t *, int64_t *, int64_t *, float *, float *, float *, int64_t *, void *, size_t, hipStream_t);
 
+// cluster_scores.hip
+int64_t cluster_spectra_capacity(int64_t);
+size_t cluster_spectra_ws_bytes(int64_t, int32_t);
+int cluster_spectra(const int64_t *, int32_t, const int64_t *, int64_t, int64_t *, void *, size_t, hipStream_t);
+
 // kscan.hip
 size_t cc_labels_ws_bytes(int64_t);
 int cc_labels(const int64_t *, int64_t, const int32_t *, const int32_t *, int32_t, int32_t, const int64_t *,
@@ -476,6 +481,15 @@ int gnntrk_cluster_table(const int64_t *labels, const int64_t *particle_id, cons
     return cluster_table(labels, particle_id, pt, eta, reconstructable, n, cluster_size, maj_hits, maj_pid,
                          maj_pid_hits, maj_pt, maj_eta, maj_reconstructable, n_bad, workspace, workspace_bytes,
                          (hipStream_t)stream);
+}
+
+int64_t gnntrk_cluster_spectra_capacity(int64_t n) { return cluster_spectra_capacity(n); }
+size_t gnntrk_cluster_spectra_workspace_bytes(int64_t n, int32_t n_trials) {
+    return cluster_spectra_ws_bytes(n, n_trials);
+}
+int gnntrk_cluster_spectra(const int64_t *labels, int32_t n_trials, const int64_t *truth, int64_t n, int64_t *out,
+                           void *workspace, size_t workspace_bytes, void *stream) {
+    return cluster_spectra(labels, n_trials, truth, n, out, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 size_t gnntrk_cc_labels_workspace_bytes(int64_t n) { return cc_labels_ws_bytes(n); }

@@ -1007,6 +1007,35 @@ int gnntrk_cluster_table(const int64_t *labels, const int64_t *particle_id, cons
                          float *maj_reconstructable, int64_t *n_bad, void *workspace, size_t workspace_bytes,
                          void *stream);
 
+/* The size spectra behind the clustering scores of metrics/cluster_metrics.py:400-456 (common_metrics'
+ * v_measure, homogeneity, completeness, adjusted_rand and fowlkes_mallows, which the reference hands to
+ * sklearn, and count_hits_per_cluster) for n_trials labellings of the same n hits at once.  All five scores
+ * are functions of three multisets: the sizes of the truth classes, the sizes of the predicted clusters and
+ * the non-zero cells of their contingency table.  Each is returned as its SPECTRUM: the distinct sizes with
+ * the number of classes / clusters / cells of exactly that size.  The sizes of a spectrum sum to n, so it has
+ * at most D(n) = floor((sqrt(8 n + 1) - 1) / 2) entries = gnntrk_cluster_spectra_capacity(n) (0 for n <= 0).
+ * Device pointers:
+ *   labels   [n_trials][n] int64 cluster labels;   truth  [n] int64 class ids, may be NULL.
+ * Labels and truth ids are CATEGORIES of any int64 value, as sklearn treats what the reference passes it: a
+ * negative label is an ordinary cluster (DBSCAN's -1 noise is ONE cluster - unlike gnntrk_tracking_metrics),
+ * truth id 0 is an ordinary class, nothing needs densifying and no label is out of range.
+ * out (int64, (1 + 2 * n_trials) spectra of 1 + 2 * D(n) values each, overwritten):
+ *   spectrum 0            the truth classes;
+ *   spectrum 1 + 2 t      the clusters of trial t;
+ *   spectrum 2 + 2 t      the contingency cells of trial t;
+ *   inside a spectrum     [0] = d, the number of entries, then d pairs (size, multiplicity) in NO particular
+ *                         order (every size once); the values behind them are 0.
+ * truth == NULL: only the cluster spectra are filled, the class and cell spectra have d = 0.  n == 0 writes
+ * d = 0 everywhere and launches nothing.  Integer arithmetic only: the set of pairs does not depend on the
+ * order in which atomics land.  workspace: gnntrk_cluster_spectra_workspace_bytes(n, n_trials) (one hash
+ * table of 2n..4n slots per spectrum).  No host synchronisation.
+ * GNNTRK_EINVAL for n_trials outside 1..GNNTRK_TRACKING_MAX_TRIALS, n < 0, NULL labels, out or workspace, a
+ * small workspace; GNNTRK_EUNSUPPORTED for n >= 2^30. */
+int64_t gnntrk_cluster_spectra_capacity(int64_t n);
+size_t gnntrk_cluster_spectra_workspace_bytes(int64_t n, int32_t n_trials);
+int gnntrk_cluster_spectra(const int64_t *labels, int32_t n_trials, const int64_t *truth, int64_t n, int64_t *out,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------ k-scan (metric learning)
  * The device part of GraphConstructionKNNScanner (graph_construction/k_scanner.py:203-285) beyond the
  * neighbour search: connected components and the integer counts behind its records.
