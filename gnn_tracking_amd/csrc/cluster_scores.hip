@@ -171,14 +171,21 @@ __global__ __launch_bounds__(kTpb) void cs_compact_kernel(int step, int64_t cap,
 
 }  // namespace
 
-int64_t cluster_spectra_capacity(int64_t n) { return capacity(n); }
+}  // namespace gnntrk
 
-size_t cluster_spectra_ws_bytes(int64_t n, int32_t n_trials) {
+using namespace gnntrk;
+
+extern "C" {
+
+int64_t gnntrk_cluster_spectra_capacity(int64_t n) { return capacity(n); }
+
+size_t gnntrk_cluster_spectra_workspace_bytes(int64_t n, int32_t n_trials) {
     return make_ws(nullptr, n < 0 ? 0 : n, n_trials < 1 ? 1 : n_trials).total;
 }
 
-int cluster_spectra(const int64_t *labels, int32_t n_trials, const int64_t *truth, int64_t n, int64_t *out,
-                    void *workspace, size_t workspace_bytes, hipStream_t stream) {
+int gnntrk_cluster_spectra(const int64_t *labels, int32_t n_trials, const int64_t *truth, int64_t n, int64_t *out,
+                           void *workspace, size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     char msg[160];
     int rc = check_count_i30("cluster_spectra", "hit", n);
     if (rc) return rc;
@@ -211,4 +218,4 @@ int cluster_spectra(const int64_t *labels, int32_t n_trials, const int64_t *trut
     return check_launch("cluster_spectra: spectra");
 }
 
-}  // namespace gnntrk
+}  // extern "C"

@@ -190,13 +190,6 @@ static int compact_run(F flag, int64_t n, int32_t *idx, uint8_t *mask, int32_t *
     return check_launch(who);
 }
 
-int threshold_compact_launch(const float *w, int64_t n, float threshold, uint8_t *mask, int32_t *idx, int64_t *n_out,
-                             void *ws, size_t ws_bytes, hipStream_t stream) {
-    if (n > 0 && (!w || !mask)) return fail(GNNTRK_EINVAL, "threshold_compact: NULL argument");
-    return compact_run(FlagThreshold{w, threshold, ((uintptr_t)w & 15) == 0}, n, idx, mask, nullptr, n_out, ws, ws_bytes, stream,
-                       "threshold_compact");
-}
-
 // idx = ascending positions of the non-zero bytes, newid = their ranks (or -1), n_out[0] = count
 int compact_bytes_launch(const uint8_t *flags, int64_t n, int32_t *idx, int32_t *newid, int64_t *n_out, void *ws,
                          size_t ws_bytes, hipStream_t stream) {
@@ -205,9 +198,26 @@ int compact_bytes_launch(const uint8_t *flags, int64_t n, int32_t *idx, int32_t 
                        stream, "compact_bytes");
 }
 
-int connected_nodes_launch(const int64_t *edge_index, int64_t n_edges, int64_t n_nodes, uint8_t *hit,
-                           int32_t *node_idx, int32_t *newid, int64_t *n_out, int64_t *edge_index_out, void *ws,
-                           size_t ws_bytes, hipStream_t stream) {
+}  // namespace gnntrk
+
+using namespace gnntrk;
+
+extern "C" {
+
+size_t gnntrk_compact_workspace_bytes(int64_t n) { return compact_ws_bytes(n); }
+
+int gnntrk_threshold_compact(const float *w, int64_t n, float threshold, uint8_t *mask, int32_t *idx, int64_t *n_out,
+                             void *workspace, size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n > 0 && (!w || !mask)) return fail(GNNTRK_EINVAL, "threshold_compact: NULL argument");
+    return compact_run(FlagThreshold{w, threshold, ((uintptr_t)w & 15) == 0}, n, idx, mask, nullptr, n_out, workspace,
+                       workspace_bytes, stream, "threshold_compact");
+}
+
+int gnntrk_connected_nodes(const int64_t *edge_index, int64_t n_edges, int64_t n_nodes, uint8_t *hit, int32_t *node_idx,
+                           int32_t *newid, int64_t *n_out, int64_t *edge_index_out, void *workspace,
+                           size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     if (n_edges < 0 || n_nodes < 0 || n_nodes > 0x7fffffff || n_edges > 0x3fffffff)
         return fail(GNNTRK_EUNSUPPORTED, "connected_nodes: sizes must fit int32");
     if (!n_out) return fail(GNNTRK_EINVAL, "connected_nodes: NULL count output");
@@ -221,8 +231,8 @@ int connected_nodes_launch(const int64_t *edge_index, int64_t n_edges, int64_t n
     if (m > 0)
         hipLaunchKernelGGL(mark_nodes_kernel, dim3(stream_blocks(m)), dim3(kCTpb), 0, stream, edge_index, m, n_nodes,
                            hit, n_out + 1);
-    rc = compact_run(FlagByte{hit, ((uintptr_t)hit & 7) == 0}, n_nodes, node_idx, nullptr, newid, n_out, ws, ws_bytes, stream,
-                     "connected_nodes");
+    rc = compact_run(FlagByte{hit, ((uintptr_t)hit & 7) == 0}, n_nodes, node_idx, nullptr, newid, n_out, workspace,
+                     workspace_bytes, stream, "connected_nodes");
     if (rc) return rc;
     if (m > 0)
         hipLaunchKernelGGL(relabel_kernel, dim3(stream_blocks(m)), dim3(kCTpb), 0, stream, edge_index, m, n_nodes,
@@ -230,4 +240,4 @@ int connected_nodes_launch(const int64_t *edge_index, int64_t n_edges, int64_t n
     return check_launch("connected_nodes");
 }
 
-}  // namespace gnntrk
+}  // extern "C"

@@ -320,28 +320,29 @@ static void radius_launch(const float *x, int64_t n, int dim, int stride, double
     });
 }
 
-int radius_count_launch(const float *x, int64_t n, int dim, int stride, double radius, int32_t *cnt,
-                        int64_t *offsets, hipStream_t stream) {
-    int rc = check_points(x, n, dim, stride, radius, "radius_count");
+// the brute-force passes: what gnntrk_radius_count / _fill run, and what the *_ws entries fall back to
+static int radius_count(const float *x, int64_t n, int dim, int x_stride, double radius, int32_t *cnt, int64_t *offsets,
+                        hipStream_t stream) {
+    int rc = check_points(x, n, dim, x_stride, radius, "radius_count");
     if (rc) return rc;
     if (!offsets) return fail(GNNTRK_EINVAL, "radius_count: NULL offsets");
     if (n == 0) return check_hip(hipMemsetAsync(offsets, 0, sizeof(int64_t), stream), "radius_count");
     if (!cnt) return fail(GNNTRK_EINVAL, "radius_count: NULL counts");
-    radius_launch<false>(x, n, dim, stride, radius * radius, cnt, nullptr, nullptr, nullptr, stream);
+    radius_launch<false>(x, n, dim, x_stride, radius * radius, cnt, nullptr, nullptr, nullptr, stream);
     scan_counts_launch(cnt, 0x7fffffff, n, offsets, stream);
     return check_launch("radius_count");
 }
 
-int radius_fill_launch(const float *x, int64_t n, int dim, int stride, double radius, const int64_t *off,
+static int radius_fill(const float *x, int64_t n, int dim, int x_stride, double radius, const int64_t *offsets,
                        int32_t *nbr, double *dist, hipStream_t stream) {
-    int rc = check_points(x, n, dim, stride, radius, "radius_fill");
+    int rc = check_points(x, n, dim, x_stride, radius, "radius_fill");
     if (rc || n == 0) return rc;
-    if (!off || !nbr || !dist) return fail(GNNTRK_EINVAL, "radius_fill: NULL argument");
-    radius_launch<true>(x, n, dim, stride, radius * radius, nullptr, off, nbr, dist, stream);
+    if (!offsets || !nbr || !dist) return fail(GNNTRK_EINVAL, "radius_fill: NULL argument");
+    radius_launch<true>(x, n, dim, x_stride, radius * radius, nullptr, offsets, nbr, dist, stream);
     return check_launch("radius_fill");
 }
 
-// ---- pruned graph: workspace and launchers ---------------------------------------------------
+// ---- pruned graph: workspaces and launch helpers ---------------------------------------------
 // ws_points: the sorted chunks (host_util.h: chunks_ws) - filled by the count pass, read by the fill pass;
 // ws_edges (fill pass): staging of the unordered lists, m_edges * 12 bytes
 struct RadiusEdgesWs {
@@ -361,14 +362,6 @@ static RadiusEdgesWs radius_edges_ws(void *base, int64_t m_edges) {
 constexpr int64_t kRadiusPrunedMinRows = 4096;
 constexpr int64_t kRadiusPrunedMaxDegree = 256;  // denser graphs: nothing to prune, ordering would dominate
 
-size_t radius_points_ws_bytes(int64_t n, int dim) {
-    if (n < 1 || n > 0x7fffffff || dim < 1 || dim > 16) return 0;
-    size_t total;
-    chunks_ws(nullptr, n, dim, &total);
-    return total;
-}
-size_t radius_edges_ws_bytes(int64_t m_edges) { return radius_edges_ws(nullptr, m_edges).total; }
-
 // the pruned kernel of either pass over the chunks c
 template <bool FILL>
 static void radius_pruned_launch(const SpatialChunks &c, int64_t n, int dim, double r2, int32_t *cnt, const int64_t *off,
@@ -379,68 +372,6 @@ static void radius_pruned_launch(const SpatialChunks &c, int64_t n, int dim, dou
                            (const float *)c.xs, (const int32_t *)c.sidx, (const float *)c.box, n, c.n_chunks, r2, cnt, off,
                            nbr, dist);
     });
-}
-
-int radius_count_ws_launch(const float *x, int64_t n, int dim, int stride, double radius, int32_t *cnt,
-                           int64_t *offsets, void *ws_points, size_t ws_bytes, int flags, hipStream_t stream) {
-    const bool pruned = ws_points && dim <= 16 && !(flags & 2) && ((flags & 1) || n >= kRadiusPrunedMinRows) && n > 0;
-    if (!pruned) return radius_count_launch(x, n, dim, stride, radius, cnt, offsets, stream);
-    int rc = check_points(x, n, dim, stride, radius, "radius_count");
-    if (rc) return rc;
-    if (!offsets || !cnt) return fail(GNNTRK_EINVAL, "radius_count: NULL argument");
-    size_t need;
-    const SpatialChunks c = chunks_ws(ws_points, n, dim, &need);
-    if (ws_bytes < need) return fail(GNNTRK_EINVAL, "radius_count: workspace too small");
-    rc = spatial_chunks_build(x, n, dim, stride, nullptr, 0, c, stream);
-    if (rc) return rc;
-    radius_pruned_launch<false>(c, n, dim, radius * radius, cnt, nullptr, nullptr, nullptr, stream);
-    scan_counts_launch(cnt, 0x7fffffff, n, offsets, stream);
-    return check_launch("radius_count(pruned)");
-}
-
-int radius_fill_ws_launch(const float *x, int64_t n, int dim, int stride, double radius, const int64_t *off,
-                          int64_t m_edges, int32_t *nbr, double *dist, void *ws_points, size_t ws_bytes,
-                          void *ws_edges, size_t ws_edges_bytes, int flags, hipStream_t stream) {
-    const bool pruned = ws_points && ws_edges && dim <= 16 && !(flags & 2) && n > 0 &&
-                        ((flags & 1) || (n >= kRadiusPrunedMinRows && m_edges <= kRadiusPrunedMaxDegree * n));
-    if (!pruned) return radius_fill_launch(x, n, dim, stride, radius, off, nbr, dist, stream);
-    int rc = check_points(x, n, dim, stride, radius, "radius_fill");
-    if (rc) return rc;
-    if (!off || !nbr || !dist || m_edges < 0) return fail(GNNTRK_EINVAL, "radius_fill: bad argument");
-    size_t need;
-    const SpatialChunks c = chunks_ws(ws_points, n, dim, &need);
-    const RadiusEdgesWs e = radius_edges_ws(ws_edges, m_edges);
-    if (ws_bytes < need || ws_edges_bytes < e.total) return fail(GNNTRK_EINVAL, "radius_fill: workspace too small");
-    radius_pruned_launch<true>(c, n, dim, radius * radius, nullptr, off, e.t_nbr, e.t_dist, stream);
-    hipLaunchKernelGGL(radius_order_kernel, dim3((unsigned)ceil_div(n, kRWaves)), dim3(kRTpb), 0, stream, off, n,
-                       (const int32_t *)e.t_nbr, (const double *)e.t_dist, nbr, dist);
-    return check_launch("radius_fill(pruned)");
-}
-
-int dbscan_init_launch(const int64_t *off, const double *dist, int64_t n, double eps, int min_pts, uint8_t *core,
-                       int32_t *root, hipStream_t stream) {
-    if (n < 0 || n > 0x7fffffff) return fail(GNNTRK_EUNSUPPORTED, "dbscan: n must fit int32");
-    if (n == 0) return GNNTRK_OK;
-    if (!off || !core || !root) return fail(GNNTRK_EINVAL, "dbscan_init: NULL argument");
-    hipLaunchKernelGGL(dbscan_init_kernel, dim3(blocks_for(n, 16)), dim3(256), 0, stream, off, dist, n, eps, min_pts,
-                       core, root);
-    return check_launch("dbscan_init");
-}
-
-int dbscan_propagate_launch(const int64_t *off, const int32_t *nbr, const double *dist, int64_t n, double eps,
-                            const uint8_t *core, int32_t *root, int rounds, int32_t *changed,
-                            hipStream_t stream) {
-    if (!changed) return fail(GNNTRK_EINVAL, "dbscan_propagate: NULL flag");
-    if (n == 0) return check_hip(hipMemsetAsync(changed, 0, sizeof(int32_t), stream), "dbscan_propagate");
-    if (!off || !core || !root || rounds < 1) return fail(GNNTRK_EINVAL, "dbscan_propagate: bad argument");
-    for (int r = 0; r < rounds; ++r) {
-        // the flag reports the LAST round only: zero means the fixpoint has been reached
-        int rc = check_hip(hipMemsetAsync(changed, 0, sizeof(int32_t), stream), "dbscan_propagate(memset)");
-        if (rc) return rc;
-        hipLaunchKernelGGL(dbscan_propagate_kernel, dim3(blocks_for(n, 16)), dim3(256), 0, stream, off, nbr, dist, n,
-                           eps, core, root, changed);
-    }
-    return check_launch("dbscan_propagate");
 }
 
 struct LabelsWs {
@@ -460,22 +391,115 @@ static LabelsWs labels_ws(void *base, int64_t n) {
     w.total = ws.off;
     return w;
 }
-size_t dbscan_ws_bytes(int64_t n) { return labels_ws(nullptr, n).total; }
 
-int dbscan_labels_launch(const int64_t *off, const int32_t *nbr, const double *dist, int64_t n, double eps,
-                         const uint8_t *core, const int32_t *root, int64_t *labels, int64_t *n_clusters, void *ws,
-                         size_t ws_bytes, hipStream_t stream) {
+}  // namespace gnntrk
+
+using namespace gnntrk;
+
+extern "C" {
+
+int gnntrk_radius_count(const float *x, int64_t n, int32_t dim, int32_t x_stride, double radius, int32_t *cnt,
+                        int64_t *offsets, void *stream) {
+    return radius_count(x, n, dim, x_stride, radius, cnt, offsets, (hipStream_t)stream);
+}
+
+int gnntrk_radius_fill(const float *x, int64_t n, int32_t dim, int32_t x_stride, double radius, const int64_t *offsets,
+                       int32_t *nbr, double *dist, void *stream) {
+    return radius_fill(x, n, dim, x_stride, radius, offsets, nbr, dist, (hipStream_t)stream);
+}
+
+size_t gnntrk_radius_points_workspace_bytes(int64_t n, int32_t dim) {
+    if (n < 1 || n > 0x7fffffff || dim < 1 || dim > 16) return 0;
+    size_t total;
+    chunks_ws(nullptr, n, dim, &total);
+    return total;
+}
+
+size_t gnntrk_radius_edges_workspace_bytes(int64_t m_edges) { return radius_edges_ws(nullptr, m_edges).total; }
+
+int gnntrk_radius_count_ws(const float *x, int64_t n, int32_t dim, int32_t x_stride, double radius, int32_t *cnt,
+                           int64_t *offsets, void *ws_points, size_t ws_points_bytes, int32_t flags, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const bool pruned = ws_points && dim <= 16 && !(flags & 2) && ((flags & 1) || n >= kRadiusPrunedMinRows) && n > 0;
+    if (!pruned) return radius_count(x, n, dim, x_stride, radius, cnt, offsets, stream);
+    int rc = check_points(x, n, dim, x_stride, radius, "radius_count");
+    if (rc) return rc;
+    if (!offsets || !cnt) return fail(GNNTRK_EINVAL, "radius_count: NULL argument");
+    size_t need;
+    const SpatialChunks c = chunks_ws(ws_points, n, dim, &need);
+    if (ws_points_bytes < need) return fail(GNNTRK_EINVAL, "radius_count: workspace too small");
+    rc = spatial_chunks_build(x, n, dim, x_stride, nullptr, 0, c, stream);
+    if (rc) return rc;
+    radius_pruned_launch<false>(c, n, dim, radius * radius, cnt, nullptr, nullptr, nullptr, stream);
+    scan_counts_launch(cnt, 0x7fffffff, n, offsets, stream);
+    return check_launch("radius_count(pruned)");
+}
+
+int gnntrk_radius_fill_ws(const float *x, int64_t n, int32_t dim, int32_t x_stride, double radius,
+                          const int64_t *offsets, int64_t m_edges, int32_t *nbr, double *dist, void *ws_points,
+                          size_t ws_points_bytes, void *ws_edges, size_t ws_edges_bytes, int32_t flags, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const bool pruned = ws_points && ws_edges && dim <= 16 && !(flags & 2) && n > 0 &&
+                        ((flags & 1) || (n >= kRadiusPrunedMinRows && m_edges <= kRadiusPrunedMaxDegree * n));
+    if (!pruned) return radius_fill(x, n, dim, x_stride, radius, offsets, nbr, dist, stream);
+    int rc = check_points(x, n, dim, x_stride, radius, "radius_fill");
+    if (rc) return rc;
+    if (!offsets || !nbr || !dist || m_edges < 0) return fail(GNNTRK_EINVAL, "radius_fill: bad argument");
+    size_t need;
+    const SpatialChunks c = chunks_ws(ws_points, n, dim, &need);
+    const RadiusEdgesWs e = radius_edges_ws(ws_edges, m_edges);
+    if (ws_points_bytes < need || ws_edges_bytes < e.total)
+        return fail(GNNTRK_EINVAL, "radius_fill: workspace too small");
+    radius_pruned_launch<true>(c, n, dim, radius * radius, nullptr, offsets, e.t_nbr, e.t_dist, stream);
+    hipLaunchKernelGGL(radius_order_kernel, dim3((unsigned)ceil_div(n, kRWaves)), dim3(kRTpb), 0, stream, offsets, n,
+                       (const int32_t *)e.t_nbr, (const double *)e.t_dist, nbr, dist);
+    return check_launch("radius_fill(pruned)");
+}
+
+int gnntrk_dbscan_init(const int64_t *offsets, const double *dist, int64_t n, double eps, int32_t min_pts,
+                       uint8_t *core, int32_t *root, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n < 0 || n > 0x7fffffff) return fail(GNNTRK_EUNSUPPORTED, "dbscan: n must fit int32");
+    if (n == 0) return GNNTRK_OK;
+    if (!offsets || !core || !root) return fail(GNNTRK_EINVAL, "dbscan_init: NULL argument");
+    hipLaunchKernelGGL(dbscan_init_kernel, dim3(blocks_for(n, 16)), dim3(256), 0, stream, offsets, dist, n, eps,
+                       min_pts, core, root);
+    return check_launch("dbscan_init");
+}
+
+int gnntrk_dbscan_propagate(const int64_t *offsets, const int32_t *nbr, const double *dist, int64_t n, double eps,
+                            const uint8_t *core, int32_t *root, int32_t rounds, int32_t *changed, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!changed) return fail(GNNTRK_EINVAL, "dbscan_propagate: NULL flag");
+    if (n == 0) return check_hip(hipMemsetAsync(changed, 0, sizeof(int32_t), stream), "dbscan_propagate");
+    if (!offsets || !core || !root || rounds < 1) return fail(GNNTRK_EINVAL, "dbscan_propagate: bad argument");
+    for (int r = 0; r < rounds; ++r) {
+        // the flag reports the LAST round only: zero means the fixpoint has been reached
+        int rc = check_hip(hipMemsetAsync(changed, 0, sizeof(int32_t), stream), "dbscan_propagate(memset)");
+        if (rc) return rc;
+        hipLaunchKernelGGL(dbscan_propagate_kernel, dim3(blocks_for(n, 16)), dim3(256), 0, stream, offsets, nbr, dist,
+                           n, eps, core, root, changed);
+    }
+    return check_launch("dbscan_propagate");
+}
+
+size_t gnntrk_dbscan_workspace_bytes(int64_t n) { return labels_ws(nullptr, n).total; }
+
+int gnntrk_dbscan_labels(const int64_t *offsets, const int32_t *nbr, const double *dist, int64_t n, double eps,
+                         const uint8_t *core, const int32_t *root, int64_t *labels, int64_t *n_clusters,
+                         void *workspace, size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     if (!n_clusters) return fail(GNNTRK_EINVAL, "dbscan_labels: NULL count output");
     if (n == 0) return check_hip(hipMemsetAsync(n_clusters, 0, sizeof(int64_t), stream), "dbscan_labels");
-    if (!off || !core || !root || !labels) return fail(GNNTRK_EINVAL, "dbscan_labels: NULL argument");
-    const LabelsWs w = labels_ws(ws, n);
-    if (!ws || ws_bytes < w.total) return fail(GNNTRK_EINVAL, "dbscan_labels: workspace too small");
+    if (!offsets || !core || !root || !labels) return fail(GNNTRK_EINVAL, "dbscan_labels: NULL argument");
+    const LabelsWs w = labels_ws(workspace, n);
+    if (!workspace || workspace_bytes < w.total) return fail(GNNTRK_EINVAL, "dbscan_labels: workspace too small");
     hipLaunchKernelGGL(dbscan_roots_kernel, dim3(blocks_for(n, 16)), dim3(256), 0, stream, core, root, n, w.is_root);
     int rc = compact_bytes_launch(w.is_root, n, w.root_list, w.rank, n_clusters, w.compact, compact_ws_bytes(n), stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(dbscan_labels_kernel, dim3(blocks_for(n, 16)), dim3(256), 0, stream, off, nbr, dist, n, eps,
+    hipLaunchKernelGGL(dbscan_labels_kernel, dim3(blocks_for(n, 16)), dim3(256), 0, stream, offsets, nbr, dist, n, eps,
                        core, root, w.rank, labels);
     return check_launch("dbscan_labels");
 }
 
-}  // namespace gnntrk
+}  // extern "C"

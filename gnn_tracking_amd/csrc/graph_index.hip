@@ -1097,7 +1097,7 @@ static size_t library_ws_bytes(int64_t E) {
 
 // (carry: bit 0 = carried rows, bit 1 = node_rank given: room for the renumbered int32 edge list behind the plan)
 static size_t remap_arr_bytes(int64_t E) { return align_up((size_t)(E > 0 ? E : 1) * sizeof(int32_t), 256); }
-size_t graph_index_ws_bytes(int64_t N, int64_t E, int carry) {
+static size_t graph_index_ws_bytes(int64_t N, int64_t E, int carry) {
     const size_t lib = library_ws_bytes(E);
     const OwnPlan p = own_plan(N, E, (carry & 1) != 0);
     const size_t own = p.ok ? align_up(p.bytes, 256) + ((carry & 2) ? 2 * remap_arr_bytes(E) : 0) : 0;
@@ -1145,8 +1145,9 @@ static int library_build(const int64_t *edge_index, const gnntrk_graph_index *o,
     return GNNTRK_OK;
 }
 
-int graph_index_build(const int64_t *edge_index, const gnntrk_graph_index *o, const gnntrk_graph_index_carry *cy,
-                      void *ws, size_t ws_bytes, int flags, hipStream_t stream) {
+static int graph_index_build(const int64_t *edge_index, const gnntrk_graph_index *o,
+                             const gnntrk_graph_index_carry *cy, void *ws, size_t ws_bytes, int flags,
+                             hipStream_t stream) {
     if (!o) return fail(GNNTRK_EINVAL, "graph_index_build: NULL output descriptor");
     const int64_t E = o->n_edges, N = o->n_nodes;
     if (E < 0 || N < 0 || E > 0x7fffffff || N > 0x7fffffff)
@@ -1278,29 +1279,6 @@ __global__ __launch_bounds__(kTpb) void gi_place_kernel(gnntrk_graph_index part,
         }
     }
 }
-int graph_index_place(const gnntrk_graph_index *part, int64_t node_offset, int64_t edge_offset,
-                      const gnntrk_graph_index *batch, const uint8_t *label_part, uint8_t *label_batch,
-                      const uint16_t *rows_part, uint16_t *rows_batch, const int32_t *node_perm_part,
-                      int32_t *node_perm_batch, const int32_t *node_rank_part, int32_t *node_rank_batch,
-                      hipStream_t stream) {
-    if (!part || !batch) return fail(GNNTRK_EINVAL, "graph_index_place: NULL descriptor");
-    if (node_offset < 0 || edge_offset < 0 || node_offset + part->n_nodes > batch->n_nodes ||
-        edge_offset + part->n_edges > batch->n_edges || batch->n_edges > 0x7fffffff || batch->n_nodes > 0x7fffffff)
-        return fail(GNNTRK_EINVAL, "graph_index_place: the event does not fit the batch at these offsets");
-    if ((label_part != nullptr) != (label_batch != nullptr) || (rows_part != nullptr) != (rows_batch != nullptr) ||
-        (node_perm_part != nullptr) != (node_perm_batch != nullptr) || (node_perm_part != nullptr) != (node_rank_part != nullptr) ||
-        (node_rank_part != nullptr) != (node_rank_batch != nullptr))
-        return fail(GNNTRK_EINVAL, "graph_index_place: carried / node-order arrays must come in pairs");
-    if (rows_part && ((((uintptr_t)rows_part | (uintptr_t)rows_batch) & 7) != 0))
-        return fail(GNNTRK_EINVAL, "graph_index_place: carried rows are 8-byte rows");
-    const int64_t work = part->n_edges / 4 > part->n_nodes ? part->n_edges / 4 : part->n_nodes;
-    hipLaunchKernelGGL(gi_place_kernel, dim3(stream_grid(work + 1)), dim3(kTpb), 0, stream, *part, *batch,
-                       (int32_t)node_offset, (int32_t)edge_offset, label_part, label_batch,
-                       reinterpret_cast<const uint2 *>(rows_part), reinterpret_cast<uint2 *>(rows_batch), node_perm_part,
-                       node_perm_batch, node_rank_part, node_rank_batch);
-    return check_launch("graph_index_place");
-}
-
 // ------------------------------------------------------------------ node order (gnntrk_node_order)
 // Per-event renumbering of the nodes by a caller-supplied key (one float per node: the hits' azimuth for
 // tracking graphs, whose edges join hits of neighbouring azimuth): new ids = rank of (event, key, old id).
@@ -1441,43 +1419,103 @@ static bool node_order_own(int64_t n, int64_t n_events, const int64_t *batch, Ow
     plan = own_plan(keys, n, false);
     return plan.ok && !plan.dense;
 }
-size_t node_order_ws_bytes(int64_t n) {
-    const size_t m = (size_t)(n > 0 ? n : 1);
-    const size_t t64 = sort_pairs_u64_temp_bytes(n), t32 = sort_pairs_temp_bytes(n);
+
+}  // namespace gnntrk
+
+using namespace gnntrk;
+
+extern "C" {
+
+size_t gnntrk_graph_index_workspace_bytes(int64_t n_nodes, int64_t n_edges) {
+    return graph_index_ws_bytes(n_nodes, n_edges, 0);
+}
+
+size_t gnntrk_graph_index_workspace_bytes_carry(int64_t n_nodes, int64_t n_edges, int32_t carry_rows) {
+    return graph_index_ws_bytes(n_nodes, n_edges, carry_rows);
+}
+
+int gnntrk_graph_index_build(const int64_t *edge_index, const gnntrk_graph_index *out, void *workspace,
+                             size_t workspace_bytes, void *stream) {
+    return graph_index_build(edge_index, out, nullptr, workspace, workspace_bytes, 0, (hipStream_t)stream);
+}
+
+int gnntrk_graph_index_build_ex(const int64_t *edge_index, const gnntrk_graph_index *out, void *workspace,
+                                size_t workspace_bytes, int32_t flags, void *stream) {
+    return graph_index_build(edge_index, out, nullptr, workspace, workspace_bytes, flags, (hipStream_t)stream);
+}
+
+int gnntrk_graph_index_build_carry(const int64_t *edge_index, const gnntrk_graph_index *out,
+                                   const gnntrk_graph_index_carry *carry, void *workspace, size_t workspace_bytes,
+                                   int32_t flags, void *stream) {
+    return graph_index_build(edge_index, out, carry, workspace, workspace_bytes, flags, (hipStream_t)stream);
+}
+
+int gnntrk_graph_index_place(const gnntrk_graph_index *part, int64_t node_offset, int64_t edge_offset,
+                             const gnntrk_graph_index *batch, const uint8_t *label_part, uint8_t *label_batch,
+                             const uint16_t *rows_part, uint16_t *rows_batch, const int32_t *node_perm_part,
+                             int32_t *node_perm_batch, const int32_t *node_rank_part, int32_t *node_rank_batch,
+                             void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!part || !batch) return fail(GNNTRK_EINVAL, "graph_index_place: NULL descriptor");
+    if (node_offset < 0 || edge_offset < 0 || node_offset + part->n_nodes > batch->n_nodes ||
+        edge_offset + part->n_edges > batch->n_edges || batch->n_edges > 0x7fffffff || batch->n_nodes > 0x7fffffff)
+        return fail(GNNTRK_EINVAL, "graph_index_place: the event does not fit the batch at these offsets");
+    if ((label_part != nullptr) != (label_batch != nullptr) || (rows_part != nullptr) != (rows_batch != nullptr) ||
+        (node_perm_part != nullptr) != (node_perm_batch != nullptr) || (node_perm_part != nullptr) != (node_rank_part != nullptr) ||
+        (node_rank_part != nullptr) != (node_rank_batch != nullptr))
+        return fail(GNNTRK_EINVAL, "graph_index_place: carried / node-order arrays must come in pairs");
+    if (rows_part && ((((uintptr_t)rows_part | (uintptr_t)rows_batch) & 7) != 0))
+        return fail(GNNTRK_EINVAL, "graph_index_place: carried rows are 8-byte rows");
+    const int64_t work = part->n_edges / 4 > part->n_nodes ? part->n_edges / 4 : part->n_nodes;
+    hipLaunchKernelGGL(gi_place_kernel, dim3(stream_grid(work + 1)), dim3(kTpb), 0, stream, *part, *batch,
+                       (int32_t)node_offset, (int32_t)edge_offset, label_part, label_batch,
+                       reinterpret_cast<const uint2 *>(rows_part), reinterpret_cast<uint2 *>(rows_batch), node_perm_part,
+                       node_perm_batch, node_rank_part, node_rank_batch);
+    return check_launch("graph_index_place");
+}
+
+size_t gnntrk_node_order_workspace_bytes(int64_t n_nodes) {
+    const size_t m = (size_t)(n_nodes > 0 ? n_nodes : 1);
+    const size_t t64 = sort_pairs_u64_temp_bytes(n_nodes), t32 = sort_pairs_temp_bytes(n_nodes);
     const size_t lib = 2 * align_up(m * 8, 256) + 2 * align_up(m * 4, 256) + align_up(t64 > t32 ? t64 : t32, 256);
     // own form: min / max + flag words | quantised keys | row pointers of the (event, level) pairs | the sort's plan
-    const OwnPlan p = own_plan(kNoMaxKeys, n > 0 ? n : 1, false);
+    const OwnPlan p = own_plan(kNoMaxKeys, n_nodes > 0 ? n_nodes : 1, false);
     const size_t own = 1024 + align_up(m * 4, 256) + align_up((size_t)(kNoMaxKeys + 1) * 4, 256) + (p.ok ? p.bytes : 0);
     return lib > own ? lib : own;
 }
-int node_order(const float *key, int64_t key_stride, const int64_t *batch, int64_t n_events, int64_t n, int32_t *perm,
-               int32_t *rank, void *ws, size_t ws_bytes, hipStream_t stream) {
-    if (n < 0 || n > 0x7fffffff) return fail(GNNTRK_EUNSUPPORTED, "node_order: sizes must fit int32");
-    if (n == 0) return GNNTRK_OK;
+
+int gnntrk_node_order(const float *key, int64_t key_stride, const int64_t *batch, int64_t n_events, int64_t n_nodes,
+                      int32_t *perm, int32_t *rank, void *workspace, size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_nodes < 0 || n_nodes > 0x7fffffff) return fail(GNNTRK_EUNSUPPORTED, "node_order: sizes must fit int32");
+    if (n_nodes == 0) return GNNTRK_OK;
     if (!key || key_stride < 1 || !perm || !rank) return fail(GNNTRK_EINVAL, "node_order: NULL argument");
-    if (!ws || ws_bytes < node_order_ws_bytes(n)) return fail(GNNTRK_EINVAL, "node_order: workspace too small");
-    char *p = reinterpret_cast<char *>(ws);
-    const int grid = stream_grid(n);
+    if (!workspace || workspace_bytes < gnntrk_node_order_workspace_bytes(n_nodes))
+        return fail(GNNTRK_EINVAL, "node_order: workspace too small");
+    char *p = reinterpret_cast<char *>(workspace);
+    const int grid = stream_grid(n_nodes);
     OwnPlan plan;
     int64_t n_keys = 0;
-    if (node_order_own(n, n_events, batch, plan, n_keys)) {
+    if (node_order_own(n_nodes, n_events, batch, plan, n_keys)) {
         uint32_t *mm = reinterpret_cast<uint32_t *>(p);          // per event {~min image, max image}; [128]: bad event ids
         int32_t *q = reinterpret_cast<int32_t *>(p + 1024);
-        int32_t *rowptr = reinterpret_cast<int32_t *>(p + 1024 + align_up((size_t)n * 4, 256));
+        int32_t *rowptr = reinterpret_cast<int32_t *>(p + 1024 + align_up((size_t)n_nodes * 4, 256));
         char *sort_ws = reinterpret_cast<char *>(rowptr) + align_up((size_t)(kNoMaxKeys + 1) * 4, 256);
         int rc = check_hip(hipMemsetAsync(mm, 0, 1024, stream), "node_order(memset)");
         if (rc) return rc;
         const int64_t ev = batch ? n_events : 1;
-        hipLaunchKernelGGL(no_minmax_kernel, dim3(grid), dim3(kTpb), 0, stream, key, key_stride, batch, n, ev, mm);
-        hipLaunchKernelGGL(no_qkeys_kernel, dim3(grid), dim3(kTpb), 0, stream, key, key_stride, batch, n, ev, mm, q,
-                           reinterpret_cast<int *>(mm + 2 * kNoMaxEvents));
+        hipLaunchKernelGGL(no_minmax_kernel, dim3(grid), dim3(kTpb), 0, stream, key, key_stride, batch, n_nodes, ev,
+                           mm);
+        hipLaunchKernelGGL(no_qkeys_kernel, dim3(grid), dim3(kTpb), 0, stream, key, key_stride, batch, n_nodes, ev, mm,
+                           q, reinterpret_cast<int *>(mm + 2 * kNoMaxEvents));
         KeysCsr keys{q};
         OutNode out{perm, rank, rowptr};
-        rc = own_sort<KeysCsr, OutNode, false>(plan, keys, out, 0, n_keys, n, sort_ws, reinterpret_cast<int *>(mm + 2 * kNoMaxEvents), stream);
+        rc = own_sort<KeysCsr, OutNode, false>(plan, keys, out, 0, n_keys, n_nodes, sort_ws,
+                                               reinterpret_cast<int *>(mm + 2 * kNoMaxEvents), stream);
         if (rc) return rc;
         return check_launch("node_order");
     }
-    const size_t k8 = align_up((size_t)n * 8, 256), v4 = align_up((size_t)n * 4, 256);
+    const size_t k8 = align_up((size_t)n_nodes * 8, 256), v4 = align_up((size_t)n_nodes * 4, 256);
     unsigned long long *ka = reinterpret_cast<unsigned long long *>(p), *kb = reinterpret_cast<unsigned long long *>(p + k8);
     uint32_t *va = reinterpret_cast<uint32_t *>(p + 2 * k8), *vb = reinterpret_cast<uint32_t *>(p + 2 * k8 + v4);
     void *temp = p + 2 * k8 + 2 * v4;
@@ -1490,15 +1528,16 @@ int node_order(const float *key, int64_t key_stride, const int64_t *batch, int64
     int rc;
     if (ebits <= 8) {   // one 32-bit key (see no_keys32_kernel)
         uint32_t *k32a = reinterpret_cast<uint32_t *>(ka), *k32b = reinterpret_cast<uint32_t *>(kb);
-        hipLaunchKernelGGL(no_keys32_kernel, dim3(grid), dim3(kTpb), 0, stream, key, key_stride, batch, n, ebits, k32a, va);
-        rc = sort_pairs_u32(k32a, k32b, va, vb, n, 32, temp, sort_pairs_temp_bytes(n), stream);
+        hipLaunchKernelGGL(no_keys32_kernel, dim3(grid), dim3(kTpb), 0, stream, key, key_stride, batch, n_nodes, ebits,
+                           k32a, va);
+        rc = sort_pairs_u32(k32a, k32b, va, vb, n_nodes, 32, temp, sort_pairs_temp_bytes(n_nodes), stream);
     } else {
-        hipLaunchKernelGGL(no_keys_kernel, dim3(grid), dim3(kTpb), 0, stream, key, key_stride, batch, n, ka, va);
-        rc = sort_pairs_u64_bits(ka, kb, va, vb, n, 32 + ebits, temp, sort_pairs_u64_temp_bytes(n), stream);
+        hipLaunchKernelGGL(no_keys_kernel, dim3(grid), dim3(kTpb), 0, stream, key, key_stride, batch, n_nodes, ka, va);
+        rc = sort_pairs_u64_bits(ka, kb, va, vb, n_nodes, 32 + ebits, temp, sort_pairs_u64_temp_bytes(n_nodes), stream);
     }
     if (rc) return rc;
-    hipLaunchKernelGGL(no_finish_kernel, dim3(grid), dim3(kTpb), 0, stream, vb, n, perm, rank);
+    hipLaunchKernelGGL(no_finish_kernel, dim3(grid), dim3(kTpb), 0, stream, vb, n_nodes, perm, rank);
     return check_launch("node_order");
 }
 
-}  // namespace gnntrk
+}  // extern "C"

@@ -742,8 +742,8 @@ __global__ __launch_bounds__(256) void edge_labels_kernel(const int64_t *__restr
     }
 }
 
-int knn_search_launch(const float *x, int64_t n, int dim, int stride, int k, float max_radius,
-                      const int64_t *seg_ptr, int n_seg, int32_t *nbr, int32_t *cnt, hipStream_t stream) {
+static int knn_search_launch(const float *x, int64_t n, int dim, int stride, int k, float max_radius,
+                             const int64_t *seg_ptr, int n_seg, int32_t *nbr, int32_t *cnt, hipStream_t stream) {
     if (!x || !nbr || !cnt || n < 0 || dim < 1 || stride < dim || k < 1)
         return fail(GNNTRK_EINVAL, "knn_search: bad argument");
     if (seg_ptr && n_seg < 1) return fail(GNNTRK_EINVAL, "knn_search: seg_ptr needs n_seg >= 1");
@@ -844,7 +844,49 @@ static int knn_pruned_qw(int dim, int k, int *cap_out) {
     return (dim > 8 && qw == 8) ? 4 : qw;  // 16 coordinates per query: four queries fill the registers
 }
 
-size_t knn_workspace_bytes(int64_t n, int dim, int k) {
+constexpr int64_t kKnnPrunedMinRows = 8192;  // below this the sort + boxes cost more than they save
+
+// off[0..n] = exclusive scan of min(cnt[i], k_take) (also the condensation-point selection's scan)
+void scan_counts_launch(const int32_t *cnt, int k_take, int64_t n, int64_t *off, hipStream_t stream) {
+    const int nt = n < 65536 ? 256 : 1024;
+    if ((reinterpret_cast<uintptr_t>(cnt) & 15u) == 0)
+        hipLaunchKernelGGL(scan_counts_kernel<true>, dim3(1), dim3(nt), 0, stream, cnt, k_take, n, off);
+    else
+        hipLaunchKernelGGL(scan_counts_kernel<false>, dim3(1), dim3(nt), 0, stream, cnt, k_take, n, off);
+}
+
+static int knn_emit_launch(const int32_t *nbr, const int32_t *cnt, int64_t n, int k_stride, int k, int64_t *offsets,
+                           int64_t *edge_index, int64_t m_total, hipStream_t stream) {
+    if (!nbr || !cnt || !offsets || n < 0 || k < 1 || k > k_stride)
+        return fail(GNNTRK_EINVAL, "knn_emit: bad argument");
+    if (n == 0) return GNNTRK_OK;
+    if (!edge_index) {  // phase 1: offsets only (offsets[n] = total edge count)
+        scan_counts_launch(cnt, k, n, offsets, stream);
+        return check_launch("knn_emit(scan)");
+    }
+    if (m_total > 0)
+        hipLaunchKernelGGL(knn_emit_kernel, dim3(blocks_for(n * k, 8)), dim3(256), 0, stream, nbr, cnt,
+                           (const int64_t *)offsets, n, k_stride, k, m_total, edge_index);
+    return check_launch("knn_emit");
+}
+
+}  // namespace gnntrk
+
+using namespace gnntrk;
+
+extern "C" {
+
+int gnntrk_knn_search(const float *x, int64_t n, int32_t dim, int32_t x_stride, int32_t k, float max_radius,
+                      int32_t *nbr, int32_t *cnt, void *stream) {
+    return knn_search_launch(x, n, dim, x_stride, k, max_radius, nullptr, 0, nbr, cnt, (hipStream_t)stream);
+}
+
+int gnntrk_knn_search_batched(const float *x, int64_t n, int32_t dim, int32_t x_stride, int32_t k, float max_radius,
+                              const int64_t *seg_ptr, int32_t n_seg, int32_t *nbr, int32_t *cnt, void *stream) {
+    return knn_search_launch(x, n, dim, x_stride, k, max_radius, seg_ptr, n_seg, nbr, cnt, (hipStream_t)stream);
+}
+
+size_t gnntrk_knn_workspace_bytes(int64_t n, int32_t dim, int32_t k) {
     int cap;
     if (n <= 0 || dim < 1 || k < 1 || n > 0x7fffffff || knn_pruned_qw(dim, k, &cap) == 0) return 0;
     size_t total;
@@ -852,23 +894,23 @@ size_t knn_workspace_bytes(int64_t n, int dim, int k) {
     return total;
 }
 
-constexpr int64_t kKnnPrunedMinRows = 8192;  // below this the sort + boxes cost more than they save
-
-int knn_search_ws_launch(const float *x, int64_t n, int dim, int stride, int k, float max_radius,
-                         const int64_t *seg_ptr, int n_seg, int32_t *nbr, int32_t *cnt, void *ws,
-                         size_t ws_bytes, int flags, hipStream_t stream) {
+int gnntrk_knn_search_ws(const float *x, int64_t n, int32_t dim, int32_t x_stride, int32_t k, float max_radius,
+                         const int64_t *seg_ptr, int32_t n_seg, int32_t *nbr, int32_t *cnt, void *workspace,
+                         size_t workspace_bytes, int32_t flags, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     int cap = 0;
     const int qw = (n > 0 && dim >= 1 && k >= 1 && n <= 0x7fffffff) ? knn_pruned_qw(dim, k, &cap) : 0;
     const bool force_brute = (flags & 2) != 0, force_pruned = (flags & 1) != 0;
-    bool pruned = qw != 0 && ws != nullptr && !force_brute && (force_pruned || n >= kKnnPrunedMinRows);
+    bool pruned = qw != 0 && workspace != nullptr && !force_brute && (force_pruned || n >= kKnnPrunedMinRows);
     if (pruned && seg_ptr && n_seg > 65536) pruned = false;
-    if (!pruned) return knn_search_launch(x, n, dim, stride, k, max_radius, seg_ptr, n_seg, nbr, cnt, stream);
-    if (!x || !nbr || !cnt || stride < dim) return fail(GNNTRK_EINVAL, "knn_search: bad argument");
+    if (!pruned) return knn_search_launch(x, n, dim, x_stride, k, max_radius, seg_ptr, n_seg, nbr, cnt, stream);
+    if (!x || !nbr || !cnt || x_stride < dim) return fail(GNNTRK_EINVAL, "knn_search: bad argument");
     if (seg_ptr && n_seg < 1) return fail(GNNTRK_EINVAL, "knn_search: seg_ptr needs n_seg >= 1");
     size_t need;
-    const SpatialChunks c = chunks_ws(ws, n, dim, &need);
-    if (ws_bytes < need) return fail(GNNTRK_EINVAL, "knn_search: workspace too small (gnntrk_knn_workspace_bytes)");
-    const int rc = spatial_chunks_build(x, n, dim, stride, seg_ptr, n_seg, c, stream);
+    const SpatialChunks c = chunks_ws(workspace, n, dim, &need);
+    if (workspace_bytes < need)
+        return fail(GNNTRK_EINVAL, "knn_search: workspace too small (gnntrk_knn_workspace_bytes)");
+    const int rc = spatial_chunks_build(x, n, dim, x_stride, seg_ptr, n_seg, c, stream);
     if (rc != GNNTRK_OK) return rc;
     const unsigned grid = (unsigned)ceil_div(n, (int64_t)qw * kKnnWaves);
     dispatch_dp<4, 8, 16>(dim, [&](auto DP) {
@@ -894,47 +936,36 @@ int knn_search_ws_launch(const float *x, int64_t n, int dim, int stride, int k, 
     return check_launch("knn_search(pruned)");
 }
 
-// off[0..n] = exclusive scan of min(cnt[i], k_take) (also the condensation-point selection's scan)
-void scan_counts_launch(const int32_t *cnt, int k_take, int64_t n, int64_t *off, hipStream_t stream) {
-    const int nt = n < 65536 ? 256 : 1024;
-    if ((reinterpret_cast<uintptr_t>(cnt) & 15u) == 0)
-        hipLaunchKernelGGL(scan_counts_kernel<true>, dim3(1), dim3(nt), 0, stream, cnt, k_take, n, off);
-    else
-        hipLaunchKernelGGL(scan_counts_kernel<false>, dim3(1), dim3(nt), 0, stream, cnt, k_take, n, off);
+int gnntrk_knn_emit(const int32_t *nbr, const int32_t *cnt, int64_t n, int32_t k, int64_t *offsets, int64_t *edge_index,
+                    int64_t n_edges, void *stream) {
+    return knn_emit_launch(nbr, cnt, n, k, k, offsets, edge_index, n_edges, (hipStream_t)stream);
 }
 
-int knn_emit_launch(const int32_t *nbr, const int32_t *cnt, int64_t n, int k_stride, int k, int64_t *offsets,
-                    int64_t *edge_index, int64_t m_total, hipStream_t stream) {
-    if (!nbr || !cnt || !offsets || n < 0 || k < 1 || k > k_stride)
-        return fail(GNNTRK_EINVAL, "knn_emit: bad argument");
-    if (n == 0) return GNNTRK_OK;
-    if (!edge_index) {  // phase 1: offsets only (offsets[n] = total edge count)
-        scan_counts_launch(cnt, k, n, offsets, stream);
-        return check_launch("knn_emit(scan)");
-    }
-    if (m_total > 0)
-        hipLaunchKernelGGL(knn_emit_kernel, dim3(blocks_for(n * k, 8)), dim3(256), 0, stream, nbr, cnt,
-                           (const int64_t *)offsets, n, k_stride, k, m_total, edge_index);
-    return check_launch("knn_emit");
+int gnntrk_knn_emit_prefix(const int32_t *nbr, const int32_t *cnt, int64_t n, int32_t k_stride, int32_t k_take,
+                           int64_t *offsets, int64_t *edge_index, int64_t n_edges, void *stream) {
+    return knn_emit_launch(nbr, cnt, n, k_stride, k_take, offsets, edge_index, n_edges, (hipStream_t)stream);
 }
 
-int edge_features_launch(const float *x, int dim, int stride, const int64_t *ei, int64_t m,
-                         float *out, hipStream_t stream) {
-    if (!x || dim < 1 || stride < dim || m < 0) return fail(GNNTRK_EINVAL, "edge_features: bad argument");
-    if (m == 0) return GNNTRK_OK;
-    if (!ei || !out) return fail(GNNTRK_EINVAL, "edge_features: NULL pointer");
-    hipLaunchKernelGGL(edge_features_kernel, dim3(blocks_for(m * dim, 8)), dim3(256), 0, stream, x, dim,
-                       stride, ei, m, out);
+int gnntrk_edge_features(const float *x, int32_t dim, int32_t x_stride, const int64_t *edge_index, int64_t n_edges,
+                         float *out, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!x || dim < 1 || x_stride < dim || n_edges < 0) return fail(GNNTRK_EINVAL, "edge_features: bad argument");
+    if (n_edges == 0) return GNNTRK_OK;
+    if (!edge_index || !out) return fail(GNNTRK_EINVAL, "edge_features: NULL pointer");
+    hipLaunchKernelGGL(edge_features_kernel, dim3(blocks_for(n_edges * dim, 8)), dim3(256), 0, stream, x, dim,
+                       x_stride, edge_index, n_edges, out);
     return check_launch("edge_features");
 }
 
-int edge_labels_launch(const int64_t *pid, const int64_t *ei, int64_t m, int64_t *y,
-                       hipStream_t stream) {
-    if (m < 0) return fail(GNNTRK_EINVAL, "edge_labels: bad argument");
-    if (m == 0) return GNNTRK_OK;
-    if (!pid || !ei || !y) return fail(GNNTRK_EINVAL, "edge_labels: NULL pointer");
-    hipLaunchKernelGGL(edge_labels_kernel, dim3(blocks_for(m, 8)), dim3(256), 0, stream, pid, ei, m, y);
+int gnntrk_edge_labels(const int64_t *particle_id, const int64_t *edge_index, int64_t n_edges, int64_t *y,
+                       void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_edges < 0) return fail(GNNTRK_EINVAL, "edge_labels: bad argument");
+    if (n_edges == 0) return GNNTRK_OK;
+    if (!particle_id || !edge_index || !y) return fail(GNNTRK_EINVAL, "edge_labels: NULL pointer");
+    hipLaunchKernelGGL(edge_labels_kernel, dim3(blocks_for(n_edges, 8)), dim3(256), 0, stream, particle_id, edge_index,
+                       n_edges, y);
     return check_launch("edge_labels");
 }
 
-}  // namespace gnntrk
+}  // extern "C"

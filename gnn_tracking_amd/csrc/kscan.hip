@@ -293,11 +293,18 @@ __global__ void ks_finish_kernel(Ws w, Plan plan, unsigned long long *__restrict
 
 }  // namespace
 
-size_t cc_labels_ws_bytes(int64_t n) { return align_up(4 * (size_t)(n < 0 ? 0 : n), 256); }
+}  // namespace gnntrk
 
-int cc_labels(const int64_t *edge_index, int64_t n_edges, const int32_t *nbr, const int32_t *cnt, int32_t k_stride,
-              int32_t k, const int64_t *same_pid, const uint8_t *node_mask, int64_t n, int64_t *labels,
-              int64_t *n_bad, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+using namespace gnntrk;
+
+extern "C" {
+
+size_t gnntrk_cc_labels_workspace_bytes(int64_t n) { return align_up(4 * (size_t)(n < 0 ? 0 : n), 256); }
+
+int gnntrk_cc_labels(const int64_t *edge_index, int64_t n_edges, const int32_t *nbr, const int32_t *cnt,
+                     int32_t k_stride, int32_t k, const int64_t *same_pid, const uint8_t *node_mask, int64_t n,
+                     int64_t *labels, int64_t *n_bad, void *workspace, size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     char msg[160];
     int rc = check_count_i30("cc_labels", "node", n);
     if (rc) return rc;
@@ -312,7 +319,8 @@ int cc_labels(const int64_t *edge_index, int64_t n_edges, const int32_t *nbr, co
         return fail(GNNTRK_EINVAL, "cc_labels: negative edge count");
     }
     if (n > 0 && !labels) return fail(GNNTRK_EINVAL, "cc_labels: NULL labels");
-    if (n > 0 && (rc = check_workspace("cc_labels", workspace, workspace_bytes, cc_labels_ws_bytes(n)))) return rc;
+    if (n > 0 && (rc = check_workspace("cc_labels", workspace, workspace_bytes, gnntrk_cc_labels_workspace_bytes(n))))
+        return rc;
     if (n_bad && (rc = check_hip(hipMemsetAsync(n_bad, 0, sizeof(int64_t), stream), "cc_labels: clear"))) return rc;
     if (n == 0) return GNNTRK_OK;
     auto *parent = (int32_t *)workspace;
@@ -328,12 +336,13 @@ int cc_labels(const int64_t *edge_index, int64_t n_edges, const int32_t *nbr, co
     return check_launch("cc_labels");
 }
 
-size_t kscan_counts_ws_bytes(int64_t n) { return make_ws(nullptr, n < 0 ? 0 : n).total; }
+size_t gnntrk_kscan_counts_workspace_bytes(int64_t n) { return make_ws(nullptr, n < 0 ? 0 : n).total; }
 
-int kscan_counts(const int32_t *nbr, const int32_t *cnt, int64_t n, int32_t k_stride, const int32_t *ks,
-                 int32_t n_ks, const int64_t *pid, const uint8_t *node_mask, const int64_t *true_edge_index,
-                 int64_t n_true_edges, int64_t *out, int64_t *labels, void *workspace, size_t workspace_bytes,
-                 hipStream_t stream) {
+int gnntrk_kscan_counts(const int32_t *nbr, const int32_t *cnt, int64_t n, int32_t k_stride, const int32_t *ks,
+                        int32_t n_ks, const int64_t *particle_id, const uint8_t *node_mask,
+                        const int64_t *true_edge_index, int64_t n_true_edges, int64_t *out, int64_t *labels,
+                        void *workspace, size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     char msg[160];
     int rc = check_count_i30("kscan_counts", "hit", n);
     if (rc) return rc;
@@ -351,7 +360,7 @@ int kscan_counts(const int32_t *nbr, const int32_t *cnt, int64_t n, int32_t k_st
     if (n_true_edges < 0) return fail(GNNTRK_EINVAL, "kscan_counts: negative number of true edges");
     if (n_true_edges > 0 && !true_edge_index) return fail(GNNTRK_EINVAL, "kscan_counts: NULL true_edge_index");
     if (!out) return fail(GNNTRK_EINVAL, "kscan_counts: NULL output");
-    if (n > 0 && (!nbr || !cnt || !pid || !node_mask || !labels))
+    if (n > 0 && (!nbr || !cnt || !particle_id || !node_mask || !labels))
         return fail(GNNTRK_EINVAL, "kscan_counts: NULL neighbour table, particle ids, node mask or labels");
     if (n > 0 && (rc = check_workspace("kscan_counts", workspace, workspace_bytes, make_ws(nullptr, n).total)))
         return rc;
@@ -376,7 +385,7 @@ int kscan_counts(const int32_t *nbr, const int32_t *cnt, int64_t n, int32_t k_st
     auto *o = reinterpret_cast<unsigned long long *>(out);
     const int gn = blocks_for(n, 8);
     hipLaunchKernelGGL(ks_init_kernel, dim3(gn), dim3(kTpb), 0, stream, w, n);
-    hipLaunchKernelGGL(ks_particles_kernel, dim3(gn), dim3(kTpb), 0, stream, pid, node_mask, n, w);
+    hipLaunchKernelGGL(ks_particles_kernel, dim3(gn), dim3(kTpb), 0, stream, particle_id, node_mask, n, w);
     if (n_true_edges > 0)
         hipLaunchKernelGGL(ks_true_edges_kernel, dim3(blocks_for(n_true_edges, 8)), dim3(kTpb), 0, stream,
                            true_edge_index, n_true_edges, n, node_mask, w);
@@ -386,7 +395,7 @@ int kscan_counts(const int32_t *nbr, const int32_t *cnt, int64_t n, int32_t k_st
         const int32_t hi = plan.k[s];
         if (hi > lo) {
             hipLaunchKernelGGL(ks_union_kernel, dim3(blocks_for(n * (hi - lo), 8)), dim3(kTpb), 0, stream, nbr, cnt, n,
-                               k_stride, lo, hi, pid, node_mask, w, (int32_t)s);
+                               k_stride, lo, hi, particle_id, node_mask, w, (int32_t)s);
             lo = hi;
         }
         hipLaunchKernelGGL(ks_compress_kernel, dim3(gn), dim3(kTpb), 0, stream, node_mask, n, w,
@@ -400,4 +409,4 @@ int kscan_counts(const int32_t *nbr, const int32_t *cnt, int64_t n, int32_t k_st
     return check_launch("kscan_counts: finish");
 }
 
-}  // namespace gnntrk
+}  // extern "C"

@@ -410,9 +410,16 @@ AucWs auc_ws(void *base, int64_t n) {
 
 }  // namespace
 
-int bcs_counts(const float *w, const void *y, int32_t y_kind, const int32_t *perm, const void *src, const void *tgt,
-               int32_t ids_i64, const float *pt, const float *cuts, int32_t n_cuts, const float *thr, int32_t n_thr,
-               int64_t n, int64_t *counts, hipStream_t stream) {
+}  // namespace gnntrk
+
+using namespace gnntrk;
+
+extern "C" {
+
+int gnntrk_bcs_counts(const float *w, const void *y, int32_t y_kind, const int32_t *perm, const void *src,
+                      const void *tgt, int32_t ids_i64, const float *pt, const float *cuts, int32_t n_cuts,
+                      const float *thr, int32_t n_thr, int64_t n, int64_t *counts, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     Cuts c;
     int rc = check_common("bcs_counts", w, y, y_kind, src, tgt, pt, cuts, n_cuts, n, c);
     if (rc) return rc;
@@ -436,11 +443,12 @@ int bcs_counts(const float *w, const void *y, int32_t y_kind, const int32_t *per
     return check_launch("bcs_counts");
 }
 
-size_t roc_auc_ws_bytes(int64_t n) { return auc_ws(nullptr, n < 0 ? 0 : n).total; }
+size_t gnntrk_roc_auc_workspace_bytes(int64_t n) { return auc_ws(nullptr, n < 0 ? 0 : n).total; }
 
-int roc_auc(const float *w, const void *y, int32_t y_kind, const int32_t *perm, const void *src, const void *tgt,
-            int32_t ids_i64, const float *pt, const float *cuts, int32_t n_cuts, const double *max_fprs, int32_t n_fpr,
-            int64_t n, int64_t *out, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+int gnntrk_roc_auc(const float *w, const void *y, int32_t y_kind, const int32_t *perm, const void *src, const void *tgt,
+                   int32_t ids_i64, const float *pt, const float *cuts, int32_t n_cuts, const double *max_fprs,
+                   int32_t n_fpr, int64_t n, int64_t *out, void *workspace, size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     Cuts c;
     int rc = check_common("roc_auc", w, y, y_kind, src, tgt, pt, cuts, n_cuts, n, c);
     if (rc) return rc;
@@ -481,4 +489,4 @@ int roc_auc(const float *w, const void *y, int32_t y_kind, const int32_t *perm, 
     return GNNTRK_OK;
 }
 
-}  // namespace gnntrk
+}  // extern "C"

@@ -726,7 +726,7 @@ __global__ __launch_bounds__(kBlock) void reduce_partials_kernel(const float *__
     }
 }
 
-// ------------------------------------------------------------------ launchers
+// ------------------------------------------------------------------ host side: the C entries launch
 // n_rows == 0 is a valid no-op: row pointers may then be NULL (what an empty tensor hands over)
 static int check_mlp(const gnntrk_mlp &m, int n_seg, const gnntrk_seg *seg, int64_t n_rows) {
     if (m.n_layers != 2 && m.n_layers != 3) return fail(GNNTRK_EUNSUPPORTED, "mlp: n_layers must be 2 or 3");
@@ -792,20 +792,149 @@ static bool static_shape(int ksi, int ksh, int kso, bool three, int n_items) {
         }                                                                       \
     }
 
-// Name of the instantiation the launchers below pick (as rocprofv3 prints it), so that
+// Fixed-order sum of n_part partial blocks (parameter layout of part_layout()) into the
+// gradient tensors; n_part = 0 writes zeros.  Shared with the bf16 kernels (mlp_bf16.hip).
+int reduce_partials_launch(const float *part, int n_part, const gnntrk_mlp *mlp, float *const gW[3],
+                           float *const gb[3], int accumulate, hipStream_t stream) {
+    const BwdPartLayout pl = part_layout(*mlp);
+    const int rgrid = (pl.total + 63) / 64;
+    auto rfn = reduce_partials_kernel;
+    hipLaunchKernelGGL(rfn, dim3(rgrid), dim3(kBlock), 0, stream, part, n_part, pl.total, *mlp, gW[0], gW[1],
+                       gW[2], gb[0], gb[1], gb[2], accumulate);
+    return check_launch("mlp_backward(reduce)");
+}
+
+}  // namespace gnntrk
+
+using namespace gnntrk;
+
+extern "C" {
+
+int gnntrk_mlp_forward(const gnntrk_mlp_fwd_args *args, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!args) return fail(GNNTRK_EINVAL, "mlp_forward: NULL args");
+    int rc = check_mlp(args->mlp, args->n_seg, args->seg, args->n_rows);
+    if (rc) return rc;
+    if (args->n_rows == 0) return GNNTRK_OK;  // nothing to write: NULL row pointers are fine
+    if (!args->out || args->out_stride < args->mlp.out_dim) return fail(GNNTRK_EINVAL, "mlp_forward: bad output");
+    if (args->epilogue < 0 || args->epilogue > 3) return fail(GNNTRK_EINVAL, "mlp_forward: bad epilogue");
+    if (args->epilogue == GNNTRK_EPI_RESIDUAL && (!args->res || args->res_stride < args->mlp.out_dim))
+        return fail(GNNTRK_EINVAL, "mlp_forward: residual epilogue needs res");
+    if (args->n_rows < 0) return fail(GNNTRK_EINVAL, "mlp_forward: negative n_rows");
+    if (args->n_rows == 0) return GNNTRK_OK;
+    const int n_items = count_items(args->n_seg, args->seg);
+    if (n_items > kMaxItems) return fail(GNNTRK_EUNSUPPORTED, "mlp_forward: too many input segments/chunks (max 16 4-feature chunks)");
+    int kt = (args->mlp.in_dim + 15) / 16;
+    const int ht = (args->mlp.hidden + 15) / 16;
+    while (4 * kt + 4 < n_items) ++kt;  // the load list of an instantiation holds 4*KT+4 items
+    // (the persistent grid of an instantiation = its resident workgroups, tile_mlp.h: the static shapes hold 124-156
+    //  registers = three, not four, workgroups per CU)
+    const int ksh = make_dimmap(args->mlp.hidden).ks, kso = make_dimmap(args->mlp.out_dim).ks;
+    const bool three = args->mlp.n_layers == 3;
+    // static instantiations need their own load-list capacity
+    const int ksi = (n_items <= 4 * ((args->mlp.in_dim + 15) / 16) + 4) ? make_dimmap(args->mlp.in_dim).ks : -1;
+#define CALL_FWD_S(KSI, KSH, KSO, THREE, NIT)                                                                     \
+    if (!done_ && ksi == KSI && ksh == KSH && kso == KSO && three == THREE && n_items <= NIT) {                   \
+        constexpr auto kfn = mlp_fwd_kernel<(KSI + 3) / 4, (KSH + 3) / 4, StaticDims<KSI, KSH, KSO, THREE, NIT>>; \
+        launch(kfn, tile_grid(args->n_rows, resident_blocks<kfn>(kFwdBlocksPerCu)), kBlock, stream, *args);       \
+        done_ = true;                                                                                             \
+    }
+#define CALL_FWD_D(K, H)                                                                                    \
+    {                                                                                                       \
+        constexpr auto kfn = mlp_fwd_kernel<K, H, DynDims>;                                                 \
+        launch(kfn, tile_grid(args->n_rows, resident_blocks<kfn>(kFwdBlocksPerCu)), kBlock, stream, *args); \
+    }
+    GNNTRK_DISPATCH(CALL_FWD_S, CALL_FWD_D)
+#undef CALL_FWD_S
+#undef CALL_FWD_D
+    return check_launch("mlp_forward");
+}
+
+size_t gnntrk_mlp_backward_workspace_bytes(const gnntrk_mlp *mlp) {
+    if (!mlp) return 0;
+    const BwdPartLayout pl = part_layout(*mlp);
+    return (size_t)cu_count() * kBwdWavesPerCu * (size_t)pl.total * sizeof(float);
+}
+
+int gnntrk_mlp_backward(const gnntrk_mlp_bwd_args *args, void *workspace, size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!args) return fail(GNNTRK_EINVAL, "mlp_backward: NULL args");
+    int rc = check_mlp(args->mlp, args->n_seg, args->seg, args->n_rows);
+    if (rc) return rc;
+    const bool empty = args->n_rows == 0;  // no rows: only the parameter gradients are written (zeros)
+    if (args->n_gout < 1 || args->n_gout > 2 ||
+        (!empty && (!args->gout[0].ptr || (args->n_gout == 2 && !args->gout[1].ptr))))
+        return fail(GNNTRK_EINVAL, "mlp_backward: bad upstream gradient terms");
+    if (args->epilogue < 0 || args->epilogue > 3) return fail(GNNTRK_EINVAL, "mlp_backward: bad epilogue");
+    if (args->n_rows < 0) return fail(GNNTRK_EINVAL, "mlp_backward: negative n_rows");
+    for (int j = 0; j < args->n_seg; ++j)
+        if (args->gseg[j].ptr && (args->gseg[j].idx || args->gseg[j].accumulate))
+            return fail(GNNTRK_EUNSUPPORTED,
+                        "mlp_backward: gseg.idx / gseg.accumulate are reserved (row-aligned '=' only)");
+    const bool want_dw = args->gW[0] != nullptr;
+    if (want_dw) {
+        for (int i = 0; i < args->mlp.n_layers; ++i)
+            if (!args->gW[i]) return fail(GNNTRK_EINVAL, "mlp_backward: gW must be all set or all NULL");
+        if (!workspace || workspace_bytes < gnntrk_mlp_backward_workspace_bytes(&args->mlp))
+            return fail(GNNTRK_EINVAL, "mlp_backward: workspace too small");
+    }
+    const BwdPartLayout pl = part_layout(args->mlp);
+    int grid = 0, wpb = 4;
+    const int n_items = count_items(args->n_seg, args->seg);
+    if (n_items > kMaxItems) return fail(GNNTRK_EUNSUPPORTED, "mlp_backward: too many input segments/chunks (max 16 4-feature chunks)");
+    const bool items_fit = n_items <= 4 * ((args->mlp.in_dim + 15) / 16) + 4;
+    // the static kernels also rely on the constant-one rows for the bias gradients
+    const bool ones_ok = (args->mlp.in_dim % 16) != 0 && (args->mlp.hidden % 16) != 0;
+    const int ksi0 = (items_fit && ones_ok) ? make_dimmap(args->mlp.in_dim).ks : -1,
+              ksh0 = make_dimmap(args->mlp.hidden).ks, kso0 = make_dimmap(args->mlp.out_dim).ks;
+    if (args->n_rows > 0) {
+        int kt = (args->mlp.in_dim + 15) / 16;
+        const int ht = (args->mlp.hidden + 15) / 16;
+        while (4 * kt + 4 < n_items) ++kt;
+        const bool is_static = static_shape(ksi0, ksh0, kso0, args->mlp.n_layers == 3, n_items);
+        wpb = is_static ? 8 : 4;
+        grid = tile_grid(args->n_rows, is_static ? 1 : 2, wpb);
+        float *part = reinterpret_cast<float *>(workspace);
+        const int ksi = ksi0, ksh = ksh0, kso = kso0;
+        const bool three = args->mlp.n_layers == 3;
+#define CALL_BWD_S(KSI, KSH, KSO, THREE, NIT)                                                              \
+    if (!done_ && ksi == KSI && ksh == KSH && kso == KSO && three == THREE && n_items <= NIT) {            \
+        auto kfn = mlp_bwd_kernel<(KSI + 3) / 4, (KSH + 3) / 4, StaticDims<KSI, KSH, KSO, THREE, NIT>, 8>; \
+        hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), 0, stream, *args, part);                            \
+        done_ = true;                                                                                      \
+    }
+#define CALL_BWD_D(K, H)                                                        \
+    {                                                                           \
+        auto kfn = mlp_bwd_kernel<K, H, DynDims, 4>;                            \
+        hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), 0, stream, *args, part); \
+    }
+        GNNTRK_DISPATCH(CALL_BWD_S, CALL_BWD_D)
+#undef CALL_BWD_S
+#undef CALL_BWD_D
+        rc = check_launch("mlp_backward");
+        if (rc) return rc;
+    }
+    if (want_dw && !(args->debug_flags & 32))
+        rc = reduce_partials_launch(reinterpret_cast<const float *>(workspace), grid * wpb, &args->mlp, args->gW,
+                                    args->gb, args->accumulate_params, stream);
+    return rc;
+}
+
+// Name of the instantiation the launchers pick (as rocprofv3 prints it), so that
 // host-side timers and profiles can be matched kernel by kernel.
-int mlp_kernel_name(const gnntrk_mlp *m, int n_seg, const gnntrk_seg *seg, int backward,
-                    char *buf, size_t len) {
-    if (!m || !seg || !buf || len == 0) return fail(GNNTRK_EINVAL, "mlp_kernel_name: bad argument");
+int gnntrk_mlp_kernel_name(const gnntrk_mlp *mlp, int32_t n_seg, const gnntrk_seg *seg, int32_t backward, char *buf,
+                           size_t len) {
+    if (backward & 2) return mlp16_kernel_name(mlp, n_seg, seg, backward & 1, buf, len);   // bf16: mlp_bf16.hip
+    if (!mlp || !seg || !buf || len == 0) return fail(GNNTRK_EINVAL, "mlp_kernel_name: bad argument");
     const int n_items = count_items(n_seg, seg);
-    int kt = (m->in_dim + 15) / 16;
-    const int ht = (m->hidden + 15) / 16;
+    int kt = (mlp->in_dim + 15) / 16;
+    const int ht = (mlp->hidden + 15) / 16;
     const bool items_fit = n_items <= 4 * kt + 4;
     while (4 * kt + 4 < n_items) ++kt;
-    const bool ones_ok = (m->in_dim % 16) != 0 && (m->hidden % 16) != 0;
-    const int ksi = (items_fit && (!backward || ones_ok)) ? make_dimmap(m->in_dim).ks : -1;
-    const int ksh = make_dimmap(m->hidden).ks, kso = make_dimmap(m->out_dim).ks;
-    const bool three = m->n_layers == 3;
+    const bool ones_ok = (mlp->in_dim % 16) != 0 && (mlp->hidden % 16) != 0;
+    const int ksi = (items_fit && (!backward || ones_ok)) ? make_dimmap(mlp->in_dim).ks : -1;
+    const int ksh = make_dimmap(mlp->hidden).ks, kso = make_dimmap(mlp->out_dim).ks;
+    const bool three = mlp->n_layers == 3;
     const char *dir = backward ? "bwd" : "fwd";
 #define NAME_S(KSI, KSH, KSO, THREE, NIT)                                                       \
     if (!done_ && ksi == KSI && ksh == KSH && kso == KSO && three == THREE && n_items <= NIT) { \
@@ -822,124 +951,4 @@ int mlp_kernel_name(const gnntrk_mlp *m, int n_seg, const gnntrk_seg *seg, int b
     return GNNTRK_OK;
 }
 
-int mlp_forward_launch(const gnntrk_mlp_fwd_args *a, hipStream_t stream) {
-    if (!a) return fail(GNNTRK_EINVAL, "mlp_forward: NULL args");
-    int rc = check_mlp(a->mlp, a->n_seg, a->seg, a->n_rows);
-    if (rc) return rc;
-    if (a->n_rows == 0) return GNNTRK_OK;  // nothing to write: NULL row pointers are fine
-    if (!a->out || a->out_stride < a->mlp.out_dim) return fail(GNNTRK_EINVAL, "mlp_forward: bad output");
-    if (a->epilogue < 0 || a->epilogue > 3) return fail(GNNTRK_EINVAL, "mlp_forward: bad epilogue");
-    if (a->epilogue == GNNTRK_EPI_RESIDUAL && (!a->res || a->res_stride < a->mlp.out_dim))
-        return fail(GNNTRK_EINVAL, "mlp_forward: residual epilogue needs res");
-    if (a->n_rows < 0) return fail(GNNTRK_EINVAL, "mlp_forward: negative n_rows");
-    if (a->n_rows == 0) return GNNTRK_OK;
-    const int n_items = count_items(a->n_seg, a->seg);
-    if (n_items > kMaxItems) return fail(GNNTRK_EUNSUPPORTED, "mlp_forward: too many input segments/chunks (max 16 4-feature chunks)");
-    int kt = (a->mlp.in_dim + 15) / 16;
-    const int ht = (a->mlp.hidden + 15) / 16;
-    while (4 * kt + 4 < n_items) ++kt;  // the load list of an instantiation holds 4*KT+4 items
-    // (the persistent grid of an instantiation = its resident workgroups, tile_mlp.h: the static shapes hold 124-156
-    //  registers = three, not four, workgroups per CU)
-    const int ksh = make_dimmap(a->mlp.hidden).ks, kso = make_dimmap(a->mlp.out_dim).ks;
-    const bool three = a->mlp.n_layers == 3;
-    // static instantiations need their own load-list capacity
-    const int ksi = (n_items <= 4 * ((a->mlp.in_dim + 15) / 16) + 4) ? make_dimmap(a->mlp.in_dim).ks : -1;
-#define CALL_FWD_S(KSI, KSH, KSO, THREE, NIT)                                                  \
-    if (!done_ && ksi == KSI && ksh == KSH && kso == KSO && three == THREE && n_items <= NIT) { \
-        constexpr auto kfn = mlp_fwd_kernel<(KSI + 3) / 4, (KSH + 3) / 4, StaticDims<KSI, KSH, KSO, THREE, NIT>>; \
-        launch(kfn, tile_grid(a->n_rows, resident_blocks<kfn>(kFwdBlocksPerCu)), kBlock, stream, *a); \
-        done_ = true;                                                                           \
-    }
-#define CALL_FWD_D(K, H)                                                                \
-    {                                                                                   \
-        constexpr auto kfn = mlp_fwd_kernel<K, H, DynDims>;                             \
-        launch(kfn, tile_grid(a->n_rows, resident_blocks<kfn>(kFwdBlocksPerCu)), kBlock, stream, *a); \
-    }
-    GNNTRK_DISPATCH(CALL_FWD_S, CALL_FWD_D)
-#undef CALL_FWD_S
-#undef CALL_FWD_D
-    return check_launch("mlp_forward");
-}
-
-size_t mlp_backward_ws_bytes(const gnntrk_mlp *m) {
-    if (!m) return 0;
-    const BwdPartLayout pl = part_layout(*m);
-    return (size_t)cu_count() * kBwdWavesPerCu * (size_t)pl.total * sizeof(float);
-}
-
-int mlp_backward_launch(const gnntrk_mlp_bwd_args *a, void *ws, size_t ws_bytes,
-                        hipStream_t stream) {
-    if (!a) return fail(GNNTRK_EINVAL, "mlp_backward: NULL args");
-    int rc = check_mlp(a->mlp, a->n_seg, a->seg, a->n_rows);
-    if (rc) return rc;
-    const bool empty = a->n_rows == 0;  // no rows: only the parameter gradients are written (zeros)
-    if (a->n_gout < 1 || a->n_gout > 2 || (!empty && (!a->gout[0].ptr || (a->n_gout == 2 && !a->gout[1].ptr))))
-        return fail(GNNTRK_EINVAL, "mlp_backward: bad upstream gradient terms");
-    if (a->epilogue < 0 || a->epilogue > 3) return fail(GNNTRK_EINVAL, "mlp_backward: bad epilogue");
-    if (a->n_rows < 0) return fail(GNNTRK_EINVAL, "mlp_backward: negative n_rows");
-    for (int j = 0; j < a->n_seg; ++j)
-        if (a->gseg[j].ptr && (a->gseg[j].idx || a->gseg[j].accumulate))
-            return fail(GNNTRK_EUNSUPPORTED,
-                        "mlp_backward: gseg.idx / gseg.accumulate are reserved (row-aligned '=' only)");
-    const bool want_dw = a->gW[0] != nullptr;
-    if (want_dw) {
-        for (int i = 0; i < a->mlp.n_layers; ++i)
-            if (!a->gW[i]) return fail(GNNTRK_EINVAL, "mlp_backward: gW must be all set or all NULL");
-        if (!ws || ws_bytes < mlp_backward_ws_bytes(&a->mlp))
-            return fail(GNNTRK_EINVAL, "mlp_backward: workspace too small");
-    }
-    const BwdPartLayout pl = part_layout(a->mlp);
-    int grid = 0, wpb = 4;
-    const int n_items = count_items(a->n_seg, a->seg);
-    if (n_items > kMaxItems) return fail(GNNTRK_EUNSUPPORTED, "mlp_backward: too many input segments/chunks (max 16 4-feature chunks)");
-    const bool items_fit = n_items <= 4 * ((a->mlp.in_dim + 15) / 16) + 4;
-    // the static kernels also rely on the constant-one rows for the bias gradients
-    const bool ones_ok = (a->mlp.in_dim % 16) != 0 && (a->mlp.hidden % 16) != 0;
-    const int ksi0 = (items_fit && ones_ok) ? make_dimmap(a->mlp.in_dim).ks : -1,
-              ksh0 = make_dimmap(a->mlp.hidden).ks, kso0 = make_dimmap(a->mlp.out_dim).ks;
-    if (a->n_rows > 0) {
-        int kt = (a->mlp.in_dim + 15) / 16;
-        const int ht = (a->mlp.hidden + 15) / 16;
-        while (4 * kt + 4 < n_items) ++kt;
-        const bool is_static = static_shape(ksi0, ksh0, kso0, a->mlp.n_layers == 3, n_items);
-        wpb = is_static ? 8 : 4;
-        grid = tile_grid(a->n_rows, is_static ? 1 : 2, wpb);
-        float *part = reinterpret_cast<float *>(ws);
-        const int ksi = ksi0, ksh = ksh0, kso = kso0;
-        const bool three = a->mlp.n_layers == 3;
-#define CALL_BWD_S(KSI, KSH, KSO, THREE, NIT)                                                  \
-    if (!done_ && ksi == KSI && ksh == KSH && kso == KSO && three == THREE && n_items <= NIT) { \
-        auto kfn = mlp_bwd_kernel<(KSI + 3) / 4, (KSH + 3) / 4, StaticDims<KSI, KSH, KSO, THREE, NIT>, 8>; \
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), 0, stream, *a, part);                    \
-        done_ = true;                                                                           \
-    }
-#define CALL_BWD_D(K, H)                                                                \
-    {                                                                                   \
-        auto kfn = mlp_bwd_kernel<K, H, DynDims, 4>;                                    \
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), 0, stream, *a, part);            \
-    }
-        GNNTRK_DISPATCH(CALL_BWD_S, CALL_BWD_D)
-#undef CALL_BWD_S
-#undef CALL_BWD_D
-        rc = check_launch("mlp_backward");
-        if (rc) return rc;
-    }
-    if (want_dw && !(a->debug_flags & 32))
-        rc = reduce_partials_launch(reinterpret_cast<const float *>(ws), grid * wpb, &a->mlp, a->gW, a->gb,
-                                    a->accumulate_params, stream);
-    return rc;
-}
-
-// Fixed-order sum of n_part partial blocks (parameter layout of part_layout()) into the
-// gradient tensors; n_part = 0 writes zeros.  Shared with the bf16 kernels (mlp_bf16.hip).
-int reduce_partials_launch(const float *part, int n_part, const gnntrk_mlp *mlp, float *const gW[3],
-                           float *const gb[3], int accumulate, hipStream_t stream) {
-    const BwdPartLayout pl = part_layout(*mlp);
-    const int rgrid = (pl.total + 63) / 64;
-    auto rfn = reduce_partials_kernel;
-    hipLaunchKernelGGL(rfn, dim3(rgrid), dim3(kBlock), 0, stream, part, n_part, pl.total, *mlp, gW[0], gW[1],
-                       gW[2], gb[0], gb[1], gb[2], accumulate);
-    return check_launch("mlp_backward(reduce)");
-}
-
-}  // namespace gnntrk
+}  // extern "C"

@@ -1,4 +1,4 @@
-// Backward launchers of the bf16-storage fused MLP kernels (mlp_bf16_kernels.h).  The
+// Backward launchers and C entries of the bf16-storage fused MLP kernels (mlp_bf16_kernels.h).  The
 // instantiations with an fp32 upstream gradient (EPI_SIGMOID: the edge-weight head) are
 // compiled in mlp_bf16_g32.hip, the forward kernels in mlp_bf16_fwd.hip (own scheduling
 // strategy, see _build.py), so the three parts also build in parallel.
@@ -8,7 +8,6 @@ namespace gnntrk {
 
 int launch_bwd16_g32(const gnntrk_mlp_bwd_args *a, const SlotPlan &P, float *part, uint8_t *trash, hipStream_t stream,
                      const gnntrk_head_bce *bce, int *grid_out);  // mlp_bf16_g32.hip
-
 
 int mlp16_kernel_name(const gnntrk_mlp *m, int n_seg, const gnntrk_seg *seg, int backward, char *buf,
                       size_t len) {
@@ -22,65 +21,10 @@ int mlp16_kernel_name(const gnntrk_mlp *m, int n_seg, const gnntrk_seg *seg, int
     return GNNTRK_OK;
 }
 
-// exact backward instantiation (needs the gradient slices and the epilogue): the selection of the launcher, printed
-int mlp16_bwd_kernel_name(const gnntrk_mlp_bwd_args *a, char *buf, size_t len) {
-    if (!a || !buf || len == 0) return fail(GNNTRK_EINVAL, "mlp_kernel_name: bad argument");
-    SlotPlan P;
-    make_slot_plan(P, a->mlp, a->n_seg, a->seg, a->gseg);
-    BufPlan B;
-    const Bwd16Sel S = bwd16_select(a, P, B);
-    const char *three = S.three ? "true" : "false", *g32 = S.g32 ? "true" : "false";
-    if (S.kind == Bwd16Sel::kOt)
-        snprintf(buf, len, "mlp16_bwd_ot_kernel<%d, %d, %d, %s>", S.KI, S.HT, S.OT, three);
-    else if (S.kind == Bwd16Sel::kBi8 || S.kind == Bwd16Sel::kBi)
-        snprintf(buf, len, "mlp16_bwd_bi_kernel<%d, %d, %d, %s, %s>", S.KI, S.HT, S.GT, three, g32);
-    else   // (as rocprofv3 prints the instantiation: a template argument that itself ends in '>' is followed by a space)
-        snprintf(buf, len, "mlp16_bwd_kernel<%d, %d, %d, %s, %s, %d, %s%s>", S.KI, S.HT, S.GT, three, g32, S.D, S.io_name,
-                 S.io_name[strlen(S.io_name) - 1] == '>' ? " " : "");
-    return GNNTRK_OK;
-}
-
-// the number of upstream terms (2 or 3) the launch described by `a` can take: 3 where it runs
-// buffer-addressed with a further term on the tile's rows
-int mlp_backward_bf16_max_terms(const gnntrk_mlp_bwd_args *a) {
-    if (!a || a->epilogue == GNNTRK_EPI_SIGMOID || a->n_rows <= 0 || a->n_gout < 1 || a->n_gout > 3) return 2;
-    SlotPlan P;
-    make_slot_plan(P, a->mlp, a->n_seg, a->seg, a->gseg);
-    if (!P.ok || P.KI != 1) return 2;
-    gnntrk_mlp_bwd_args b = *a;
-    while (b.n_gout < 3) {   // probe with stand-in terms: rows of the tile, sized like the first term
-        b.gout[b.n_gout] = b.gout[0];
-        b.gout[b.n_gout].idx = nullptr;
-        b.gout[b.n_gout].rows = (int32_t)(a->n_rows < 0x7fffffff ? a->n_rows : 0x7fffffff);
-        b.n_gout += 1;
-    }
-    BufPlan B;
-    const Bwd16Sel S = bwd16_select(&b, P, B);
-    return (S.kind == Bwd16Sel::kBuf && S.terms == 3) ? 3 : 2;
-}
-
-// 1 if the launch described by `a` (fold block filled in) runs on an instantiation that folds inside the kernel
-int mlp_backward_bf16_can_fold(const gnntrk_mlp_bwd_args *a) {
-    if (!a || !a->fold.ids || a->fold.seg < 0 || a->fold.seg >= a->n_seg || a->n_rows <= 0 || a->n_rows > 0x7fffffff ||
-        a->n_gout < 1 || a->n_gout > 3)
-        return 0;
-    SlotPlan P;
-    make_slot_plan(P, a->mlp, a->n_seg, a->seg, a->gseg);
-    if (!P.ok) return 0;
-    BufPlan B;
-    const Bwd16Sel S = bwd16_select(a, P, B);
-    return (S.kind == Bwd16Sel::kBuf && S.fold) ? 1 : 0;
-}
-
 // workspace = one partial block per wave | one 8-byte trash slot per lane
 static size_t bwd16_partial_bytes(const gnntrk_mlp *m) {
     return align_up((size_t)cu_count() * kBwd16BlocksPerCuMax * kWaves * (size_t)part_total(*m) * sizeof(float), 256);
 }
-size_t mlp_backward_bf16_ws_bytes(const gnntrk_mlp *m) {
-    if (!m) return 0;
-    return bwd16_partial_bytes(m) + (size_t)cu_count() * kBwd16BlocksPerCuMax * kWaves * 64 * 8;
-}
-
 // the launch of gnntrk_mlp_backward_bf16_bce as the shared launcher takes it: the upstream term is a stand-in that
 // describes w_out (fp32 [n_rows]) - the buffer plan is the fp32-upstream head's, and the kernel stores W through
 // the term's descriptor
@@ -97,40 +41,7 @@ static bool bce_args(const gnntrk_mlp_bwd_args *a, const gnntrk_head_bce *bce, g
     return true;
 }
 
-int mlp_backward_bf16_bce_supported(const gnntrk_mlp_bwd_args *a, const gnntrk_head_bce *bce) {
-    gnntrk_mlp_bwd_args b;
-    if (!bce_args(a, bce, b) || b.n_seg < 1 || b.n_seg > GNNTRK_MAX_SEGS) return 0;
-    SlotPlan P;
-    make_slot_plan(P, b.mlp, b.n_seg, b.seg, b.gseg);
-    if (!P.ok) return 0;
-    BufPlan B;
-    return bwd16_select(&b, P, B).bce ? 1 : 0;
-}
-
-int mlp16_bwd_bce_kernel_name(const gnntrk_mlp_bwd_args *a, const gnntrk_head_bce *bce, char *buf, size_t len) {
-    if (!buf || len == 0) return fail(GNNTRK_EINVAL, "mlp_kernel_name: bad argument");
-    if (!mlp_backward_bf16_bce_supported(a, bce))
-        return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16_bce: not the buffer-addressed head shape");
-    SlotPlan P;
-    make_slot_plan(P, a->mlp, a->n_seg, a->seg, a->gseg);
-    snprintf(buf, len, "mlp16_bwd_bce_kernel<%d>", P.HT);
-    return GNNTRK_OK;
-}
-
-static int bwd16_launch(const gnntrk_mlp_bwd_args *a, void *ws, size_t ws_bytes, hipStream_t stream,
-                        const gnntrk_head_bce *bce);
-int mlp_backward_bf16_launch(const gnntrk_mlp_bwd_args *a, void *ws, size_t ws_bytes, hipStream_t stream) {
-    return bwd16_launch(a, ws, ws_bytes, stream, nullptr);
-}
-int mlp_backward_bf16_bce_launch(const gnntrk_mlp_bwd_args *a, const gnntrk_head_bce *bce, void *ws, size_t ws_bytes,
-                                 hipStream_t stream) {
-    gnntrk_mlp_bwd_args b;
-    if (!bce_args(a, bce, b)) return fail(GNNTRK_EINVAL, "mlp_backward_bf16_bce: bad argument");
-    if (b.epilogue != GNNTRK_EPI_SIGMOID || b.fold.ids)
-        return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16_bce: the SIGMOID epilogue, no fold");
-    return bwd16_launch(&b, ws, ws_bytes, stream, bce);
-}
-
+// what gnntrk_mlp_backward_bf16 (bce == NULL) and gnntrk_mlp_backward_bf16_bce share
 static int bwd16_launch(const gnntrk_mlp_bwd_args *a, void *ws, size_t ws_bytes, hipStream_t stream,
                         const gnntrk_head_bce *bce) {
     if (!a) return fail(GNNTRK_EINVAL, "mlp_backward_bf16: NULL args");
@@ -165,17 +76,17 @@ static int bwd16_launch(const gnntrk_mlp_bwd_args *a, void *ws, size_t ws_bytes,
             f.n_nodes <= 0 || a->gseg[f.seg].stride != 8 || ((uintptr_t)a->gseg[f.seg].ptr & 15) != 0 ||
             false)
             return fail(GNNTRK_EINVAL, "mlp_backward_bf16: bad fold block (include/gnntrk.h: gnntrk_gfold)");
-        if (!mlp_backward_bf16_can_fold(a))
+        if (!gnntrk_mlp_backward_bf16_can_fold(a))
             return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16: this launch does not take a fold (gnntrk_mlp_backward_bf16_can_fold)");
     }
-    if (a->n_gout == 3 && a->n_rows > 0 && mlp_backward_bf16_max_terms(a) < 3)
+    if (a->n_gout == 3 && a->n_rows > 0 && gnntrk_mlp_backward_bf16_max_terms(a) < 3)
         return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16: three upstream terms only on the buffer-addressed shapes "
                                          "(gnntrk_mlp_backward_bf16_max_terms)");
     const bool want_dw = a->gW[0] != nullptr;
     if (want_dw)
         for (int i = 0; i < a->mlp.n_layers; ++i)
             if (!a->gW[i]) return fail(GNNTRK_EINVAL, "mlp_backward_bf16: gW must be all set or all NULL");
-    if (!ws || ws_bytes < mlp_backward_bf16_ws_bytes(&a->mlp))
+    if (!ws || ws_bytes < gnntrk_mlp_backward_bf16_workspace_bytes(&a->mlp))
         return fail(GNNTRK_EINVAL, "mlp_backward_bf16: workspace too small (always required)");
     SlotPlan P;
     make_slot_plan(P, a->mlp, a->n_seg, a->seg, a->gseg);
@@ -200,3 +111,100 @@ static int bwd16_launch(const gnntrk_mlp_bwd_args *a, void *ws, size_t ws_bytes,
 }
 
 }  // namespace gnntrk
+
+using namespace gnntrk;
+
+extern "C" {
+
+// exact backward instantiation (needs the gradient slices and the epilogue): the selection of the launcher, printed
+int gnntrk_mlp_backward_bf16_kernel_name(const gnntrk_mlp_bwd_args *args, char *buf, size_t len) {
+    if (!args || !buf || len == 0) return fail(GNNTRK_EINVAL, "mlp_kernel_name: bad argument");
+    SlotPlan P;
+    make_slot_plan(P, args->mlp, args->n_seg, args->seg, args->gseg);
+    BufPlan B;
+    const Bwd16Sel S = bwd16_select(args, P, B);
+    const char *three = S.three ? "true" : "false", *g32 = S.g32 ? "true" : "false";
+    if (S.kind == Bwd16Sel::kOt)
+        snprintf(buf, len, "mlp16_bwd_ot_kernel<%d, %d, %d, %s>", S.KI, S.HT, S.OT, three);
+    else if (S.kind == Bwd16Sel::kBi8 || S.kind == Bwd16Sel::kBi)
+        snprintf(buf, len, "mlp16_bwd_bi_kernel<%d, %d, %d, %s, %s>", S.KI, S.HT, S.GT, three, g32);
+    else   // (as rocprofv3 prints the instantiation: a template argument that itself ends in '>' is followed by a space)
+        snprintf(buf, len, "mlp16_bwd_kernel<%d, %d, %d, %s, %s, %d, %s%s>", S.KI, S.HT, S.GT, three, g32, S.D, S.io_name,
+                 S.io_name[strlen(S.io_name) - 1] == '>' ? " " : "");
+    return GNNTRK_OK;
+}
+
+// the number of upstream terms (2 or 3) the launch described by `args` can take: 3 where it runs
+// buffer-addressed with a further term on the tile's rows
+int gnntrk_mlp_backward_bf16_max_terms(const gnntrk_mlp_bwd_args *args) {
+    if (!args || args->epilogue == GNNTRK_EPI_SIGMOID || args->n_rows <= 0 || args->n_gout < 1 || args->n_gout > 3)
+        return 2;
+    SlotPlan P;
+    make_slot_plan(P, args->mlp, args->n_seg, args->seg, args->gseg);
+    if (!P.ok || P.KI != 1) return 2;
+    gnntrk_mlp_bwd_args b = *args;
+    while (b.n_gout < 3) {   // probe with stand-in terms: rows of the tile, sized like the first term
+        b.gout[b.n_gout] = b.gout[0];
+        b.gout[b.n_gout].idx = nullptr;
+        b.gout[b.n_gout].rows = (int32_t)(args->n_rows < 0x7fffffff ? args->n_rows : 0x7fffffff);
+        b.n_gout += 1;
+    }
+    BufPlan B;
+    const Bwd16Sel S = bwd16_select(&b, P, B);
+    return (S.kind == Bwd16Sel::kBuf && S.terms == 3) ? 3 : 2;
+}
+
+// 1 if the launch described by `args` (fold block filled in) runs on an instantiation that folds inside the kernel
+int gnntrk_mlp_backward_bf16_can_fold(const gnntrk_mlp_bwd_args *args) {
+    if (!args || !args->fold.ids || args->fold.seg < 0 || args->fold.seg >= args->n_seg || args->n_rows <= 0 ||
+        args->n_rows > 0x7fffffff || args->n_gout < 1 || args->n_gout > 3)
+        return 0;
+    SlotPlan P;
+    make_slot_plan(P, args->mlp, args->n_seg, args->seg, args->gseg);
+    if (!P.ok) return 0;
+    BufPlan B;
+    const Bwd16Sel S = bwd16_select(args, P, B);
+    return (S.kind == Bwd16Sel::kBuf && S.fold) ? 1 : 0;
+}
+
+size_t gnntrk_mlp_backward_bf16_workspace_bytes(const gnntrk_mlp *mlp) {
+    if (!mlp) return 0;
+    return bwd16_partial_bytes(mlp) + (size_t)cu_count() * kBwd16BlocksPerCuMax * kWaves * 64 * 8;
+}
+
+int gnntrk_mlp_backward_bf16_bce_supported(const gnntrk_mlp_bwd_args *args, const gnntrk_head_bce *bce) {
+    gnntrk_mlp_bwd_args b;
+    if (!bce_args(args, bce, b) || b.n_seg < 1 || b.n_seg > GNNTRK_MAX_SEGS) return 0;
+    SlotPlan P;
+    make_slot_plan(P, b.mlp, b.n_seg, b.seg, b.gseg);
+    if (!P.ok) return 0;
+    BufPlan B;
+    return bwd16_select(&b, P, B).bce ? 1 : 0;
+}
+
+int gnntrk_mlp_backward_bf16_bce_kernel_name(const gnntrk_mlp_bwd_args *args, const gnntrk_head_bce *bce, char *buf,
+                                             size_t len) {
+    if (!buf || len == 0) return fail(GNNTRK_EINVAL, "mlp_kernel_name: bad argument");
+    if (!gnntrk_mlp_backward_bf16_bce_supported(args, bce))
+        return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16_bce: not the buffer-addressed head shape");
+    SlotPlan P;
+    make_slot_plan(P, args->mlp, args->n_seg, args->seg, args->gseg);
+    snprintf(buf, len, "mlp16_bwd_bce_kernel<%d>", P.HT);
+    return GNNTRK_OK;
+}
+
+int gnntrk_mlp_backward_bf16(const gnntrk_mlp_bwd_args *args, void *workspace, size_t workspace_bytes, void *stream) {
+    return bwd16_launch(args, workspace, workspace_bytes, (hipStream_t)stream, nullptr);
+}
+
+int gnntrk_mlp_backward_bf16_bce(const gnntrk_mlp_bwd_args *args, const gnntrk_head_bce *bce, void *workspace,
+                                 size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    gnntrk_mlp_bwd_args b;
+    if (!bce_args(args, bce, b)) return fail(GNNTRK_EINVAL, "mlp_backward_bf16_bce: bad argument");
+    if (b.epilogue != GNNTRK_EPI_SIGMOID || b.fold.ids)
+        return fail(GNNTRK_EUNSUPPORTED, "mlp_backward_bf16_bce: the SIGMOID epilogue, no fold");
+    return bwd16_launch(&b, workspace, workspace_bytes, stream, bce);
+}
+
+}  // extern "C"

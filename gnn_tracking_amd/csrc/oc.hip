@@ -966,18 +966,7 @@ __global__ __launch_bounds__(kOcTpb) void oc_cps_spatial_kernel(const OcParams p
     }
 }
 
-// ---- launchers -----------------------------------------------------------------------
-int good_node_mask_launch(const float *pt, const int64_t *pid, const float *reco, const float *eta,
-                          int64_t n, float pt_thld, float max_eta, uint8_t *mask,
-                          hipStream_t stream) {
-    if (n < 0) return fail(GNNTRK_EINVAL, "good_node_mask: bad argument");
-    if (n == 0) return GNNTRK_OK;
-    if (!pt || !pid || !reco || !eta || !mask) return fail(GNNTRK_EINVAL, "good_node_mask: NULL pointer");
-    hipLaunchKernelGGL(good_node_mask_kernel, dim3(oc_grid(n)), dim3(kOcTpb), 0, stream, pt, pid, reco,
-                       eta, n, pt_thld, max_eta, mask);
-    return check_launch("good_node_mask");
-}
-
+// ---- host side: workspaces, checks; the C entries launch -----------------------------------
 struct SelectWs {
     u64 *keys_a, *keys_b;
     uint32_t *vals_a, *vals_b;
@@ -1002,31 +991,6 @@ static SelectWs select_ws(void *base, int64_t n) {
     w.total = ws.off;
     return w;
 }
-size_t oc_select_ws_bytes(int64_t n) { return select_ws(nullptr, n).total; }
-
-int oc_select_launch(const float *score, const int64_t *pid, const uint8_t *mask, int64_t n, int mode,
-                     int32_t *alphas, int32_t *gid, int32_t *n_cp, void *ws, size_t ws_bytes,
-                     hipStream_t stream) {
-    if (!score || !pid || !mask || !alphas || !gid || !n_cp || n < 1 || (mode != 0 && mode != 1))
-        return fail(GNNTRK_EINVAL, "oc_select_cps: bad argument");
-    if (n > 0x7fffffff) return fail(GNNTRK_EUNSUPPORTED, "oc_select_cps: n must fit int32");
-    const SelectWs w = select_ws(ws, n);
-    if (!ws || ws_bytes < w.total) return fail(GNNTRK_EINVAL, "oc_select_cps: workspace too small");
-    const int grid = oc_grid(n);
-    hipLaunchKernelGGL(oc_keys_kernel, dim3(grid), dim3(kOcTpb), 0, stream, pid, n, w.keys_a, w.vals_a);
-    int rc = sort_pairs_u64(w.keys_a, w.keys_b, w.vals_a, w.vals_b, n, w.temp, w.temp_bytes, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(oc_segment_best_kernel, dim3(grid), dim3(kOcTpb), 0, stream,
-                       (const u64 *)w.keys_b, (const uint32_t *)w.vals_b, score, mask, n, mode, w.flag, w.best);
-    scan_counts_launch(w.flag, 0x7fffffff, n, w.off, stream);
-    rc = check_hip(hipMemsetAsync(gid, 0xff, (size_t)n * sizeof(int32_t), stream), "oc_select_cps(memset)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(oc_assign_kernel, dim3(grid), dim3(kOcTpb), 0, stream, (const u64 *)w.keys_b,
-                       (const uint32_t *)w.vals_b, (const int32_t *)w.flag, (const int32_t *)w.best,
-                       (const int64_t *)w.off, n, alphas, gid, n_cp);
-    return check_launch("oc_select_cps");
-}
-
 static int oc_check(const gnntrk_oc_args *a) {
     if (!a || !a->x || !a->beta || !a->particle_id || !a->mask || !a->gid || !a->alphas || !a->n_cp)
         return fail(GNNTRK_EINVAL, "oc_potential: NULL pointer");
@@ -1045,60 +1009,6 @@ static OcParams oc_params(const gnntrk_oc_args *a) {
     p.seed = a->rep_seed;
     p.cap_nbr = a->cap_nbr;
     return p;
-}
-
-size_t oc_forward_ws_bytes(int64_t n) { return (size_t)oc_grid(n) * 4 * sizeof(double); }
-
-int oc_forward_launch(const gnntrk_oc_args *a, float *out, void *ws, size_t ws_bytes, hipStream_t stream) {
-    int rc = oc_check(a);
-    if (rc) return rc;
-    if (!out || !ws || ws_bytes < oc_forward_ws_bytes(a->n)) return fail(GNNTRK_EINVAL, "oc_forward: workspace too small");
-    const OcParams p = oc_params(a);
-    const int grid = oc_grid(a->n);
-    double *part = reinterpret_cast<double *>(ws);
-    dispatch_dp<2, 4, 8, 16, 32>(a->dim, [&](auto DP) {
-        hipLaunchKernelGGL(oc_forward_kernel<decltype(DP)::value>, dim3(grid), dim3(kOcTpb), 0, stream, p, part);
-    });
-    hipLaunchKernelGGL(oc_finalize_kernel, dim3(1), dim3(kOcTpb), 0, stream, p, (const double *)part, grid, out);
-    return check_launch("oc_forward");
-}
-
-// partial buffer of the condensation-point pass: [slices][kOcCpBatch][dim padded + 1] floats
-size_t oc_backward_ws_bytes(int64_t n, int dim) {
-    (void)n;
-    const int dp = dim <= 2 ? 2 : dim <= 4 ? 4 : dim <= 8 ? 8 : dim <= 16 ? 16 : 32;
-    return (size_t)kOcSlices * kOcCpBatch * (dp + 1) * sizeof(float);
-}
-
-int oc_backward_launch(const gnntrk_oc_args *a, const float *g, const float *fwd, float *gx, float *gbeta,
-                       int64_t max_cps, void *ws, size_t ws_bytes, hipStream_t stream) {
-    int rc = oc_check(a);
-    if (rc) return rc;
-    if (!g || !fwd || !gx || !gbeta || max_cps < 1) return fail(GNNTRK_EINVAL, "oc_backward: bad argument");
-    if (!ws || ws_bytes < oc_backward_ws_bytes(a->n, a->dim)) return fail(GNNTRK_EINVAL, "oc_backward: workspace too small");
-    const OcParams p = oc_params(a);
-    const int grid = oc_grid(a->n);
-    dispatch_dp<2, 4, 8, 16, 32>(a->dim, [&](auto DP) {
-        hipLaunchKernelGGL(oc_backward_hits_kernel<decltype(DP)::value>, dim3(grid), dim3(kOcTpb), 0, stream, p, g, fwd, gx,
-                           gbeta);
-    });
-    // condensation-point side in batches of kOcCpBatch (the count K lives on the device: batches
-    // past it exit at once), each batch cut into hit slices
-    int64_t n_chunks = (a->n + kOcChunk - 1) / kOcChunk;
-    const int slices = (int)(n_chunks < kOcSlices ? n_chunks : kOcSlices);
-    float *part = reinterpret_cast<float *>(ws);
-    for (int64_t kb = 0; kb < max_cps; kb += kOcCpBatch) {
-        const int64_t in_batch = (max_cps - kb < kOcCpBatch) ? (max_cps - kb) : kOcCpBatch;
-        const int kgrid = oc_grid(in_batch);
-        dispatch_dp<2, 4, 8, 16, 32>(a->dim, [&](auto DP) {
-            constexpr int dp = decltype(DP)::value;
-            hipLaunchKernelGGL(oc_backward_cps_kernel<dp>, dim3(kgrid, slices), dim3(kOcTpb), 0, stream, p, g, fwd,
-                               (int)kb, part);
-            hipLaunchKernelGGL(oc_backward_cps_reduce_kernel<dp>, dim3(kgrid), dim3(kOcTpb), 0, stream, p, g, fwd,
-                               (int)kb, slices, (const float *)part, gx, gbeta);
-        });
-    }
-    return check_launch("oc_backward");
 }
 
 // ---- spatial passes: workspace layout and launchers ------------------------------------------
@@ -1140,22 +1050,128 @@ static OcSpatialWs oc_spatial_ws(void *base, int64_t n, int dim) {
                      w.gvals_b /* gorder */, w.gkeys_b /* gkeys */, w.gstart, w.c.n_chunks};
     return w;
 }
-size_t oc_spatial_ws_bytes(int64_t n, int dim) {
+
+}  // namespace gnntrk
+
+using namespace gnntrk;
+
+extern "C" {
+
+int gnntrk_good_node_mask(const float *pt, const int64_t *particle_id, const float *reconstructable, const float *eta,
+                          int64_t n, float pt_thld, float max_eta, uint8_t *mask, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n < 0) return fail(GNNTRK_EINVAL, "good_node_mask: bad argument");
+    if (n == 0) return GNNTRK_OK;
+    if (!pt || !particle_id || !reconstructable || !eta || !mask)
+        return fail(GNNTRK_EINVAL, "good_node_mask: NULL pointer");
+    hipLaunchKernelGGL(good_node_mask_kernel, dim3(oc_grid(n)), dim3(kOcTpb), 0, stream, pt, particle_id,
+                       reconstructable, eta, n, pt_thld, max_eta, mask);
+    return check_launch("good_node_mask");
+}
+
+size_t gnntrk_oc_select_workspace_bytes(int64_t n) { return select_ws(nullptr, n).total; }
+
+int gnntrk_oc_select_cps(const float *score, const int64_t *particle_id, const uint8_t *mask, int64_t n, int32_t mode,
+                         int32_t *alphas, int32_t *gid, int32_t *n_cp, void *workspace, size_t workspace_bytes,
+                         void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!score || !particle_id || !mask || !alphas || !gid || !n_cp || n < 1 || (mode != 0 && mode != 1))
+        return fail(GNNTRK_EINVAL, "oc_select_cps: bad argument");
+    if (n > 0x7fffffff) return fail(GNNTRK_EUNSUPPORTED, "oc_select_cps: n must fit int32");
+    const SelectWs w = select_ws(workspace, n);
+    if (!workspace || workspace_bytes < w.total) return fail(GNNTRK_EINVAL, "oc_select_cps: workspace too small");
+    const int grid = oc_grid(n);
+    hipLaunchKernelGGL(oc_keys_kernel, dim3(grid), dim3(kOcTpb), 0, stream, particle_id, n, w.keys_a, w.vals_a);
+    int rc = sort_pairs_u64(w.keys_a, w.keys_b, w.vals_a, w.vals_b, n, w.temp, w.temp_bytes, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(oc_segment_best_kernel, dim3(grid), dim3(kOcTpb), 0, stream,
+                       (const u64 *)w.keys_b, (const uint32_t *)w.vals_b, score, mask, n, mode, w.flag, w.best);
+    scan_counts_launch(w.flag, 0x7fffffff, n, w.off, stream);
+    rc = check_hip(hipMemsetAsync(gid, 0xff, (size_t)n * sizeof(int32_t), stream), "oc_select_cps(memset)");
+    if (rc) return rc;
+    hipLaunchKernelGGL(oc_assign_kernel, dim3(grid), dim3(kOcTpb), 0, stream, (const u64 *)w.keys_b,
+                       (const uint32_t *)w.vals_b, (const int32_t *)w.flag, (const int32_t *)w.best,
+                       (const int64_t *)w.off, n, alphas, gid, n_cp);
+    return check_launch("oc_select_cps");
+}
+
+size_t gnntrk_oc_forward_workspace_bytes(int64_t n) { return (size_t)oc_grid(n) * 4 * sizeof(double); }
+
+int gnntrk_oc_forward(const gnntrk_oc_args *args, float *out, void *workspace, size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = oc_check(args);
+    if (rc) return rc;
+    if (!out || !workspace || workspace_bytes < gnntrk_oc_forward_workspace_bytes(args->n))
+        return fail(GNNTRK_EINVAL, "oc_forward: workspace too small");
+    const OcParams p = oc_params(args);
+    const int grid = oc_grid(args->n);
+    double *part = reinterpret_cast<double *>(workspace);
+    dispatch_dp<2, 4, 8, 16, 32>(args->dim, [&](auto DP) {
+        hipLaunchKernelGGL(oc_forward_kernel<decltype(DP)::value>, dim3(grid), dim3(kOcTpb), 0, stream, p, part);
+    });
+    hipLaunchKernelGGL(oc_finalize_kernel, dim3(1), dim3(kOcTpb), 0, stream, p, (const double *)part, grid, out);
+    return check_launch("oc_forward");
+}
+
+// partial buffer of the condensation-point pass: [slices][kOcCpBatch][dim padded + 1] floats
+size_t gnntrk_oc_backward_workspace_bytes(int64_t n, int32_t dim) {
+    (void)n;
+    const int dp = dim <= 2 ? 2 : dim <= 4 ? 4 : dim <= 8 ? 8 : dim <= 16 ? 16 : 32;
+    return (size_t)kOcSlices * kOcCpBatch * (dp + 1) * sizeof(float);
+}
+
+int gnntrk_oc_backward(const gnntrk_oc_args *args, const float *g, const float *fwd, float *gx, float *gbeta,
+                       int64_t max_cps, void *workspace, size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = oc_check(args);
+    if (rc) return rc;
+    if (!g || !fwd || !gx || !gbeta || max_cps < 1) return fail(GNNTRK_EINVAL, "oc_backward: bad argument");
+    if (!workspace || workspace_bytes < gnntrk_oc_backward_workspace_bytes(args->n, args->dim))
+        return fail(GNNTRK_EINVAL, "oc_backward: workspace too small");
+    const OcParams p = oc_params(args);
+    const int grid = oc_grid(args->n);
+    dispatch_dp<2, 4, 8, 16, 32>(args->dim, [&](auto DP) {
+        hipLaunchKernelGGL(oc_backward_hits_kernel<decltype(DP)::value>, dim3(grid), dim3(kOcTpb), 0, stream, p, g, fwd, gx,
+                           gbeta);
+    });
+    // condensation-point side in batches of kOcCpBatch (the count K lives on the device: batches
+    // past it exit at once), each batch cut into hit slices
+    int64_t n_chunks = (args->n + kOcChunk - 1) / kOcChunk;
+    const int slices = (int)(n_chunks < kOcSlices ? n_chunks : kOcSlices);
+    float *part = reinterpret_cast<float *>(workspace);
+    for (int64_t kb = 0; kb < max_cps; kb += kOcCpBatch) {
+        const int64_t in_batch = (max_cps - kb < kOcCpBatch) ? (max_cps - kb) : kOcCpBatch;
+        const int kgrid = oc_grid(in_batch);
+        dispatch_dp<2, 4, 8, 16, 32>(args->dim, [&](auto DP) {
+            constexpr int dp = decltype(DP)::value;
+            hipLaunchKernelGGL(oc_backward_cps_kernel<dp>, dim3(kgrid, slices), dim3(kOcTpb), 0, stream, p, g, fwd,
+                               (int)kb, part);
+            hipLaunchKernelGGL(oc_backward_cps_reduce_kernel<dp>, dim3(kgrid), dim3(kOcTpb), 0, stream, p, g, fwd,
+                               (int)kb, slices, (const float *)part, gx, gbeta);
+        });
+    }
+    return check_launch("oc_backward");
+}
+
+size_t gnntrk_oc_spatial_workspace_bytes(int64_t n, int32_t dim) {
     if (n < 1 || n > 0x7fffffff || dim < 1 || dim > 16) return 0;
     return oc_spatial_ws(nullptr, n, dim).total;
 }
 
-int oc_forward_spatial_launch(const gnntrk_oc_args *a, float *out, void *ws, size_t ws_bytes, hipStream_t stream) {
-    int rc = oc_check(a);
+int gnntrk_oc_forward_spatial(const gnntrk_oc_args *args, float *out, void *spatial, size_t spatial_bytes,
+                              void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = oc_check(args);
     if (rc) return rc;
-    if (a->dim > 16) return fail(GNNTRK_EUNSUPPORTED, "oc_forward_spatial: dim > 16 (use gnntrk_oc_forward)");
-    const OcSpatialWs w = oc_spatial_ws(ws, a->n, a->dim);
-    if (!out || !ws || ws_bytes < w.total) return fail(GNNTRK_EINVAL, "oc_forward_spatial: workspace too small");
-    const OcParams p = oc_params(a);
-    rc = spatial_chunks_build(a->x, a->n, a->dim, a->stride, nullptr, 0, w.c, stream);
+    if (args->dim > 16) return fail(GNNTRK_EUNSUPPORTED, "oc_forward_spatial: dim > 16 (use gnntrk_oc_forward)");
+    const OcSpatialWs w = oc_spatial_ws(spatial, args->n, args->dim);
+    if (!out || !spatial || spatial_bytes < w.total)
+        return fail(GNNTRK_EINVAL, "oc_forward_spatial: workspace too small");
+    const OcParams p = oc_params(args);
+    rc = spatial_chunks_build(args->x, args->n, args->dim, args->stride, nullptr, 0, w.c, stream);
     if (rc) return rc;
-    const int rgrid = oc_grid((int64_t)w.c.n_chunks * 64), kgrid = oc_grid(a->n), hgrid = w.c.n_chunks;
-    dispatch_dp<4, 8, 16>(a->dim, [&](auto DP) {
+    const int rgrid = oc_grid((int64_t)w.c.n_chunks * 64), kgrid = oc_grid(args->n), hgrid = w.c.n_chunks;
+    dispatch_dp<4, 8, 16>(args->dim, [&](auto DP) {
         constexpr int dp = decltype(DP)::value;
         hipLaunchKernelGGL(oc_hit_records_kernel<dp>, dim3(rgrid), dim3(kOcTpb), 0, stream, p, w.sp, w.hq, w.hpid, w.hcap,
                            w.hcapd2);
@@ -1168,24 +1184,26 @@ int oc_forward_spatial_launch(const gnntrk_oc_args *a, float *out, void *ws, siz
     return check_launch("oc_forward_spatial");
 }
 
-int oc_backward_spatial_launch(const gnntrk_oc_args *a, const float *g, const float *fwd, float *gx, float *gbeta,
-                               int64_t max_cps, void *ws, size_t ws_bytes, hipStream_t stream) {
-    int rc = oc_check(a);
+int gnntrk_oc_backward_spatial(const gnntrk_oc_args *args, const float *g, const float *fwd, float *gx, float *gbeta,
+                               int64_t max_cps, void *spatial, size_t spatial_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = oc_check(args);
     if (rc) return rc;
-    if (a->dim > 16) return fail(GNNTRK_EUNSUPPORTED, "oc_backward_spatial: dim > 16 (use gnntrk_oc_backward)");
+    if (args->dim > 16) return fail(GNNTRK_EUNSUPPORTED, "oc_backward_spatial: dim > 16 (use gnntrk_oc_backward)");
     if (!g || !fwd || !gx || !gbeta || max_cps < 1) return fail(GNNTRK_EINVAL, "oc_backward_spatial: bad argument");
-    const OcSpatialWs w = oc_spatial_ws(ws, a->n, a->dim);
-    if (!ws || ws_bytes < w.total) return fail(GNNTRK_EINVAL, "oc_backward_spatial: workspace too small");
-    const OcParams p = oc_params(a);
-    const int hgrid = w.c.n_chunks, ngrid = oc_grid(a->n);
+    const OcSpatialWs w = oc_spatial_ws(spatial, args->n, args->dim);
+    if (!spatial || spatial_bytes < w.total) return fail(GNNTRK_EINVAL, "oc_backward_spatial: workspace too small");
+    const OcParams p = oc_params(args);
+    const int hgrid = w.c.n_chunks, ngrid = oc_grid(args->n);
     // the by-gid ordering of the hits (for the points' attractive share)
-    hipLaunchKernelGGL(oc_gid_keys_kernel, dim3(ngrid), dim3(kOcTpb), 0, stream, a->gid, a->n, w.gkeys_a, w.gvals_a);
-    rc = sort_pairs_u32(w.gkeys_a, w.gkeys_b, w.gvals_a, w.gvals_b, a->n, 32, w.gtemp, w.gtemp_bytes, stream);
+    hipLaunchKernelGGL(oc_gid_keys_kernel, dim3(ngrid), dim3(kOcTpb), 0, stream, args->gid, args->n, w.gkeys_a,
+                       w.gvals_a);
+    rc = sort_pairs_u32(w.gkeys_a, w.gkeys_b, w.gvals_a, w.gvals_b, args->n, 32, w.gtemp, w.gtemp_bytes, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(oc_gid_starts_kernel, dim3(ngrid), dim3(kOcTpb), 0, stream, (const uint32_t *)w.gkeys_b, a->n,
+    hipLaunchKernelGGL(oc_gid_starts_kernel, dim3(ngrid), dim3(kOcTpb), 0, stream, (const uint32_t *)w.gkeys_b, args->n,
                        w.gstart);
-    const int cgrid = (int)(max_cps < a->n ? max_cps : a->n);
-    dispatch_dp<4, 8, 16>(a->dim, [&](auto DP) {
+    const int cgrid = (int)(max_cps < args->n ? max_cps : args->n);
+    dispatch_dp<4, 8, 16>(args->dim, [&](auto DP) {
         constexpr int dp = decltype(DP)::value;
         hipLaunchKernelGGL((oc_hits_spatial_kernel<dp, true>), dim3(hgrid), dim3(kOcTpb), 0, stream, p, w.sp, g, fwd,
                            (double *)nullptr, gx, gbeta);
@@ -1194,4 +1212,4 @@ int oc_backward_spatial_launch(const gnntrk_oc_args *a, const float *g, const fl
     return check_launch("oc_backward_spatial");
 }
 
-}  // namespace gnntrk
+}  // extern "C"

@@ -366,9 +366,9 @@ int rows_to_bf16_launch(const float *in, int dim, int in_stride, const int32_t *
     return check_launch("rows_to_bf16");
 }
 
-int segment_sum_bf16_launch(const uint16_t *rows, int dim, int row_stride, const int32_t *rowptr,
-                            const int32_t *pos, int64_t n_seg, uint16_t *out, int out_stride,
-                            const uint16_t *addend, int addend_stride, hipStream_t stream) {
+static int segment_sum_bf16_launch(const uint16_t *rows, int dim, int row_stride, const int32_t *rowptr,
+                                   const int32_t *pos, int64_t n_seg, uint16_t *out, int out_stride,
+                                   const uint16_t *addend, int addend_stride, hipStream_t stream) {
     if (n_seg == 0) return GNNTRK_OK;
     if (addend && !rows_ok(addend, dim, addend_stride)) return fail(GNNTRK_EINVAL, "segment_sum_bf16: bad addend rows");
     // rows may be NULL when there are no rows at all (every segment empty)
@@ -412,17 +412,6 @@ int segment_sum_bf16_launch(const uint16_t *rows, int dim, int row_stride, const
     GNNTRK_SEGSUM16(1) GNNTRK_SEGSUM16(2) GNNTRK_SEGSUM16(3) GNNTRK_SEGSUM16(4)
 #undef GNNTRK_SEGSUM16
     return check_launch("segment_sum_bf16");
-}
-
-int permute_rows_bf16_launch(const uint16_t *in, int dim, int in_stride, const int32_t *idx, int64_t n_rows,
-                             uint16_t *out, int out_stride, int scatter, hipStream_t stream) {
-    if (n_rows == 0) return GNNTRK_OK;
-    if (!idx || n_rows < 0 || !rows_ok(in, dim, in_stride) || !rows_ok(out, dim, out_stride))
-        return fail(GNNTRK_EINVAL, "permute_rows_bf16: bad argument");
-    const int nch = (dim + 3) / 4;
-    hipLaunchKernelGGL(permute_rows_bf16_kernel, dim3(grid_for_threads(n_rows * nch)), dim3(kTpb16), 0, stream,
-                       in, nch, in_stride, idx, n_rows, out, out_stride, scatter);
-    return check_launch("permute_rows_bf16");
 }
 
 // ------------------------------------------------------------------ carries + gate of the in-kernel target fold
@@ -476,8 +465,9 @@ __global__ __launch_bounds__(kTpb16) void fold_finish_bf16_kernel(uint16_t *__re
     }
 }
 
-int fold_finish_bf16_launch(uint16_t *out, int out_stride, int64_t n_nodes, const int32_t *rowptr, const uint16_t *carry,
-                            int64_t n_units, const uint16_t *x, int x_stride, hipStream_t stream) {
+static int fold_finish_bf16_launch(uint16_t *out, int out_stride, int64_t n_nodes, const int32_t *rowptr,
+                                   const uint16_t *carry, int64_t n_units, const uint16_t *x, int x_stride,
+                                   hipStream_t stream) {
     if (n_units == 0 || n_nodes == 0) return GNNTRK_OK;
     if (!out || !carry || !rowptr || n_units < 0 || n_nodes < 0 || out_stride != 8 || ((uintptr_t)out & 15) != 0 ||
         ((uintptr_t)carry & 15) != 0 || (x && (x_stride != 8 || ((uintptr_t)x & 15) != 0)))
@@ -488,3 +478,45 @@ int fold_finish_bf16_launch(uint16_t *out, int out_stride, int64_t n_nodes, cons
 }
 
 }  // namespace gnntrk
+
+using namespace gnntrk;
+
+extern "C" {
+
+int gnntrk_rows_to_bf16(const float *in, int32_t dim, int32_t in_stride, const int32_t *idx, int64_t n_rows,
+                        uint16_t *out, int32_t out_stride, void *stream) {
+    return rows_to_bf16_launch(in, dim, in_stride, idx, n_rows, out, out_stride, (hipStream_t)stream);
+}
+
+int gnntrk_segment_sum_bf16(const uint16_t *rows, int32_t dim, int32_t row_stride, const int32_t *rowptr,
+                            const int32_t *pos, int64_t n_segments, uint16_t *out, int32_t out_stride, void *stream) {
+    return segment_sum_bf16_launch(rows, dim, row_stride, rowptr, pos, n_segments, out, out_stride, nullptr, 0,
+                                   (hipStream_t)stream);
+}
+
+int gnntrk_segment_sum_bf16_add(const uint16_t *rows, int32_t dim, int32_t row_stride, const int32_t *rowptr,
+                                const int32_t *pos, int64_t n_segments, const uint16_t *addend, int32_t addend_stride,
+                                uint16_t *out, int32_t out_stride, void *stream) {
+    return segment_sum_bf16_launch(rows, dim, row_stride, rowptr, pos, n_segments, out, out_stride, addend,
+                                   addend_stride, (hipStream_t)stream);
+}
+
+int gnntrk_permute_rows_bf16(const uint16_t *in, int32_t dim, int32_t in_stride, const int32_t *idx, int64_t n_rows,
+                             uint16_t *out, int32_t out_stride, int32_t scatter, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_rows == 0) return GNNTRK_OK;
+    if (!idx || n_rows < 0 || !rows_ok(in, dim, in_stride) || !rows_ok(out, dim, out_stride))
+        return fail(GNNTRK_EINVAL, "permute_rows_bf16: bad argument");
+    const int nch = (dim + 3) / 4;
+    hipLaunchKernelGGL(permute_rows_bf16_kernel, dim3(grid_for_threads(n_rows * nch)), dim3(kTpb16), 0, stream,
+                       in, nch, in_stride, idx, n_rows, out, out_stride, scatter);
+    return check_launch("permute_rows_bf16");
+}
+
+int gnntrk_fold_finish_bf16(uint16_t *out, int32_t out_stride, int64_t n_nodes, const int32_t *rowptr, int64_t n_units,
+                            const uint16_t *x, int32_t x_stride, void *stream) {
+    return fold_finish_bf16_launch(out, out_stride, n_nodes, rowptr, out + n_nodes * out_stride, n_units, x, x_stride,
+                                   (hipStream_t)stream);
+}
+
+}  // extern "C"

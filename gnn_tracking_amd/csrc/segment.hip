@@ -343,33 +343,45 @@ __global__ __launch_bounds__(kTpb) void focal_bwd_kernel(const float *__restrict
     }
 }
 
-// ------------------------------------------------------------------ launchers
-int segment_sum_launch(const float *rows, int dim, int row_stride, const int32_t *rowptr,
-                       const int32_t *pos, int64_t n_seg, float *out, int out_stride,
-                       int accumulate, hipStream_t stream) {
-    if (n_seg == 0) return GNNTRK_OK;
+// ------------------------------------------------------------------ host side: the C entries launch
+static int bce_grid(int64_t n) {
+    int g = blocks_for(n, 8);
+    return g > 1024 ? 1024 : g;
+}
+
+}  // namespace gnntrk
+
+using namespace gnntrk;
+
+extern "C" {
+
+int gnntrk_segment_sum(const float *rows, int32_t dim, int32_t row_stride, const int32_t *rowptr, const int32_t *pos,
+                       int64_t n_segments, float *out, int32_t out_stride, int32_t accumulate, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_segments == 0) return GNNTRK_OK;
     // rows may be NULL when there are no rows at all (every segment empty: zeros are written)
-    if (!rowptr || !out || dim < 1 || row_stride < dim || out_stride < dim || n_seg < 0)
+    if (!rowptr || !out || dim < 1 || row_stride < dim || out_stride < dim || n_segments < 0)
         return fail(GNNTRK_EINVAL, "segment_sum: bad argument");
     if (rows && dim == 4 && row_stride == 4 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0) {
-        hipLaunchKernelGGL(segment_sum4_kernel, dim3(blocks_for(n_seg, 8)), dim3(kTpb), 0, stream, rows,
-                           rowptr, pos, n_seg, out, out_stride, accumulate);
+        hipLaunchKernelGGL(segment_sum4_kernel, dim3(blocks_for(n_segments, 8)), dim3(kTpb), 0, stream, rows,
+                           rowptr, pos, n_segments, out, out_stride, accumulate);
         return check_launch("segment_sum");
     }
     if (rows && dim % 4 == 0 && row_stride % 4 == 0 && out_stride % 4 == 0 &&
         ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(out)) & 15) == 0) {
-        hipLaunchKernelGGL(segment_sum_v4_kernel, dim3(blocks_for(n_seg * (dim / 4), 8)), dim3(kTpb), 0, stream,
-                           reinterpret_cast<const float4 *>(rows), dim / 4, row_stride / 4, rowptr, pos, n_seg,
+        hipLaunchKernelGGL(segment_sum_v4_kernel, dim3(blocks_for(n_segments * (dim / 4), 8)), dim3(kTpb), 0, stream,
+                           reinterpret_cast<const float4 *>(rows), dim / 4, row_stride / 4, rowptr, pos, n_segments,
                            reinterpret_cast<float4 *>(out), out_stride / 4, accumulate);
         return check_launch("segment_sum");
     }
-    hipLaunchKernelGGL(segment_sum_kernel, dim3(blocks_for(n_seg * dim, 8)), dim3(kTpb), 0, stream,
-                       rows, dim, row_stride, rowptr, pos, n_seg, out, out_stride, accumulate);
+    hipLaunchKernelGGL(segment_sum_kernel, dim3(blocks_for(n_segments * dim, 8)), dim3(kTpb), 0, stream,
+                       rows, dim, row_stride, rowptr, pos, n_segments, out, out_stride, accumulate);
     return check_launch("segment_sum");
 }
 
-int permute_rows_launch(const float *in, int dim, int in_stride, const int32_t *idx, int64_t n_rows,
-                        float *out, int out_stride, int scatter, hipStream_t stream) {
+int gnntrk_permute_rows(const float *in, int32_t dim, int32_t in_stride, const int32_t *idx, int64_t n_rows, float *out,
+                        int32_t out_stride, int32_t scatter, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     if (n_rows == 0) return GNNTRK_OK;  // empty tensors may carry NULL pointers
     if (!in || !idx || !out || dim < 1 || in_stride < dim || out_stride < dim || n_rows < 0)
         return fail(GNNTRK_EINVAL, "permute_rows: bad argument");
@@ -378,107 +390,112 @@ int permute_rows_launch(const float *in, int dim, int in_stride, const int32_t *
     return check_launch("permute_rows");
 }
 
-int axpby_launch(float a, const float *x, float b, const float *y, const float *mask, float *out,
-                 int64_t n, hipStream_t stream) {
+int gnntrk_axpby(float a, const float *x, float b, const float *y, const float *relu_mask, float *out, int64_t n,
+                 void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     if (n == 0) return GNNTRK_OK;
     if (!x || !out || n < 0) return fail(GNNTRK_EINVAL, "axpby: bad argument");
-    hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, a, x, b, y, mask,
+    hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, a, x, b, y, relu_mask,
                        out, n);
     return check_launch("axpby");
 }
 
-static int bce_grid(int64_t n) {
-    int g = blocks_for(n, 8);
-    return g > 1024 ? 1024 : g;
-}
-
-size_t bce_ws_bytes(int64_t n) {
+size_t gnntrk_bce_workspace_bytes(int64_t n) {
     (void)n;
     return 1024 * sizeof(double);
 }
 
-int bce_forward_launch(const float *w, const float *y, const int64_t *src_node, const float *pt,
-                       float thld, int64_t n, float *loss, void *ws, size_t ws_bytes,
-                       hipStream_t stream) {
-    if (!w || !y || !loss || n < 1) return fail(GNNTRK_EINVAL, "bce_forward: bad argument");
-    if (thld > 0.f && (!src_node || !pt))
+int gnntrk_bce_forward(const float *w, const float *y, const int64_t *src_node, const float *pt, float pt_thld,
+                       int64_t n, float *loss_out, void *workspace, size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!w || !y || !loss_out || n < 1) return fail(GNNTRK_EINVAL, "bce_forward: bad argument");
+    if (pt_thld > 0.f && (!src_node || !pt))
         return fail(GNNTRK_EINVAL, "bce_forward: pt threshold needs edge_index and pt");
-    if (!ws || ws_bytes < bce_ws_bytes(n)) return fail(GNNTRK_EINVAL, "bce_forward: workspace too small");
+    if (!workspace || workspace_bytes < gnntrk_bce_workspace_bytes(n))
+        return fail(GNNTRK_EINVAL, "bce_forward: workspace too small");
     const int g = bce_grid(n);
-    double *part = reinterpret_cast<double *>(ws);
-    hipLaunchKernelGGL(bce_partial_kernel, dim3(g), dim3(kTpb), 0, stream, w, y, src_node, pt, thld,
+    double *part = reinterpret_cast<double *>(workspace);
+    hipLaunchKernelGGL(bce_partial_kernel, dim3(g), dim3(kTpb), 0, stream, w, y, src_node, pt, pt_thld,
                        n, part);
     hipLaunchKernelGGL(bce_final_kernel, dim3(1), dim3(kTpb), 0, stream,
-                       reinterpret_cast<const double *>(part), g, n, loss);
+                       reinterpret_cast<const double *>(part), g, n, loss_out);
     return check_launch("bce_forward");
 }
 
-int bce_backward_launch(const float *w, const float *y, const int64_t *src_node, const float *pt,
-                        float thld, int64_t n, const float *gscale, float *gw, hipStream_t stream) {
+int gnntrk_bce_backward(const float *w, const float *y, const int64_t *src_node, const float *pt, float pt_thld,
+                        int64_t n, const float *gscale, float *gw, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     if (!w || !y || !gscale || !gw || n < 1) return fail(GNNTRK_EINVAL, "bce_backward: bad argument");
-    if (thld > 0.f && (!src_node || !pt))
+    if (pt_thld > 0.f && (!src_node || !pt))
         return fail(GNNTRK_EINVAL, "bce_backward: pt threshold needs edge_index and pt");
     hipLaunchKernelGGL(bce_bwd_kernel, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, w, y, src_node,
-                       pt, thld, n, gscale, gw);
+                       pt, pt_thld, n, gscale, gw);
     return check_launch("bce_backward");
 }
 
-int bce_csr_launch(const float *w, const uint8_t *label, const int32_t *src_csr, const float *pt, float thld, int64_t n,
-                   float *loss, float *gw_unit, void *ws, size_t ws_bytes, hipStream_t stream) {
-    if (!w || !label || !loss || n < 1) return fail(GNNTRK_EINVAL, "bce_csr: bad argument");
-    if (thld > 0.f && (!src_csr || !pt)) return fail(GNNTRK_EINVAL, "bce_csr: pt threshold needs the CSR source ids and pt");
-    if (!ws || ws_bytes < bce_ws_bytes(n)) return fail(GNNTRK_EINVAL, "bce_csr: workspace too small");
+int gnntrk_bce_csr(const float *w, const uint8_t *label_csr, const int32_t *src_csr, const float *pt, float pt_thld,
+                   int64_t n, float *loss, float *gw_unit, void *workspace, size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!w || !label_csr || !loss || n < 1) return fail(GNNTRK_EINVAL, "bce_csr: bad argument");
+    if (pt_thld > 0.f && (!src_csr || !pt))
+        return fail(GNNTRK_EINVAL, "bce_csr: pt threshold needs the CSR source ids and pt");
+    if (!workspace || workspace_bytes < gnntrk_bce_workspace_bytes(n))
+        return fail(GNNTRK_EINVAL, "bce_csr: workspace too small");
     const int g = bce_grid(n);
-    double *part = reinterpret_cast<double *>(ws);
-    const bool vec = (((uintptr_t)w | (uintptr_t)gw_unit) & 15) == 0 && ((uintptr_t)label & 3) == 0;
-    hipLaunchKernelGGL(bce_csr_kernel, dim3(g), dim3(kTpb), 0, stream, w, label, src_csr, pt, thld, n, vec, part,
+    double *part = reinterpret_cast<double *>(workspace);
+    const bool vec = (((uintptr_t)w | (uintptr_t)gw_unit) & 15) == 0 && ((uintptr_t)label_csr & 3) == 0;
+    hipLaunchKernelGGL(bce_csr_kernel, dim3(g), dim3(kTpb), 0, stream, w, label_csr, src_csr, pt, pt_thld, n, vec, part,
                        gw_unit);
     hipLaunchKernelGGL(bce_final_kernel, dim3(1), dim3(kTpb), 0, stream, reinterpret_cast<const double *>(part), g, n,
                        loss);
     return check_launch("bce_csr");
 }
 
-int edge_targets_csr_launch(const void *y, int y_is_u8, const int32_t *perm, const int32_t *src_csr, const float *pt,
-                            float thld, int64_t n, float *out, hipStream_t stream) {
+int gnntrk_edge_targets_csr(const void *y, int32_t y_is_u8, const int32_t *perm, const int32_t *src_csr,
+                            const float *pt, float pt_thld, int64_t n, float *out, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     if (n == 0) return GNNTRK_OK;
     if (!y || !perm || !out || n < 0) return fail(GNNTRK_EINVAL, "edge_targets_csr: bad argument");
-    if (thld > 0.f && (!src_csr || !pt))
+    if (pt_thld > 0.f && (!src_csr || !pt))
         return fail(GNNTRK_EINVAL, "edge_targets_csr: pt threshold needs the CSR source ids and pt");
     if (y_is_u8)
         hipLaunchKernelGGL(edge_targets_csr_kernel<uint8_t>, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream,
-                           reinterpret_cast<const uint8_t *>(y), perm, src_csr, pt, thld, n, out);
+                           reinterpret_cast<const uint8_t *>(y), perm, src_csr, pt, pt_thld, n, out);
     else
         hipLaunchKernelGGL(edge_targets_csr_kernel<float>, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream,
-                           reinterpret_cast<const float *>(y), perm, src_csr, pt, thld, n, out);
+                           reinterpret_cast<const float *>(y), perm, src_csr, pt, pt_thld, n, out);
     return check_launch("edge_targets_csr");
 }
 
-int focal_forward_launch(const float *w, const float *y, const int64_t *src_node, const float *pt, float thld,
-                         float alpha, float gamma, float pos_weight, int haughty, int64_t n, float *loss, void *ws,
-                         size_t ws_bytes, hipStream_t stream) {
-    if (!w || !y || !loss || n < 1) return fail(GNNTRK_EINVAL, "focal_forward: bad argument");
+int gnntrk_focal_forward(const float *w, const float *y, const int64_t *src_node, const float *pt, float pt_thld,
+                         float alpha, float gamma, float pos_weight, int32_t haughty, int64_t n, float *loss_out,
+                         void *workspace, size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!w || !y || !loss_out || n < 1) return fail(GNNTRK_EINVAL, "focal_forward: bad argument");
     if (!(gamma >= 0.f) || !(alpha >= 0.f && alpha <= 1.f)) return fail(GNNTRK_EINVAL, "focal_forward: bad alpha / gamma");
-    if (thld > 0.f && (!src_node || !pt))
+    if (pt_thld > 0.f && (!src_node || !pt))
         return fail(GNNTRK_EINVAL, "focal_forward: pt threshold needs edge_index and pt");
-    if (!ws || ws_bytes < bce_ws_bytes(n)) return fail(GNNTRK_EINVAL, "focal_forward: workspace too small");
+    if (!workspace || workspace_bytes < gnntrk_bce_workspace_bytes(n))
+        return fail(GNNTRK_EINVAL, "focal_forward: workspace too small");
     const int g = bce_grid(n);
-    double *part = reinterpret_cast<double *>(ws);
-    hipLaunchKernelGGL(focal_partial_kernel, dim3(g), dim3(kTpb), 0, stream, w, y, src_node, pt, thld, alpha, gamma,
+    double *part = reinterpret_cast<double *>(workspace);
+    hipLaunchKernelGGL(focal_partial_kernel, dim3(g), dim3(kTpb), 0, stream, w, y, src_node, pt, pt_thld, alpha, gamma,
                        pos_weight, haughty, n, part);
     hipLaunchKernelGGL(bce_final_kernel, dim3(1), dim3(kTpb), 0, stream, reinterpret_cast<const double *>(part), g, n,
-                       loss);
+                       loss_out);
     return check_launch("focal_forward");
 }
 
-int focal_backward_launch(const float *w, const float *y, const int64_t *src_node, const float *pt, float thld,
-                          float alpha, float gamma, float pos_weight, int haughty, int64_t n, const float *gscale,
-                          float *gw, hipStream_t stream) {
+int gnntrk_focal_backward(const float *w, const float *y, const int64_t *src_node, const float *pt, float pt_thld,
+                          float alpha, float gamma, float pos_weight, int32_t haughty, int64_t n, const float *gscale,
+                          float *gw, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     if (!w || !y || !gscale || !gw || n < 1) return fail(GNNTRK_EINVAL, "focal_backward: bad argument");
-    if (thld > 0.f && (!src_node || !pt))
+    if (pt_thld > 0.f && (!src_node || !pt))
         return fail(GNNTRK_EINVAL, "focal_backward: pt threshold needs edge_index and pt");
-    hipLaunchKernelGGL(focal_bwd_kernel, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, w, y, src_node, pt, thld, alpha,
-                       gamma, pos_weight, haughty, n, gscale, gw);
+    hipLaunchKernelGGL(focal_bwd_kernel, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, w, y, src_node, pt, pt_thld,
+                       alpha, gamma, pos_weight, haughty, n, gscale, gw);
     return check_launch("focal_backward");
 }
 
-}  // namespace gnntrk
+}  // extern "C"

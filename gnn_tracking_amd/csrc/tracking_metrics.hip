@@ -423,15 +423,33 @@ int check_hits(const char *entry, int64_t n, int32_t n_trials, const void *label
     return GNNTRK_OK;
 }
 
-}  // namespace
-
+// what the three workspace-size entries share
 size_t tracking_metrics_ws_bytes(int64_t n, int32_t n_trials) {
     return make_ws(nullptr, n < 0 ? 0 : n, n_trials < 1 ? 1 : n_trials).total;
 }
 
-int tracking_metrics(const int64_t *labels, int32_t n_trials, const int64_t *pid, const float *pt, const float *eta,
-                     const float *reco, int64_t n, const float *cuts, int32_t n_cuts, float max_eta,
-                     int32_t count_thld, int64_t *out, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+}  // namespace
+}  // namespace gnntrk
+
+using namespace gnntrk;
+
+extern "C" {
+
+size_t gnntrk_tracking_metrics_workspace_bytes(int64_t n, int32_t n_trials) {
+    return tracking_metrics_ws_bytes(n, n_trials);
+}
+
+size_t gnntrk_tracking_metrics_windows_workspace_bytes(int64_t n, int32_t n_trials) {
+    return tracking_metrics_ws_bytes(n, n_trials);
+}
+
+size_t gnntrk_cluster_table_workspace_bytes(int64_t n) { return tracking_metrics_ws_bytes(n, 1); }
+
+int gnntrk_tracking_metrics(const int64_t *labels, int32_t n_trials, const int64_t *particle_id, const float *pt,
+                            const float *eta, const float *reconstructable, int64_t n, const float *cuts,
+                            int32_t n_cuts, float max_eta, int32_t predicted_count_thld, int64_t *out, void *workspace,
+                            size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     char msg[160];
     int rc = check_count_i30("tracking_metrics", "hit", n);
     if (rc) return rc;
@@ -444,27 +462,30 @@ int tracking_metrics(const int64_t *labels, int32_t n_trials, const int64_t *pid
     sel.max_eta = max_eta;
     if ((rc = fill_cuts(sel.cuts, cuts, n_cuts, "tracking_metrics"))) return rc;
     if (!out) return fail(GNNTRK_EINVAL, "tracking_metrics: NULL output");
-    if ((rc = check_hits("tracking_metrics", n, n_trials, labels, pid, pt, eta, reco, workspace, workspace_bytes)))
+    if ((rc = check_hits("tracking_metrics", n, n_trials, labels, particle_id, pt, eta, reconstructable, workspace,
+                         workspace_bytes)))
         return rc;
     const size_t n_out = (size_t)n_cuts + (size_t)n_trials * n_cuts * 4 + 1;
     rc = check_hip(hipMemsetAsync(out, 0, sizeof(int64_t) * n_out, stream), "tracking_metrics: clear");
     if (rc || n == 0) return rc;
     const Ws w = make_ws(workspace, n, n_trials);
     auto *o = reinterpret_cast<unsigned long long *>(out);
-    if ((rc = fill_tables("tracking_metrics", labels, n_trials, pid, pt, eta, reco, n, sel, w, o + n_out - 1, stream)))
+    if ((rc = fill_tables("tracking_metrics", labels, n_trials, particle_id, pt, eta, reconstructable, n, sel, w,
+                          o + n_out - 1, stream)))
         return rc;
     hipLaunchKernelGGL(tm_particle_kernel, dim3(blocks_for((int64_t)w.S, 4)), dim3(kTpb), 0, stream, sel.cuts, max_eta,
                        w, o);
     const int gx = (int)((blocks_for(n, 8) + n_trials - 1) / n_trials);
-    hipLaunchKernelGGL(tm_clusters_kernel, dim3(gx < 1 ? 1 : gx, (unsigned)n_trials), dim3(kTpb), 0, stream, pid, n,
-                       sel.cuts, count_thld, w, o + n_cuts);
+    hipLaunchKernelGGL(tm_clusters_kernel, dim3(gx < 1 ? 1 : gx, (unsigned)n_trials), dim3(kTpb), 0, stream,
+                       particle_id, n, sel.cuts, predicted_count_thld, w, o + n_cuts);
     return check_launch("tracking_metrics: clusters");
 }
 
-int tracking_metrics_windows(const int64_t *labels, int32_t n_trials, const int64_t *pid, const float *pt,
-                             const float *eta, const float *reco, int64_t n, const float *windows, int32_t n_win,
-                             int32_t count_thld, int64_t *out, void *workspace, size_t workspace_bytes,
-                             hipStream_t stream) {
+int gnntrk_tracking_metrics_windows(const int64_t *labels, int32_t n_trials, const int64_t *particle_id,
+                                    const float *pt, const float *eta, const float *reconstructable, int64_t n,
+                                    const float *windows, int32_t n_win, int32_t predicted_count_thld, int64_t *out,
+                                    void *workspace, size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     char msg[160];
     int rc = check_count_i30("tracking_metrics_windows", "hit", n);
     if (rc) return rc;
@@ -474,8 +495,8 @@ int tracking_metrics_windows(const int64_t *labels, int32_t n_trials, const int6
     }
     if (!windows) return fail(GNNTRK_EINVAL, "tracking_metrics_windows: NULL windows");
     if (!out) return fail(GNNTRK_EINVAL, "tracking_metrics_windows: NULL output");
-    if ((rc = check_hits("tracking_metrics_windows", n, n_trials, labels, pid, pt, eta, reco, workspace,
-                         workspace_bytes)))
+    if ((rc = check_hits("tracking_metrics_windows", n, n_trials, labels, particle_id, pt, eta, reconstructable,
+                         workspace, workspace_bytes)))
         return rc;
     WinSel sel{};
     sel.win.n = n_win;
@@ -486,36 +507,40 @@ int tracking_metrics_windows(const int64_t *labels, int32_t n_trials, const int6
     if (rc || n == 0) return rc;
     const Ws w = make_ws(workspace, n, n_trials);
     auto *o = reinterpret_cast<unsigned long long *>(out);
-    if ((rc = fill_tables("tracking_metrics_windows", labels, n_trials, pid, pt, eta, reco, n, sel, w, o + n_out - 1,
-                          stream)))
+    if ((rc = fill_tables("tracking_metrics_windows", labels, n_trials, particle_id, pt, eta, reconstructable, n, sel, w,
+                          o + n_out - 1, stream)))
         return rc;
     hipLaunchKernelGGL(tmw_particle_kernel, dim3(blocks_for((int64_t)w.S, 4)), dim3(kTpb), 0, stream, sel.win, w, o);
     const int gx = (int)((blocks_for(n, 8) + n_trials - 1) / n_trials);
-    hipLaunchKernelGGL(tmw_clusters_kernel, dim3(gx < 1 ? 1 : gx, (unsigned)n_trials), dim3(kTpb), 0, stream, pid, n,
-                       n_win, count_thld, w, o + n_win);
+    hipLaunchKernelGGL(tmw_clusters_kernel, dim3(gx < 1 ? 1 : gx, (unsigned)n_trials), dim3(kTpb), 0, stream,
+                       particle_id, n, n_win, predicted_count_thld, w, o + n_win);
     return check_launch("tracking_metrics_windows: clusters");
 }
 
-int cluster_table(const int64_t *labels, const int64_t *pid, const float *pt, const float *eta, const float *reco,
-                  int64_t n, int64_t *cluster_size, int64_t *maj_hits, int64_t *maj_pid, int64_t *maj_pid_hits,
-                  float *maj_pt, float *maj_eta, float *maj_reco, int64_t *n_bad, void *workspace,
-                  size_t workspace_bytes, hipStream_t stream) {
+int gnntrk_cluster_table(const int64_t *labels, const int64_t *particle_id, const float *pt, const float *eta,
+                         const float *reconstructable, int64_t n, int64_t *cluster_size, int64_t *maj_hits,
+                         int64_t *maj_pid, int64_t *maj_pid_hits, float *maj_pt, float *maj_eta,
+                         float *maj_reconstructable, int64_t *n_bad, void *workspace, size_t workspace_bytes,
+                         void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     int rc = check_count_i30("cluster_table", "hit", n);
     if (rc) return rc;
     if (!n_bad) return fail(GNNTRK_EINVAL, "cluster_table: NULL n_bad");
-    if (n > 0 && (!cluster_size || !maj_hits || !maj_pid || !maj_pid_hits || !maj_pt || !maj_eta || !maj_reco))
+    if (n > 0 &&
+        (!cluster_size || !maj_hits || !maj_pid || !maj_pid_hits || !maj_pt || !maj_eta || !maj_reconstructable))
         return fail(GNNTRK_EINVAL, "cluster_table: NULL output column");
-    if ((rc = check_hits("cluster_table", n, 1, labels, pid, pt, eta, reco, workspace, workspace_bytes))) return rc;
+    if ((rc = check_hits("cluster_table", n, 1, labels, particle_id, pt, eta, reconstructable, workspace, workspace_bytes)))
+        return rc;
     rc = check_hip(hipMemsetAsync(n_bad, 0, sizeof(int64_t), stream), "cluster_table: clear");
     if (rc || n == 0) return rc;
     const Ws w = make_ws(workspace, n, 1);
     // (no windows: the hits leave no mask, only the particle table and its sums are wanted)
-    if ((rc = fill_tables("cluster_table", labels, 1, pid, pt, eta, reco, n, WinSel{}, w,
+    if ((rc = fill_tables("cluster_table", labels, 1, particle_id, pt, eta, reconstructable, n, WinSel{}, w,
                           reinterpret_cast<unsigned long long *>(n_bad), stream)))
         return rc;
-    hipLaunchKernelGGL(tm_table_kernel, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, pid, n, w, cluster_size,
-                       maj_hits, maj_pid, maj_pid_hits, maj_pt, maj_eta, maj_reco);
+    hipLaunchKernelGGL(tm_table_kernel, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, particle_id, n, w, cluster_size,
+                       maj_hits, maj_pid, maj_pid_hits, maj_pt, maj_eta, maj_reconstructable);
     return check_launch("cluster_table: rows");
 }
 
-}  // namespace gnntrk
+}  // extern "C"
