@@ -366,7 +366,7 @@ def condensation_loss_tiger(*, beta, x, particle_id, mask, q_min=0.01) -> dict:
 
 
 def condensation_loss_chunked(*, beta, x, particle_id, mask, mode: str, q_min=0.01, radius=1.0,
-                              weights=(1.0, 1.0, 0.0, 0.0), chunk: int = 4096) -> dict:
+                              weights=(1.0, 1.0, 0.0, 0.0), chunk: int = 4096, norm_att_fp64: bool = False) -> dict:
     """The two functions above in float64 with O(chunk x K) memory: the same sums taken
     over blocks of hits, loss terms and the gradient of ``att + w_rep rep + w_coward coward
     + w_noise noise`` w.r.t. (x, beta) accumulated block by block.  It exists so that the
@@ -376,7 +376,13 @@ def condensation_loss_chunked(*, beta, x, particle_id, mask, mode: str, q_min=0.
     cases.  ``mode``: "rg" (oc.py:87-161; condensation points from the masked hits,
     attraction of masked non-CP hits, repulsion 1 - sqrt(1e-9 + d2) inside the unit ball) or
     "tiger" (oc.py:251-347; condensation points = arg-max charge over ALL hits of a
-    particle of interest, attraction of all its hits, repulsion 1 - d)."""
+    particle of interest, attraction of all its hits, repulsion 1 - d).
+
+    ``norm_att_fp64``: the reference's ``eps + n_hits_oi - n_particles_oi`` is float + int64 tensor, i.e. fp32: the
+    1e-9 is lost, and an event in which every hit of interest is its own particle has ``norm_att`` = 0 and a 0/0
+    attractive term.  With this switch the formula is taken as written (fp64: 1e-9 there, attractive term 0, a
+    condensation point's distance to itself exactly 0), which is what the kernels do; for every other event the two
+    differ by 1e-9 / (n_oi - K)."""
     assert mode in ("rg", "tiger")
     w_att, w_rep, w_cow, w_noise = weights
     N = int(mask.shape[0])
@@ -397,6 +403,8 @@ def condensation_loss_chunked(*, beta, x, particle_id, mask, mode: str, q_min=0.
     K = int(alphas.shape[0])
     pid_k = particle_id[alphas]
     norm_att = float(1e-9 + mask.sum() - K)   # as the reference: float + int64 tensor promotes to fp32
+    if norm_att_fp64:
+        norm_att = 1e-9 + int(mask.sum()) - K
     norm_rep = 1e-9 + (K - 1) * N
     b = beta.detach().double().requires_grad_(True)
     xx = x.detach().double().requires_grad_(True)
@@ -407,6 +415,8 @@ def condensation_loss_chunked(*, beta, x, particle_id, mask, mode: str, q_min=0.
         q = torch.arctanh(b) ** 2 + q_min
         xj, xk, qj, qk = xx[sl], xx[alphas], q[sl], q[alphas]
         d2 = ((xj ** 2).sum(1).view(-1, 1) + (xk ** 2).sum(1).view(1, -1) - 2.0 * xj @ xk.T).clamp_min(0.0)
+        if norm_att_fp64:   # (a point's distance to itself is 0, not the 1e-16 |x|^2 left by the expanded form: / 1e-9)
+            d2 = d2 * (torch.arange(sl.start, sl.stop).view(-1, 1) != alphas.view(1, -1))
         same = particle_id[sl].view(-1, 1) == pid_k.view(1, -1)
         qq = qj.view(-1, 1) * qk.view(1, -1)
         a_sel = same & att_rows[sl].view(-1, 1)
