@@ -29,7 +29,9 @@
 //   capacity (hub nodes) is ranked from global memory in tiles - slower, same result.
 //
 //   Algorithmic bytes per edge: count 8 + split 16 + 8 + sort 8 + 12, then 4 + 4 + 8 + 8 + 8 = 84
-//   (+ 0.3 table entries per edge x 12 B); the library path moved about 260.
+//   (+ 0.3 table entries per edge x 12 B); the library path moved about 260.  Renumbered, with a carried label
+//   and carried rows (the training step): remap with the count inside 16 + 8, split 8 + 1 + 16 in and 16 out (the
+//   row rides in the record), sort 16 in and 12 + 1 + 8 out, then the same 32 by source = 134.
 #include "host_util.h"
 #include "tile_bf16.h"
 
@@ -38,7 +40,13 @@ namespace gnntrk {
 constexpr int kTpb = 256;
 
 #ifndef GNNTRK_REMAP_NT
-#define GNNTRK_REMAP_NT 3   // (bit 0: non-temporal id loads, bit 1: non-temporal stores of gi_remap_kernel - A/B builds)
+#define GNNTRK_REMAP_NT 3   // (bit 0: non-temporal id loads, bit 1: non-temporal stores, bit 3: non-temporal table lookups of the remap pass - A/B builds)
+#endif
+#ifndef GNNTRK_GI_REMAP_COUNT
+#define GNNTRK_GI_REMAP_COUNT 1   // (0: the remap as a pass of its own, then gi_count_kernel<KeysCoo32> over what it wrote - A/B builds)
+#endif
+#ifndef GNNTRK_NO_KEY_COPY
+#define GNNTRK_NO_KEY_COPY 1   // (0: both node-order passes walk the key column at the caller's row stride - A/B builds)
 #endif
 #ifndef GNNTRK_NO_LIBRARY_SORT_OFF
 #define GNNTRK_NO_LIBRARY_SORT_OFF 0   // (1: gnntrk_node_order always takes the exact radix form - A/B builds)
@@ -79,8 +87,8 @@ constexpr int kScanTpb = 256, kScanItems = 16, kScanTile = kScanTpb * kScanItems
 
 // first sort: key = target (COO row 1), payload = source (row 0), value = edge id.  Two per-edge
 // inputs of the caller can ride along into CSR order (gnntrk_graph_index_carry): a 1-byte label in
-// bit 31 of the value (edge ids are below 2^31), a row of four floats as four bf16 in a second
-// 8-byte record array
+// bit 31 of the value (edge ids are below 2^31), a row of four floats as four bf16 in the second
+// half of a 16-byte record
 struct KeysCoo {
     const int64_t *src, *tgt;
     int64_t N;
@@ -170,10 +178,11 @@ struct KeysCoo {
         return *reinterpret_cast<const f32x4 *>(rows + e * rows_stride);
     }
 };
-// first sort over a RENUMBERED edge list (gnntrk_graph_index_carry.node_rank): gi_remap_kernel has written both
-// endpoint rows as validated int32 new ids (one streaming pass with every lane's eight table lookups in flight:
+// first sort over a RENUMBERED edge list (gnntrk_graph_index_carry.node_rank): gi_remap_count_kernel has written
+// both endpoint rows as validated int32 new ids (one streaming pass with every lane's eight table lookups in flight:
 // inside the count / split kernels, whose occupancy is one workgroup per CU, the same lookups cost 1.7 ms per
-// 64 M edges, here about a third of that); the count and split then read 4 + 8 bytes per edge instead of 8 + 16
+// 64 M edges, here under half of that) and has counted the targets on the way; the split then reads 8 bytes per
+// edge instead of 16
 struct KeysCoo32 {
     const int32_t *src, *tgt;
     const uint8_t *label;
@@ -249,11 +258,12 @@ struct KeysCoo32 {
     }
 };
 // both endpoint rows of the COO list through the renumbering: ids checked (counted, clamped), translated, written
-// as int32.  A lane takes four consecutive edges: 16-byte id loads, eight lookups in flight, 16-byte stores.
-__global__ __launch_bounds__(kTpb) void gi_remap_kernel(const int64_t *__restrict__ src, const int64_t *__restrict__ tgt,
-                                                        int64_t E, int64_t N, const int32_t *__restrict__ rank, int vec,
-                                                        int32_t *__restrict__ src32, int32_t *__restrict__ tgt32,
-                                                        int *__restrict__ bad) {
+// as int32.  A lane takes four consecutive edges e .. e + 3 (e a multiple of four, e1 = end of the lane's range):
+// 16-byte id loads, eight lookups in flight, 16-byte stores.  kt[] = the translated targets (0 past e1).
+__device__ __forceinline__ void gi_remap4(const int64_t *__restrict__ src, const int64_t *__restrict__ tgt, int64_t e,
+                                          int64_t e1, int64_t N, const int32_t *__restrict__ rank, int vec,
+                                          int32_t *__restrict__ src32, int32_t *__restrict__ tgt32,
+                                          int *__restrict__ bad, uint32_t kt[4]) {
     auto chk = [&](long long v) -> long long {
         if (v < 0 || v >= N) {
             atomicAdd(bad, 1);
@@ -261,53 +271,73 @@ __global__ __launch_bounds__(kTpb) void gi_remap_kernel(const int64_t *__restric
         }
         return v;
     };
-    const int64_t n4 = (E + 3) / 4;
-    for (int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kTpb) {
-        const int64_t e = 4 * i;
-        if (vec && e + 4 <= E) {
-            // (the id streams and the outputs pass through once: non-temporal, the lookup table keeps the L2)
-            typedef int i4_hw __attribute__((ext_vector_type(4)));
-            auto ld2 = [](const int64_t *p, long long &a, long long &b) {   // two ids as one 16-byte non-temporal load
-#if GNNTRK_REMAP_NT & 1
-                const i4_hw v = __builtin_nontemporal_load(reinterpret_cast<const i4_hw *>(p));
-#else
-                const i4_hw v = *reinterpret_cast<const i4_hw *>(p);
-#endif
-                a = (long long)(((unsigned long long)(uint32_t)v[1] << 32) | (uint32_t)v[0]);
-                b = (long long)(((unsigned long long)(uint32_t)v[3] << 32) | (uint32_t)v[2]);
-            };
-            long long it[4], is[4];
-            ld2(tgt + e, it[0], it[1]);
-            ld2(tgt + e + 2, it[2], it[3]);
-            ld2(src + e, is[0], is[1]);
-            ld2(src + e + 2, is[2], is[3]);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                it[q] = chk(it[q]);
-                is[q] = chk(is[q]);
-            }
+    auto look = [&](long long v) -> int {
 #if GNNTRK_REMAP_NT & 4   // (timing probe: no table lookups - results are NOT a renumbering)
-            const i4_hw ot = {(int)it[0], (int)it[1], (int)it[2], (int)it[3]};
-            const i4_hw os = {(int)is[0], (int)is[1], (int)is[2], (int)is[3]};
+        return (int)v;
+#elif GNNTRK_REMAP_NT & 8
+        return __builtin_nontemporal_load(rank + v);
 #else
-            const i4_hw ot = {rank[it[0]], rank[it[1]], rank[it[2]], rank[it[3]]};
-            const i4_hw os = {rank[is[0]], rank[is[1]], rank[is[2]], rank[is[3]]};
+        return rank[v];
 #endif
+    };
+    if (vec && e + 4 <= e1) {
+        // (the id streams and the outputs pass through once: non-temporal, the lookup table keeps the L2)
+        typedef int i4_hw __attribute__((ext_vector_type(4)));
+        auto ld2 = [](const int64_t *p, long long &a, long long &b) {   // two ids as one 16-byte non-temporal load
+#if GNNTRK_REMAP_NT & 1
+            const i4_hw v = __builtin_nontemporal_load(reinterpret_cast<const i4_hw *>(p));
+#else
+            const i4_hw v = *reinterpret_cast<const i4_hw *>(p);
+#endif
+            a = (long long)(((unsigned long long)(uint32_t)v[1] << 32) | (uint32_t)v[0]);
+            b = (long long)(((unsigned long long)(uint32_t)v[3] << 32) | (uint32_t)v[2]);
+        };
+        long long it[4], is[4];
+        ld2(tgt + e, it[0], it[1]);
+        ld2(tgt + e + 2, it[2], it[3]);
+        ld2(src + e, is[0], is[1]);
+        ld2(src + e + 2, is[2], is[3]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            it[q] = chk(it[q]);
+            is[q] = chk(is[q]);
+        }
+        const i4_hw ot = {look(it[0]), look(it[1]), look(it[2]), look(it[3])};
+        const i4_hw os = {look(is[0]), look(is[1]), look(is[2]), look(is[3])};
 #if GNNTRK_REMAP_NT & 2
-            __builtin_nontemporal_store(ot, reinterpret_cast<i4_hw *>(tgt32 + e));
-            __builtin_nontemporal_store(os, reinterpret_cast<i4_hw *>(src32 + e));
+        __builtin_nontemporal_store(ot, reinterpret_cast<i4_hw *>(tgt32 + e));
+        __builtin_nontemporal_store(os, reinterpret_cast<i4_hw *>(src32 + e));
 #else
-            *reinterpret_cast<i4_hw *>(tgt32 + e) = ot;
-            *reinterpret_cast<i4_hw *>(src32 + e) = os;
+        *reinterpret_cast<i4_hw *>(tgt32 + e) = ot;
+        *reinterpret_cast<i4_hw *>(src32 + e) = os;
 #endif
-        } else {
-            for (int q = 0; q < 4 && e + q < E; ++q) {
-                tgt32[e + q] = rank[chk(tgt[e + q])];
-                src32[e + q] = rank[chk(src[e + q])];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) kt[q] = (uint32_t)ot[q];
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            kt[q] = 0u;
+            if (e + q < e1) {
+                const int t = look(chk(tgt[e + q])), u = look(chk(src[e + q]));
+                tgt32[e + q] = t;
+                src32[e + q] = u;
+                kt[q] = (uint32_t)t;
             }
         }
     }
 }
+#if !GNNTRK_GI_REMAP_COUNT
+__global__ __launch_bounds__(kTpb) void gi_remap_kernel(const int64_t *__restrict__ src, const int64_t *__restrict__ tgt,
+                                                        int64_t E, int64_t N, const int32_t *__restrict__ rank, int vec,
+                                                        int32_t *__restrict__ src32, int32_t *__restrict__ tgt32,
+                                                        int *__restrict__ bad) {
+    const int64_t n4 = (E + 3) / 4;
+    for (int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kTpb) {
+        uint32_t kt[4];
+        gi_remap4(src, tgt, 4 * i, E, N, rank, vec, src32, tgt32, bad, kt);
+    }
+}
+#endif
 // second sort: key = source of the CSR-ordered list (already validated), value = CSR position
 struct KeysCsr {
     const int32_t *src;
@@ -359,8 +389,75 @@ __device__ __forceinline__ int gi_window_start(uint32_t first_key) {
     return b < 0 ? 0 : b;
 }
 
+// Which chunk a workgroup of gi_remap_count_kernel takes.  Workgroups b and b + 8 are observed to share an XCD
+// (nothing promises it: it buys speed only), so a run of consecutive chunks goes to ONE XCD, whose L2 then holds the
+// renumbering tables of those chunks' events instead of a little of every event's.  The grid is
+// gi_chunk_grid(n_chunks) workgroups; a chunk >= n_chunks is none.  (The split gains nothing from this order:
+// 788 against 790 us per 64 M edges.)
+#ifndef GNNTRK_GI_REMAP_XCD
+#define GNNTRK_GI_REMAP_XCD 1   // (0: gi_remap_count_kernel takes its chunks in launch order - A/B builds)
+#endif
+constexpr int kXcd = 8;
+__device__ __forceinline__ int gi_chunk_of_block() {
+#if GNNTRK_GI_REMAP_XCD
+    return (int)(blockIdx.x % kXcd) * (int)(gridDim.x / kXcd) + (int)(blockIdx.x / kXcd);
+#else
+    return (int)blockIdx.x;
+#endif
+}
+static int gi_chunk_grid(int n_chunks) { return (n_chunks + kXcd - 1) / kXcd * kXcd; }
+
 // step 1.  tbl[bucket * n_chunks + chunk] = edges of the chunk in the bucket (tbl zeroed before);
-// range[chunk] = (first, last) touched window slot
+// range[chunk] = (first, last) touched window slot.
+// The keys k4[] of a lane's four consecutive edges e .. e + 3 into the chunk's counters
+// (consecutive edges of an ordered list share their bucket: one counter update per run of a lane's four)
+__device__ __forceinline__ void gi_count4(const uint32_t k4[4], int64_t e, int64_t e1, int w0, uint32_t *s_cnt,
+                                          uint32_t *__restrict__ tbl, int n_chunks, int c) {
+    auto bump = [&](uint32_t b, uint32_t by) {
+        const uint32_t d = b - (uint32_t)w0;
+        if (d < (uint32_t)kWin)
+            atomicAdd(&s_cnt[d], by);
+        else
+            atomicAdd(&tbl[(size_t)b * n_chunks + c], by);
+    };
+    uint32_t run_b = k4[0] >> kSH, run_n = 1;
+#pragma unroll
+    for (int q = 1; q < 4; ++q) {
+        if (e + q >= e1) break;
+        const uint32_t b = k4[q] >> kSH;
+        if (b == run_b) {
+            run_n += 1;
+        } else {
+            bump(run_b, run_n);
+            run_b = b;
+            run_n = 1;
+        }
+    }
+    bump(run_b, run_n);
+}
+// the chunk's window into the table, its touched range into range[c] (all threads of the workgroup; s_lo / s_hi
+// start at kWin / -1)
+template <int TPB>
+__device__ __forceinline__ void gi_count_flush(const uint32_t *s_cnt, int *s_lo, int *s_hi, int w0, int n_chunks, int c,
+                                               uint32_t *__restrict__ tbl, int2 *__restrict__ range) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    int lo = kWin, hi = -1;
+    for (int d = tid; d < kWin; d += TPB) {
+        const uint32_t v = s_cnt[d];
+        if (v) {
+            tbl[(size_t)(w0 + d) * n_chunks + c] = v;
+            lo = d < lo ? d : lo;
+            hi = d > hi ? d : hi;
+        }
+    }
+    if (hi >= 0) {
+        atomicMin(s_lo, lo);
+        atomicMax(s_hi, hi);
+    }
+    __syncthreads();
+    if (tid == 0) range[c] = int2{*s_lo, *s_hi};
+}
 template <class K>
 __global__ __launch_bounds__(kCountTpb) void gi_count_kernel(K keys, int64_t E, int chunk, int n_chunks, int NB,
                                                              uint32_t *__restrict__ tbl, int2 *__restrict__ range,
@@ -379,49 +476,55 @@ __global__ __launch_bounds__(kCountTpb) void gi_count_kernel(K keys, int64_t E, 
     for (int64_t e = e0 + 4 * tid; e < e1; e += 4 * kCountTpb) {
         uint32_t k4[4];
         keys.keys4(e, e1, k4, bad);
-        // (consecutive edges of an ordered list share their bucket: one counter update per run of a lane's four)
-        auto bump = [&](uint32_t b, uint32_t by) {
-            const uint32_t d = b - (uint32_t)w0;
-            if (d < (uint32_t)kWin)
-                atomicAdd(&s_cnt[d], by);
-            else
-                atomicAdd(&tbl[(size_t)b * n_chunks + c], by);
-        };
-        uint32_t run_b = k4[0] >> kSH, run_n = 1;
-#pragma unroll
-        for (int q = 1; q < 4; ++q) {
-            if (e + q >= e1) break;
-            const uint32_t b = k4[q] >> kSH;
-            if (b == run_b) {
-                run_n += 1;
-            } else {
-                bump(run_b, run_n);
-                run_b = b;
-                run_n = 1;
-            }
-        }
-        bump(run_b, run_n);
+        gi_count4(k4, e, e1, w0, s_cnt, tbl, n_chunks, c);
     }
-    __syncthreads();
-    int lo = kWin, hi = -1;
-    for (int d = tid; d < kWin; d += kCountTpb) {
-        const uint32_t v = s_cnt[d];
-        if (v) {
-            tbl[(size_t)(w0 + d) * n_chunks + c] = v;
-            lo = d < lo ? d : lo;
-            hi = d > hi ? d : hi;
-        }
-    }
-    if (hi >= 0) {
-        atomicMin(&s_lo, lo);
-        atomicMax(&s_hi, hi);
-    }
-    __syncthreads();
-    if (tid == 0) range[c] = int2{s_lo, s_hi};
+    gi_count_flush<kCountTpb>(s_cnt, &s_lo, &s_hi, w0, n_chunks, c, tbl, range);
     (void)NB;
 }
+#if GNNTRK_GI_REMAP_COUNT
+// The remap pass in the sort's chunk geometry (one workgroup per chunk), counting the translated targets as it
+// writes them: step 1 of the by-target sort without a pass of its own over tgt32.  The lookups want every lane
+// slot of a CU filled (inside the count / split kernels, one 1024-lane workgroup per CU, they cost 1.7 ms per
+// 64 M edges): two workgroups of 1024 lanes per CU - at most 64 registers, a 16 KB window each.
+constexpr int kRemapTpb = 1024;
+__global__ __launch_bounds__(kRemapTpb, 8) void gi_remap_count_kernel(
+    const int64_t *__restrict__ src, const int64_t *__restrict__ tgt, int64_t E, int64_t N,
+    const int32_t *__restrict__ rank, int vec, int32_t *__restrict__ src32, int32_t *__restrict__ tgt32, int chunk,
+    int n_chunks, uint32_t *__restrict__ tbl, int2 *__restrict__ range, int *__restrict__ bad) {
+    __shared__ uint32_t s_cnt[kWin];
+    __shared__ int s_lo, s_hi, s_w0;
+    // (all chunks are in flight at once, and a chunk's lookups go to its own event's table - 600 KB at 150 k hits: in
+    // launch order every XCD's L2 sees the tables of all 32 events and the whole build takes 4.33 ms, this way 3.57)
+    const int tid = threadIdx.x, c = gi_chunk_of_block();
+    if (c >= n_chunks) return;
+    const int64_t e0 = (int64_t)c * chunk, e1 = e0 + chunk < E ? e0 + chunk : E;
+    for (int d = tid; d < kWin; d += kRemapTpb) s_cnt[d] = 0;
+    if (tid == 0) {
+        s_lo = kWin;
+        s_hi = -1;
+        // the window starts from the chunk's first TRANSLATED target (clamped as the pass below clamps it, counted there)
+        long long v = tgt[e0];
+        v = v < 0 ? 0 : v >= N ? N - 1 : v;
+#if GNNTRK_REMAP_NT & 4
+        s_w0 = gi_window_start((uint32_t)v);
+#else
+        s_w0 = gi_window_start((uint32_t)rank[v]);
+#endif
+    }
+    __syncthreads();
+    const int w0 = s_w0;
+    for (int64_t e = e0 + 4 * tid; e < e1; e += 4 * kRemapTpb) {
+        uint32_t k4[4];
+        gi_remap4(src, tgt, e, e1, N, rank, vec, src32, tgt32, bad, k4);
+        gi_count4(k4, e, e1, w0, s_cnt, tbl, n_chunks, c);
+    }
+    gi_count_flush<kRemapTpb>(s_cnt, &s_lo, &s_hi, w0, n_chunks, c, tbl, range);
+}
+#endif
 
-// step 2: exclusive scan of tbl[0 .. T] in place (tbl[T] = total), three kernels
+// step 2: exclusive scan of tbl[0 .. T] in place (tbl[T] = total), two kernels: the tiles' sums, then every tile
+// scans itself behind the sum of the tiles before it (a tile adds those up itself: a few thousand values out of the
+// L2) and leaves base[b] = the scanned tbl[b * n_chunks], the first record of bucket b (b <= NB), on the way
 __global__ __launch_bounds__(kScanTpb) void gi_scan_sums_kernel(const uint32_t *__restrict__ v, int64_t n,
                                                                 uint32_t *__restrict__ sums) {
     __shared__ uint32_t s[kScanTpb];
@@ -446,34 +549,17 @@ __global__ __launch_bounds__(kScanTpb) void gi_scan_sums_kernel(const uint32_t *
     if (tid == 0) sums[blockIdx.x] = s[0];
 }
 
-__global__ __launch_bounds__(1024) void gi_scan_tiles_kernel(uint32_t *__restrict__ sums, int n) {
-    __shared__ uint32_t s[1024];
-    const int tid = threadIdx.x;
-    const int per = (n + 1023) / 1024;
-    const int lo = tid * per, hi = lo + per < n ? lo + per : n;
-    uint32_t mine = 0;
-    for (int i = lo; i < hi; ++i) mine += sums[i];
-    s[tid] = mine;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const uint32_t v = tid >= d ? s[tid - d] : 0u;
-        __syncthreads();
-        s[tid] += v;
-        __syncthreads();
-    }
-    uint32_t run = s[tid] - mine;
-    for (int i = lo; i < hi; ++i) {
-        const uint32_t c = sums[i];
-        sums[i] = run;
-        run += c;
-    }
-}
-
 __global__ __launch_bounds__(kScanTpb) void gi_scan_apply_kernel(uint32_t *__restrict__ v, int64_t n,
-                                                                 const uint32_t *__restrict__ sums) {
+                                                                 const uint32_t *__restrict__ sums, int n_chunks,
+                                                                 uint32_t *__restrict__ base) {
     __shared__ uint32_t s[kScanTpb];
+    __shared__ uint32_t s_before[kScanTpb / 64];
     const int tid = threadIdx.x;
     const int64_t i0 = (int64_t)blockIdx.x * kScanTile + (int64_t)tid * kScanItems;
+    uint32_t before = 0;   // sum of the tiles before this one
+    for (int i = tid; i < (int)blockIdx.x; i += kScanTpb) before += sums[i];
+    for (int o = 32; o > 0; o >>= 1) before += (uint32_t)__shfl_xor((int)before, o);
+    if ((tid & 63) == 0) s_before[tid >> 6] = before;
     uint32_t x[kScanItems];
     const bool full = i0 + kScanItems <= n;
     if (full) {
@@ -494,18 +580,29 @@ __global__ __launch_bounds__(kScanTpb) void gi_scan_apply_kernel(uint32_t *__res
     for (int q = 0; q < kScanItems; ++q) t += x[q];
     s[tid] = t;
     __syncthreads();
+    before = 0;
+#pragma unroll
+    for (int w = 0; w < kScanTpb / 64; ++w) before += s_before[w];
     for (int d = 1; d < kScanTpb; d <<= 1) {
         const uint32_t u = tid >= d ? s[tid - d] : 0u;
         __syncthreads();
         s[tid] += u;
         __syncthreads();
     }
-    uint32_t run = sums[blockIdx.x] + s[tid] - t;
+    uint32_t run = before + s[tid] - t;
+    // (entries b * n_chunks among the thread's sixteen: the first at `nb`, relative to i0)
+    int64_t bk = (i0 + n_chunks - 1) / n_chunks;
+    int64_t nb = bk * n_chunks - i0;
 #pragma unroll
     for (int q = 0; q < kScanItems; ++q) {
         const uint32_t c = x[q];
         x[q] = run;
         run += c;
+        if (q == nb && i0 + q < n) {
+            base[bk] = x[q];
+            bk += 1;
+            nb += n_chunks;
+        }
     }
     if (full) {
 #pragma unroll
@@ -516,13 +613,6 @@ __global__ __launch_bounds__(kScanTpb) void gi_scan_apply_kernel(uint32_t *__res
         for (int q = 0; q < kScanItems; ++q)
             if (i0 + q < n) v[i0 + q] = x[q];
     }
-}
-
-// base[b] = first record of bucket b (b <= NB), taken before step 3's cursors touch the table
-__global__ __launch_bounds__(kTpb) void gi_bases_kernel(const uint32_t *__restrict__ tbl, int n_chunks, int NB,
-                                                        uint32_t *__restrict__ base) {
-    const int b = blockIdx.x * kTpb + threadIdx.x;
-    if (b <= NB) base[b] = tbl[(size_t)b * n_chunks];
 }
 
 // exclusive scan of one value per thread over a workgroup of kSplitTpb threads (wave shuffles + one
@@ -549,20 +639,34 @@ __device__ __forceinline__ uint32_t gi_block_exscan(uint32_t v, uint32_t *s_wsum
     return pre + inc - v;
 }
 
-// step 3.  part[pos] = {lo: value (edge id [| label << 31] / CSR position), hi: low << pbits | payload}.
+// step 3.  part[pos] = {x: value (edge id [| label << 31] / CSR position), y: low << pbits | payload}.
 // A tile of 4096 edges is first grouped by bucket in LDS (rank inside the tile's bucket from an LDS
 // counter, tile-local starts from a scan over the chunk's touched window range), then written out
 // with consecutive lanes on consecutive records of a run: the stores coalesce.  ROWS: the
-// caller's per-edge rows (four floats -> four bf16) take the same way into part_rows[pos].
+// caller's per-edge row (four floats -> four bf16) is the record's second half {z, w}: one 16-byte
+// record per edge through one staging image.
+template <bool ROWS>
+struct GiRec {
+    typedef uint2 type;
+    static __device__ __forceinline__ uint2 make(uint32_t x, uint32_t y, const f32x4 &) { return uint2{x, y}; }
+};
+template <>
+struct GiRec<true> {
+    typedef uint4 type;
+    static __device__ __forceinline__ uint4 make(uint32_t x, uint32_t y, const f32x4 &rv) {
+        return uint4{x, y, bf16x2_pack(rv[0], rv[1]), bf16x2_pack(rv[2], rv[3])};
+    }
+};
 template <class K, bool ROWS>
 __global__ __launch_bounds__(kSplitTpb, GNNTRK_GI_SPLIT_WG * kSplitTpb / 256) void gi_split_kernel(K keys, int64_t E, int chunk, int n_chunks, int pbits,
                                                              uint32_t *__restrict__ tbl,
                                                              const int2 *__restrict__ range,
-                                                             uint2 *__restrict__ part, uint2 *__restrict__ part_rows,
+                                                             typename GiRec<ROWS>::type *__restrict__ part,
                                                              int *__restrict__ bad) {
+    typedef typename GiRec<ROWS>::type Rec;
     __shared__ uint32_t s_off[kWin];     // next free record of the (bucket, chunk) run
     __shared__ uint32_t s_cnt[kWin];     // tile: records per bucket, then the tile-local start
-    __shared__ uint2 s_stage[kSplitTile];
+    __shared__ Rec s_stage[kSplitTile];
     __shared__ uint16_t s_slot[kSplitTile];
     __shared__ uint32_t s_wsum[kSplitTpb / 64];
     const int tid = threadIdx.x, c = blockIdx.x;
@@ -605,11 +709,7 @@ __global__ __launch_bounds__(kSplitTpb, GNNTRK_GI_SPLIT_WG * kSplitTpb / 256) vo
                         rk[q] = atomicAdd(&s_cnt[d], 1u);
                     } else {   // outside the chunk's LDS window: cursor in the table itself, direct stores
                         const uint32_t pos = atomicAdd(&tbl[(size_t)b * n_chunks + c], 1u);
-                        part[pos] = rec[q];
-                        if (ROWS) {
-                            const f32x4 rv = rraw[q];
-                            part_rows[pos] = uint2{bf16x2_pack(rv[0], rv[1]), bf16x2_pack(rv[2], rv[3])};
-                        }
+                        part[pos] = GiRec<ROWS>::make(rec[q].x, rec[q].y, rraw[ROWS ? q : 0]);
                     }
                 }
             }
@@ -631,32 +731,17 @@ __global__ __launch_bounds__(kSplitTpb, GNNTRK_GI_SPLIT_WG * kSplitTpb / 256) vo
                 run += cn;
             }
         __syncthreads();
-        uint32_t sp[kSplitR];
 #pragma unroll
         for (int q = 0; q < kSplitR; ++q)
             if (slot[q] != 0xffffffffu) {
-                sp[q] = s_cnt[slot[q]] + rk[q];
-                s_stage[sp[q]] = rec[q];
-                s_slot[sp[q]] = (uint16_t)slot[q];
+                const uint32_t spq = s_cnt[slot[q]] + rk[q];
+                s_stage[spq] = GiRec<ROWS>::make(rec[q].x, rec[q].y, rraw[ROWS ? q : 0]);
+                s_slot[spq] = (uint16_t)slot[q];
             }
         __syncthreads();
         for (uint32_t j = tid; j < tile_n; j += kSplitTpb) {
             const uint32_t d = s_slot[j];
             part[s_off[d] - s_cnt[d] + j] = s_stage[j];
-        }
-        if (ROWS) {   // the rows through the same staging image
-            __syncthreads();
-#pragma unroll
-            for (int q = 0; q < kSplitR; ++q)
-                if (slot[q] != 0xffffffffu) {
-                    const f32x4 rv = rraw[q];
-                    s_stage[sp[q]] = uint2{bf16x2_pack(rv[0], rv[1]), bf16x2_pack(rv[2], rv[3])};
-                }
-            __syncthreads();
-            for (uint32_t j = tid; j < tile_n; j += kSplitTpb) {
-                const uint32_t d = s_slot[j];
-                part_rows[s_off[d] - s_cnt[d] + j] = s_stage[j];
-            }
         }
         __syncthreads();
         // advance the run cursors by the tile's counts (count = next start - own start; the last
@@ -675,65 +760,78 @@ __global__ __launch_bounds__(kSplitTpb, GNNTRK_GI_SPLIT_WG * kSplitTpb / 256) vo
     }
 }
 
-// step 4 outputs.  kValMask: bits of a record's value that order it; kPos: the kernel keeps the
-// slot -> partition position map (the carried rows are fetched from part_rows at write-out)
+// step 4 outputs.  kValMask: bits of a record's value that order it; kRows: 16-byte records whose second half is
+// the carried row (row(): the row of final position k)
 template <bool ROWS>
 struct OutCsr {   // first sort
     static constexpr uint32_t kValMask = 0x7fffffffu;
-    static constexpr bool kPos = ROWS;
+    static constexpr bool kRows = ROWS;
     int32_t *perm, *tgt, *src, *rowptr;
     uint32_t pmask;
     uint8_t *label_csr;
-    const uint2 *part_rows;
     uint16_t *rows_csr;
     int rows_out_stride;
-    __device__ __forceinline__ void ranked(uint32_t k, uint32_t val, uint32_t hi, uint32_t pos) const {
+    __device__ __forceinline__ void ranked(uint32_t k, uint32_t val, uint32_t hi) const {
         perm[k] = (int32_t)(val & kValMask);
         src[k] = (int32_t)(hi & pmask);
         if (label_csr) label_csr[k] = (uint8_t)(val >> 31);
-        if (ROWS) *reinterpret_cast<uint2 *>(rows_csr + (size_t)k * rows_out_stride) = part_rows[pos];
+    }
+    __device__ __forceinline__ void row(uint32_t k, uint2 r) const {
+        if (ROWS) *reinterpret_cast<uint2 *>(rows_csr + (size_t)k * rows_out_stride) = r;
     }
     __device__ __forceinline__ void slot(uint32_t k, uint32_t node) const { tgt[k] = (int32_t)node; }
 };
 struct OutSrc {   // second sort
     static constexpr uint32_t kValMask = 0xffffffffu;
-    static constexpr bool kPos = false;
+    static constexpr bool kRows = false;
     int32_t *spos, *spos_inv, *rowptr;
-    __device__ __forceinline__ void ranked(uint32_t k, uint32_t val, uint32_t, uint32_t) const {
+    __device__ __forceinline__ void ranked(uint32_t k, uint32_t val, uint32_t) const {
         spos[k] = (int32_t)val;
         if (spos_inv) spos_inv[val] = (int32_t)k;
     }
+    __device__ __forceinline__ void row(uint32_t, uint2) const {}
     __device__ __forceinline__ void slot(uint32_t, uint32_t) const {}
 };
 
 template <class O>
-__global__ __launch_bounds__(kSortTpb) void gi_bucket_sort_kernel(const uint2 *__restrict__ part,
+__global__ __launch_bounds__(kSortTpb) void gi_bucket_sort_kernel(const typename GiRec<O::kRows>::type *__restrict__ part_,
                                                                   const uint32_t *__restrict__ base_arr, int NB,
                                                                   int64_t N, int64_t E, int pbits, int chunk, O out) {
     constexpr uint32_t VM = O::kValMask;
+    // the records as 8-byte halves: half kRS * i is record i's {value, low | payload}, the half behind it its row
+    constexpr uint32_t kRS = O::kRows ? 2 : 1;
+    const uint2 *__restrict__ part = reinterpret_cast<const uint2 *>(part_);
     __shared__ uint32_t s_hist[kBins], s_start[kBins], s_wsum[kBins / 64];
     __shared__ uint2 s_rec[kCap];
-    __shared__ uint16_t s_pos[O::kPos ? kCap : 1];
+    __shared__ uint16_t s_fin[O::kRows ? kCap : 1];   // slot after the first placement -> final slot
     const int tid = threadIdx.x, b = blockIdx.x, lane = tid & 63, wv = tid >> 6;
     const uint32_t base = base_arr[b], M = base_arr[b + 1] - base;
+    part += (size_t)base * kRS;   // (the bucket's region)
     const uint32_t node0 = (uint32_t)b << kSH;
     const bool fits = M <= (uint32_t)kCap;
     if (tid < kBins) s_hist[tid] = 0;
     __syncthreads();
     // the bucket's records: all loads of a thread in flight at once, kept in registers until placed
-    uint2 rec[kSortR];
+    // (with rows: the row half stays with the thread that loaded it until the record's final slot is known)
+    uint2 rec[kSortR], rrow[O::kRows ? kSortR : 1];
     uint32_t ord[kSortR];
     if (fits) {
 #pragma unroll
         for (int q = 0; q < kSortR; ++q) {
             const uint32_t i = tid + q * kSortTpb;
-            rec[q] = i < M ? part[base + i] : uint2{0u, 0u};
+            if constexpr (O::kRows) {
+                const uint4 v = i < M ? part_[base + i] : uint4{0u, 0u, 0u, 0u};
+                rec[q] = uint2{v.x, v.y};
+                rrow[q] = uint2{v.z, v.w};
+            } else {
+                rec[q] = i < M ? part[i] : uint2{0u, 0u};
+            }
         }
 #pragma unroll
         for (int q = 0; q < kSortR; ++q)
             if (tid + q * kSortTpb < M) ord[q] = atomicAdd(&s_hist[rec[q].y >> pbits], 1u);
     } else {
-        for (uint32_t i = tid; i < M; i += kSortTpb) atomicAdd(&s_hist[part[base + i].y >> pbits], 1u);
+        for (uint32_t i = tid; i < M; i += kSortTpb) atomicAdd(&s_hist[part[(size_t)i * kRS].y >> pbits], 1u);
     }
     __syncthreads();
     // exclusive scan of the 256 node counts (waves 0..3: shuffle scan + wave totals)
@@ -765,14 +863,13 @@ __global__ __launch_bounds__(kSortTpb) void gi_bucket_sort_kernel(const uint2 *_
             if (tid + q * kSortTpb < M) {
                 const uint32_t sl = s_start[rec[q].y >> pbits] + ord[q];
                 s_rec[sl] = rec[q];
-                if (O::kPos) s_pos[sl] = (uint16_t)(tid + q * kSortTpb);
+                ord[q] = sl;
             }
         __syncthreads();
         // rank every record inside its node's list, then bring the image into the final order in place, so
         // that the arrays leave with consecutive lanes on consecutive positions (a wave's store touches a few
         // lines instead of up to 64)
         uint32_t dst[kSortR];
-        uint16_t ps[O::kPos ? kSortR : 1];
 #pragma unroll
         for (int q = 0; q < kSortR; ++q) {
             const uint32_t j = tid + q * kSortTpb;
@@ -783,21 +880,26 @@ __global__ __launch_bounds__(kSortTpb) void gi_bucket_sort_kernel(const uint2 *_
                 for (uint32_t t = 0; t < n; ++t) cnt += (s_rec[st + t].x & VM) < (r.x & VM) ? 1u : 0u;
                 rec[q] = r;
                 dst[q] = st + cnt;
-                if (O::kPos) ps[q] = s_pos[j];
+                if (O::kRows) s_fin[j] = (uint16_t)dst[q];
                 out.slot(base + j, node0 + low);
             }
         }
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < kSortR; ++q)
-            if (tid + q * kSortTpb < M) {
-                s_rec[dst[q]] = rec[q];
-                if (O::kPos) s_pos[dst[q]] = ps[q];
-            }
+            if (tid + q * kSortTpb < M) s_rec[dst[q]] = rec[q];
         __syncthreads();
         for (uint32_t j = tid; j < M; j += kSortTpb) {
             const uint2 r = s_rec[j];
-            out.ranked(base + j, r.x, r.y, base + (O::kPos ? (uint32_t)s_pos[j] : 0u));
+            out.ranked(base + j, r.x, r.y);
+        }
+        if (O::kRows) {   // the rows through the same image, from the threads that hold them
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < kSortR; ++q)
+                if (tid + q * kSortTpb < M) s_rec[s_fin[ord[q]]] = rrow[O::kRows ? q : 0];
+            __syncthreads();
+            for (uint32_t j = tid; j < M; j += kSortTpb) out.row(base + j, s_rec[j]);
         }
     } else {
         // a bucket beyond the LDS capacity: groups of consecutive nodes whose lists fit are taken one
@@ -805,8 +907,11 @@ __global__ __launch_bounds__(kSortTpb) void gi_bucket_sort_kernel(const uint2 *_
         // node beyond the capacity (a hub) is ranked against tiles of its own list streamed through
         // LDS - quadratic in the hub's degree, same result
         __shared__ uint32_t s_cur[kBins];
-        // (with carried rows the last third of the record image holds 32-bit partition positions)
-        constexpr uint32_t kCapG = O::kPos ? (uint32_t)kCap * 2 / 3 : (uint32_t)kCap;
+        // (with carried rows the last third of the record image holds 32-bit positions in the bucket's region: the
+        // row is fetched from its record at write-out)
+        constexpr uint32_t kCapG = O::kRows ? (uint32_t)kCap * 2 / 3 : (uint32_t)kCap;
+        auto row_at = [&](uint32_t i) { return part[(size_t)i * kRS + (kRS - 1)]; };
+        (void)row_at;
         uint32_t *s_pos32 = reinterpret_cast<uint32_t *>(s_rec + kCapG);
         int g0 = 0;
         while (g0 < kBins) {
@@ -826,7 +931,7 @@ __global__ __launch_bounds__(kSortTpb) void gi_bucket_sort_kernel(const uint2 *_
                 for (int t = tid; t < 2 * kMaxChunks; t += kSortTpb) h_all[t] = 0u;
                 __syncthreads();
                 for (uint32_t i = tid; i < M; i += kSortTpb) {
-                    const uint2 r = part[base + i];
+                    const uint2 r = part[(size_t)i * kRS];
                     const uint32_t ck = (r.x & VM) / (uint32_t)chunk;
                     atomicAdd(&h_all[ck], 1u);
                     if ((int)(r.y >> pbits) == g0) atomicAdd(&h_hub[ck], 1u);
@@ -845,16 +950,17 @@ __global__ __launch_bounds__(kSortTpb) void gi_bucket_sort_kernel(const uint2 *_
                 __syncthreads();
                 if (n <= (uint32_t)GNNTRK_GI_HUB_BITMAP_MIN) {   // a walk over the record's own run
                     for (uint32_t i = tid; i < M; i += kSortTpb) {
-                        const uint2 r = part[base + i];
+                        const uint2 r = part[(size_t)i * kRS];
                         if ((int)(r.y >> pbits) != g0) continue;
                         const uint32_t ck = (r.x & VM) / (uint32_t)chunk;
                         const uint32_t r0 = h_all[ck], r1 = ck + 1 < (uint32_t)kMaxChunks ? h_all[ck + 1] : M;
                         uint32_t cnt = h_hub[ck];
                         for (uint32_t t = r0; t < r1; ++t) {
-                            const uint2 q = part[base + t];
+                            const uint2 q = part[(size_t)t * kRS];
                             cnt += ((int)(q.y >> pbits) == g0 && (q.x & VM) < (r.x & VM)) ? 1u : 0u;
                         }
-                        out.ranked(base + st0 + cnt, r.x, r.y, base + i);
+                        out.ranked(base + st0 + cnt, r.x, r.y);
+                        if (O::kRows) out.row(base + st0 + cnt, row_at(i));
                     }
                 } else {
                     // a large hub: the values of a run are distinct ids of ONE chunk, so the hub records of a run
@@ -874,7 +980,7 @@ __global__ __launch_bounds__(kSortTpb) void gi_bucket_sort_kernel(const uint2 *_
                             for (uint32_t w = tid; w < kSpanW; w += kSortTpb) bm[w] = 0u;
                             __syncthreads();
                             for (uint32_t t = r0 + tid; t < r1; t += kSortTpb) {
-                                const uint2 q = part[base + t];
+                                const uint2 q = part[(size_t)t * kRS];
                                 const uint32_t d = (q.x & VM) - lo;
                                 if ((int)(q.y >> pbits) == g0 && d < kSpan) atomicOr(&bm[d >> 5], 1u << (d & 31u));
                             }
@@ -903,12 +1009,13 @@ __global__ __launch_bounds__(kSortTpb) void gi_bucket_sort_kernel(const uint2 *_
                             }
                             __syncthreads();
                             for (uint32_t t = r0 + tid; t < r1; t += kSortTpb) {
-                                const uint2 q = part[base + t];
+                                const uint2 q = part[(size_t)t * kRS];
                                 const uint32_t d = (q.x & VM) - lo;
                                 if ((int)(q.y >> pbits) == g0 && d < kSpan) {
                                     const uint32_t w = d >> 5;
                                     const uint32_t below = (uint32_t)__popc(bm[w] & ((1u << (d & 31u)) - 1u));
-                                    out.ranked(base + st0 + before + pw[w] + below, q.x, q.y, base + t);
+                                    out.ranked(base + st0 + before + pw[w] + below, q.x, q.y);
+                                    if (O::kRows) out.row(base + st0 + before + pw[w] + below, row_at(t));
                                 }
                             }
                             before += span_total;
@@ -925,12 +1032,12 @@ __global__ __launch_bounds__(kSortTpb) void gi_bucket_sort_kernel(const uint2 *_
             if (tid < kBins) s_cur[tid] = 0;
             __syncthreads();
             for (uint32_t i = tid; i < M; i += kSortTpb) {
-                const uint2 r = part[base + i];
+                const uint2 r = part[(size_t)i * kRS];
                 const int low = (int)(r.y >> pbits);
                 if (low >= g0 && low < g1) {
                     const uint32_t sl = s_start[low] - st0 + atomicAdd(&s_cur[low], 1u);
                     s_rec[sl] = r;
-                    if (O::kPos) s_pos32[sl] = i;
+                    if (O::kRows) s_pos32[sl] = i;
                 }
             }
             __syncthreads();
@@ -939,7 +1046,8 @@ __global__ __launch_bounds__(kSortTpb) void gi_bucket_sort_kernel(const uint2 *_
                 const uint32_t low = r.y >> pbits, st = s_start[low] - st0, n = s_hist[low];
                 uint32_t cnt = 0;
                 for (uint32_t t = 0; t < n; ++t) cnt += (s_rec[st + t].x & VM) < (r.x & VM) ? 1u : 0u;
-                out.ranked(base + st0 + st + cnt, r.x, r.y, base + (O::kPos ? s_pos32[j] : 0u));
+                out.ranked(base + st0 + st + cnt, r.x, r.y);
+                if (O::kRows) out.row(base + st0 + st + cnt, row_at(s_pos32[j]));
                 out.slot(base + st0 + j, node0 + low);
             }
             g0 = g1;
@@ -947,13 +1055,14 @@ __global__ __launch_bounds__(kSortTpb) void gi_bucket_sort_kernel(const uint2 *_
     }
 }
 
+constexpr size_t kHeader = 256;   // flag words in front of a sort's workspace (first word: ids out of range)
 struct OwnPlan {
     bool ok;      // the own sort can run this shape
     bool dense;   // ... but most buckets would overflow the LDS capacity: the library form is faster
     int NB, n_chunks, chunk, bitsN;
     int64_t T;   // table entries (+ 1 total)
     int n_tiles;
-    size_t off_range, off_base, off_tbl, off_sums, off_part, off_rows, bytes;
+    size_t off_range, off_base, off_tbl, off_sums, off_part, bytes;
 };
 
 static int bits_for(int64_t n) {
@@ -983,44 +1092,51 @@ static OwnPlan own_plan(int64_t N, int64_t E, bool rows) {
     // graph whose every bucket fits.)
     p.dense = E / p.NB > kCap * 9 / 10;
     p.n_tiles = (int)ceil_div(p.T + 1, kScanTile);
-    size_t o = 256;
+    // (the table follows the 256-byte header - the caller's flag words - so that one fill zeroes both)
+    size_t o = kHeader;
+    p.off_tbl = o;
+    o += align_up((size_t)(p.T + 1) * 4, 256);
     p.off_range = o;
     o += align_up((size_t)p.n_chunks * sizeof(int2), 256);
     p.off_base = o;
     o += align_up((size_t)(p.NB + 1) * 4, 256);
-    p.off_tbl = o;
-    o += align_up((size_t)(p.T + 1) * 4, 256);
     p.off_sums = o;
     o += align_up((size_t)p.n_tiles * 4, 256);
-    p.off_part = o;
-    o += align_up((size_t)E * 8, 256);
-    p.off_rows = o;   // the carried rows in partition order
-    if (rows) o += align_up((size_t)E * 8, 256);
+    p.off_part = o;   // (with carried rows: 16-byte records)
+    o += align_up((size_t)E * (rows ? 16 : 8), 256);
     p.bytes = o;
     p.ok = true;
     return p;
 }
 
+// zeroes the table, with `header` the flag words in front of it as well: one fill per sort
+static int own_zero(const OwnPlan &p, char *ws, bool header, hipStream_t stream) {
+    char *from = ws + (header ? 0 : p.off_tbl);
+    return check_hip(hipMemsetAsync(from, 0, (header ? p.off_tbl : 0) + (size_t)(p.T + 1) * 4, stream),
+                     "graph_index_build(memset)");
+}
+
+// kZero: 0 = the caller has zeroed the table AND run step 1 (gi_remap_count_kernel), 1 = zero the table,
+// 2 = zero the header in front of it too
 template <class K, class O, bool ROWS>
 static int own_sort(const OwnPlan &p, K keys, O out, int pbits, int64_t N, int64_t E, char *ws, int *bad,
-                    hipStream_t stream) {
+                    int zero, hipStream_t stream) {
     int2 *range = reinterpret_cast<int2 *>(ws + p.off_range);
     uint32_t *base = reinterpret_cast<uint32_t *>(ws + p.off_base);
     uint32_t *tbl = reinterpret_cast<uint32_t *>(ws + p.off_tbl);
     uint32_t *sums = reinterpret_cast<uint32_t *>(ws + p.off_sums);
-    uint2 *part = reinterpret_cast<uint2 *>(ws + p.off_part);
-    int rc = check_hip(hipMemsetAsync(tbl, 0, (size_t)(p.T + 1) * 4, stream), "graph_index_build(memset)");
-    if (rc) return rc;
-    hipLaunchKernelGGL((gi_count_kernel<K>), dim3(p.n_chunks), dim3(kCountTpb), 0, stream, keys, E, p.chunk,
-                       p.n_chunks, p.NB, tbl, range, bad);
+    typename GiRec<ROWS>::type *part = reinterpret_cast<typename GiRec<ROWS>::type *>(ws + p.off_part);
+    if (zero) {
+        const int rc = own_zero(p, ws, zero == 2, stream);
+        if (rc) return rc;
+        hipLaunchKernelGGL((gi_count_kernel<K>), dim3(p.n_chunks), dim3(kCountTpb), 0, stream, keys, E, p.chunk,
+                           p.n_chunks, p.NB, tbl, range, bad);
+    }
     hipLaunchKernelGGL(gi_scan_sums_kernel, dim3(p.n_tiles), dim3(kScanTpb), 0, stream, tbl, p.T + 1, sums);
-    hipLaunchKernelGGL(gi_scan_tiles_kernel, dim3(1), dim3(1024), 0, stream, sums, p.n_tiles);
-    hipLaunchKernelGGL(gi_scan_apply_kernel, dim3(p.n_tiles), dim3(kScanTpb), 0, stream, tbl, p.T + 1, sums);
-    hipLaunchKernelGGL(gi_bases_kernel, dim3((int)ceil_div(p.NB + 1, kTpb)), dim3(kTpb), 0, stream, tbl, p.n_chunks,
-                       p.NB, base);
-    uint2 *part_rows = reinterpret_cast<uint2 *>(ws + p.off_rows);
+    hipLaunchKernelGGL(gi_scan_apply_kernel, dim3(p.n_tiles), dim3(kScanTpb), 0, stream, tbl, p.T + 1, sums,
+                       p.n_chunks, base);
     hipLaunchKernelGGL((gi_split_kernel<K, ROWS>), dim3(p.n_chunks), dim3(kSplitTpb), 0, stream, keys, E, p.chunk,
-                       p.n_chunks, pbits, tbl, range, part, part_rows, bad);
+                       p.n_chunks, pbits, tbl, range, part, bad);
     hipLaunchKernelGGL((gi_bucket_sort_kernel<O>), dim3(p.NB), dim3(kSortTpb), 0, stream, part, base, p.NB, N, E,
                        pbits, p.chunk, out);
     return GNNTRK_OK;
@@ -1169,40 +1285,56 @@ static int graph_index_build(const int64_t *edge_index, const gnntrk_graph_index
         return fail(GNNTRK_EINVAL, "graph_index_build: workspace too small");
 
     char *p = reinterpret_cast<char *>(ws);
-    int *bad = reinterpret_cast<int *>(p);
-    int rc = check_hip(hipMemsetAsync(bad, 0, 256, stream), "graph_index_build(memset)");
-    if (rc) return rc;
+    int *bad = reinterpret_cast<int *>(p);   // (the header's first word)
+    int rc = GNNTRK_OK;
+    const OwnPlan plan = own_plan(N, E, rows != nullptr);
+    const bool own = E > 0 && plan.ok && !(flags & 1) && (!plan.dense || (flags & 2));
+    if (!own) {   // (the own form zeroes the flag words together with its table)
+        rc = check_hip(hipMemsetAsync(bad, 0, kHeader, stream), "graph_index_build(memset)");
+        if (rc) return rc;
+    }
     if (E > 0) {
-        const OwnPlan plan = own_plan(N, E, rows != nullptr);
-        if (plan.ok && !(flags & 1) && (!plan.dense || (flags & 2))) {
+        if (own) {
             const int vec = (((uintptr_t)edge_index | (uintptr_t)(edge_index + E)) & 15) == 0 &&
                             (!label || ((uintptr_t)label & 3) == 0);
             const KeysCoo k1{edge_index, edge_index + E, N, label, rows, rows ? cy->rows_stride : 0, vec, nullptr};
             const uint32_t pmask = (uint32_t)(((uint64_t)1 << plan.bitsN) - 1);
             const OutCsr<true> o1r{o->perm, o->tgt, o->src, o->rowptr_t, pmask, label ? cy->label_csr : nullptr,
-                                   reinterpret_cast<const uint2 *>(p + plan.off_rows), rows ? cy->rows_csr_bf16 : nullptr,
-                                   rows ? cy->out_stride : 0};
+                                   rows ? cy->rows_csr_bf16 : nullptr, rows ? cy->out_stride : 0};
             const OutCsr<false> o1{o->perm, o->tgt, o->src, o->rowptr_t, pmask, label ? cy->label_csr : nullptr,
-                                   nullptr, nullptr, 0};
+                                   nullptr, 0};
             if (rank) {   // renumbered: one pass writes the translated int32 list, the sort reads that
                 int32_t *src32 = reinterpret_cast<int32_t *>(p + align_up(plan.bytes, 256));
                 int32_t *tgt32 = reinterpret_cast<int32_t *>(p + align_up(plan.bytes, 256) + remap_arr_bytes(E));
                 const int vec_ids = (((uintptr_t)edge_index | (uintptr_t)(edge_index + E)) & 15) == 0;
+#if GNNTRK_GI_REMAP_COUNT
+                rc = own_zero(plan, p, true, stream);
+                if (rc) return rc;
+                hipLaunchKernelGGL(gi_remap_count_kernel, dim3(gi_chunk_grid(plan.n_chunks)), dim3(kRemapTpb), 0, stream, edge_index,
+                                   edge_index + E, E, N, rank, vec_ids, src32, tgt32, plan.chunk, plan.n_chunks,
+                                   reinterpret_cast<uint32_t *>(p + plan.off_tbl),
+                                   reinterpret_cast<int2 *>(p + plan.off_range), bad);
+                constexpr int kz = 0;
+#else
+                rc = check_hip(hipMemsetAsync(bad, 0, kHeader, stream), "graph_index_build(memset)");
+                if (rc) return rc;
                 hipLaunchKernelGGL(gi_remap_kernel, dim3(stream_grid((E + 3) / 4)), dim3(kTpb), 0, stream, edge_index,
                                    edge_index + E, E, N, rank, vec_ids, src32, tgt32, bad);
+                constexpr int kz = 1;
+#endif
                 const KeysCoo32 k32{src32, tgt32, label, rows, rows ? cy->rows_stride : 0,
                                     (!label || ((uintptr_t)label & 3) == 0) ? 1 : 0};
-                rc = rows ? own_sort<KeysCoo32, OutCsr<true>, true>(plan, k32, o1r, plan.bitsN, N, E, p, bad, stream)
-                          : own_sort<KeysCoo32, OutCsr<false>, false>(plan, k32, o1, plan.bitsN, N, E, p, bad, stream);
+                rc = rows ? own_sort<KeysCoo32, OutCsr<true>, true>(plan, k32, o1r, plan.bitsN, N, E, p, bad, kz, stream)
+                          : own_sort<KeysCoo32, OutCsr<false>, false>(plan, k32, o1, plan.bitsN, N, E, p, bad, kz, stream);
             } else if (rows) {
-                rc = own_sort<KeysCoo, OutCsr<true>, true>(plan, k1, o1r, plan.bitsN, N, E, p, bad, stream);
+                rc = own_sort<KeysCoo, OutCsr<true>, true>(plan, k1, o1r, plan.bitsN, N, E, p, bad, 2, stream);
             } else {
-                rc = own_sort<KeysCoo, OutCsr<false>, false>(plan, k1, o1, plan.bitsN, N, E, p, bad, stream);
+                rc = own_sort<KeysCoo, OutCsr<false>, false>(plan, k1, o1, plan.bitsN, N, E, p, bad, 2, stream);
             }
             if (rc) return rc;
             const KeysCsr k2{o->src};
             const OutSrc o2{o->spos, o->spos_inv, o->rowptr_s};
-            rc = own_sort<KeysCsr, OutSrc, false>(plan, k2, o2, 0, N, E, p, bad, stream);
+            rc = own_sort<KeysCsr, OutSrc, false>(plan, k2, o2, 0, N, E, p, bad, 1, stream);
         } else {
             rc = library_build(edge_index, o, p, bad, N, E, rank, stream);
             if (rc) return rc;
@@ -1327,13 +1459,16 @@ __global__ __launch_bounds__(kTpb) void no_finish_kernel(const uint32_t *__restr
 // pass, one key pass and the sort's own passes over N records instead of four radix passes of the library.
 constexpr int kNoLevels = 1 << 16;
 constexpr int kNoMaxEvents = 64;
+constexpr size_t kNoHead = 1024;   // bytes of the own form's minima / maxima and flag words
 // per EVENT: mm[2 b] = max of the INVERTED order-preserving image of the key (= the minimum), mm[2 b + 1] = max of the
 // image; both start from a zero fill.  (Per event, not per call: an event then gets the same levels - hence the same
 // order - whether it is ordered alone or inside a collated batch, which is what lets cached per-event indices be
 // placed into a batch, gnntrk_graph_index_place.)
+// keyc (optional): the key column as a dense array - the key pass then reads 4 bytes per node instead of a line of
+// the caller's rows
 __global__ __launch_bounds__(kTpb) void no_minmax_kernel(const float *__restrict__ key, int64_t stride,
                                                          const int64_t *__restrict__ batch, int64_t n, int64_t n_events,
-                                                         uint32_t *__restrict__ mm) {
+                                                         uint32_t *__restrict__ mm, float *__restrict__ keyc) {
     __shared__ uint32_t s_mm[2 * kNoMaxEvents];
     for (int t = threadIdx.x; t < 2 * kNoMaxEvents; t += kTpb) s_mm[t] = 0u;
     __syncthreads();
@@ -1341,6 +1476,7 @@ __global__ __launch_bounds__(kTpb) void no_minmax_kernel(const float *__restrict
         const int64_t i = i0 + threadIdx.x;
         const bool in = i < n;
         const float v = in ? key[i * stride] : 0.f;
+        if (in && keyc) keyc[i] = v;
         long long b = (in && batch) ? batch[i] : 0;
         b = b < 0 ? 0 : b >= n_events ? n_events - 1 : b;   // (counted as bad in the key pass)
         uint32_t u = __float_as_uint(v);
@@ -1399,12 +1535,13 @@ __global__ __launch_bounds__(kTpb) void no_qkeys_kernel(const float *__restrict_
 }
 struct OutNode {   // the sort's outputs for the node order: perm[new] = old, rank[old] = new
     static constexpr uint32_t kValMask = 0xffffffffu;
-    static constexpr bool kPos = false;
+    static constexpr bool kRows = false;
     int32_t *perm, *rank, *rowptr;
-    __device__ __forceinline__ void ranked(uint32_t k, uint32_t val, uint32_t, uint32_t) const {
+    __device__ __forceinline__ void ranked(uint32_t k, uint32_t val, uint32_t) const {
         perm[k] = (int32_t)val;
         rank[val] = (int32_t)k;
     }
+    __device__ __forceinline__ void row(uint32_t, uint2) const {}
     __device__ __forceinline__ void slot(uint32_t, uint32_t) const {}
 };
 // (event, level) pairs the own form takes: the table of the counting sort is bounded by it
@@ -1478,9 +1615,10 @@ size_t gnntrk_node_order_workspace_bytes(int64_t n_nodes) {
     const size_t m = (size_t)(n_nodes > 0 ? n_nodes : 1);
     const size_t t64 = sort_pairs_u64_temp_bytes(n_nodes), t32 = sort_pairs_temp_bytes(n_nodes);
     const size_t lib = 2 * align_up(m * 8, 256) + 2 * align_up(m * 4, 256) + align_up(t64 > t32 ? t64 : t32, 256);
-    // own form: min / max + flag words | quantised keys | row pointers of the (event, level) pairs | the sort's plan
+    // own form: min / max + flag words | the sort's plan | quantised keys | dense keys | row pointers of the (event, level) pairs
     const OwnPlan p = own_plan(kNoMaxKeys, n_nodes > 0 ? n_nodes : 1, false);
-    const size_t own = 1024 + align_up(m * 4, 256) + align_up((size_t)(kNoMaxKeys + 1) * 4, 256) + (p.ok ? p.bytes : 0);
+    const size_t own = kNoHead + (p.ok ? align_up(p.bytes, 256) : 0) + 2 * align_up(m * 4, 256) +
+                       align_up((size_t)(kNoMaxKeys + 1) * 4, 256);
     return lib > own ? lib : own;
 }
 
@@ -1497,21 +1635,37 @@ int gnntrk_node_order(const float *key, int64_t key_stride, const int64_t *batch
     OwnPlan plan;
     int64_t n_keys = 0;
     if (node_order_own(n_nodes, n_events, batch, plan, n_keys)) {
-        uint32_t *mm = reinterpret_cast<uint32_t *>(p);          // per event {~min image, max image}; [128]: bad event ids
-        int32_t *q = reinterpret_cast<int32_t *>(p + 1024);
-        int32_t *rowptr = reinterpret_cast<int32_t *>(p + 1024 + align_up((size_t)n_nodes * 4, 256));
-        char *sort_ws = reinterpret_cast<char *>(rowptr) + align_up((size_t)(kNoMaxKeys + 1) * 4, 256);
-        int rc = check_hip(hipMemsetAsync(mm, 0, 1024, stream), "node_order(memset)");
+        // per event {~min image, max image}; [128]: bad event ids.  The sort's workspace starts inside this block, so that
+        // its table follows the block and one fill zeroes the minima / maxima, the flag word and the table
+        uint32_t *mm = reinterpret_cast<uint32_t *>(p);
+        int *bad = reinterpret_cast<int *>(mm + 2 * kNoMaxEvents);
+        char *sort_ws = p + kNoHead - kHeader;
+        const size_t arr = align_up((size_t)n_nodes * 4, 256);
+        int32_t *q = reinterpret_cast<int32_t *>(p + kNoHead + align_up(plan.bytes, 256));
+        float *keyc = reinterpret_cast<float *>(reinterpret_cast<char *>(q) + arr);
+        int32_t *rowptr = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(keyc) + arr);
+        int rc = check_hip(hipMemsetAsync(p, 0, kNoHead - kHeader + plan.off_tbl + (size_t)(plan.T + 1) * 4, stream),
+                           "node_order(memset)");
         if (rc) return rc;
         const int64_t ev = batch ? n_events : 1;
+#if GNNTRK_NO_KEY_COPY
         hipLaunchKernelGGL(no_minmax_kernel, dim3(grid), dim3(kTpb), 0, stream, key, key_stride, batch, n_nodes, ev,
-                           mm);
+                           mm, keyc);
+        hipLaunchKernelGGL(no_qkeys_kernel, dim3(grid), dim3(kTpb), 0, stream, keyc, (int64_t)1, batch, n_nodes, ev, mm,
+                           q, bad);
+#else
+        hipLaunchKernelGGL(no_minmax_kernel, dim3(grid), dim3(kTpb), 0, stream, key, key_stride, batch, n_nodes, ev,
+                           mm, (float *)nullptr);
         hipLaunchKernelGGL(no_qkeys_kernel, dim3(grid), dim3(kTpb), 0, stream, key, key_stride, batch, n_nodes, ev, mm,
-                           q, reinterpret_cast<int *>(mm + 2 * kNoMaxEvents));
+                           q, bad);
+#endif
         KeysCsr keys{q};
         OutNode out{perm, rank, rowptr};
-        rc = own_sort<KeysCsr, OutNode, false>(plan, keys, out, 0, n_keys, n_nodes, sort_ws,
-                                               reinterpret_cast<int *>(mm + 2 * kNoMaxEvents), stream);
+        hipLaunchKernelGGL((gi_count_kernel<KeysCsr>), dim3(plan.n_chunks), dim3(kCountTpb), 0, stream, keys,
+                           n_nodes, plan.chunk, plan.n_chunks, plan.NB,
+                           reinterpret_cast<uint32_t *>(sort_ws + plan.off_tbl),
+                           reinterpret_cast<int2 *>(sort_ws + plan.off_range), bad);
+        rc = own_sort<KeysCsr, OutNode, false>(plan, keys, out, 0, n_keys, n_nodes, sort_ws, bad, 0, stream);
         if (rc) return rc;
         return check_launch("node_order");
     }
