@@ -1262,6 +1262,12 @@ def _wide_mlp(segs: Sequence[Seg], weights, biases, *, n_rows: int, epilogue: in
 _KNN_FLAGS = int(os.environ.get("GNNTRK_KNN_FLAGS", "0"))
 
 
+def _radius_admits_nothing(max_radius: Optional[float]) -> bool:
+    """``dists < max_radius`` holds for no edge: a radius that is 0, negative or NaN.  (The C entries read
+    ``max_radius <= 0`` as "no radius" - what ``None`` is passed as - so such a radius must not reach them.)"""
+    return max_radius is not None and not (max_radius > 0)
+
+
 def _knn_search(lib, x: Tensor, k: int, r: float, seg_ptr: Optional[Tensor], nbr: Tensor, cnt: Tensor, st) -> None:
     """``gnntrk_knn_search_ws``: the neighbour search with the workspace of its pruned form
     (identical output to the brute-force entry points; the library picks the form)."""
@@ -1280,7 +1286,11 @@ def knn_graph(x: Tensor, k: int, max_radius: Optional[float] = None, seg_ptr: Op
     ascending distance, self excluded; with ``max_radius`` only ``||x_j - x_i|| < r``.
     ``seg_ptr`` (int64 ``[S + 1]`` row offsets of the events of a collated batch): neighbours
     are searched inside the query's own event - torch_cluster's ``batch`` argument, all events
-    in one launch."""
+    in one launch.
+    ``max_radius=None`` is the only way to search without a radius: the reference keeps
+    ``edge_index[:, dists < max_radius]``, so a radius that is 0, negative or NaN keeps no edge
+    (an empty ``[2, 0]`` list, no launch) - as do ``knn_scan`` for every k and
+    ``knn_kth_neighbor`` (all -1)."""
     _capi.require_device(x)
     lib = _capi.load()
     if x.dim() != 2:
@@ -1288,7 +1298,7 @@ def knn_graph(x: Tensor, k: int, max_radius: Optional[float] = None, seg_ptr: Op
     x = _as_rows(x.detach())
     n, dim = int(x.shape[0]), int(x.shape[1])
     dev = x.device
-    if n <= 1:
+    if n <= 1 or _radius_admits_nothing(max_radius):
         return torch.empty(2, 0, dtype=torch.int64, device=dev)
     kk = min(int(k), n - 1)
     nbr = torch.empty(n * kk, dtype=torch.int32, device=dev)
@@ -1313,7 +1323,7 @@ def knn_kth_neighbor(x: Tensor, k: int, max_radius: Optional[float] = None) -> T
     lib = _capi.load()
     x = _as_rows(x.detach().to(torch.float32))
     n, dim = int(x.shape[0]), int(x.shape[1])
-    if n - 1 < k:   # fewer candidates than the cap: it never binds
+    if n - 1 < k or _radius_admits_nothing(max_radius):   # fewer candidates than the cap (or none): it never binds
         return torch.full((n,), -1, dtype=torch.int32, device=x.device)
     nbr = torch.empty(n * k, dtype=torch.int32, device=x.device)
     cnt = torch.empty(n, dtype=torch.int32, device=x.device)
@@ -1356,7 +1366,7 @@ def knn_scan(x: Tensor, ks: Sequence[int], max_radius: Optional[float] = None) -
     x = _as_rows(x.detach())
     n, dim = int(x.shape[0]), int(x.shape[1])
     dev = x.device
-    if n <= 1:
+    if n <= 1 or _radius_admits_nothing(max_radius):
         return {k: torch.empty(2, 0, dtype=torch.int64, device=dev) for k in ks}
     kmax = min(max(ks), n - 1)
     nbr = torch.empty(n * kmax, dtype=torch.int32, device=dev)

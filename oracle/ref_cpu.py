@@ -809,13 +809,37 @@ def radius_neighbors(x, radius: float):
     return off, nbr.astype(np.int64), np.sqrt(d2[src, nbr])
 
 
-def dbscan_labels(x, max_eps: float, eps: float, min_pts: int):
-    """postprocessing/fastrescanner.py:41-66 with sklearn's ``dbscan_inner`` restated: edges
-    with dist <= eps; core = at least ``min_pts`` neighbours (self included); depth-first
-    expansion from every unlabelled core point in index order; noise = -1."""
+def radius_neighbors_blocked(x, radius: float, rows: int = 512):
+    """``radius_neighbors`` without the dense n x n matrices: the same expressions on ``rows`` queries at a time
+    (element by element the same fp64 operations in the same order, so the same bits)."""
     import numpy as np
 
-    off, nbr, dist = radius_neighbors(x, max(max_eps, eps))
+    x64 = np.asarray(x, dtype=np.float64)
+    n, dim = x64.shape
+    counts, nbrs, dists = [np.zeros(0, dtype=np.int64)], [np.zeros(0, dtype=np.int64)], [np.zeros(0)]
+    for s in range(0, n, rows):
+        q = x64[s:s + rows]
+        d2 = np.zeros((q.shape[0], n))
+        for d in range(dim):
+            t = q[:, None, d] - x64[None, :, d]
+            d2 = d2 + t * t
+        keep = d2 <= radius * radius
+        src, nbr = np.nonzero(keep)
+        counts.append(keep.sum(1).astype(np.int64))
+        nbrs.append(nbr.astype(np.int64))
+        dists.append(np.sqrt(d2[src, nbr]))
+    off = np.concatenate([[0], np.cumsum(np.concatenate(counts))]).astype(np.int64)
+    return off, np.concatenate(nbrs), np.concatenate(dists)
+
+
+def dbscan_labels(x, max_eps: float, eps: float, min_pts: int, graph=None):
+    """postprocessing/fastrescanner.py:41-66 with sklearn's ``dbscan_inner`` restated: edges
+    with dist <= eps; core = at least ``min_pts`` neighbours (self included); depth-first
+    expansion from every unlabelled core point in index order; noise = -1.  ``graph``: the
+    ``radius_neighbors`` of ``x`` at ``max(max_eps, eps)`` where the caller has it already."""
+    import numpy as np
+
+    off, nbr, dist = graph if graph is not None else radius_neighbors(x, max(max_eps, eps))
     n = len(off) - 1
     lists = [nbr[off[i]:off[i + 1]][dist[off[i]:off[i + 1]] <= eps] for i in range(n)]
     core = np.array([len(v) >= min_pts for v in lists], dtype=bool)
