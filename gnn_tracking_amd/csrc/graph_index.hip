@@ -2,7 +2,11 @@
 // See gnntrk_graph_index in include/gnntrk.h (replaces the gather / scatter bookkeeping of PyG's
 // MessagePassing.propagate, models/interaction_network.py:36,67).  HBM-bound integer work.
 //
-// Own two-level counting sort (round 3; the library radix sort stays for shapes outside it):
+// Two forms with the same results.  The own two-level counting sort below is the one that runs; the library radix
+// sort (further down) takes what the own form does not: very dense graphs (own_plan's `dense`), tables beyond
+// kMaxTable, and flags bit 0, which the tests use as their reference (bit 1 forces the own form).  There is one
+// path through the own form and one build hook, GNNTRK_GI_HUB_BITMAP_MIN; the variants it was measured against are
+// written up in DESIGN.md section 4.5.
 //
 //   a node id is split into (bucket = id >> 8, low = id & 255).  The edge list is cut into chunks of
 //   consecutive edges (one workgroup each).
@@ -26,7 +30,8 @@
 //   counters of a chunk live in an LDS window of 4096 buckets (kWin) placed a third below the chunk's first id and the
 //   runs it writes are hundreds of bytes long.  Ids outside the window (one giant unsorted graph)
 //   take global atomics on the table itself - slower, same result.  A bucket beyond the LDS
-//   capacity (hub nodes) is ranked from global memory in tiles - slower, same result.
+//   capacity is sorted in groups of nodes that fit, a hub node run by run from global memory (gi_sort_group,
+//   gi_hub_walk, gi_hub_bitmaps) - slower, same result.
 //
 //   Algorithmic bytes per edge: count 8 + split 16 + 8 + sort 8 + 12, then 4 + 4 + 8 + 8 + 8 = 84
 //   (+ 0.3 table entries per edge x 12 B); the library path moved about 260.  Renumbered, with a carried label
@@ -39,28 +44,10 @@ namespace gnntrk {
 
 constexpr int kTpb = 256;
 
-#ifndef GNNTRK_REMAP_NT
-#define GNNTRK_REMAP_NT 3   // (bit 0: non-temporal id loads, bit 1: non-temporal stores, bit 3: non-temporal table lookups of the remap pass - A/B builds)
-#endif
-#ifndef GNNTRK_GI_REMAP_COUNT
-#define GNNTRK_GI_REMAP_COUNT 1   // (0: the remap as a pass of its own, then gi_count_kernel<KeysCoo32> over what it wrote - A/B builds)
-#endif
-#ifndef GNNTRK_NO_KEY_COPY
-#define GNNTRK_NO_KEY_COPY 1   // (0: both node-order passes walk the key column at the caller's row stride - A/B builds)
-#endif
-#ifndef GNNTRK_NO_LIBRARY_SORT_OFF
-#define GNNTRK_NO_LIBRARY_SORT_OFF 0   // (1: gnntrk_node_order always takes the exact radix form - A/B builds)
-#endif
 // ------------------------------------------------------------------ own counting sort
-#ifndef GNNTRK_GI_SH
-#define GNNTRK_GI_SH 8
-#endif
-#ifndef GNNTRK_GI_SORT_TPB
-#define GNNTRK_GI_SORT_TPB 512
-#endif
-constexpr int kSH = GNNTRK_GI_SH;       // nodes per bucket = 256
+constexpr int kSH = 8;                  // nodes per bucket = 256
 constexpr int kBins = 1 << kSH;
-constexpr int kSortTpb = GNNTRK_GI_SORT_TPB;
+constexpr int kSortTpb = 512;
 constexpr int kSortR = 10;              // records a thread of the bucket sort holds in registers
 constexpr int kCap = kSortTpb * kSortR; // records of a bucket the bucket sort holds in LDS (5120)
 constexpr int kWin = 4096;              // bucket counters a chunk holds in LDS
@@ -68,22 +55,36 @@ constexpr int kWin = 4096;              // bucket counters a chunk holds in LDS
 // SLOWER (split by target 1.18 against 1.12 ms, by source 0.38 against 0.33): the open (bucket, chunk) runs of
 // the resident chunks - about 600 partially written lines per chunk and output array - then no longer fit an
 // XCD's 4 MB L2, and the runs leave it in pieces.
-#ifndef GNNTRK_GI_SPLIT_TPB
-#define GNNTRK_GI_SPLIT_TPB 1024
-#endif
-#ifndef GNNTRK_GI_SPLIT_WG
-#define GNNTRK_GI_SPLIT_WG 1
-#endif
-constexpr int kSplitTpb = GNNTRK_GI_SPLIT_TPB;
+constexpr int kSplitTpb = 1024;
+constexpr int kSplitWg = 1;             // split workgroups resident on a CU
 constexpr int kCountTpb = 1024;
 constexpr int kSplitR = 4;              // edges per thread and tile of the split
 constexpr int kSplitTile = kSplitTpb * kSplitR;
 constexpr int kMaxChunks = 512;
 #ifndef GNNTRK_GI_HUB_BITMAP_MIN
-#define GNNTRK_GI_HUB_BITMAP_MIN 65536   // hub nodes above this degree are ranked through per-run bitmaps (the emulator build: 8192)
+// hub nodes above this degree are ranked through per-run bitmaps.  The one build hook of this unit: the emulator
+// build of the tests sets 8192, so that the bitmap path is reachable at emulator sizes
+#define GNNTRK_GI_HUB_BITMAP_MIN 65536
 #endif
 constexpr int64_t kMaxTable = (int64_t)96 << 20;   // table entries (4 B each)
 constexpr int kScanTpb = 256, kScanItems = 16, kScanTile = kScanTpb * kScanItems;
+
+// A node id as the caller gave it: outside [0, N) it is counted in *bad and clamped.  kNullable: `bad` may be
+// nullptr, for an id that another pass counts (the passes that always count are spared the test)
+template <bool kNullable>
+__device__ __forceinline__ int64_t gi_clamped(int64_t v, int64_t N, int *bad) {
+    if (v < 0 || v >= N) {
+        if (!kNullable || bad) atomicAdd(bad, 1);
+        v = v < 0 ? 0 : N - 1;
+    }
+    return v;
+}
+// Four consecutive int32 a[e .. e + 3] of an own 16-byte aligned array (e a multiple of four, e1 = end of the
+// lane's range): one 16-byte load, item by item with 0 past e1 at the tail
+__device__ __forceinline__ int4 gi_load4(const int32_t *a, int64_t e, int64_t e1) {
+    if (e + 4 <= e1) return *reinterpret_cast<const int4 *>(a + e);
+    return int4{e < e1 ? a[e] : 0, e + 1 < e1 ? a[e + 1] : 0, e + 2 < e1 ? a[e + 2] : 0, 0};
+}
 
 // first sort: key = target (COO row 1), payload = source (row 0), value = edge id.  Two per-edge
 // inputs of the caller can ride along into CSR order (gnntrk_graph_index_carry): a 1-byte label in
@@ -96,14 +97,6 @@ struct KeysCoo {
     const float *rows;
     int rows_stride;
     __device__ __forceinline__ uint32_t key(int64_t e, int *bad) const { return checked(tgt[e], bad); }
-    __device__ __forceinline__ uint32_t payload(int64_t e, int *bad) const { return checked(src[e], bad); }
-    __device__ __forceinline__ uint32_t value(int64_t e) const {
-        return (uint32_t)e | ((label && label[e]) ? 0x80000000u : 0u);
-    }
-    __device__ __forceinline__ uint2 row(int64_t e) const {
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(rows + e * rows_stride);
-        return uint2{bf16x2_pack(v[0], v[1]), bf16x2_pack(v[2], v[3])};
-    }
     // four consecutive edges e .. e + 3 of one lane (e a multiple of four): with `vec` (16-byte aligned id rows,
     // 4-byte aligned labels) the ids come as 16-byte loads - 8-byte-per-lane streams top out near 3 TB/s here
     int vec;
@@ -112,10 +105,7 @@ struct KeysCoo {
     // the new numbering.  The table of one event (600 KB at 150 k hits) stays in the XCD's L2.
     const int32_t *rank;
     __device__ __forceinline__ uint32_t checked(int64_t v, int *bad) const {
-        if (v < 0 || v >= N) {
-            if (bad) atomicAdd(bad, 1);
-            v = v < 0 ? 0 : N - 1;
-        }
+        v = gi_clamped<true>(v, N, bad);
         return rank ? (uint32_t)rank[v] : (uint32_t)v;
     }
     __device__ __forceinline__ void keys4(int64_t e, int64_t e1, uint32_t k[4], int *bad) const {
@@ -190,32 +180,12 @@ struct KeysCoo32 {
     int rows_stride;
     int vec;   // 4-byte aligned labels
     __device__ __forceinline__ uint32_t key(int64_t e, int *) const { return (uint32_t)tgt[e]; }
-    __device__ __forceinline__ uint32_t payload(int64_t e, int *) const { return (uint32_t)src[e]; }
-    __device__ __forceinline__ uint32_t value(int64_t e) const {
-        return (uint32_t)e | ((label && label[e]) ? 0x80000000u : 0u);
-    }
-    __device__ __forceinline__ uint2 row(int64_t e) const {
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(rows + e * rows_stride);
-        return uint2{bf16x2_pack(v[0], v[1]), bf16x2_pack(v[2], v[3])};
-    }
-    __device__ __forceinline__ void keys4(int64_t e, int64_t e1, uint32_t k[4], int *) const {
-        if (e + 4 <= e1) {   // (own 16-byte aligned arrays; e is a multiple of four)
-            const int4 a = *reinterpret_cast<const int4 *>(tgt + e);
-            k[0] = (uint32_t)a.x;
-            k[1] = (uint32_t)a.y;
-            k[2] = (uint32_t)a.z;
-            k[3] = (uint32_t)a.w;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) k[q] = e + q < e1 ? (uint32_t)tgt[e + q] : 0u;
-        }
-    }
     struct Raw {
         int4 t, s;
         uint32_t l4;
     };
     __device__ __forceinline__ void load_raw(int64_t e, int64_t e1, Raw &r) const {
-        if (e + 4 <= e1) {
+        if (e + 4 <= e1) {   // (own 16-byte aligned arrays; e is a multiple of four)
             r.t = *reinterpret_cast<const int4 *>(tgt + e);
             r.s = *reinterpret_cast<const int4 *>(src + e);
             if (!label) {
@@ -264,31 +234,11 @@ __device__ __forceinline__ void gi_remap4(const int64_t *__restrict__ src, const
                                           int64_t e1, int64_t N, const int32_t *__restrict__ rank, int vec,
                                           int32_t *__restrict__ src32, int32_t *__restrict__ tgt32,
                                           int *__restrict__ bad, uint32_t kt[4]) {
-    auto chk = [&](long long v) -> long long {
-        if (v < 0 || v >= N) {
-            atomicAdd(bad, 1);
-            v = v < 0 ? 0 : N - 1;
-        }
-        return v;
-    };
-    auto look = [&](long long v) -> int {
-#if GNNTRK_REMAP_NT & 4   // (timing probe: no table lookups - results are NOT a renumbering)
-        return (int)v;
-#elif GNNTRK_REMAP_NT & 8
-        return __builtin_nontemporal_load(rank + v);
-#else
-        return rank[v];
-#endif
-    };
     if (vec && e + 4 <= e1) {
         // (the id streams and the outputs pass through once: non-temporal, the lookup table keeps the L2)
         typedef int i4_hw __attribute__((ext_vector_type(4)));
         auto ld2 = [](const int64_t *p, long long &a, long long &b) {   // two ids as one 16-byte non-temporal load
-#if GNNTRK_REMAP_NT & 1
             const i4_hw v = __builtin_nontemporal_load(reinterpret_cast<const i4_hw *>(p));
-#else
-            const i4_hw v = *reinterpret_cast<const i4_hw *>(p);
-#endif
             a = (long long)(((unsigned long long)(uint32_t)v[1] << 32) | (uint32_t)v[0]);
             b = (long long)(((unsigned long long)(uint32_t)v[3] << 32) | (uint32_t)v[2]);
         };
@@ -297,20 +247,16 @@ __device__ __forceinline__ void gi_remap4(const int64_t *__restrict__ src, const
         ld2(tgt + e + 2, it[2], it[3]);
         ld2(src + e, is[0], is[1]);
         ld2(src + e + 2, is[2], is[3]);
+        // (all eight ids checked before the first lookup: the lookups then leave together)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            it[q] = chk(it[q]);
-            is[q] = chk(is[q]);
+            it[q] = gi_clamped<false>(it[q], N, bad);
+            is[q] = gi_clamped<false>(is[q], N, bad);
         }
-        const i4_hw ot = {look(it[0]), look(it[1]), look(it[2]), look(it[3])};
-        const i4_hw os = {look(is[0]), look(is[1]), look(is[2]), look(is[3])};
-#if GNNTRK_REMAP_NT & 2
+        const i4_hw ot = {rank[it[0]], rank[it[1]], rank[it[2]], rank[it[3]]};
+        const i4_hw os = {rank[is[0]], rank[is[1]], rank[is[2]], rank[is[3]]};
         __builtin_nontemporal_store(ot, reinterpret_cast<i4_hw *>(tgt32 + e));
         __builtin_nontemporal_store(os, reinterpret_cast<i4_hw *>(src32 + e));
-#else
-        *reinterpret_cast<i4_hw *>(tgt32 + e) = ot;
-        *reinterpret_cast<i4_hw *>(src32 + e) = os;
-#endif
 #pragma unroll
         for (int q = 0; q < 4; ++q) kt[q] = (uint32_t)ot[q];
     } else {
@@ -318,7 +264,7 @@ __device__ __forceinline__ void gi_remap4(const int64_t *__restrict__ src, const
         for (int q = 0; q < 4; ++q) {
             kt[q] = 0u;
             if (e + q < e1) {
-                const int t = look(chk(tgt[e + q])), u = look(chk(src[e + q]));
+                const int t = rank[gi_clamped<false>(tgt[e + q], N, bad)], u = rank[gi_clamped<false>(src[e + q], N, bad)];
                 tgt32[e + q] = t;
                 src32[e + q] = u;
                 kt[q] = (uint32_t)t;
@@ -326,47 +272,21 @@ __device__ __forceinline__ void gi_remap4(const int64_t *__restrict__ src, const
         }
     }
 }
-#if !GNNTRK_GI_REMAP_COUNT
-__global__ __launch_bounds__(kTpb) void gi_remap_kernel(const int64_t *__restrict__ src, const int64_t *__restrict__ tgt,
-                                                        int64_t E, int64_t N, const int32_t *__restrict__ rank, int vec,
-                                                        int32_t *__restrict__ src32, int32_t *__restrict__ tgt32,
-                                                        int *__restrict__ bad) {
-    const int64_t n4 = (E + 3) / 4;
-    for (int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kTpb) {
-        uint32_t kt[4];
-        gi_remap4(src, tgt, 4 * i, E, N, rank, vec, src32, tgt32, bad, kt);
-    }
-}
-#endif
 // second sort: key = source of the CSR-ordered list (already validated), value = CSR position
 struct KeysCsr {
     const int32_t *src;
     __device__ __forceinline__ uint32_t key(int64_t e, int *) const { return (uint32_t)src[e]; }
-    __device__ __forceinline__ uint32_t payload(int64_t, int *) const { return 0u; }
-    __device__ __forceinline__ uint32_t value(int64_t e) const { return (uint32_t)e; }
-    __device__ __forceinline__ uint2 row(int64_t) const { return uint2{0u, 0u}; }
     __device__ __forceinline__ void keys4(int64_t e, int64_t e1, uint32_t k[4], int *) const {
-        if (e + 4 <= e1) {   // (the CSR list is an own 16-byte aligned array; e is a multiple of four)
-            const int4 a = *reinterpret_cast<const int4 *>(src + e);
-            k[0] = (uint32_t)a.x;
-            k[1] = (uint32_t)a.y;
-            k[2] = (uint32_t)a.z;
-            k[3] = (uint32_t)a.w;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) k[q] = e + q < e1 ? (uint32_t)src[e + q] : 0u;
-        }
+        const int4 a = gi_load4(src, e, e1);
+        k[0] = (uint32_t)a.x;
+        k[1] = (uint32_t)a.y;
+        k[2] = (uint32_t)a.z;
+        k[3] = (uint32_t)a.w;
     }
     struct Raw {
         int4 a;
     };
-    __device__ __forceinline__ void load_raw(int64_t e, int64_t e1, Raw &r) const {
-        if (e + 4 <= e1) {
-            r.a = *reinterpret_cast<const int4 *>(src + e);
-        } else {
-            r.a = int4{e < e1 ? src[e] : 0, e + 1 < e1 ? src[e + 1] : 0, e + 2 < e1 ? src[e + 2] : 0, 0};
-        }
-    }
+    __device__ __forceinline__ void load_raw(int64_t e, int64_t e1, Raw &r) const { r.a = gi_load4(src, e, e1); }
     __device__ __forceinline__ void decode(const Raw &r, int64_t e, uint32_t k[4], uint32_t p[4], uint32_t v[4],
                                            int *) const {
         k[0] = (uint32_t)r.a.x;
@@ -394,16 +314,9 @@ __device__ __forceinline__ int gi_window_start(uint32_t first_key) {
 // renumbering tables of those chunks' events instead of a little of every event's.  The grid is
 // gi_chunk_grid(n_chunks) workgroups; a chunk >= n_chunks is none.  (The split gains nothing from this order:
 // 788 against 790 us per 64 M edges.)
-#ifndef GNNTRK_GI_REMAP_XCD
-#define GNNTRK_GI_REMAP_XCD 1   // (0: gi_remap_count_kernel takes its chunks in launch order - A/B builds)
-#endif
 constexpr int kXcd = 8;
 __device__ __forceinline__ int gi_chunk_of_block() {
-#if GNNTRK_GI_REMAP_XCD
     return (int)(blockIdx.x % kXcd) * (int)(gridDim.x / kXcd) + (int)(blockIdx.x / kXcd);
-#else
-    return (int)blockIdx.x;
-#endif
 }
 static int gi_chunk_grid(int n_chunks) { return (n_chunks + kXcd - 1) / kXcd * kXcd; }
 
@@ -481,7 +394,6 @@ __global__ __launch_bounds__(kCountTpb) void gi_count_kernel(K keys, int64_t E, 
     gi_count_flush<kCountTpb>(s_cnt, &s_lo, &s_hi, w0, n_chunks, c, tbl, range);
     (void)NB;
 }
-#if GNNTRK_GI_REMAP_COUNT
 // The remap pass in the sort's chunk geometry (one workgroup per chunk), counting the translated targets as it
 // writes them: step 1 of the by-target sort without a pass of its own over tgt32.  The lookups want every lane
 // slot of a CU filled (inside the count / split kernels, one 1024-lane workgroup per CU, they cost 1.7 ms per
@@ -503,13 +415,7 @@ __global__ __launch_bounds__(kRemapTpb, 8) void gi_remap_count_kernel(
         s_lo = kWin;
         s_hi = -1;
         // the window starts from the chunk's first TRANSLATED target (clamped as the pass below clamps it, counted there)
-        long long v = tgt[e0];
-        v = v < 0 ? 0 : v >= N ? N - 1 : v;
-#if GNNTRK_REMAP_NT & 4
-        s_w0 = gi_window_start((uint32_t)v);
-#else
-        s_w0 = gi_window_start((uint32_t)rank[v]);
-#endif
+        s_w0 = gi_window_start((uint32_t)rank[gi_clamped<true>(tgt[e0], N, nullptr)]);
     }
     __syncthreads();
     const int w0 = s_w0;
@@ -520,7 +426,6 @@ __global__ __launch_bounds__(kRemapTpb, 8) void gi_remap_count_kernel(
     }
     gi_count_flush<kRemapTpb>(s_cnt, &s_lo, &s_hi, w0, n_chunks, c, tbl, range);
 }
-#endif
 
 // step 2: exclusive scan of tbl[0 .. T] in place (tbl[T] = total), two kernels: the tiles' sums, then every tile
 // scans itself behind the sum of the tiles before it (a tile adds those up itself: a few thousand values out of the
@@ -658,7 +563,7 @@ struct GiRec<true> {
     }
 };
 template <class K, bool ROWS>
-__global__ __launch_bounds__(kSplitTpb, GNNTRK_GI_SPLIT_WG * kSplitTpb / 256) void gi_split_kernel(K keys, int64_t E, int chunk, int n_chunks, int pbits,
+__global__ __launch_bounds__(kSplitTpb, kSplitWg * kSplitTpb / 256) void gi_split_kernel(K keys, int64_t E, int chunk, int n_chunks, int pbits,
                                                              uint32_t *__restrict__ tbl,
                                                              const int2 *__restrict__ range,
                                                              typename GiRec<ROWS>::type *__restrict__ part,
@@ -761,7 +666,7 @@ __global__ __launch_bounds__(kSplitTpb, GNNTRK_GI_SPLIT_WG * kSplitTpb / 256) vo
 }
 
 // step 4 outputs.  kValMask: bits of a record's value that order it; kRows: 16-byte records whose second half is
-// the carried row (row(): the row of final position k)
+// the carried row (row(): the row of final position k); node_start(): the row pointer of a node, entry N = E
 template <bool ROWS>
 struct OutCsr {   // first sort
     static constexpr uint32_t kValMask = 0x7fffffffu;
@@ -780,6 +685,7 @@ struct OutCsr {   // first sort
         if (ROWS) *reinterpret_cast<uint2 *>(rows_csr + (size_t)k * rows_out_stride) = r;
     }
     __device__ __forceinline__ void slot(uint32_t k, uint32_t node) const { tgt[k] = (int32_t)node; }
+    __device__ __forceinline__ void node_start(int64_t node, uint32_t pos) const { rowptr[node] = (int32_t)pos; }
 };
 struct OutSrc {   // second sort
     static constexpr uint32_t kValMask = 0xffffffffu;
@@ -791,17 +697,233 @@ struct OutSrc {   // second sort
     }
     __device__ __forceinline__ void row(uint32_t, uint2) const {}
     __device__ __forceinline__ void slot(uint32_t, uint32_t) const {}
+    __device__ __forceinline__ void node_start(int64_t node, uint32_t pos) const { rowptr[node] = (int32_t)pos; }
 };
+
+// step 4: the four regimes of gi_bucket_sort_kernel.  Common arguments: `part` = the bucket's region as 8-byte
+// halves (half kRS * i is record i's {value, low | payload}, the half behind it its row), base = its first output
+// position, M = its records, node0 = its first node, s_hist / s_start = records per node / first record of a node
+// inside the bucket, s_rec = the record image.
+template <class O>
+constexpr uint32_t kGiRS = O::kRows ? 2 : 1;
+// records a group of nodes may hold: with carried rows the last third of the record image holds 32-bit positions in
+// the bucket's region (the row is fetched from its record at write-out)
+template <class O>
+constexpr uint32_t kGiCapG = O::kRows ? (uint32_t)kCap * 2 / 3 : (uint32_t)kCap;
+
+// The bucket fits the image (M <= kCap).  rec / rrow: the thread's records as loaded (record tid + q * kSortTpb),
+// ord: their order of arrival inside their node's list.
+template <class O>
+__device__ __forceinline__ void gi_sort_fits(uint2 (&rec)[kSortR], const uint2 (&rrow)[O::kRows ? kSortR : 1],
+                                             uint32_t (&ord)[kSortR], uint32_t base, uint32_t M, uint32_t node0,
+                                             int pbits, const uint32_t *s_hist, const uint32_t *s_start, uint2 *s_rec,
+                                             uint16_t *s_fin, const O &out) {
+    constexpr uint32_t VM = O::kValMask;
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < kSortR; ++q)
+        if (tid + q * kSortTpb < M) {
+            const uint32_t sl = s_start[rec[q].y >> pbits] + ord[q];
+            s_rec[sl] = rec[q];
+            ord[q] = sl;
+        }
+    __syncthreads();
+    // rank every record inside its node's list, then bring the image into the final order in place, so
+    // that the arrays leave with consecutive lanes on consecutive positions (a wave's store touches a few
+    // lines instead of up to 64)
+    uint32_t dst[kSortR];
+#pragma unroll
+    for (int q = 0; q < kSortR; ++q) {
+        const uint32_t j = tid + q * kSortTpb;
+        if (j < M) {
+            const uint2 r = s_rec[j];
+            const uint32_t low = r.y >> pbits, st = s_start[low], n = s_hist[low];
+            uint32_t cnt = 0;
+            for (uint32_t t = 0; t < n; ++t) cnt += (s_rec[st + t].x & VM) < (r.x & VM) ? 1u : 0u;
+            rec[q] = r;
+            dst[q] = st + cnt;
+            if (O::kRows) s_fin[j] = (uint16_t)dst[q];
+            out.slot(base + j, node0 + low);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < kSortR; ++q)
+        if (tid + q * kSortTpb < M) s_rec[dst[q]] = rec[q];
+    __syncthreads();
+    for (uint32_t j = tid; j < M; j += kSortTpb) {
+        const uint2 r = s_rec[j];
+        out.ranked(base + j, r.x, r.y);
+    }
+    if (O::kRows) {   // the rows through the same image, from the threads that hold them
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < kSortR; ++q)
+            if (tid + q * kSortTpb < M) s_rec[s_fin[ord[q]]] = rrow[O::kRows ? q : 0];
+        __syncthreads();
+        for (uint32_t j = tid; j < M; j += kSortTpb) out.row(base + j, s_rec[j]);
+    }
+}
+
+// A group of consecutive nodes g0 .. g1 - 1 whose lists fit the image together: one pass over the bucket's records
+// (served by the L2) collects them.  s_cur: a cursor per node.
+template <class O>
+__device__ __forceinline__ void gi_sort_group(const uint2 *__restrict__ part, uint32_t base, uint32_t M, uint32_t node0,
+                                              int pbits, int g0, int g1, const uint32_t *s_hist,
+                                              const uint32_t *s_start, uint32_t *s_cur, uint2 *s_rec, const O &out) {
+    constexpr uint32_t VM = O::kValMask, kRS = kGiRS<O>;
+    const int tid = threadIdx.x;
+    uint32_t *s_pos32 = reinterpret_cast<uint32_t *>(s_rec + kGiCapG<O>);
+    const uint32_t st0 = s_start[g0], n_g = (g1 < kBins ? s_start[g1] : M) - st0;
+    __syncthreads();
+    if (tid < kBins) s_cur[tid] = 0;
+    __syncthreads();
+    for (uint32_t i = tid; i < M; i += kSortTpb) {
+        const uint2 r = part[(size_t)i * kRS];
+        const int low = (int)(r.y >> pbits);
+        if (low >= g0 && low < g1) {
+            const uint32_t sl = s_start[low] - st0 + atomicAdd(&s_cur[low], 1u);
+            s_rec[sl] = r;
+            if (O::kRows) s_pos32[sl] = i;
+        }
+    }
+    __syncthreads();
+    for (uint32_t j = tid; j < n_g; j += kSortTpb) {
+        const uint2 r = s_rec[j];
+        const uint32_t low = r.y >> pbits, st = s_start[low] - st0, n = s_hist[low];
+        uint32_t cnt = 0;
+        for (uint32_t t = 0; t < n; ++t) cnt += (s_rec[st + t].x & VM) < (r.x & VM) ? 1u : 0u;
+        out.ranked(base + st0 + st + cnt, r.x, r.y);
+        if (O::kRows) out.row(base + st0 + st + cnt, part[(size_t)s_pos32[j] * kRS + (kRS - 1)]);
+        out.slot(base + st0 + j, node0 + low);
+    }
+}
+
+// A hub: node g0's list alone exceeds the image.
+// The bucket's region is a sequence of runs, one per CHUNK of the edge list, in chunk order (step 2's scan lays
+// (bucket, chunk) out chunk after chunk), and a record's value - an edge id / a CSR position - says which chunk it
+// came from: value / chunk.  So a hub record's rank is the number of hub records in earlier runs (a histogram over
+// the chunks) + the number of hub records of its OWN run with a smaller value.  (Comparing every hub record with
+// every record of the bucket is O(M^2 / 512) per workgroup - seconds for a million-edge hub.)
+// gi_hub_runs leaves h_all[ck] = first record of chunk ck's run, h_hub[ck] = hub records in the runs before it.
+template <class O>
+__device__ __forceinline__ void gi_hub_runs(const uint2 *__restrict__ part, uint32_t M, int pbits, int chunk, int g0,
+                                            uint32_t *h_all, uint32_t *h_hub) {
+    constexpr uint32_t VM = O::kValMask, kRS = kGiRS<O>;
+    const int tid = threadIdx.x;
+    __syncthreads();
+    for (int t = tid; t < 2 * kMaxChunks; t += kSortTpb) h_all[t] = 0u;
+    __syncthreads();
+    for (uint32_t i = tid; i < M; i += kSortTpb) {
+        const uint2 r = part[(size_t)i * kRS];
+        const uint32_t ck = (r.x & VM) / (uint32_t)chunk;
+        atomicAdd(&h_all[ck], 1u);
+        if ((int)(r.y >> pbits) == g0) atomicAdd(&h_hub[ck], 1u);
+    }
+    __syncthreads();
+    if (tid == 0) {   // exclusive scans over at most 512 chunks
+        uint32_t a_ = 0, h_ = 0;
+        for (int ck = 0; ck < kMaxChunks; ++ck) {
+            const uint32_t va = h_all[ck], vh = h_hub[ck];
+            h_all[ck] = a_;
+            h_hub[ck] = h_;
+            a_ += va;
+            h_ += vh;
+        }
+    }
+    __syncthreads();
+}
+// ... the rank inside the own run by a walk over that run only (pos0 = the hub's first output position)
+template <class O>
+__device__ __forceinline__ void gi_hub_walk(const uint2 *__restrict__ part, uint32_t pos0, uint32_t M, int pbits,
+                                            int chunk, int g0, const uint32_t *h_all, const uint32_t *h_hub,
+                                            const O &out) {
+    constexpr uint32_t VM = O::kValMask, kRS = kGiRS<O>;
+    for (uint32_t i = threadIdx.x; i < M; i += kSortTpb) {
+        const uint2 r = part[(size_t)i * kRS];
+        if ((int)(r.y >> pbits) != g0) continue;
+        const uint32_t ck = (r.x & VM) / (uint32_t)chunk;
+        const uint32_t r0 = h_all[ck], r1 = ck + 1 < (uint32_t)kMaxChunks ? h_all[ck + 1] : M;
+        uint32_t cnt = h_hub[ck];
+        for (uint32_t t = r0; t < r1; ++t) {
+            const uint2 q = part[(size_t)t * kRS];
+            cnt += ((int)(q.y >> pbits) == g0 && (q.x & VM) < (r.x & VM)) ? 1u : 0u;
+        }
+        out.ranked(pos0 + cnt, r.x, r.y);
+        if (O::kRows) out.row(pos0 + cnt, part[(size_t)i * kRS + (kRS - 1)]);
+    }
+}
+// ... a large hub (n records): the values of a run are distinct ids of ONE chunk, so the hub records of a run are
+// the set bits of a bitmap over the chunk's id range (spans of 128 K ids: 16 KB of LDS) and a record's rank inside
+// its run is the number of set bits below its own - linear in the bucket's size (a 2 M-edge hub: 5 s with the walk
+// above, milliseconds this way).  bm: the span's bitmap, pw: the exclusive prefix of its words' bit counts.
+constexpr uint32_t kHubSpanW = 4096, kHubSpan = kHubSpanW * 32;
+template <class O>
+__device__ __forceinline__ void gi_hub_bitmaps(const uint2 *__restrict__ part, uint32_t pos0, uint32_t M, uint32_t n,
+                                               int pbits, int chunk, int g0, const uint32_t *h_all,
+                                               const uint32_t *h_hub, uint32_t *bm, uint32_t *pw, const O &out) {
+    constexpr uint32_t VM = O::kValMask, kRS = kGiRS<O>, kSpanW = kHubSpanW, kSpan = kHubSpan;
+    const int tid = threadIdx.x;
+    for (int ck = 0; ck < kMaxChunks; ++ck) {
+        const uint32_t r0 = h_all[ck], r1 = ck + 1 < kMaxChunks ? h_all[ck + 1] : M;
+        const uint32_t hub_here = (ck + 1 < kMaxChunks ? h_hub[ck + 1] : n) - h_hub[ck];
+        if (hub_here == 0u) continue;   // (uniform)
+        uint32_t before = h_hub[ck];
+        for (uint32_t lo = (uint32_t)ck * (uint32_t)chunk, sub = 0; sub < (uint32_t)chunk; sub += kSpan, lo += kSpan) {
+            __syncthreads();
+            for (uint32_t w = tid; w < kSpanW; w += kSortTpb) bm[w] = 0u;
+            __syncthreads();
+            for (uint32_t t = r0 + tid; t < r1; t += kSortTpb) {
+                const uint2 q = part[(size_t)t * kRS];
+                const uint32_t d = (q.x & VM) - lo;
+                if ((int)(q.y >> pbits) == g0 && d < kSpan) atomicOr(&bm[d >> 5], 1u << (d & 31u));
+            }
+            __syncthreads();
+            // exclusive prefix of the words' bit counts: eight words per thread + a scan of the
+            // 512 thread sums through pw's upper half
+            uint32_t mine = 0;
+            constexpr uint32_t kPer = kSpanW / kSortTpb;
+            for (uint32_t j = 0; j < kPer; ++j) mine += (uint32_t)__popc(bm[tid * kPer + j]);
+            uint32_t *ts = pw;   // thread sums, scanned in place
+            ts[tid] = mine;
+            __syncthreads();
+            for (uint32_t off = 1; off < (uint32_t)kSortTpb; off <<= 1) {
+                const uint32_t v = tid >= (int)off ? ts[tid - off] : 0u;
+                __syncthreads();
+                ts[tid] += v;
+                __syncthreads();
+            }
+            const uint32_t excl = ts[tid] - mine, span_total = ts[kSortTpb - 1];
+            __syncthreads();
+            uint32_t run_ = excl;
+            for (uint32_t j = 0; j < kPer; ++j) {
+                const uint32_t w = tid * kPer + j, c_ = (uint32_t)__popc(bm[w]);
+                pw[w] = run_;
+                run_ += c_;
+            }
+            __syncthreads();
+            for (uint32_t t = r0 + tid; t < r1; t += kSortTpb) {
+                const uint2 q = part[(size_t)t * kRS];
+                const uint32_t d = (q.x & VM) - lo;
+                if ((int)(q.y >> pbits) == g0 && d < kSpan) {
+                    const uint32_t w = d >> 5;
+                    const uint32_t below = (uint32_t)__popc(bm[w] & ((1u << (d & 31u)) - 1u));
+                    out.ranked(pos0 + before + pw[w] + below, q.x, q.y);
+                    if (O::kRows) out.row(pos0 + before + pw[w] + below, part[(size_t)t * kRS + (kRS - 1)]);
+                }
+            }
+            before += span_total;
+        }
+    }
+}
 
 template <class O>
 __global__ __launch_bounds__(kSortTpb) void gi_bucket_sort_kernel(const typename GiRec<O::kRows>::type *__restrict__ part_,
                                                                   const uint32_t *__restrict__ base_arr, int NB,
                                                                   int64_t N, int64_t E, int pbits, int chunk, O out) {
-    constexpr uint32_t VM = O::kValMask;
-    // the records as 8-byte halves: half kRS * i is record i's {value, low | payload}, the half behind it its row
-    constexpr uint32_t kRS = O::kRows ? 2 : 1;
+    constexpr uint32_t kRS = kGiRS<O>;
     const uint2 *__restrict__ part = reinterpret_cast<const uint2 *>(part_);
-    __shared__ uint32_t s_hist[kBins], s_start[kBins], s_wsum[kBins / 64];
+    __shared__ uint32_t s_hist[kBins], s_start[kBins], s_wsum[kBins / 64], s_cur[kBins];
     __shared__ uint2 s_rec[kCap];
     __shared__ uint16_t s_fin[O::kRows ? kCap : 1];   // slot after the first placement -> final slot
     const int tid = threadIdx.x, b = blockIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -853,203 +975,38 @@ __global__ __launch_bounds__(kSortTpb) void gi_bucket_sort_kernel(const typename
         for (int w = 0; w < kBins / 64; ++w) pre += w < wv ? s_wsum[w] : 0u;
         const uint32_t st = pre + inc - cnt_mine;
         s_start[tid] = st;
-        if ((int64_t)node0 + tid < N) out.rowptr[node0 + tid] = (int32_t)(base + st);
+        if ((int64_t)node0 + tid < N) out.node_start(node0 + tid, base + st);
     }
-    if (b == NB - 1 && tid == 0) out.rowptr[N] = (int32_t)E;
+    if (b == NB - 1 && tid == 0) out.node_start(N, (uint32_t)E);
     __syncthreads();
     if (fits) {
-#pragma unroll
-        for (int q = 0; q < kSortR; ++q)
-            if (tid + q * kSortTpb < M) {
-                const uint32_t sl = s_start[rec[q].y >> pbits] + ord[q];
-                s_rec[sl] = rec[q];
-                ord[q] = sl;
-            }
-        __syncthreads();
-        // rank every record inside its node's list, then bring the image into the final order in place, so
-        // that the arrays leave with consecutive lanes on consecutive positions (a wave's store touches a few
-        // lines instead of up to 64)
-        uint32_t dst[kSortR];
-#pragma unroll
-        for (int q = 0; q < kSortR; ++q) {
-            const uint32_t j = tid + q * kSortTpb;
-            if (j < M) {
-                const uint2 r = s_rec[j];
-                const uint32_t low = r.y >> pbits, st = s_start[low], n = s_hist[low];
-                uint32_t cnt = 0;
-                for (uint32_t t = 0; t < n; ++t) cnt += (s_rec[st + t].x & VM) < (r.x & VM) ? 1u : 0u;
-                rec[q] = r;
-                dst[q] = st + cnt;
-                if (O::kRows) s_fin[j] = (uint16_t)dst[q];
-                out.slot(base + j, node0 + low);
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < kSortR; ++q)
-            if (tid + q * kSortTpb < M) s_rec[dst[q]] = rec[q];
-        __syncthreads();
-        for (uint32_t j = tid; j < M; j += kSortTpb) {
-            const uint2 r = s_rec[j];
-            out.ranked(base + j, r.x, r.y);
-        }
-        if (O::kRows) {   // the rows through the same image, from the threads that hold them
-            __syncthreads();
-#pragma unroll
-            for (int q = 0; q < kSortR; ++q)
-                if (tid + q * kSortTpb < M) s_rec[s_fin[ord[q]]] = rrow[O::kRows ? q : 0];
-            __syncthreads();
-            for (uint32_t j = tid; j < M; j += kSortTpb) out.row(base + j, s_rec[j]);
-        }
+        gi_sort_fits(rec, rrow, ord, base, M, node0, pbits, s_hist, s_start, s_rec, s_fin, out);
     } else {
         // a bucket beyond the LDS capacity: groups of consecutive nodes whose lists fit are taken one
-        // after the other (one pass over the bucket's records per group, served by the L2); a single
-        // node beyond the capacity (a hub) is ranked against tiles of its own list streamed through
-        // LDS - quadratic in the hub's degree, same result
-        __shared__ uint32_t s_cur[kBins];
-        // (with carried rows the last third of the record image holds 32-bit positions in the bucket's region: the
-        // row is fetched from its record at write-out)
-        constexpr uint32_t kCapG = O::kRows ? (uint32_t)kCap * 2 / 3 : (uint32_t)kCap;
-        auto row_at = [&](uint32_t i) { return part[(size_t)i * kRS + (kRS - 1)]; };
-        (void)row_at;
-        uint32_t *s_pos32 = reinterpret_cast<uint32_t *>(s_rec + kCapG);
+        // after the other; a single node beyond the capacity is a hub
         int g0 = 0;
         while (g0 < kBins) {
             const uint32_t st0 = s_start[g0];
             int g1 = g0;
-            while (g1 < kBins && (g1 + 1 < kBins ? s_start[g1 + 1] : M) - st0 <= kCapG) ++g1;
-            if (g1 == g0) {   // hub node g0: its list alone exceeds the LDS capacity
-                // The bucket's region is a sequence of runs, one per CHUNK of the edge list, in chunk order (step 2's
-                // scan lays (bucket, chunk) out chunk after chunk), and a record's value - an edge id / a CSR position -
-                // says which chunk it came from: value / chunk.  So a hub record's rank is the number of hub records
-                // in earlier runs (a histogram over the chunks) + the number of hub records of its OWN run with a
-                // smaller value (a walk over that run only).  Until round 5 every hub record was compared with every
-                // record of the bucket: O(M^2 / 512) per workgroup - seconds for a million-edge hub.
+            while (g1 < kBins && (g1 + 1 < kBins ? s_start[g1 + 1] : M) - st0 <= kGiCapG<O>) ++g1;
+            if (g1 == g0) {
                 const uint32_t n = s_hist[g0];
-                uint32_t *h_all = reinterpret_cast<uint32_t *>(s_rec), *h_hub = h_all + kMaxChunks;   // (s_rec is free here)
-                __syncthreads();
-                for (int t = tid; t < 2 * kMaxChunks; t += kSortTpb) h_all[t] = 0u;
-                __syncthreads();
-                for (uint32_t i = tid; i < M; i += kSortTpb) {
-                    const uint2 r = part[(size_t)i * kRS];
-                    const uint32_t ck = (r.x & VM) / (uint32_t)chunk;
-                    atomicAdd(&h_all[ck], 1u);
-                    if ((int)(r.y >> pbits) == g0) atomicAdd(&h_hub[ck], 1u);
-                }
-                __syncthreads();
-                if (tid == 0) {   // exclusive scans over at most 512 chunks
-                    uint32_t a_ = 0, h_ = 0;
-                    for (int ck = 0; ck < kMaxChunks; ++ck) {
-                        const uint32_t va = h_all[ck], vh = h_hub[ck];
-                        h_all[ck] = a_;
-                        h_hub[ck] = h_;
-                        a_ += va;
-                        h_ += vh;
-                    }
-                }
-                __syncthreads();
-                if (n <= (uint32_t)GNNTRK_GI_HUB_BITMAP_MIN) {   // a walk over the record's own run
-                    for (uint32_t i = tid; i < M; i += kSortTpb) {
-                        const uint2 r = part[(size_t)i * kRS];
-                        if ((int)(r.y >> pbits) != g0) continue;
-                        const uint32_t ck = (r.x & VM) / (uint32_t)chunk;
-                        const uint32_t r0 = h_all[ck], r1 = ck + 1 < (uint32_t)kMaxChunks ? h_all[ck + 1] : M;
-                        uint32_t cnt = h_hub[ck];
-                        for (uint32_t t = r0; t < r1; ++t) {
-                            const uint2 q = part[(size_t)t * kRS];
-                            cnt += ((int)(q.y >> pbits) == g0 && (q.x & VM) < (r.x & VM)) ? 1u : 0u;
-                        }
-                        out.ranked(base + st0 + cnt, r.x, r.y);
-                        if (O::kRows) out.row(base + st0 + cnt, row_at(i));
-                    }
-                } else {
-                    // a large hub: the values of a run are distinct ids of ONE chunk, so the hub records of a run
-                    // are the set bits of a bitmap over the chunk's id range (spans of 128 K ids: 16 KB of LDS) and
-                    // a record's rank inside its run is the number of set bits below its own - linear in the
-                    // bucket's size (a 2 M-edge hub: 5 s with the walk above, milliseconds this way)
-                    constexpr uint32_t kSpanW = 4096, kSpan = kSpanW * 32;
-                    uint32_t *bm = h_all + 2 * kMaxChunks, *pw = bm + kSpanW;
-                    static_assert((2 * kMaxChunks + 2 * 4096) * sizeof(uint32_t) <= sizeof(s_rec), "hub scratch exceeds s_rec");
-                    for (int ck = 0; ck < kMaxChunks; ++ck) {
-                        const uint32_t r0 = h_all[ck], r1 = ck + 1 < kMaxChunks ? h_all[ck + 1] : M;
-                        const uint32_t hub_here = (ck + 1 < kMaxChunks ? h_hub[ck + 1] : n) - h_hub[ck];
-                        if (hub_here == 0u) continue;   // (uniform)
-                        uint32_t before = h_hub[ck];
-                        for (uint32_t lo = (uint32_t)ck * (uint32_t)chunk, sub = 0; sub < (uint32_t)chunk; sub += kSpan, lo += kSpan) {
-                            __syncthreads();
-                            for (uint32_t w = tid; w < kSpanW; w += kSortTpb) bm[w] = 0u;
-                            __syncthreads();
-                            for (uint32_t t = r0 + tid; t < r1; t += kSortTpb) {
-                                const uint2 q = part[(size_t)t * kRS];
-                                const uint32_t d = (q.x & VM) - lo;
-                                if ((int)(q.y >> pbits) == g0 && d < kSpan) atomicOr(&bm[d >> 5], 1u << (d & 31u));
-                            }
-                            __syncthreads();
-                            // exclusive prefix of the words' bit counts: eight words per thread + a scan of the
-                            // 512 thread sums through pw's upper half
-                            uint32_t mine = 0;
-                            constexpr uint32_t kPer = kSpanW / kSortTpb;
-                            for (uint32_t j = 0; j < kPer; ++j) mine += (uint32_t)__popc(bm[tid * kPer + j]);
-                            uint32_t *ts = pw;   // thread sums, scanned in place
-                            ts[tid] = mine;
-                            __syncthreads();
-                            for (uint32_t off = 1; off < (uint32_t)kSortTpb; off <<= 1) {
-                                const uint32_t v = tid >= (int)off ? ts[tid - off] : 0u;
-                                __syncthreads();
-                                ts[tid] += v;
-                                __syncthreads();
-                            }
-                            const uint32_t excl = ts[tid] - mine, span_total = ts[kSortTpb - 1];
-                            __syncthreads();
-                            uint32_t run_ = excl;
-                            for (uint32_t j = 0; j < kPer; ++j) {
-                                const uint32_t w = tid * kPer + j, c_ = (uint32_t)__popc(bm[w]);
-                                pw[w] = run_;
-                                run_ += c_;
-                            }
-                            __syncthreads();
-                            for (uint32_t t = r0 + tid; t < r1; t += kSortTpb) {
-                                const uint2 q = part[(size_t)t * kRS];
-                                const uint32_t d = (q.x & VM) - lo;
-                                if ((int)(q.y >> pbits) == g0 && d < kSpan) {
-                                    const uint32_t w = d >> 5;
-                                    const uint32_t below = (uint32_t)__popc(bm[w] & ((1u << (d & 31u)) - 1u));
-                                    out.ranked(base + st0 + before + pw[w] + below, q.x, q.y);
-                                    if (O::kRows) out.row(base + st0 + before + pw[w] + below, row_at(t));
-                                }
-                            }
-                            before += span_total;
-                        }
-                    }
-                }
+                // (s_rec is free here: the chunk histograms, the bitmap of a span and its prefix)
+                uint32_t *h_all = reinterpret_cast<uint32_t *>(s_rec), *h_hub = h_all + kMaxChunks;
+                uint32_t *bm = h_hub + kMaxChunks, *pw = bm + kHubSpanW;
+                static_assert((2 * kMaxChunks + 2 * kHubSpanW) * sizeof(uint32_t) <= kCap * sizeof(uint2),
+                              "hub scratch exceeds s_rec");
+                gi_hub_runs<O>(part, M, pbits, chunk, g0, h_all, h_hub);
+                if (n <= (uint32_t)GNNTRK_GI_HUB_BITMAP_MIN)
+                    gi_hub_walk(part, base + st0, M, pbits, chunk, g0, h_all, h_hub, out);
+                else
+                    gi_hub_bitmaps(part, base + st0, M, n, pbits, chunk, g0, h_all, h_hub, bm, pw, out);
                 for (uint32_t j = tid; j < n; j += kSortTpb) out.slot(base + st0 + j, node0 + (uint32_t)g0);
                 __syncthreads();   // (the histograms lived in s_rec: the next group refills it)
                 g0 += 1;
                 continue;
             }
-            const uint32_t n_g = (g1 < kBins ? s_start[g1] : M) - st0;
-            __syncthreads();
-            if (tid < kBins) s_cur[tid] = 0;
-            __syncthreads();
-            for (uint32_t i = tid; i < M; i += kSortTpb) {
-                const uint2 r = part[(size_t)i * kRS];
-                const int low = (int)(r.y >> pbits);
-                if (low >= g0 && low < g1) {
-                    const uint32_t sl = s_start[low] - st0 + atomicAdd(&s_cur[low], 1u);
-                    s_rec[sl] = r;
-                    if (O::kRows) s_pos32[sl] = i;
-                }
-            }
-            __syncthreads();
-            for (uint32_t j = tid; j < n_g; j += kSortTpb) {
-                const uint2 r = s_rec[j];
-                const uint32_t low = r.y >> pbits, st = s_start[low] - st0, n = s_hist[low];
-                uint32_t cnt = 0;
-                for (uint32_t t = 0; t < n; ++t) cnt += (s_rec[st + t].x & VM) < (r.x & VM) ? 1u : 0u;
-                out.ranked(base + st0 + st + cnt, r.x, r.y);
-                if (O::kRows) out.row(base + st0 + st + cnt, row_at(s_pos32[j]));
-                out.slot(base + st0 + j, node0 + low);
-            }
+            gi_sort_group(part, base, M, node0, pbits, g0, g1, s_hist, s_start, s_cur, s_rec, out);
             g0 = g1;
         }
     }
@@ -1109,46 +1066,45 @@ static OwnPlan own_plan(int64_t N, int64_t E, bool rows) {
     return p;
 }
 
-// zeroes the table, with `header` the flag words in front of it as well: one fill per sort
-static int own_zero(const OwnPlan &p, char *ws, bool header, hipStream_t stream) {
-    char *from = ws + (header ? 0 : p.off_tbl);
-    return check_hip(hipMemsetAsync(from, 0, (header ? p.off_tbl : 0) + (size_t)(p.T + 1) * 4, stream),
-                     "graph_index_build(memset)");
+static uint32_t *own_tbl(const OwnPlan &p, char *ws) { return reinterpret_cast<uint32_t *>(ws + p.off_tbl); }
+static int2 *own_range(const OwnPlan &p, char *ws) { return reinterpret_cast<int2 *>(ws + p.off_range); }
+
+// One fill per sort (measured): the table and the `head` bytes in front of it - 0, or the flag words the table follows
+static int own_zero(const OwnPlan &p, char *ws, size_t head, hipStream_t stream) {
+    return check_hip(hipMemsetAsync(ws + p.off_tbl - head, 0, head + (size_t)(p.T + 1) * 4, stream),
+                     "counting sort(memset)");
 }
 
-// kZero: 0 = the caller has zeroed the table AND run step 1 (gi_remap_count_kernel), 1 = zero the table,
-// 2 = zero the header in front of it too
-template <class K, class O, bool ROWS>
-static int own_sort(const OwnPlan &p, K keys, O out, int pbits, int64_t N, int64_t E, char *ws, int *bad,
-                    int zero, hipStream_t stream) {
-    int2 *range = reinterpret_cast<int2 *>(ws + p.off_range);
+// step 1 over a zeroed table (the renumbered build has gi_remap_count_kernel in its place)
+template <class K>
+static void own_count(const OwnPlan &p, K keys, int64_t E, char *ws, int *bad, hipStream_t stream) {
+    hipLaunchKernelGGL((gi_count_kernel<K>), dim3(p.n_chunks), dim3(kCountTpb), 0, stream, keys, E, p.chunk,
+                       p.n_chunks, p.NB, own_tbl(p, ws), own_range(p, ws), bad);
+}
+
+// steps 2 - 4 over a counted table
+template <class K, class O>
+static void own_sort(const OwnPlan &p, K keys, O out, int pbits, int64_t N, int64_t E, char *ws, int *bad,
+                     hipStream_t stream) {
+    typedef typename GiRec<O::kRows>::type Rec;
+    int2 *range = own_range(p, ws);
+    uint32_t *tbl = own_tbl(p, ws);
     uint32_t *base = reinterpret_cast<uint32_t *>(ws + p.off_base);
-    uint32_t *tbl = reinterpret_cast<uint32_t *>(ws + p.off_tbl);
     uint32_t *sums = reinterpret_cast<uint32_t *>(ws + p.off_sums);
-    typename GiRec<ROWS>::type *part = reinterpret_cast<typename GiRec<ROWS>::type *>(ws + p.off_part);
-    if (zero) {
-        const int rc = own_zero(p, ws, zero == 2, stream);
-        if (rc) return rc;
-        hipLaunchKernelGGL((gi_count_kernel<K>), dim3(p.n_chunks), dim3(kCountTpb), 0, stream, keys, E, p.chunk,
-                           p.n_chunks, p.NB, tbl, range, bad);
-    }
+    Rec *part = reinterpret_cast<Rec *>(ws + p.off_part);
     hipLaunchKernelGGL(gi_scan_sums_kernel, dim3(p.n_tiles), dim3(kScanTpb), 0, stream, tbl, p.T + 1, sums);
     hipLaunchKernelGGL(gi_scan_apply_kernel, dim3(p.n_tiles), dim3(kScanTpb), 0, stream, tbl, p.T + 1, sums,
                        p.n_chunks, base);
-    hipLaunchKernelGGL((gi_split_kernel<K, ROWS>), dim3(p.n_chunks), dim3(kSplitTpb), 0, stream, keys, E, p.chunk,
+    hipLaunchKernelGGL((gi_split_kernel<K, O::kRows>), dim3(p.n_chunks), dim3(kSplitTpb), 0, stream, keys, E, p.chunk,
                        p.n_chunks, pbits, tbl, range, part, bad);
     hipLaunchKernelGGL((gi_bucket_sort_kernel<O>), dim3(p.NB), dim3(kSortTpb), 0, stream, part, base, p.NB, N, E,
                        pbits, p.chunk, out);
-    return GNNTRK_OK;
 }
 
-// -------------------------------------------- library path (shapes outside the own sort)
+// -------------------------------------------- library path (flags bit 0, dense graphs, shapes outside the own sort)
 // (ids out of range are counted and clamped, as in the own form; `rank`: see KeysCoo)
 __device__ __forceinline__ uint32_t gi_checked(int64_t v, int64_t N, const int32_t *rank, int *bad) {
-    if (v < 0 || v >= N) {
-        atomicAdd(bad, 1);
-        v = v < 0 ? 0 : N - 1;
-    }
+    v = gi_clamped<false>(v, N, bad);
     return rank ? (uint32_t)rank[v] : (uint32_t)v;
 }
 __global__ __launch_bounds__(kTpb) void gi_keys_kernel(const int64_t *__restrict__ ids, int64_t E,
@@ -1303,38 +1259,34 @@ static int graph_index_build(const int64_t *edge_index, const gnntrk_graph_index
                                    rows ? cy->rows_csr_bf16 : nullptr, rows ? cy->out_stride : 0};
             const OutCsr<false> o1{o->perm, o->tgt, o->src, o->rowptr_t, pmask, label ? cy->label_csr : nullptr,
                                    nullptr, 0};
-            if (rank) {   // renumbered: one pass writes the translated int32 list, the sort reads that
+            // the record width once: 16-byte records where rows are carried
+            auto first_sort = [&](auto keys) {
+                if (rows)
+                    own_sort(plan, keys, o1r, plan.bitsN, N, E, p, bad, stream);
+                else
+                    own_sort(plan, keys, o1, plan.bitsN, N, E, p, bad, stream);
+            };
+            rc = own_zero(plan, p, kHeader, stream);
+            if (rc) return rc;
+            if (rank) {   // renumbered: one pass writes the translated int32 list and counts it, the sort reads that
                 int32_t *src32 = reinterpret_cast<int32_t *>(p + align_up(plan.bytes, 256));
                 int32_t *tgt32 = reinterpret_cast<int32_t *>(p + align_up(plan.bytes, 256) + remap_arr_bytes(E));
                 const int vec_ids = (((uintptr_t)edge_index | (uintptr_t)(edge_index + E)) & 15) == 0;
-#if GNNTRK_GI_REMAP_COUNT
-                rc = own_zero(plan, p, true, stream);
-                if (rc) return rc;
                 hipLaunchKernelGGL(gi_remap_count_kernel, dim3(gi_chunk_grid(plan.n_chunks)), dim3(kRemapTpb), 0, stream, edge_index,
                                    edge_index + E, E, N, rank, vec_ids, src32, tgt32, plan.chunk, plan.n_chunks,
-                                   reinterpret_cast<uint32_t *>(p + plan.off_tbl),
-                                   reinterpret_cast<int2 *>(p + plan.off_range), bad);
-                constexpr int kz = 0;
-#else
-                rc = check_hip(hipMemsetAsync(bad, 0, kHeader, stream), "graph_index_build(memset)");
-                if (rc) return rc;
-                hipLaunchKernelGGL(gi_remap_kernel, dim3(stream_grid((E + 3) / 4)), dim3(kTpb), 0, stream, edge_index,
-                                   edge_index + E, E, N, rank, vec_ids, src32, tgt32, bad);
-                constexpr int kz = 1;
-#endif
-                const KeysCoo32 k32{src32, tgt32, label, rows, rows ? cy->rows_stride : 0,
-                                    (!label || ((uintptr_t)label & 3) == 0) ? 1 : 0};
-                rc = rows ? own_sort<KeysCoo32, OutCsr<true>, true>(plan, k32, o1r, plan.bitsN, N, E, p, bad, kz, stream)
-                          : own_sort<KeysCoo32, OutCsr<false>, false>(plan, k32, o1, plan.bitsN, N, E, p, bad, kz, stream);
-            } else if (rows) {
-                rc = own_sort<KeysCoo, OutCsr<true>, true>(plan, k1, o1r, plan.bitsN, N, E, p, bad, 2, stream);
+                                   own_tbl(plan, p), own_range(plan, p), bad);
+                first_sort(KeysCoo32{src32, tgt32, label, rows, rows ? cy->rows_stride : 0,
+                                     (!label || ((uintptr_t)label & 3) == 0) ? 1 : 0});
             } else {
-                rc = own_sort<KeysCoo, OutCsr<false>, false>(plan, k1, o1, plan.bitsN, N, E, p, bad, 2, stream);
+                own_count(plan, k1, E, p, bad, stream);
+                first_sort(k1);
             }
-            if (rc) return rc;
             const KeysCsr k2{o->src};
             const OutSrc o2{o->spos, o->spos_inv, o->rowptr_s};
-            rc = own_sort<KeysCsr, OutSrc, false>(plan, k2, o2, 0, N, E, p, bad, 1, stream);
+            rc = own_zero(plan, p, 0, stream);
+            if (rc) return rc;
+            own_count(plan, k2, E, p, bad, stream);
+            own_sort(plan, k2, o2, 0, N, E, p, bad, stream);
         } else {
             rc = library_build(edge_index, o, p, bad, N, E, rank, stream);
             if (rc) return rc;
@@ -1417,13 +1369,20 @@ __global__ __launch_bounds__(kTpb) void gi_place_kernel(gnntrk_graph_index part,
 // One 64-bit radix sort of N pairs; the graph-index build then reads every node id through `rank`
 // (gnntrk_graph_index_carry.node_rank), so neighbouring nodes of the graph get neighbouring rows - the
 // gathers of x[src] and the source-sorted gradient stores become local.
+// The order-preserving integer image of a float (NaNs at the ends), and its inverse
+__device__ __forceinline__ uint32_t no_image(float v) {
+    const uint32_t u = __float_as_uint(v);
+    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float no_unimage(uint32_t u) {
+    return __uint_as_float((u >> 31) ? (u ^ 0x80000000u) : ~u);
+}
 __global__ __launch_bounds__(kTpb) void no_keys_kernel(const float *__restrict__ key, int64_t stride,
                                                        const int64_t *__restrict__ batch, int64_t n,
                                                        unsigned long long *__restrict__ keys,
                                                        uint32_t *__restrict__ vals) {
     for (int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTpb) {
-        uint32_t u = __float_as_uint(key[i * stride]);
-        u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;   // order-preserving map of the floats (NaNs at the ends)
+        const uint32_t u = no_image(key[i * stride]);
         const unsigned long long b = batch ? (unsigned long long)(uint32_t)batch[i] : 0ull;
         keys[i] = (b << 32) | u;
         vals[i] = (uint32_t)i;
@@ -1436,8 +1395,7 @@ __global__ __launch_bounds__(kTpb) void no_keys32_kernel(const float *__restrict
                                                          const int64_t *__restrict__ batch, int64_t n, int ebits,
                                                          uint32_t *__restrict__ keys, uint32_t *__restrict__ vals) {
     for (int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTpb) {
-        uint32_t u = __float_as_uint(key[i * stride]);
-        u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;
+        const uint32_t u = no_image(key[i * stride]);
         const uint32_t b = (batch && ebits > 0) ? (uint32_t)batch[i] << (32 - ebits) : 0u;
         keys[i] = b | (ebits > 0 ? u >> ebits : u);
         vals[i] = (uint32_t)i;
@@ -1479,8 +1437,7 @@ __global__ __launch_bounds__(kTpb) void no_minmax_kernel(const float *__restrict
         if (in && keyc) keyc[i] = v;
         long long b = (in && batch) ? batch[i] : 0;
         b = b < 0 ? 0 : b >= n_events ? n_events - 1 : b;   // (counted as bad in the key pass)
-        uint32_t u = __float_as_uint(v);
-        u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;
+        const uint32_t u = no_image(v);
         const bool on = in && v == v;   // (NaN keys take the last level, they do not set the range)
         uint32_t nlo = on ? ~u : 0u, hi = on ? u : 0u;
         const int b0 = __shfl((int)b, 0);
@@ -1504,9 +1461,6 @@ __global__ __launch_bounds__(kTpb) void no_minmax_kernel(const float *__restrict
     for (int t = threadIdx.x; t < 2 * kNoMaxEvents; t += kTpb)
         if (s_mm[t]) atomicMax(&mm[t], s_mm[t]);
 }
-__device__ __forceinline__ float no_unimage(uint32_t u) {
-    return __uint_as_float((u >> 31) ? (u ^ 0x80000000u) : ~u);
-}
 __global__ __launch_bounds__(kTpb) void no_qkeys_kernel(const float *__restrict__ key, int64_t stride,
                                                         const int64_t *__restrict__ batch, int64_t n, int64_t n_events,
                                                         const uint32_t *__restrict__ mm, int32_t *__restrict__ q,
@@ -1523,7 +1477,9 @@ __global__ __launch_bounds__(kTpb) void no_qkeys_kernel(const float *__restrict_
     for (int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTpb) {
         const float v = key[i * stride];
         long long b = batch ? batch[i] : 0;
-        if (b < 0 || b >= n_events) {   // (an event id outside the stated count: counted, clamped - the caller checks)
+        // (an event id outside the stated count: counted, clamped.  The count stays in the workspace, word 2 *
+        // kNoMaxEvents of its head block, and nothing reads it: reading it back would make the host wait)
+        if (b < 0 || b >= n_events) {
             atomicAdd(bad, 1);
             b = b < 0 ? 0 : n_events - 1;
         }
@@ -1536,18 +1492,19 @@ __global__ __launch_bounds__(kTpb) void no_qkeys_kernel(const float *__restrict_
 struct OutNode {   // the sort's outputs for the node order: perm[new] = old, rank[old] = new
     static constexpr uint32_t kValMask = 0xffffffffu;
     static constexpr bool kRows = false;
-    int32_t *perm, *rank, *rowptr;
+    int32_t *perm, *rank;
     __device__ __forceinline__ void ranked(uint32_t k, uint32_t val, uint32_t) const {
         perm[k] = (int32_t)val;
         rank[val] = (int32_t)k;
     }
     __device__ __forceinline__ void row(uint32_t, uint2) const {}
     __device__ __forceinline__ void slot(uint32_t, uint32_t) const {}
+    // (nobody asks where an (event, level) pair starts: up to 4 M row pointers per call stay unwritten)
+    __device__ __forceinline__ void node_start(int64_t, uint32_t) const {}
 };
 // (event, level) pairs the own form takes: the table of the counting sort is bounded by it
 constexpr int64_t kNoMaxKeys = (int64_t)kNoMaxEvents * kNoLevels;
 static bool node_order_own(int64_t n, int64_t n_events, const int64_t *batch, OwnPlan &plan, int64_t &keys) {
-    if (GNNTRK_NO_LIBRARY_SORT_OFF) return false;
     const int64_t ev = batch ? n_events : 1;
     if (ev < 1) return false;   // (event count not stated: the exact radix form)
     if (ev > kNoMaxEvents) return false;
@@ -1615,10 +1572,9 @@ size_t gnntrk_node_order_workspace_bytes(int64_t n_nodes) {
     const size_t m = (size_t)(n_nodes > 0 ? n_nodes : 1);
     const size_t t64 = sort_pairs_u64_temp_bytes(n_nodes), t32 = sort_pairs_temp_bytes(n_nodes);
     const size_t lib = 2 * align_up(m * 8, 256) + 2 * align_up(m * 4, 256) + align_up(t64 > t32 ? t64 : t32, 256);
-    // own form: min / max + flag words | the sort's plan | quantised keys | dense keys | row pointers of the (event, level) pairs
+    // own form: min / max + flag words | the sort's plan | quantised keys | dense keys
     const OwnPlan p = own_plan(kNoMaxKeys, n_nodes > 0 ? n_nodes : 1, false);
-    const size_t own = kNoHead + (p.ok ? align_up(p.bytes, 256) : 0) + 2 * align_up(m * 4, 256) +
-                       align_up((size_t)(kNoMaxKeys + 1) * 4, 256);
+    const size_t own = kNoHead + (p.ok ? align_up(p.bytes, 256) : 0) + 2 * align_up(m * 4, 256);
     return lib > own ? lib : own;
 }
 
@@ -1635,38 +1591,27 @@ int gnntrk_node_order(const float *key, int64_t key_stride, const int64_t *batch
     OwnPlan plan;
     int64_t n_keys = 0;
     if (node_order_own(n_nodes, n_events, batch, plan, n_keys)) {
-        // per event {~min image, max image}; [128]: bad event ids.  The sort's workspace starts inside this block, so that
-        // its table follows the block and one fill zeroes the minima / maxima, the flag word and the table
+        // per event {~min image, max image}; [128]: bad event ids.  The sort's header is the end of this block, so that
+        // its table follows the block and the sort's one fill zeroes the minima / maxima, the flag word and the table
+        static_assert((2 * kNoMaxEvents + 1) * sizeof(uint32_t) <= kNoHead - kHeader, "the head block holds the minima / maxima and the flag word");
         uint32_t *mm = reinterpret_cast<uint32_t *>(p);
         int *bad = reinterpret_cast<int *>(mm + 2 * kNoMaxEvents);
         char *sort_ws = p + kNoHead - kHeader;
         const size_t arr = align_up((size_t)n_nodes * 4, 256);
         int32_t *q = reinterpret_cast<int32_t *>(p + kNoHead + align_up(plan.bytes, 256));
         float *keyc = reinterpret_cast<float *>(reinterpret_cast<char *>(q) + arr);
-        int32_t *rowptr = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(keyc) + arr);
-        int rc = check_hip(hipMemsetAsync(p, 0, kNoHead - kHeader + plan.off_tbl + (size_t)(plan.T + 1) * 4, stream),
-                           "node_order(memset)");
+        const int rc = own_zero(plan, sort_ws, kNoHead, stream);
         if (rc) return rc;
         const int64_t ev = batch ? n_events : 1;
-#if GNNTRK_NO_KEY_COPY
+        // (the min / max pass leaves the key column as a dense array: the key pass then reads 4 bytes per node
+        // instead of a line of the caller's rows)
         hipLaunchKernelGGL(no_minmax_kernel, dim3(grid), dim3(kTpb), 0, stream, key, key_stride, batch, n_nodes, ev,
                            mm, keyc);
         hipLaunchKernelGGL(no_qkeys_kernel, dim3(grid), dim3(kTpb), 0, stream, keyc, (int64_t)1, batch, n_nodes, ev, mm,
                            q, bad);
-#else
-        hipLaunchKernelGGL(no_minmax_kernel, dim3(grid), dim3(kTpb), 0, stream, key, key_stride, batch, n_nodes, ev,
-                           mm, (float *)nullptr);
-        hipLaunchKernelGGL(no_qkeys_kernel, dim3(grid), dim3(kTpb), 0, stream, key, key_stride, batch, n_nodes, ev, mm,
-                           q, bad);
-#endif
-        KeysCsr keys{q};
-        OutNode out{perm, rank, rowptr};
-        hipLaunchKernelGGL((gi_count_kernel<KeysCsr>), dim3(plan.n_chunks), dim3(kCountTpb), 0, stream, keys,
-                           n_nodes, plan.chunk, plan.n_chunks, plan.NB,
-                           reinterpret_cast<uint32_t *>(sort_ws + plan.off_tbl),
-                           reinterpret_cast<int2 *>(sort_ws + plan.off_range), bad);
-        rc = own_sort<KeysCsr, OutNode, false>(plan, keys, out, 0, n_keys, n_nodes, sort_ws, bad, 0, stream);
-        if (rc) return rc;
+        const KeysCsr keys{q};
+        own_count(plan, keys, n_nodes, sort_ws, bad, stream);
+        own_sort(plan, keys, OutNode{perm, rank}, 0, n_keys, n_nodes, sort_ws, bad, stream);
         return check_launch("node_order");
     }
     const size_t k8 = align_up((size_t)n_nodes * 8, 256), v4 = align_up((size_t)n_nodes * 4, 256);

@@ -379,7 +379,7 @@ GRAPH_INDEX_LISTS = (("oddE", 301, 0), ("8mod16", 300, 1), ("oddE-8mod16", 3999,
 
 
 def case_graph_index(device, spec, N=57):
-    """``gnntrk_graph_index_build_carry``, all three ``flags``: ``KeysCoo`` / ``gi_remap_kernel`` read four ids as
+    """``gnntrk_graph_index_build_carry``, all three ``flags``: ``KeysCoo`` / ``gi_remap_count_kernel`` read four ids as
     two 16-byte loads only if both id rows are 16-byte aligned, the labels as one word only if they are 4-byte
     aligned (``KeysCoo`` / ``KeysCoo32``); otherwise item by item.  Odd ``E`` and an 8-mod-16 contiguous edge list,
     each with labels at byte offsets 0 .. 3, with carried rows, and with ``order_by`` (the renumbered build).  The

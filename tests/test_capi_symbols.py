@@ -127,6 +127,7 @@ def test_round5_entry_points_validate_on_the_host(lib_path):
 
     lib = _capi.bind(ctypes.CDLL(str(lib_path)))
     assert lib.gnntrk_node_order_workspace_bytes(1000) >= 1000 * 24
+    assert lib.gnntrk_node_order_workspace_bytes(300) < (1 << 20)   # (a small event does not pay for the largest table)
     assert lib.gnntrk_node_order(None, 1, None, 0, 0, None, None, None, 0, None) == 0      # nothing to order
     assert lib.gnntrk_node_order(None, 1, None, 0, 10, None, None, None, 0, None) == 1 and b"NULL" in lib.gnntrk_last_error()
     buf = (ctypes.c_float * 16)()
