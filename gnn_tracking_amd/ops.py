@@ -24,6 +24,7 @@ from __future__ import annotations
 
 import os
 
+import collections
 import ctypes as C
 import contextlib
 import dataclasses
@@ -477,6 +478,16 @@ def prefetch_graph_index(edge_index: Tensor, n_nodes: int, stream, x: Optional[T
 
 
 # ---------------------------------------------------------------- plain helpers
+def _fold_of(by: str, gi):
+    """``(rowptr, pos)`` of the segment sum that folds CSR-ordered edge rows onto their target ("tgt") or source
+    ("src") nodes: targets are sorted in CSR order, sources are reached through ``spos``."""
+    if by == "tgt":
+        return gi.rowptr_t, None
+    if by == "src":
+        return gi.rowptr_s, gi.spos
+    raise ValueError(by)
+
+
 def _segment_sum_raw(rows: Tensor, rowptr: Tensor, pos: Optional[Tensor], n_seg: int,
                      out: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
     lib = _capi.load()
@@ -521,11 +532,7 @@ class _SegmentSum(torch.autograd.Function):
     def forward(ctx, rows, gi: GraphIndex, by: str):
         _capi.require_device(rows)
         ctx.gi, ctx.by = gi, by
-        if by == "tgt":
-            return _segment_sum_raw(rows, gi.rowptr_t, None, gi.n_nodes)
-        if by == "src":
-            return _segment_sum_raw(rows, gi.rowptr_s, gi.spos, gi.n_nodes)
-        raise ValueError(by)
+        return _segment_sum_raw(rows, *_fold_of(by, gi), gi.n_nodes)
 
     @staticmethod
     def backward(ctx, g):
@@ -616,6 +623,15 @@ class _MlpSpec:
     out_idx: Optional[Tensor]
     out_rows: int
     n_rows: int
+    grad_on: bool   # the CALLER's grad mode (inside an autograd node's forward it is always off)
+
+    @staticmethod
+    def of(segs: Sequence[Seg], weights, biases, *, n_rows: int, epilogue: int = _capi.EPI_NONE, ca: float = 0.0,
+           cb: float = 1.0, out_idx: Optional[Tensor] = None, out_rows: Optional[int] = None) -> "_MlpSpec":
+        return _MlpSpec(len(segs), len(weights), any(b is not None for b in biases),
+                        [s.idx for s in segs], [s.relu for s in segs], [s.reduce for s in segs],
+                        epilogue, float(ca), float(cb), out_idx, int(n_rows if out_rows is None else out_rows),
+                        int(n_rows), torch.is_grad_enabled())
 
 
 def _fill_mlp(weights: Sequence[Tensor], biases: Sequence[Optional[Tensor]]):
@@ -688,148 +704,289 @@ def _param_grad_sinks(weights, biases, need_w, need_b):
     return gW, gb
 
 
+# ---- the host path all six fused-MLP nodes share (the bf16-storage nodes are in ops_bf16.py) ----
+def _unpack(spec: _MlpSpec, tensors, as_rows):
+    """``segs, weights, biases, res, mlp`` of a node's ``[segs..., W..., b..., res]`` inputs: the segments as
+    kernel-ready rows of the storage mode (``as_rows``), the parameters contiguous, the descriptor filled."""
+    ns, nl = spec.n_seg, spec.n_layers
+    segs = [as_rows(t) for t in tensors[:ns]]
+    weights = [w.contiguous() for w in tensors[ns:ns + nl]]
+    biases = [None if b is None else b.contiguous() for b in tensors[ns + nl:ns + 2 * nl]]
+    res = tensors[ns + 2 * nl] if len(tensors) > ns + 2 * nl else None
+    _capi.require_device(*segs, *weights)
+    mlp = _fill_mlp(weights, biases)
+    if sum(s.shape[1] for s in segs) != mlp.in_dim:
+        raise AssertionError(
+            f"Expected feature dimension {mlp.in_dim}, got {sum(s.shape[1] for s in segs)}")
+    return segs, weights, biases, res, mlp
+
+
+def _save(ctx, spec: _MlpSpec, segs, weights, biases, *extras) -> None:
+    """What every backward needs, with a node's own ``extras`` in front (see ``_restore``)."""
+    ctx.spec = spec
+    ctx.save_for_backward(*extras, *segs, *weights, *[b for b in biases if b is not None])
+    ctx.bias_mask = [b is not None for b in biases]
+
+
+def _restore(ctx, n_extra: int = 0):
+    """``extras, segs, weights, biases, mlp`` as ``_save`` left them."""
+    ns, nl = ctx.spec.n_seg, ctx.spec.n_layers
+    saved = ctx.saved_tensors
+    segs, weights = list(saved[n_extra:n_extra + ns]), list(saved[n_extra + ns:n_extra + ns + nl])
+    rest = iter(saved[n_extra + ns + nl:])
+    biases = [next(rest) if m else None for m in ctx.bias_mask]
+    return saved[:n_extra], segs, weights, biases, _fill_mlp(weights, biases)
+
+
+def _fill_args(a, mlp, segs, idx, relu, seg_of, n_rows: int, epilogue: int, ca: float, cb: float):
+    """The part ``MlpFwdArgs`` and ``MlpBwdArgs`` have in common; ``seg_of(rows, idx, relu)``: the storage mode's
+    segment descriptor."""
+    a.mlp = mlp
+    a.n_seg, a.epilogue, a.n_rows = len(segs), epilogue, n_rows
+    a.ca, a.cb = ca, cb
+    for j, s in enumerate(segs):
+        a.seg[j] = seg_of(s, idx[j], relu[j])
+    return a
+
+
+def _seg32(t: Tensor, idx, relu: bool):
+    return _capi.Seg(_p(t), _p(idx), t.shape[1], _row_stride(t), int(relu), 0)
+
+
+def _param_grad_plan(weights, biases, need):
+    """``(any parameter gradient wanted, gradient sinks or None)``; ``need``: ``needs_input_grad`` of ``[W..., b...]``."""
+    if not any(need):
+        return False, None
+    nl = len(weights)
+    return True, _param_grad_sinks(weights, biases, need[:nl], [need[nl + i] or biases[i] is None for i in range(nl)])
+
+
+def _param_grad_fill(a, weights, biases, want_dw: bool, sinks):
+    """Point a backward launch at the buffers of its parameter gradients - the sinks (it then adds) or fresh ones
+    (it stores) - and return them as ``(gW, gb)``."""
+    nl = len(weights)
+    if not want_dw:
+        return [None] * nl, [None] * nl
+    if sinks is not None:
+        gW, gb = sinks
+    else:
+        gW = [torch.empty_like(w) for w in weights]
+        gb = [None if b is None else torch.empty_like(b) for b in biases]
+    for i in range(nl):
+        a.gW[i] = _p(gW[i])
+        a.gb[i] = _p(gb[i])
+    a.accumulate_params = 1 if sinks is not None else 0
+    return gW, gb
+
+
+def _param_grad_outs(need, gW, gb, sinks) -> list:
+    """The ``[W..., b...]`` part of what a node's backward returns."""
+    if sinks is not None:   # (already added into the parameters' gradient buffers)
+        return [None] * len(need)
+    return [g if n else None for g, n in zip([*gW, *gb], need)]
+
+
+def _require_reduce(reduce):
+    if reduce is None:
+        raise RuntimeError("gathered segment requires a `reduce` rule for backward")
+    return reduce
+
+
+def _fold_rows(rows: Tensor, idx: Tensor, reduce, n_src: int) -> Tensor:
+    """Fold the gradients of gathered rows onto their ``n_src`` source rows (``reduce`` as in ``Seg``):
+    deterministic CSR sums."""
+    if reduce == "perm":   # idx is a permutation of the source rows
+        return _permute_raw(rows, idx, scatter=True)
+    by, gi = _require_reduce(reduce)
+    return _segment_sum_raw(rows, *_fold_of(by, gi), n_src)
+
+
+def _sum_terms(gterms) -> Tensor:
+    """The upstream gradient the kernel sums per row, materialised (only the residual epilogue's pass-through
+    gradient needs it, and a node with that epilogue has a single term)."""
+    total = None
+    for g, idx in gterms:
+        rows = g if idx is None else _permute_raw(g, idx, scatter=False)
+        total = rows if total is None else total + rows
+    return total.contiguous()
+
+
+# ---- fp32: the register-resident kernels (csrc/mlp.hip) and the wide, LDS-staged ones (csrc/mlp_wide.hip) ----
+#: what tells the two kernel families apart on the host: ``forward(lib, a, spec, segs, out, keep)`` launches and returns
+#: the tensors to save in front of the common ones, ``backward(lib, a, spec, segs, need_seg, want_dw, g0, extras)``
+#: launches; ``tall_identity``: an identity segment may have more source rows than the launch (the gradient has the
+#: source's height, zero below) - the wide kernels insist on ``n_rows``
+_Fp32Kernels = collections.namedtuple("_Fp32Kernels", "forward backward n_extra tall_identity")
+_DEBUG_FLAGS = int(os.environ.get("GNNTRK_DEBUG_FLAGS", "0"))
+
+
+def _reg_forward(lib, a, spec, segs, out, keep):
+    M = spec.n_rows
+    nbytes = M * (sum(4 * s.shape[1] + (4 if spec.idx[j] is not None else 0)
+                      for j, s in enumerate(segs)) + 4 * a.mlp.out_dim
+                  + (4 if spec.out_idx is not None else 0)
+                  + (4 * a.mlp.out_dim if spec.epilogue == _capi.EPI_RESIDUAL else 0))
+    with _timed(out, kernel_key(lib, a, False), _mlp_flops_per_row(a.mlp) * M, nbytes, M):
+        _capi.check(lib.gnntrk_mlp_forward(C.byref(a), _stream(out)), lib)
+    return ()
+
+
+def _reg_backward(lib, a, spec, segs, need_seg, want_dw, g0, extras):
+    # (the workspace holds the partial sums of the parameter gradients only)
+    ws = _ws(lib.gnntrk_mlp_backward_workspace_bytes(C.byref(a.mlp)), g0) if want_dw else None
+    a.debug_flags = _DEBUG_FLAGS
+    M = spec.n_rows
+    nbytes = M * (sum(4 * s.shape[1] + (4 if spec.idx[j] is not None else 0)
+                      + (4 * s.shape[1] if need_seg[j] else 0)
+                      for j, s in enumerate(segs)) + 4 * a.mlp.out_dim
+                  + (4 if spec.out_idx is not None else 0))
+    with _timed(g0, kernel_key(lib, a, True), 3 * _mlp_flops_per_row(a.mlp) * M, nbytes, M):
+        _capi.check(lib.gnntrk_mlp_backward(C.byref(a), _p(ws), 0 if ws is None else ws.numel(), _stream(g0)), lib)
+
+
+def _wide_forward(lib, a, spec, segs, out, keep):
+    """Saves the hidden layers' pre-activations (only if a backward can follow) and, for the ReLU epilogue, the output."""
+    M = spec.n_rows
+    acts = None
+    if keep and M > 0:
+        hp = int(lib.gnntrk_mlp_wide_hidden_pad(a.mlp.hidden))
+        acts = torch.empty(spec.n_layers - 1, M, hp, dtype=torch.float32, device=out.device)
+    ws = _ws(lib.gnntrk_mlp_wide_forward_workspace_bytes(C.byref(a.mlp)), out)
+    _capi.check(lib.gnntrk_mlp_forward_wide(C.byref(a), _p(acts), _p(ws), ws.numel(), _stream(out)), lib)
+    return acts, out if spec.epilogue == _capi.EPI_RELU else None
+
+
+def _wide_backward(lib, a, spec, segs, need_seg, want_dw, g0, extras):
+    acts, out = extras
+    ws = _ws(lib.gnntrk_mlp_wide_backward_workspace_bytes(C.byref(a.mlp), spec.n_rows), g0)
+    _capi.check(lib.gnntrk_mlp_backward_wide(C.byref(a), _p(acts), _p(out), 0 if out is None else _row_stride(out),
+                                             _p(ws), ws.numel(), _stream(g0)), lib)
+
+
+_REG = _Fp32Kernels(_reg_forward, _reg_backward, 0, True)
+_WIDE = _Fp32Kernels(_wide_forward, _wide_backward, 2, False)
+
+
+def _fp32_forward(ctx, kernels: _Fp32Kernels, spec: _MlpSpec, tensors) -> Tensor:
+    """Forward launch of an fp32 node: fills ``ctx`` for ``_fp32_backward`` and returns the output rows."""
+    segs, weights, biases, res, mlp = _unpack(spec, tensors, _as_rows)
+    lib = _capi.load()
+    a = _fill_args(_capi.MlpFwdArgs(), mlp, segs, spec.idx, spec.relu, _seg32, spec.n_rows, spec.epilogue,
+                   spec.ca, spec.cb)
+    if spec.epilogue == _capi.EPI_RESIDUAL:
+        res = _as_rows(res)
+        a.res, a.res_stride = _p(res), _row_stride(res)
+    out = torch.empty(spec.out_rows, mlp.out_dim, dtype=torch.float32, device=segs[0].device)
+    a.out, a.out_stride, a.out_idx = _p(out), _row_stride(out), _p(spec.out_idx)
+    # (inside forward() grad mode is off and needs_input_grad is True for trainable parameters even under
+    #  no_grad(): the caller's grad mode travels on the spec - inference keeps nothing for a backward)
+    extras = kernels.forward(lib, a, spec, segs, out, spec.grad_on and any(ctx.needs_input_grad))
+    _save(ctx, spec, segs, weights, biases, *extras)
+    return out
+
+
+def _fp32_backward(ctx, kernels: _Fp32Kernels, gterms, need):
+    """Backward launch of an fp32 node + the folds of the gathered segments' gradients.  ``gterms``: up to three
+    ``(rows, index or None)`` upstream gradient terms, summed per row inside the kernel (include/gnntrk.h: gout);
+    ``need``: ``[spec, segs..., W..., b..., res]``.  Returns the gradients in that order."""
+    spec: _MlpSpec = ctx.spec
+    ns, nl = spec.n_seg, spec.n_layers
+    extras, segs, weights, biases, mlp = _restore(ctx, kernels.n_extra)
+    lib = _capi.load()
+    gterms = [(_as_rows(g.contiguous()), idx) for g, idx in gterms]
+    g0 = gterms[0][0]
+    a = _fill_args(_capi.MlpBwdArgs(), mlp, segs, spec.idx, spec.relu, _seg32, spec.n_rows, spec.epilogue,
+                   spec.ca, spec.cb)
+    a.n_gout = len(gterms)
+    for t, (g, idx) in enumerate(gterms):
+        a.gout[t] = _capi.GTerm(_p(g), _p(idx), _row_stride(g), 0)
+    M = spec.n_rows
+    need_seg = [bool(n) for n in need[1:1 + ns]]
+    seg_grads: list[Optional[Tensor]] = [None] * ns
+    row_tmp: list[Optional[Tensor]] = [None] * ns
+    for j, s in enumerate(segs):
+        if not need_seg[j]:
+            continue
+        if spec.idx[j] is None:
+            if s.shape[0] != M and not kernels.tall_identity:
+                raise RuntimeError("identity segments must have n_rows rows")
+            gj = seg_grads[j] = torch.empty(s.shape[0], s.shape[1], dtype=torch.float32, device=g0.device)
+            if s.shape[0] != M:
+                gj.zero_()
+        else:
+            _require_reduce(spec.reduce[j])
+            gj = row_tmp[j] = torch.empty(M, s.shape[1], dtype=torch.float32, device=g0.device)
+        a.gseg[j] = _capi.GSeg(_p(gj), None, _row_stride(gj), 0)
+    need_p = need[1 + ns:1 + ns + 2 * nl]
+    want_dw, sinks = _param_grad_plan(weights, biases, need_p)
+    gW, gb = _param_grad_fill(a, weights, biases, want_dw, sinks)
+    kernels.backward(lib, a, spec, segs, need_seg, want_dw, g0, extras)
+    for j, s in enumerate(segs):
+        if row_tmp[j] is None:
+            continue
+        if spec.reduce[j] == "perm" and s.shape[0] != M:
+            raise RuntimeError("'perm' segments must cover all source rows")
+        seg_grads[j] = _fold_rows(row_tmp[j], spec.idx[j], spec.reduce[j], s.shape[0])
+    g_res = None
+    if spec.epilogue == _capi.EPI_RESIDUAL and need[1 + ns + 2 * nl]:
+        g_res = _axpby_raw(spec.ca, _sum_terms(gterms))
+    return (None, *seg_grads, *_param_grad_outs(need_p, gW, gb, sinks), g_res)
+
+
 class _FusedMLP(torch.autograd.Function):
     @staticmethod
     def forward(ctx, spec: _MlpSpec, *tensors):
-        ns, nl = spec.n_seg, spec.n_layers
-        segs = [_as_rows(t) for t in tensors[:ns]]
-        weights = [w.contiguous() for w in tensors[ns:ns + nl]]
-        biases = [None if b is None else b.contiguous() for b in tensors[ns + nl:ns + 2 * nl]]
-        res = tensors[ns + 2 * nl]
-        _capi.require_device(*segs, *weights)
-        lib = _capi.load()
-        a = _capi.MlpFwdArgs()
-        a.mlp = _fill_mlp(weights, biases)
-        if sum(s.shape[1] for s in segs) != a.mlp.in_dim:
-            raise AssertionError(
-                f"Expected feature dimension {a.mlp.in_dim}, got {sum(s.shape[1] for s in segs)}")
-        a.n_seg, a.epilogue, a.n_rows = ns, spec.epilogue, spec.n_rows
-        for j, s in enumerate(segs):
-            a.seg[j] = _capi.Seg(_p(s), _p(spec.idx[j]), s.shape[1], _row_stride(s),
-                                 int(spec.relu[j]), 0)
-        a.ca, a.cb = spec.ca, spec.cb
-        if spec.epilogue == _capi.EPI_RESIDUAL:
-            res = _as_rows(res)
-            a.res, a.res_stride = _p(res), _row_stride(res)
-        out = torch.empty(spec.out_rows, a.mlp.out_dim, dtype=torch.float32,
-                          device=segs[0].device)
-        a.out, a.out_stride, a.out_idx = _p(out), _row_stride(out), _p(spec.out_idx)
-        M = spec.n_rows
-        nbytes = M * (sum(4 * s.shape[1] + (4 if spec.idx[j] is not None else 0)
-                          for j, s in enumerate(segs)) + 4 * a.mlp.out_dim
-                      + (4 if spec.out_idx is not None else 0)
-                      + (4 * a.mlp.out_dim if spec.epilogue == _capi.EPI_RESIDUAL else 0))
-        with _timed(out, kernel_key(lib, a, False),
-                    _mlp_flops_per_row(a.mlp) * M, nbytes, M):
-            _capi.check(lib.gnntrk_mlp_forward(C.byref(a), _stream(out)), lib)
-        ctx.spec = spec
-        ctx.save_for_backward(*segs, *weights, *[b for b in biases if b is not None])
-        ctx.bias_mask = [b is not None for b in biases]
-        return out
+        return _fp32_forward(ctx, _REG, spec, tensors)
 
     @staticmethod
     def backward(ctx, g_out):
-        spec: _MlpSpec = ctx.spec
-        ns, nl = spec.n_seg, spec.n_layers
-        saved = ctx.saved_tensors
-        segs, weights = list(saved[:ns]), list(saved[ns:ns + nl])
-        bl = list(saved[ns + nl:])
-        biases = [bl.pop(0) if m else None for m in ctx.bias_mask]
-        lib = _capi.load()
-        g_out = _as_rows(g_out.contiguous())
-        dev = g_out.device
-        a = _capi.MlpBwdArgs()
-        a.mlp = _fill_mlp(weights, biases)
-        a.n_seg, a.epilogue, a.n_rows = ns, spec.epilogue, spec.n_rows
-        a.ca, a.cb = spec.ca, spec.cb
-        for j, s in enumerate(segs):
-            a.seg[j] = _capi.Seg(_p(s), _p(spec.idx[j]), s.shape[1], _row_stride(s),
-                                 int(spec.relu[j]), 0)
-        a.n_gout = 1
-        a.gout[0] = _capi.GTerm(_p(g_out), _p(spec.out_idx), _row_stride(g_out), 0)
+        return _fp32_backward(ctx, _REG, [(g_out, ctx.spec.out_idx)], ctx.needs_input_grad)
 
-        need = ctx.needs_input_grad  # [spec, segs..., W..., b..., res]
-        M = spec.n_rows
-        seg_grads: list[Optional[Tensor]] = [None] * ns
-        row_tmp: list[Optional[Tensor]] = [None] * ns
-        for j, s in enumerate(segs):
-            if not need[1 + j]:
-                continue
-            red = spec.reduce[j]
-            if spec.idx[j] is None:
-                gj = torch.empty(s.shape[0], s.shape[1], dtype=torch.float32, device=dev)
-                if s.shape[0] != M:
-                    gj.zero_()
-                seg_grads[j] = gj
-                a.gseg[j] = _capi.GSeg(_p(gj), None, _row_stride(gj), 0)
-            else:
-                if red is None:
-                    raise RuntimeError("gathered segment requires a `reduce` rule for backward")
-                tmp = torch.empty(M, s.shape[1], dtype=torch.float32, device=dev)
-                row_tmp[j] = tmp
-                a.gseg[j] = _capi.GSeg(_p(tmp), None, _row_stride(tmp), 0)
 
-        want_dw = any(need[1 + ns:1 + ns + 2 * nl])
-        gW = [None] * nl
-        gb = [None] * nl
-        ws = None
-        sinks = None
-        if want_dw:
-            sinks = _param_grad_sinks(weights, biases, need[1 + ns:1 + ns + nl],
-                                      [need[1 + ns + nl + i] or biases[i] is None for i in range(nl)])
-            if sinks is not None:
-                gW, gb = sinks
-            else:
-                gW = [torch.empty_like(w) for w in weights]
-                gb = [None if b is None else torch.empty_like(b) for b in biases]
-            for i in range(nl):
-                a.gW[i] = _p(gW[i])
-                a.gb[i] = _p(gb[i])
-            ws = _ws(lib.gnntrk_mlp_backward_workspace_bytes(C.byref(a.mlp)), g_out)
-        a.accumulate_params = 1 if sinks is not None else 0
-        a.debug_flags = int(__import__("os").environ.get("GNNTRK_DEBUG_FLAGS", "0"))
-        nbytes = M * (sum(4 * s.shape[1] + (4 if spec.idx[j] is not None else 0)
-                          + (4 * s.shape[1] if need[1 + j] else 0)
-                          for j, s in enumerate(segs)) + 4 * a.mlp.out_dim
-                      + (4 if spec.out_idx is not None else 0))
-        if __import__("os").environ.get("GNNTRK_DEBUG_PTRS"):
-            def rng(t):
-                return "None" if t is None else f"[{t.data_ptr():#x},{t.data_ptr() + t.numel() * t.element_size():#x})"
-            print("bwd ptrs: g_out", rng(g_out), "ws", rng(ws), "segs", [rng(s) for s in segs],
-                  "W", [rng(w) for w in weights], "gW", [rng(w) for w in gW], "gb", [rng(b) for b in gb],
-                  "gseg", [rng(t) for t in seg_grads], "tmp", [rng(t) for t in row_tmp],
-                  "M", M, "dims", a.mlp.in_dim, a.mlp.hidden, a.mlp.out_dim, flush=True)
-        with _timed(g_out, kernel_key(lib, a, True),
-                    3 * _mlp_flops_per_row(a.mlp) * M, nbytes, M):
-            _capi.check(lib.gnntrk_mlp_backward(C.byref(a), _p(ws),
-                                                0 if ws is None else ws.numel(),
-                                                _stream(g_out)), lib)
+class _FusedMLPWide(torch.autograd.Function):
+    """``_FusedMLP`` on the wide fp32 kernels (csrc/mlp_wide.hip): same spec, same fold rules for gathered
+    segments; the forward keeps the hidden layers' pre-activations for the backward."""
 
-        # fold gathered row gradients onto their source rows (deterministic CSR sums)
-        for j, s in enumerate(segs):
-            if row_tmp[j] is None:
-                continue
-            if spec.reduce[j] == "perm":  # idx is a permutation of the source rows
-                if s.shape[0] != M:
-                    raise RuntimeError("'perm' segments must cover all source rows")
-                seg_grads[j] = _permute_raw(row_tmp[j], spec.idx[j], scatter=True)
-                continue
-            by, gi = spec.reduce[j]
-            rowptr, pos = (gi.rowptr_t, None) if by == "tgt" else (gi.rowptr_s, gi.spos)
-            seg_grads[j] = _segment_sum_raw(row_tmp[j], rowptr, pos, s.shape[0])
+    @staticmethod
+    def forward(ctx, spec: _MlpSpec, *tensors):
+        return _fp32_forward(ctx, _WIDE, spec, tensors)
 
-        g_res = None
-        if spec.epilogue == _capi.EPI_RESIDUAL and need[1 + ns + 2 * nl]:
-            g_dense = g_out if spec.out_idx is None else _permute_raw(g_out, spec.out_idx, False)
-            g_res = _axpby_raw(spec.ca, g_dense.contiguous())
-        outs = [None, *seg_grads]
-        if sinks is not None:   # (already added into the parameters' gradient buffers)
-            outs += [None] * (2 * nl)
-        else:
-            outs += [gW[i] if need[1 + ns + i] else None for i in range(nl)]
-            outs += [gb[i] if need[1 + ns + nl + i] else None for i in range(nl)]
-        outs.append(g_res)
-        return tuple(outs)
+    @staticmethod
+    def backward(ctx, g_out):
+        return _fp32_backward(ctx, _WIDE, [(g_out, None)], ctx.needs_input_grad)
+
+
+class _FusedINEdgeWide(torch.autograd.Function):
+    """Relational model + sum aggregation of one interaction-network layer (interaction_network.py:67-89) as
+    ONE autograd node on the wide fp32 kernels: ``(e~, aggr) = f(segments, params)``.  The backward hands the
+    kernel both upstream terms - ``g_e~[k] + g_aggr[tgt[k]]`` - so the aggregation's gradient is never
+    gathered into an edge-sized tensor (the fp32 twin of ``ops_bf16.FusedINEdge16``)."""
+
+    @staticmethod
+    def forward(ctx, spec: _MlpSpec, gi: GraphIndex, *tensors):
+        e_tilde = _fp32_forward(ctx, _WIDE, spec, tensors)
+        ctx.gi = gi
+        ctx.set_materialize_grads(False)
+        return e_tilde, _segment_sum_raw(e_tilde, gi.rowptr_t, None, gi.n_nodes)
+
+    @staticmethod
+    def backward(ctx, g_et, g_aggr):
+        gterms = []
+        if g_et is not None:
+            gterms.append((g_et, None))
+        if g_aggr is not None:
+            gterms.append((g_aggr, ctx.gi.tgt))
+        need = ctx.needs_input_grad  # [spec, gi, segs..., W..., b...]
+        if not gterms:
+            return (None,) * len(need)
+        outs = _fp32_backward(ctx, _WIDE, gterms, (need[0],) + tuple(need[2:]) + (False,))
+        return (None, None, *outs[1:-1])
+
+
+def in_edge_wide(segs, weights, biases, gi: GraphIndex, n_rows: int):
+    """``(e~, aggr)`` of one interaction-network layer in fp32 on the wide kernels (see _FusedINEdgeWide)."""
+    spec = _MlpSpec.of(segs, weights, biases, n_rows=n_rows)
+    return _FusedINEdgeWide.apply(spec, gi, *[s.t for s in segs], *weights, *biases)
 
 
 def fused_mlp(segs: Sequence[Seg], weights: Sequence[Tensor],
@@ -847,27 +1004,21 @@ def fused_mlp(segs: Sequence[Seg], weights: Sequence[Tensor],
         if s.t.dim() == 1:
             raise ValueError("fused_mlp segments must be 2-D [rows, dim]")
     bf16 = segs[0].t.dtype == torch.bfloat16
-    if not _fused_supported(segs, weights, biases, bf16, epilogue):
-        if not bf16 and out_idx is None and _wide_kernel_supported(segs, weights, epilogue):
-            # fp32 beyond the register-resident kernels (in <= 128, hidden <= 128, out <= 48): the LDS-staged
-            # kernels of csrc/mlp_wide.hip - one forward, one backward launch
-            spec = _MlpSpec(len(segs), len(weights), any(b is not None for b in biases),
-                            [s.idx for s in segs], [s.relu for s in segs], [s.reduce for s in segs],
-                            epilogue, float(ca), float(cb), None, int(n_rows), int(n_rows))
-            # (inside forward() grad mode is off and needs_input_grad is True for trainable parameters even under
-            #  no_grad(): the caller's grad mode travels on the spec - inference does not store the activations)
-            spec.grad_on = torch.is_grad_enabled()
-            return _FusedMLPWide.apply(spec, *[s.t for s in segs], *weights, *biases, res)
+    if _fused_supported(segs, weights, biases, bf16, epilogue):
+        node = _FusedMLP
+        if bf16:  # bf16-storage path (ops_bf16.py)
+            from . import ops_bf16
+            node = ops_bf16.FusedMLP16
+    elif not bf16 and out_idx is None and _wide_kernel_supported(segs, weights, epilogue):
+        # fp32 beyond the register-resident kernels (in <= 128, hidden <= 128, out <= 48): the LDS-staged
+        # kernels of csrc/mlp_wide.hip - one forward, one backward launch, one output row per input row
+        node, out_rows = _FusedMLPWide, None
+    else:
         return _wide_mlp(segs, weights, biases, n_rows=int(n_rows), epilogue=epilogue, ca=float(ca), cb=float(cb),
                          res=res, out_idx=out_idx, out_rows=int(out_rows if out_rows is not None else n_rows))
-    spec = _MlpSpec(len(segs), len(weights), any(b is not None for b in biases),
-                    [s.idx for s in segs], [s.relu for s in segs], [s.reduce for s in segs],
-                    epilogue, float(ca), float(cb), out_idx,
-                    int(out_rows if out_rows is not None else n_rows), int(n_rows))
-    if bf16:  # bf16-storage path (ops_bf16.py)
-        from . import ops_bf16
-        return ops_bf16.FusedMLP16.apply(spec, *[s.t for s in segs], *weights, *biases, res)
-    return _FusedMLP.apply(spec, *[s.t for s in segs], *weights, *biases, res)
+    spec = _MlpSpec.of(segs, weights, biases, n_rows=n_rows, epilogue=epilogue, ca=ca, cb=cb, out_idx=out_idx,
+                       out_rows=out_rows)
+    return node.apply(spec, *[s.t for s in segs], *weights, *biases, res)
 
 
 # ---- the edge-weight head deferred into its backward launch (TrackingModule.backward_step) ----
@@ -917,9 +1068,7 @@ def deferred_head(segs: Sequence[Seg], weights: Sequence[Tensor], biases, gi: "G
             or not _fused_supported(segs, weights, biases, True, _capi.EPI_SIGMOID)
             or not any(t is not None and t.requires_grad for t in [s.t for s in segs] + list(weights) + list(biases))):
         return None
-    spec = _MlpSpec(len(segs), len(weights), any(b is not None for b in biases),
-                    [s.idx for s in segs], [s.relu for s in segs], [s.reduce for s in segs],
-                    _capi.EPI_SIGMOID, float(ca), float(cb), None, int(n_rows), int(n_rows))
+    spec = _MlpSpec.of(segs, weights, biases, n_rows=n_rows, epilogue=_capi.EPI_SIGMOID, ca=ca, cb=cb)
     return PendingEdgeWeights(n_rows, segs[0].t.device, gi, head,
                               (spec, [s.t for s in segs], list(weights), list(biases)))
 
@@ -996,189 +1145,6 @@ def _wide_kernel_supported(segs: Sequence[Seg], weights: Sequence[Tensor], epilo
             and epilogue in (None, _capi.EPI_NONE, _capi.EPI_RELU, _capi.EPI_RESIDUAL))
 
 
-def _wide_forward(ctx, spec: "_MlpSpec", tensors, needs_grad: bool):
-    """Forward launch of the wide fp32 kernels for ``_FusedMLPWide`` / ``_FusedINEdgeWide``: fills ``ctx`` for
-    ``_wide_backward`` and returns the output rows."""
-    ns, nl = spec.n_seg, spec.n_layers
-    segs = [_as_rows(t) for t in tensors[:ns]]
-    weights = [w.contiguous() for w in tensors[ns:ns + nl]]
-    biases = [None if b is None else b.contiguous() for b in tensors[ns + nl:ns + 2 * nl]]
-    res = tensors[ns + 2 * nl] if len(tensors) > ns + 2 * nl else None
-    _capi.require_device(*segs, *weights)
-    lib = _capi.load()
-    a = _capi.MlpFwdArgs()
-    a.mlp = _fill_mlp(weights, biases)
-    if sum(s.shape[1] for s in segs) != a.mlp.in_dim:
-        raise AssertionError(
-            f"Expected feature dimension {a.mlp.in_dim}, got {sum(s.shape[1] for s in segs)}")
-    a.n_seg, a.epilogue, a.n_rows = ns, spec.epilogue, spec.n_rows
-    for j, s in enumerate(segs):
-        a.seg[j] = _capi.Seg(_p(s), _p(spec.idx[j]), s.shape[1], _row_stride(s), int(spec.relu[j]), 0)
-    a.ca, a.cb = spec.ca, spec.cb
-    if spec.epilogue == _capi.EPI_RESIDUAL:
-        res = _as_rows(res)
-        a.res, a.res_stride = _p(res), _row_stride(res)
-    M = spec.n_rows
-    dev = segs[0].device
-    out = torch.empty(M, a.mlp.out_dim, dtype=torch.float32, device=dev)
-    a.out, a.out_stride = _p(out), _row_stride(out)
-    acts = None
-    if needs_grad and M > 0:
-        hp = int(lib.gnntrk_mlp_wide_hidden_pad(a.mlp.hidden))
-        acts = torch.empty(nl - 1, M, hp, dtype=torch.float32, device=dev)
-    ws = _ws(lib.gnntrk_mlp_wide_forward_workspace_bytes(C.byref(a.mlp)), out)
-    _capi.check(lib.gnntrk_mlp_forward_wide(C.byref(a), _p(acts), _p(ws), ws.numel(), _stream(out)), lib)
-    ctx.spec = spec
-    ctx.save_for_backward(acts, out if spec.epilogue == _capi.EPI_RELU else None, *segs, *weights,
-                          *[b for b in biases if b is not None])
-    ctx.bias_mask = [b is not None for b in biases]
-    return out
-
-
-def _wide_backward(ctx, gterms, need):
-    """Backward launch of the wide fp32 kernels.  ``gterms``: up to three ``(rows, index or None)`` upstream
-    gradient terms, summed per row inside the kernel (include/gnntrk.h: gout); ``need``:
-    ``[spec, segs..., W..., b..., res]``.  Returns the gradients in that order."""
-    spec: _MlpSpec = ctx.spec
-    ns, nl = spec.n_seg, spec.n_layers
-    saved = ctx.saved_tensors
-    acts, out = saved[0], saved[1]
-    segs, weights = list(saved[2:2 + ns]), list(saved[2 + ns:2 + ns + nl])
-    bl = list(saved[2 + ns + nl:])
-    biases = [bl.pop(0) if m else None for m in ctx.bias_mask]
-    lib = _capi.load()
-    gterms = [(_as_rows(g.contiguous()), idx) for g, idx in gterms]
-    dev = gterms[0][0].device
-    a = _capi.MlpBwdArgs()
-    a.mlp = _fill_mlp(weights, biases)
-    a.n_seg, a.epilogue, a.n_rows = ns, spec.epilogue, spec.n_rows
-    a.ca, a.cb = spec.ca, spec.cb
-    for j, s in enumerate(segs):
-        a.seg[j] = _capi.Seg(_p(s), _p(spec.idx[j]), s.shape[1], _row_stride(s), int(spec.relu[j]), 0)
-    a.n_gout = len(gterms)
-    for t, (g, idx) in enumerate(gterms):
-        a.gout[t] = _capi.GTerm(_p(g), _p(idx), _row_stride(g), 0)
-    M = spec.n_rows
-    seg_grads: list[Optional[Tensor]] = [None] * ns
-    row_tmp: list[Optional[Tensor]] = [None] * ns
-    for j, s in enumerate(segs):
-        if not need[1 + j]:
-            continue
-        if spec.idx[j] is None:
-            if s.shape[0] != M:
-                raise RuntimeError("identity segments must have n_rows rows")
-            gj = torch.empty(M, s.shape[1], dtype=torch.float32, device=dev)
-            seg_grads[j] = gj
-            a.gseg[j] = _capi.GSeg(_p(gj), None, _row_stride(gj), 0)
-        else:
-            if spec.reduce[j] is None:
-                raise RuntimeError("gathered segment requires a `reduce` rule for backward")
-            tmp = torch.empty(M, s.shape[1], dtype=torch.float32, device=dev)
-            row_tmp[j] = tmp
-            a.gseg[j] = _capi.GSeg(_p(tmp), None, _row_stride(tmp), 0)
-    want_dw = any(need[1 + ns:1 + ns + 2 * nl])
-    gW, gb = [None] * nl, [None] * nl
-    sinks = None
-    if want_dw:
-        sinks = _param_grad_sinks(weights, biases, need[1 + ns:1 + ns + nl],
-                                  [need[1 + ns + nl + i] or biases[i] is None for i in range(nl)])
-        if sinks is not None:
-            gW, gb = sinks
-        else:
-            gW = [torch.empty_like(w) for w in weights]
-            gb = [None if b is None else torch.empty_like(b) for b in biases]
-        for i in range(nl):
-            a.gW[i] = _p(gW[i])
-            a.gb[i] = _p(gb[i])
-    a.accumulate_params = 1 if sinks is not None else 0
-    g0 = gterms[0][0]
-    ws = _ws(lib.gnntrk_mlp_wide_backward_workspace_bytes(C.byref(a.mlp), M), g0)
-    _capi.check(lib.gnntrk_mlp_backward_wide(C.byref(a), _p(acts), _p(out),
-                                             0 if out is None else _row_stride(out), _p(ws), ws.numel(),
-                                             _stream(g0)), lib)
-    for j, s in enumerate(segs):
-        if row_tmp[j] is None:
-            continue
-        if spec.reduce[j] == "perm":
-            if s.shape[0] != M:
-                raise RuntimeError("'perm' segments must cover all source rows")
-            seg_grads[j] = _permute_raw(row_tmp[j], spec.idx[j], scatter=True)
-            continue
-        by, gi = spec.reduce[j]
-        rowptr, pos = (gi.rowptr_t, None) if by == "tgt" else (gi.rowptr_s, gi.spos)
-        seg_grads[j] = _segment_sum_raw(row_tmp[j], rowptr, pos, s.shape[0])
-    g_res = None
-    if spec.epilogue == _capi.EPI_RESIDUAL and need[1 + ns + 2 * nl]:
-        g_res = _axpby_raw(spec.ca, _sum_terms(gterms))
-    outs = [None, *seg_grads]
-    if sinks is not None:
-        outs += [None] * (2 * nl)
-    else:
-        outs += [gW[i] if need[1 + ns + i] else None for i in range(nl)]
-        outs += [gb[i] if need[1 + ns + nl + i] else None for i in range(nl)]
-    outs.append(g_res)
-    return tuple(outs)
-
-
-def _sum_terms(gterms) -> Tensor:
-    """The upstream gradient the kernel sums per row, materialised (only the residual epilogue's pass-through
-    gradient needs it, and that one has a single un-gathered term)."""
-    total = None
-    for g, idx in gterms:
-        rows = g if idx is None else g.index_select(0, idx.long())
-        total = rows if total is None else total + rows
-    return total.contiguous()
-
-
-class _FusedMLPWide(torch.autograd.Function):
-    """``_FusedMLP`` on the wide fp32 kernels (csrc/mlp_wide.hip): same spec, same fold rules for gathered
-    segments; the forward keeps the hidden layers' pre-activations for the backward."""
-
-    @staticmethod
-    def forward(ctx, spec: _MlpSpec, *tensors):
-        return _wide_forward(ctx, spec, tensors, getattr(spec, "grad_on", True) and any(ctx.needs_input_grad))
-
-    @staticmethod
-    def backward(ctx, g_out):
-        return _wide_backward(ctx, [(g_out, None)], ctx.needs_input_grad)
-
-
-class _FusedINEdgeWide(torch.autograd.Function):
-    """Relational model + sum aggregation of one interaction-network layer (interaction_network.py:67-89) as
-    ONE autograd node on the wide fp32 kernels: ``(e~, aggr) = f(segments, params)``.  The backward hands the
-    kernel both upstream terms - ``g_e~[k] + g_aggr[tgt[k]]`` - so the aggregation's gradient is never
-    gathered into an edge-sized tensor (the fp32 twin of ``ops_bf16.FusedINEdge16``)."""
-
-    @staticmethod
-    def forward(ctx, spec: _MlpSpec, gi: GraphIndex, *tensors):
-        e_tilde = _wide_forward(ctx, spec, tensors, getattr(spec, "grad_on", True) and any(ctx.needs_input_grad))
-        ctx.gi = gi
-        ctx.set_materialize_grads(False)
-        return e_tilde, _segment_sum_raw(e_tilde, gi.rowptr_t, None, gi.n_nodes)
-
-    @staticmethod
-    def backward(ctx, g_et, g_aggr):
-        gterms = []
-        if g_et is not None:
-            gterms.append((g_et, None))
-        if g_aggr is not None:
-            gterms.append((g_aggr, ctx.gi.tgt))
-        need = ctx.needs_input_grad  # [spec, gi, segs..., W..., b...]
-        if not gterms:
-            return (None,) * len(need)
-        outs = _wide_backward(ctx, gterms, (need[0],) + tuple(need[2:]) + (False,))
-        return (None, None, *outs[1:-1])
-
-
-def in_edge_wide(segs, weights, biases, gi: GraphIndex, n_rows: int):
-    """``(e~, aggr)`` of one interaction-network layer in fp32 on the wide kernels (see _FusedINEdgeWide)."""
-    spec = _MlpSpec(len(segs), len(weights), any(b is not None for b in biases),
-                    [s.idx for s in segs], [s.relu for s in segs], [s.reduce for s in segs],
-                    _capi.EPI_NONE, 0.0, 1.0, None, int(n_rows), int(n_rows))
-    spec.grad_on = torch.is_grad_enabled()
-    return _FusedINEdgeWide.apply(spec, gi, *[s.t for s in segs], *weights, *biases)
-
-
 class _GatherRows(torch.autograd.Function):
     """``out[m] = t[idx[m]]``; the backward folds the row gradients onto the source rows with the
     deterministic CSR segment sums of the graph index (``reduce`` as in ``Seg``)."""
@@ -1190,15 +1156,7 @@ class _GatherRows(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        g32 = g.to(torch.float32).contiguous()
-        if ctx.reduce == "perm":
-            out = _permute_raw(g32, ctx.idx, scatter=True)
-        elif ctx.reduce is None:
-            raise RuntimeError("gathered segment requires a `reduce` rule for backward")
-        else:
-            by, gi = ctx.reduce
-            rowptr, pos = (gi.rowptr_t, None) if by == "tgt" else (gi.rowptr_s, gi.spos)
-            out = _segment_sum_raw(g32, rowptr, pos, ctx.n)
+        out = _fold_rows(g.to(torch.float32).contiguous(), ctx.idx, ctx.reduce, ctx.n)
         return out.to(ctx.dt), None, None
 
 

@@ -12,17 +12,18 @@ buffer, so ``tensor.stride(0)`` carries the padded row stride through autograd.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional, Sequence
 
 import torch
 from torch import Tensor
 
-from . import _capi
+from . import _capi, ops
 
 BF16 = torch.bfloat16
 
 
-_DEBUG_FLAGS = int(__import__("os").environ.get("GNNTRK_DEBUG_FLAGS", "0"))
+_DEBUG_FLAGS = int(os.environ.get("GNNTRK_DEBUG_FLAGS", "0"))
 
 
 def pad4(d: int) -> int:
@@ -45,8 +46,6 @@ def rows16(t: Tensor) -> Tensor:
         raise TypeError(f"bf16 path got {t.dtype}")
     ok = ((t.shape[1] == 1 or t.stride(1) == 1) and t.stride(0) % 4 == 0
           and t.stride(0) >= pad4(t.shape[1]) and t.data_ptr() % 8 == 0)
-    if t.shape[0] <= 1:
-        ok = ok and t.data_ptr() % 8 == 0 and t.stride(0) >= pad4(t.shape[1]) and t.stride(0) % 4 == 0
     if ok:
         return t
     out = empty_rows(t.shape[0], t.shape[1], t.device, zero=True)
@@ -58,7 +57,6 @@ def to_rows16(x: Tensor, idx: Optional[Tensor] = None) -> Tensor:
     """fp32 rows -> padded bf16 rows (RNE), optionally gathered: ``out[m] = x[idx[m]]``.
     One pass (gnntrk_rows_to_bf16): the dataset's fp32 ``x`` / ``edge_attr`` enter the bf16
     stack through it, ``edge_attr`` already permuted into CSR order."""
-    from . import ops
     lib = _capi.load()
     x = ops._as_rows(x.detach())
     m = int(idx.shape[0]) if idx is not None else int(x.shape[0])
@@ -78,14 +76,8 @@ def mlp_forward_raw(segs: Sequence[Tensor], idx: Sequence[Optional[Tensor]], rel
                     epilogue: int, ca: float, cb: float, res: Optional[Tensor],
                     out_idx: Optional[Tensor], out_rows: int, mlp) -> Tensor:
     """One launch of gnntrk_mlp_forward_bf16; ``segs``/``res`` kernel-ready (rows16)."""
-    from . import ops
     lib = _capi.load()
-    a = _capi.MlpFwdArgs()
-    a.mlp = mlp
-    a.n_seg, a.epilogue, a.n_rows = len(segs), epilogue, n_rows
-    for j, s in enumerate(segs):
-        a.seg[j] = _seg16(s, idx[j], relu[j])
-    a.ca, a.cb = ca, cb
+    a = ops._fill_args(_capi.MlpFwdArgs(), mlp, segs, idx, relu, _seg16, n_rows, epilogue, ca, cb)
     if epilogue == _capi.EPI_RESIDUAL:
         a.res, a.res_stride = res.data_ptr(), res.stride(0)
     dev = segs[0].device
@@ -115,7 +107,7 @@ def mlp_forward_raw(segs: Sequence[Tensor], idx: Sequence[Optional[Tensor]], rel
 #: and measured slower - the segment matrix, five more MFMAs and their packs cost the relational backward
 #: +0.35 ms per 64 M rows (2.34 -> 2.68-2.76) and the head +0.24 ms (3.02 -> 3.26), more than the 0.23 ms streaming
 #: fold + the 16 B/row store they replace: cfg3 step 24.1 against 23.4 ms
-FOLD_IN_KERNEL = __import__("os").environ.get("GNNTRK_FOLD_IN_KERNEL", "0") != "0"
+FOLD_IN_KERNEL = os.environ.get("GNNTRK_FOLD_IN_KERNEL", "0") != "0"
 
 
 def mlp_backward_raw(segs: Sequence[Tensor], idx: Sequence[Optional[Tensor]], relu: Sequence[bool],
@@ -134,14 +126,8 @@ def mlp_backward_raw(segs: Sequence[Tensor], idx: Sequence[Optional[Tensor]], re
     and the loss's gradient itself (``gnntrk_mlp_backward_bf16_bce``) and fills ``bce.w`` / ``bce.loss``; a launch
     that is not the buffer-addressed head shape runs the forward launch, the loss pass and the ordinary backward
     instead - the same kernels in the same order as without the deferral."""
-    from . import ops
     lib = _capi.load()
-    a = _capi.MlpBwdArgs()
-    a.mlp = mlp
-    a.n_seg, a.epilogue, a.n_rows = len(segs), epilogue, n_rows
-    a.ca, a.cb = ca, cb
-    for j, s in enumerate(segs):
-        a.seg[j] = _seg16(s, idx[j], relu[j])
+    a = ops._fill_args(_capi.MlpBwdArgs(), mlp, segs, idx, relu, _seg16, n_rows, epilogue, ca, cb)
     dev = segs[0].device
     slices = _Slices([None] * len(segs))
     for j, s in enumerate(segs):
@@ -217,20 +203,10 @@ def mlp_backward_raw(segs: Sequence[Tensor], idx: Sequence[Optional[Tensor]], re
     if hb is None:
         set_terms(gout)
         try_fold()
-    gW = [None] * len(weights)
-    gb = [None] * len(weights)
-    if want_dw:
-        if sinks is not None:   # (persistent fp32 gradient buffers of the parameters: ops._param_grad_sinks)
-            gW, gb = sinks
-        else:
-            gW = [torch.empty_like(w) for w in weights]
-            gb = [None if b is None else torch.empty_like(b) for b in biases]
-        for i in range(len(weights)):
-            a.gW[i] = gW[i].data_ptr()
-            a.gb[i] = ops._p(gb[i])
+    # (sinks: persistent fp32 gradient buffers of the parameters - ops._param_grad_sinks)
+    gW, gb = ops._param_grad_fill(a, weights, biases, want_dw, sinks)
     # always needed: per-wave partial blocks + the store-redirect slots of masked lanes
     ws = ops._ws(lib.gnntrk_mlp_backward_bf16_workspace_bytes(C.byref(a.mlp)), segs[0])
-    a.accumulate_params = 1 if (want_dw and sinks is not None) else 0
     # (debug_flags: 64 one 16-row tile per iteration instead of two, 128 generic per-lane I/O - A/B timing)
     M = n_rows
     # (algorithmic bytes as SURVEY 8d counts them: a gathered row and its gradient per edge, whether or not the
@@ -282,7 +258,6 @@ class HeadBce:
 
 def _bce_loss_pass(bce: "HeadBce", want_gw: bool) -> Optional[Tensor]:
     """``gnntrk_bce_csr`` on ``bce.w``: fills ``bce.loss``; the unit gradient if wanted."""
-    from . import ops
     lib = _capi.load()
     n = bce.w.numel()
     gw = torch.empty_like(bce.w) if want_gw else None
@@ -305,7 +280,6 @@ class _Slices(list):
 def segment_sum_raw(rows: Tensor, rowptr: Tensor, pos: Optional[Tensor], n_seg: int,
                     addend: Optional[Tensor] = None) -> Tensor:
     """``out[n] = bf16(sum of rows over segment n [+ addend[n]])`` - fp32 accumulation, one rounding."""
-    from . import ops
     lib = _capi.load()
     rows = rows16(rows)
     out = empty_rows(n_seg, rows.shape[1], rows.device)
@@ -324,7 +298,6 @@ def segment_sum_raw(rows: Tensor, rowptr: Tensor, pos: Optional[Tensor], n_seg: 
 
 
 def permute_raw(x: Tensor, idx: Tensor, scatter: bool) -> Tensor:
-    from . import ops
     lib = _capi.load()
     x2 = rows16(x)
     m = int(idx.shape[0])
@@ -342,11 +315,7 @@ class SegmentSum16(torch.autograd.Function):
     def forward(ctx, rows, gi, by: str):
         _capi.require_device(rows)
         ctx.gi, ctx.by = gi, by
-        if by == "tgt":
-            return segment_sum_raw(rows, gi.rowptr_t, None, gi.n_nodes)
-        if by == "src":
-            return segment_sum_raw(rows, gi.rowptr_s, gi.spos, gi.n_nodes)
-        raise ValueError(by)
+        return segment_sum_raw(rows, *ops._fold_of(by, gi), gi.n_nodes)
 
     @staticmethod
     def backward(ctx, g):
@@ -367,41 +336,36 @@ class PermuteRows16(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------ fused MLP (autograd)
+def _forward16(ctx, spec, tensors, launch: bool = True):
+    """Forward of a bf16-storage node over ``[segs..., W..., b..., res]``: fills ``ctx`` for ``_backward_common`` and
+    returns ``(the forward launch's output rows - None without ``launch`` -, the kernel-ready segments)``."""
+    segs, weights, biases, res, mlp = ops._unpack(spec, tensors, rows16)
+    if spec.epilogue != _capi.EPI_RESIDUAL:
+        res = None
+    ctx.dup_of, ctx.res_same = _alias_tables(tensors[:spec.n_seg], res)
+    ctx.res_key = ctx.stash = None
+    if res is not None:
+        res = rows16(res)
+        ctx.res_key = _tensor_key(res)
+    ops._save(ctx, spec, segs, weights, biases)
+    if not launch:
+        return None, segs
+    return mlp_forward_raw(segs, spec.idx, spec.relu, weights, biases, n_rows=spec.n_rows, epilogue=spec.epilogue,
+                           ca=spec.ca, cb=spec.cb, res=res, out_idx=spec.out_idx, out_rows=spec.out_rows, mlp=mlp), segs
+
+
 class FusedMLP16(torch.autograd.Function):
     """bf16-storage twin of ops._FusedMLP (same spec object, same reduce rules)."""
 
     @staticmethod
     def forward(ctx, spec, *tensors):
-        from . import ops
-        ns, nl = spec.n_seg, spec.n_layers
-        segs = [rows16(t) for t in tensors[:ns]]
-        weights = [w.contiguous() for w in tensors[ns:ns + nl]]
-        biases = [None if b is None else b.contiguous() for b in tensors[ns + nl:ns + 2 * nl]]
-        res = tensors[ns + 2 * nl]
-        _capi.require_device(*segs, *weights)
-        mlp = ops._fill_mlp(weights, biases)
-        if sum(s.shape[1] for s in segs) != mlp.in_dim:
-            raise AssertionError(
-                f"Expected feature dimension {mlp.in_dim}, got {sum(s.shape[1] for s in segs)}")
-        ctx.res_key = None
-        ctx.dup_of, ctx.res_same = _alias_tables(tensors[:ns], res if spec.epilogue == _capi.EPI_RESIDUAL else None)
-        if spec.epilogue == _capi.EPI_RESIDUAL:
-            res = rows16(res)
-            ctx.res_key = (res.data_ptr(), tuple(res.shape), res.stride(0))
-        out = mlp_forward_raw(segs, spec.idx, spec.relu, weights, biases, n_rows=spec.n_rows,
-                              epilogue=spec.epilogue, ca=spec.ca, cb=spec.cb, res=res,
-                              out_idx=spec.out_idx, out_rows=spec.out_rows, mlp=mlp)
-        ctx.spec = spec
-        ctx.save_for_backward(*segs, *weights, *[b for b in biases if b is not None])
-        ctx.bias_mask = [b is not None for b in biases]
-        ctx.stash = None
+        out, _ = _forward16(ctx, spec, tensors)
         if spec.epilogue != _capi.EPI_SIGMOID and spec.out_idx is None and spec.epilogue != _capi.EPI_RESIDUAL:
             _attach_stash(ctx, out)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        from . import ops
         spec = ctx.spec
         extra = _stashed_terms(ctx)
         if g_out is None:   # (every reader went through a tap)
@@ -425,20 +389,8 @@ class HeadBCE16(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, spec, bce, *tensors):
-        from . import ops
-        ns, nl = spec.n_seg, spec.n_layers
-        segs = [rows16(t) for t in tensors[:ns]]
-        weights = [w.contiguous() for w in tensors[ns:ns + nl]]
-        biases = [None if b is None else b.contiguous() for b in tensors[ns + nl:ns + 2 * nl]]
-        _capi.require_device(*segs, *weights)
-        mlp = ops._fill_mlp(weights, biases)
-        if sum(s.shape[1] for s in segs) != mlp.in_dim:
-            raise AssertionError(
-                f"Expected feature dimension {mlp.in_dim}, got {sum(s.shape[1] for s in segs)}")
-        ctx.spec, ctx.bce = spec, bce
-        ctx.dup_of, ctx.res_same = _alias_tables(tensors[:ns])
-        ctx.save_for_backward(*segs, *weights, *[b for b in biases if b is not None])
-        ctx.bias_mask = [b is not None for b in biases]
+        _forward16(ctx, spec, tensors, launch=False)
+        ctx.bce = bce
         return bce.loss.view(())
 
     @staticmethod
@@ -477,30 +429,22 @@ def _backward_common(ctx, gout, need, g_rows, node_addend=None, bce=None):
     """Shared by FusedMLP16 and FusedINEdge16: one gnntrk_mlp_backward_bf16 launch for the
     upstream terms ``gout`` + the folds of the gathered input gradients.  ``need`` is laid
     out as [spec, segs..., W..., b..., res].  Returns (grads of segs/W/b, grad of res)."""
-    from . import ops
     spec = ctx.spec
     ns, nl = spec.n_seg, spec.n_layers
-    saved = ctx.saved_tensors
-    segs, weights = list(saved[:ns]), list(saved[ns:ns + nl])
-    bl = list(saved[ns + nl:ns + nl + sum(ctx.bias_mask)])
-    biases = [bl.pop(0) if m else None for m in ctx.bias_mask]
-    mlp = ops._fill_mlp(weights, biases)
+    _, segs, weights, biases, mlp = ops._restore(ctx)
     M = spec.n_rows
     need_seg = [bool(need[1 + j]) for j in range(ns)]
     for j in range(ns):
-        if need_seg[j] and spec.idx[j] is not None and spec.reduce[j] is None:
-            raise RuntimeError("gathered segment requires a `reduce` rule for backward")
-    want_dw = any(need[1 + ns:1 + ns + 2 * nl])
+        if need_seg[j] and spec.idx[j] is not None:
+            ops._require_reduce(spec.reduce[j])
+    need_p = need[1 + ns:1 + ns + 2 * nl]
+    want_dw, sinks = ops._param_grad_plan(weights, biases, need_p)
     # source-gathered node rows: the kernel writes their per-edge gradients already in
     # source-sorted order (a permuted 16-byte store), so the fold below streams instead of
     # gathering random rows
     gidx = [spec.reduce[j][1].spos_inv
             if (need_seg[j] and isinstance(spec.reduce[j], tuple) and spec.reduce[j][0] == "src")
             else None for j in range(ns)]
-    sinks = None
-    if want_dw:
-        sinks = ops._param_grad_sinks(weights, biases, need[1 + ns:1 + ns + nl],
-                                      [need[1 + ns + nl + i] or biases[i] is None for i in range(nl)])
     # the target-gathered segment (CSR order = sorted by target): folded inside the kernel where the launch takes it
     fold = next(((j, int(segs[j].shape[0]), spec.reduce[j][1].rowptr_t) for j in range(ns)
                  if need_seg[j] and isinstance(spec.reduce[j], tuple) and spec.reduce[j][0] == "tgt"
@@ -528,15 +472,14 @@ def _backward_common(ctx, gout, need, g_rows, node_addend=None, bce=None):
             seg_grads[j] = permute_raw(slices[j], spec.idx[j], scatter=True)
         else:
             by, gi = spec.reduce[j]
-            rowptr = gi.rowptr_t if by == "tgt" else gi.rowptr_s  # (src rows are pre-sorted)
+            rowptr = ops._fold_of(by, gi)[0]   # (no position list: the kernel stored src rows in sorted order)
             # a tensor gathered twice (the node embedding by target AND by source): the second fold takes the
             # first as one more fp32 term, and the sum leaves as ONE gradient with one rounding - autograd would
             # add the two (an N-sized pass, a second rounding, and a re-padding copy of its dense result)
             # (same memory AND the same autograd tensor: two unrelated tensors that alias keep separate gradients)
             first = folded.get(_tensor_key(s)) if FOLD_ADD else None
-            if (first is not None and getattr(ctx, "dup_of", None) is not None and ctx.dup_of[j] != first
-                    and ctx.dup_of[first] != j):   # (either order: the kernel-folded segment goes first)
-                first = None
+            if first is not None and ctx.dup_of[j] != first and ctx.dup_of[first] != j:
+                first = None   # (either order: the kernel-folded segment goes first)
             if j in slices.folded:
                 # summed per node by the backward kernel itself (gnntrk_gfold): nothing to read back per edge
                 seg_grads[j] = slices[j]
@@ -559,10 +502,9 @@ def _backward_common(ctx, gout, need, g_rows, node_addend=None, bce=None):
     g_res = None
     if spec.epilogue == _capi.EPI_RESIDUAL and need[1 + ns + 2 * nl]:
         g_dense = g_rows if spec.out_idx is None else permute_raw(g_rows, spec.out_idx, False)
-        res_key = getattr(ctx, "res_key", None)
-        same = [j for j, s in enumerate(segs) if FOLD_ADD and res_key is not None and spec.idx[j] is None
-                and seg_grads[j] is not None and (s.data_ptr(), tuple(s.shape), s.stride(0)) == res_key
-                and seg_grads[j].shape == g_dense.shape and j in getattr(ctx, "res_same", (j,))]
+        same = [j for j, s in enumerate(segs) if FOLD_ADD and ctx.res_key is not None and spec.idx[j] is None
+                and seg_grads[j] is not None and _tensor_key(s) == ctx.res_key
+                and seg_grads[j].shape == g_dense.shape and j in ctx.res_same]
         if same:
             # the residue IS an identity segment of this node (resin.py:26: the layer's own input): its
             # pass-through gradient joins that segment's gradient in one pass instead of a mul and autograd's add
@@ -571,13 +513,7 @@ def _backward_common(ctx, gout, need, g_rows, node_addend=None, bce=None):
             g_res = g_dense * spec.ca
     if node_addend is not None:
         raise RuntimeError("a node gradient handed over by node_tap found no fold to join")
-    outs = list(seg_grads)
-    if sinks is not None:   # (already added into the parameters' gradient buffers)
-        outs += [None] * (2 * nl)
-    else:
-        outs += [gW[i] if need[1 + ns + i] else None for i in range(nl)]
-        outs += [gb[i] if need[1 + ns + nl + i] else None for i in range(nl)]
-    return outs, g_res
+    return [*seg_grads, *ops._param_grad_outs(need_p, gW, gb, sinks)], g_res
 
 
 class FusedINEdge16(torch.autograd.Function):
@@ -589,24 +525,10 @@ class FusedINEdge16(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, spec, gi, *tensors):
-        from . import ops
-        ns, nl = spec.n_seg, spec.n_layers
-        segs = [rows16(t) for t in tensors[:ns]]
-        weights = [w.contiguous() for w in tensors[ns:ns + nl]]
-        biases = [None if b is None else b.contiguous() for b in tensors[ns + nl:ns + 2 * nl]]
-        _capi.require_device(*segs, *weights)
-        mlp = ops._fill_mlp(weights, biases)
-        if sum(s.shape[1] for s in segs) != mlp.in_dim:
-            raise AssertionError(
-                f"Expected feature dimension {mlp.in_dim}, got {sum(s.shape[1] for s in segs)}")
-        e_tilde = mlp_forward_raw(segs, spec.idx, spec.relu, weights, biases, n_rows=spec.n_rows,
-                                  epilogue=spec.epilogue, ca=spec.ca, cb=spec.cb, res=None,
-                                  out_idx=None, out_rows=spec.out_rows, mlp=mlp)
+        ns = spec.n_seg
+        e_tilde, segs = _forward16(ctx, spec, tensors)
         aggr = segment_sum_raw(e_tilde, gi.rowptr_t, None, gi.n_nodes)
-        ctx.spec, ctx.gi = spec, gi
-        ctx.dup_of, ctx.res_same = _alias_tables(tensors[:ns])
-        ctx.save_for_backward(*segs, *weights, *[b for b in biases if b is not None])
-        ctx.bias_mask = [b is not None for b in biases]
+        ctx.gi = gi
         _attach_stash(ctx, e_tilde)
         # the node embedding this layer gathers twice (by target and by source): the object model, which reads
         # the same embedding next to `aggr`, can hand its gradient to THIS node's backward (node_tap below)
@@ -662,10 +584,10 @@ class _Tap(torch.autograd.Function):
 
 
 #: the folds of a tensor gathered twice leave as one sum (off: autograd adds the two)
-FOLD_ADD = __import__("os").environ.get("GNNTRK_FOLD_ADD", "1") != "0"
+FOLD_ADD = os.environ.get("GNNTRK_FOLD_ADD", "1") != "0"
 
 #: gradient taps on / off (off: autograd sums the two gradients of a twice-read embedding itself)
-TAP = __import__("os").environ.get("GNNTRK_GRAD_TAP", "1") != "0"
+TAP = os.environ.get("GNNTRK_GRAD_TAP", "1") != "0"
 
 
 def grad_tap(t: Tensor) -> Tensor:
@@ -721,14 +643,11 @@ def _attach_stash(ctx, out: Tensor) -> None:
 
 
 def _stashed_terms(ctx):
-    g = ctx.stash.take() if getattr(ctx, "stash", None) is not None else None
+    g = ctx.stash.take() if ctx.stash is not None else None
     return [] if g is None else [(rows16(g), None)]
 
 
 def in_edge(segs, weights, biases, gi, n_rows: int):
     """``(e~, aggr)`` of one interaction-network layer in bf16 storage (see FusedINEdge16)."""
-    from . import ops
-    spec = ops._MlpSpec(len(segs), len(weights), any(b is not None for b in biases),
-                        [s.idx for s in segs], [s.relu for s in segs], [s.reduce for s in segs],
-                        _capi.EPI_NONE, 0.0, 1.0, None, int(n_rows), int(n_rows))
+    spec = ops._MlpSpec.of(segs, weights, biases, n_rows=n_rows)
     return FusedINEdge16.apply(spec, gi, *[s.t for s in segs], *weights, *biases)
