@@ -220,6 +220,14 @@ _SIGNATURES = {
                                        C.c_size_t, _P]),
     "gnntrk_oc_forward_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gnntrk_oc_forward": (C.c_int, [C.POINTER(OcArgs), _P, _P, C.c_size_t, _P]),
+    "gnntrk_oc_select_batched_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gnntrk_oc_select_cps_batched": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P,
+                                               C.c_size_t, _P]),
+    "gnntrk_oc_forward_batched_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "gnntrk_oc_forward_batched": (C.c_int, [C.POINTER(OcArgs), _P, _P, C.c_int32, _P, _P, C.c_size_t, _P]),
+    "gnntrk_oc_backward_batched_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "gnntrk_oc_backward_batched": (C.c_int, [C.POINTER(OcArgs), _P, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_size_t,
+                                             _P]),
     "gnntrk_oc_spatial_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "gnntrk_oc_forward_spatial": (C.c_int, [C.POINTER(OcArgs), _P, _P, C.c_size_t, _P]),
     "gnntrk_oc_backward_spatial": (C.c_int, [C.POINTER(OcArgs), _P, _P, _P, _P, C.c_int64, _P, C.c_size_t, _P]),

@@ -10,6 +10,8 @@
 // the gradient w.r.t. the condensation points is the transposed pass (thread = CP, hits
 // streamed).  All sums are fixed-order (per-thread -> per-block fp64 partials -> one block):
 // deterministic, no atomics.  Bound: fp32 VALU (N*K*D fma); HBM traffic is negligible.
+// A collated batch of events runs the same kernels (BATCH = true) with every event its own problem:
+// a block is a tile of one event's hits (points) and streams that event's points (hits) only.
 //
 // The radius-graph variant's `max_num_neighbors` cap is not emulated (torch_cluster keeps an
 // implementation-defined subset when a hit has more neighbours than the cap; the reference
@@ -62,18 +64,91 @@ __global__ __launch_bounds__(kOcTpb) void oc_keys_kernel(const int64_t *__restri
     }
 }
 
+// ---- collated batches: every event its own problem ----------------------------
+// `ptr` holds the row offsets of the events ([n_seg + 1], ascending; an empty event owns no row)
+template <class P>
+__device__ __forceinline__ int oc_event_of(const P *__restrict__ ptr, int n_seg, int64_t i) {
+    int lo = 0, hi = n_seg;  // ptr[lo] <= i < ptr[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)ptr[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The rows of every event are cut into tiles of kOcTpb rows and the tiles numbered event by event: a block never
+// holds rows of two events (its staged LDS chunk belongs to one).  The row counts live on the device, so the host
+// launches ceil(n / kOcTpb) + n_seg blocks - an upper bound - and the surplus ones leave.
+struct OcTile {
+    int e;             // event
+    int64_t row, end;  // this thread's row, the end of the event's rows
+};
+template <class P>
+__device__ __forceinline__ bool oc_block_tile(const P *__restrict__ ptr, int n_seg, int block, OcTile &t) {
+    int first = 0;
+    for (int e = 0; e < n_seg; ++e) {
+        const int64_t lo = ptr[e], hi = ptr[e + 1];
+        const int tiles = (int)((hi - lo + kOcTpb - 1) / kOcTpb);
+        if (block < first + tiles) {
+            t.e = e;
+            t.row = lo + (int64_t)(block - first) * kOcTpb + threadIdx.x;
+            t.end = hi;
+            return true;
+        }
+        first += tiles;
+    }
+    return false;
+}
+// the tiles [first, first + count) of event e
+template <class P>
+__device__ __forceinline__ void oc_event_tiles(const P *__restrict__ ptr, int e, int &first, int &count) {
+    first = 0;
+    for (int i = 0; i < e; ++i) first += (int)(((int64_t)ptr[i + 1] - ptr[i] + kOcTpb - 1) / kOcTpb);
+    count = (int)(((int64_t)ptr[e + 1] - ptr[e] + kOcTpb - 1) / kOcTpb);
+}
+
+// selection of a batch: after the stable sort by particle id a second stable sort by event (the ids use all 64 bits
+// of their key: the event has no room in it).  `batch` is sorted, so event e owns the sorted positions
+// [seg_ptr[e], seg_ptr[e + 1]) as it owns those hits.
+__global__ __launch_bounds__(kOcTpb) void oc_event_keys_kernel(const uint32_t *__restrict__ order,
+                                                               const int64_t *__restrict__ seg_ptr, int n_seg, int64_t n,
+                                                               uint32_t *__restrict__ ekeys, uint32_t *__restrict__ epos) {
+    const int64_t t = (int64_t)blockIdx.x * kOcTpb + threadIdx.x;
+    if (t < n) {
+        ekeys[t] = (uint32_t)oc_event_of(seg_ptr, n_seg, order[t]);
+        epos[t] = (uint32_t)t;
+    }
+}
+__global__ __launch_bounds__(kOcTpb) void oc_event_gather_kernel(const u64 *__restrict__ keys, const uint32_t *__restrict__ order,
+                                                                 const uint32_t *__restrict__ pos, int64_t n,
+                                                                 u64 *__restrict__ keys_out, uint32_t *__restrict__ order_out) {
+    const int64_t t = (int64_t)blockIdx.x * kOcTpb + threadIdx.x;
+    if (t < n) {
+        keys_out[t] = keys[pos[t]];
+        order_out[t] = order[pos[t]];
+    }
+}
+
 // one thread per sorted position that starts a particle: best hit of the particle.
 // mode 0 (RG):    candidates = masked hits, score = beta; qualifies iff a masked hit exists
 // mode 1 (Tiger): candidates = all hits of the particle, score = q; qualifies iff any masked
 // ties -> lowest hit index (the sort is stable, so hits of a particle are in index order)
+// seg_ptr (a batch): a particle ends where its event's sorted positions end
 __global__ __launch_bounds__(kOcTpb) void oc_segment_best_kernel(
     const u64 *__restrict__ keys, const uint32_t *__restrict__ order, const float *__restrict__ score,
-    const uint8_t *__restrict__ mask, int64_t n, int mode, int32_t *__restrict__ seg_flag,
-    int32_t *__restrict__ seg_best) {
+    const uint8_t *__restrict__ mask, int64_t n, int mode, const int64_t *__restrict__ seg_ptr, int n_seg,
+    int32_t *__restrict__ seg_flag, int32_t *__restrict__ seg_best) {
     const int64_t s = (int64_t)blockIdx.x * kOcTpb + threadIdx.x;
     if (s >= n) return;
     int32_t flag = 0, best = -1;
-    if (s == 0 || keys[s] != keys[s - 1]) {
+    int64_t lo = 0;
+    if (seg_ptr) {
+        const int e = oc_event_of(seg_ptr, n_seg, s);
+        lo = seg_ptr[e];
+        n = seg_ptr[e + 1];
+    }
+    if (s == lo || keys[s] != keys[s - 1]) {
         const u64 key = keys[s];
         if (key != 0ull) {  // noise (pid 0) never is an object of interest (mask needs pid > 0)
             float bs = -1.f;
@@ -96,15 +171,25 @@ __global__ __launch_bounds__(kOcTpb) void oc_segment_best_kernel(
 
 // after the exclusive scan of seg_flag: alphas[k] = CP hit of the k-th particle of interest
 // (ascending pid); gid[h] = k for every hit of that particle, else -1
+// seg_ptr (a batch): k counts through the events in turn, cp_ptr[e] = first k of event e
 __global__ __launch_bounds__(kOcTpb) void oc_assign_kernel(
     const u64 *__restrict__ keys, const uint32_t *__restrict__ order,
     const int32_t *__restrict__ seg_flag, const int32_t *__restrict__ seg_best,
-    const int64_t *__restrict__ seg_off, int64_t n, int32_t *__restrict__ alphas,
-    int32_t *__restrict__ gid, int32_t *__restrict__ n_cp) {
+    const int64_t *__restrict__ seg_off, int64_t n, const int64_t *__restrict__ seg_ptr, int n_seg,
+    int32_t *__restrict__ alphas, int32_t *__restrict__ gid, int32_t *__restrict__ cp_ptr,
+    int32_t *__restrict__ n_cp) {
     const int64_t s = (int64_t)blockIdx.x * kOcTpb + threadIdx.x;
+    if (seg_ptr)
+        for (int64_t e = s; e <= n_seg; e += (int64_t)gridDim.x * kOcTpb) cp_ptr[e] = (int32_t)seg_off[seg_ptr[e]];
     if (s >= n) return;
     if (s == 0) n_cp[0] = (int32_t)seg_off[n];
-    if (s == 0 || keys[s] != keys[s - 1]) {
+    int64_t lo = 0;
+    if (seg_ptr) {
+        const int e = oc_event_of(seg_ptr, n_seg, s);
+        lo = seg_ptr[e];
+        n = seg_ptr[e + 1];
+    }
+    if (s == lo || keys[s] != keys[s - 1]) {
         const u64 key = keys[s];
         // gid is preset to -1: only particles of interest walk their (short) segment - the noise
         // "particle" (id 0) has a tenth of all hits and would keep one thread busy for milliseconds
@@ -132,6 +217,10 @@ struct OcParams {
     float keep;    // probability of keeping a repulsive pair (>= 1: all)
     u64 seed;
     const int32_t *cap_nbr;  // RG neighbour cap: per hit its max_num_neighbors-th nearest hit inside the radius, -1: fewer
+    // a batch (the BATCH instantiations): row offsets of the events' hits and of their condensation points
+    const int64_t *seg_ptr;
+    const int32_t *cp_ptr;
+    int32_t n_seg;
 };
 
 // The radius graph's neighbour cap (oc.py:115-117 radius_graph(max_num_neighbors)), nearest first: the
@@ -167,8 +256,35 @@ __device__ __forceinline__ float oc_q(float beta, float q_min) {
     return a * a + q_min;
 }
 
+// what a block of the hit passes works on: its hit and the condensation points [k_lo, K) it streams.
+// BATCH: a tile of one event and that event's points (false: a surplus block)
+struct OcHitBlock {
+    int64_t j;
+    bool live;
+    int k_lo, K, e;
+};
+template <bool BATCH>
+__device__ __forceinline__ bool oc_hit_block(const OcParams &p, OcHitBlock &b) {
+    if constexpr (BATCH) {
+        OcTile t;
+        if (!oc_block_tile(p.seg_ptr, p.n_seg, blockIdx.x, t)) return false;  // (block-uniform: before any barrier)
+        b.j = t.row;
+        b.live = t.row < t.end;
+        b.e = t.e;
+        b.k_lo = p.cp_ptr[t.e];
+        b.K = p.cp_ptr[t.e + 1];
+    } else {
+        b.j = (int64_t)blockIdx.x * kOcTpb + threadIdx.x;
+        b.live = b.j < p.n;
+        b.e = 0;
+        b.k_lo = 0;
+        b.K = p.n_cp[0];
+    }
+    return true;
+}
+
 // forward: per-block partial sums part[block][4] = {attractive, repulsive, n_rep_pairs, unused}
-template <int DP>
+template <int DP, bool BATCH>
 __global__ __launch_bounds__(kOcTpb) void oc_forward_kernel(const OcParams p,
                                                             double *__restrict__ part) {
     __shared__ float s_x[kOcChunk][DP];
@@ -176,9 +292,11 @@ __global__ __launch_bounds__(kOcTpb) void oc_forward_kernel(const OcParams p,
     __shared__ long long s_pid[kOcChunk];
     __shared__ int s_hit[kOcChunk];  // hit index of the staged condensation point
     __shared__ double s_red[kOcTpb / 64];
-    const int64_t j = (int64_t)blockIdx.x * kOcTpb + threadIdx.x;
-    const bool live = j < p.n;
-    const int K = p.n_cp[0];
+    OcHitBlock hb;
+    if (!oc_hit_block<BATCH>(p, hb)) return;
+    const int64_t j = hb.j;
+    const bool live = hb.live;
+    const int K = hb.K;
     float xj[DP];
     float qj = 0.f;
     long long pj = -1;
@@ -206,7 +324,7 @@ __global__ __launch_bounds__(kOcTpb) void oc_forward_kernel(const OcParams p,
     }
     const float r2 = p.radius * p.radius;
     double va = 0.0, vr = 0.0, nrep = 0.0;
-    for (int k0 = 0; k0 < K; k0 += kOcChunk) {
+    for (int k0 = hb.k_lo; k0 < K; k0 += kOcChunk) {
         __syncthreads();
         for (int i = threadIdx.x; i < kOcChunk; i += kOcTpb) {
             const int k = k0 + i;
@@ -250,19 +368,35 @@ __global__ __launch_bounds__(kOcTpb) void oc_forward_kernel(const OcParams p,
 }
 
 // out[0..3] = attractive, repulsive, coward, noise; out[4..7] = norm_att, norm_rep, K, n_rep
+// BATCH: block = event, over that event's tiles, points and hits; out[event][9]
+template <bool BATCH>
 __global__ __launch_bounds__(kOcTpb) void oc_finalize_kernel(const OcParams p,
                                                              const double *__restrict__ part,
                                                              int n_part, float *__restrict__ out) {
     __shared__ double s_red[kOcTpb / 64];
-    const int K = p.n_cp[0];
+    int k_lo = 0, k_hi = p.n_cp[0];
+    int64_t j_lo = 0, j_hi = p.n;
+    if constexpr (BATCH) {
+        const int e = blockIdx.x;
+        int first;
+        oc_event_tiles(p.seg_ptr, e, first, n_part);
+        part += (int64_t)first * 4;
+        out += e * 9;
+        k_lo = p.cp_ptr[e];
+        k_hi = p.cp_ptr[e + 1];
+        j_lo = p.seg_ptr[e];
+        j_hi = p.seg_ptr[e + 1];
+    }
+    const int K = k_hi - k_lo;
+    const int64_t n_hits = j_hi - j_lo;
     double va = 0, vr = 0, nrep = 0, cow = 0, noise = 0, n_noise = 0, n_oi = 0;
     for (int i = threadIdx.x; i < n_part; i += kOcTpb) {
         va += part[i * 4 + 0];
         vr += part[i * 4 + 1];
         nrep += part[i * 4 + 2];
     }
-    for (int k = threadIdx.x; k < K; k += kOcTpb) cow += (double)(1.f - p.beta[p.alphas[k]]);
-    for (int64_t j = threadIdx.x; j < p.n; j += kOcTpb) {
+    for (int k = k_lo + threadIdx.x; k < k_hi; k += kOcTpb) cow += (double)(1.f - p.beta[p.alphas[k]]);
+    for (int64_t j = j_lo + threadIdx.x; j < j_hi; j += kOcTpb) {
         const bool is_noise = (p.mode == 1) ? !(p.pid[j] > 0) : (p.pid[j] == 0);
         if (is_noise) {
             noise += (double)p.beta[j];
@@ -280,7 +414,7 @@ __global__ __launch_bounds__(kOcTpb) void oc_finalize_kernel(const OcParams p,
     if (threadIdx.x == 0) {
         const double eps = 1e-9;
         const double norm_att = eps + n_oi - (double)K;
-        double norm_rep = eps + ((double)K - 1.0) * (double)p.n;
+        double norm_rep = eps + ((double)K - 1.0) * (double)n_hits;
         if (p.keep < 1.f) norm_rep *= (double)p.keep;  // oc.py:328
         out[0] = (float)(va / norm_att);
         out[1] = (float)(vr / norm_rep);
@@ -296,7 +430,8 @@ __global__ __launch_bounds__(kOcTpb) void oc_finalize_kernel(const OcParams p,
 
 // backward, hit side: gx[j] and gq[j] from the pairs of hit j; g = upstream grads of the 4
 // (normalised) loss terms; norms from the forward's out[4..8]
-template <int DP>
+// (BATCH: fwd is [event][9], the norms are the event's)
+template <int DP, bool BATCH>
 __global__ __launch_bounds__(kOcTpb) void oc_backward_hits_kernel(const OcParams p,
                                                                   const float *__restrict__ g,
                                                                   const float *__restrict__ fwd,
@@ -306,9 +441,12 @@ __global__ __launch_bounds__(kOcTpb) void oc_backward_hits_kernel(const OcParams
     __shared__ float s_q[kOcChunk];
     __shared__ long long s_pid[kOcChunk];
     __shared__ int s_hit[kOcChunk];
-    const int64_t j = (int64_t)blockIdx.x * kOcTpb + threadIdx.x;
-    const bool live = j < p.n;
-    const int K = p.n_cp[0];
+    OcHitBlock hb;
+    if (!oc_hit_block<BATCH>(p, hb)) return;
+    const int64_t j = hb.j;
+    const bool live = hb.live;
+    const int K = hb.K;
+    fwd += hb.e * 9;
     const float ca = g[0] / fwd[4], cr = g[1] / fwd[5];
     float xj[DP], gxj[DP];
     float qj = 0.f, gqj = 0.f;
@@ -341,7 +479,7 @@ __global__ __launch_bounds__(kOcTpb) void oc_backward_hits_kernel(const OcParams
         }
     }
     const float r2 = p.radius * p.radius;
-    for (int k0 = 0; k0 < K; k0 += kOcChunk) {
+    for (int k0 = hb.k_lo; k0 < K; k0 += kOcChunk) {
         __syncthreads();
         for (int i = threadIdx.x; i < kOcChunk; i += kOcTpb) {
             const int k = k0 + i;
@@ -403,7 +541,11 @@ __global__ __launch_bounds__(kOcTpb) void oc_backward_hits_kernel(const OcParams
 constexpr int kOcCpBatch = 16384;  // condensation points per launch (bounds the partial buffer)
 constexpr int kOcSlices = 32;      // hit slices
 
-template <int DP>
+// BATCH: a block is a tile of one event's points and streams that event's hits, cut into gridDim.y slices; all
+// points go in one launch and the partial buffer is [slices][n] (a point's row is its index k)
+constexpr int kOcBatchSlices = 8;  // (the events already spread the point pass over the chip)
+
+template <int DP, bool BATCH>
 __global__ __launch_bounds__(kOcTpb) void oc_backward_cps_kernel(const OcParams p,
                                                                  const float *__restrict__ g,
                                                                  const float *__restrict__ fwd,
@@ -414,11 +556,25 @@ __global__ __launch_bounds__(kOcTpb) void oc_backward_cps_kernel(const OcParams 
     __shared__ int s_att[kOcChunk];  // gid if the hit takes part in the attractive sum, else -2
     __shared__ int s_cap[kOcChunk];  // neighbour cap of the staged hit: index (-1: none) and distance
     __shared__ float s_capd2[kOcChunk];
-    const int K = p.n_cp[0];
-    if (k_base + (int)blockIdx.x * kOcTpb >= K) return;  // (uniform: before any barrier)
-    const int kl = blockIdx.x * kOcTpb + threadIdx.x;    // CP inside the batch
-    const int k = k_base + kl;
-    const bool live = k < K;
+    int kl, k;             // CP inside the batch / the partial buffer, CP
+    bool live;
+    int64_t h_lo = 0, h_hi = p.n;  // the hits it meets
+    if constexpr (BATCH) {
+        OcTile t;
+        if (!oc_block_tile(p.cp_ptr, p.n_seg, blockIdx.x, t)) return;  // (uniform: before any barrier)
+        kl = k = (int)t.row;
+        live = t.row < t.end;
+        h_lo = p.seg_ptr[t.e];
+        h_hi = p.seg_ptr[t.e + 1];
+        fwd += t.e * 9;
+    } else {
+        const int K = p.n_cp[0];
+        if (k_base + (int)blockIdx.x * kOcTpb >= K) return;  // (uniform: before any barrier)
+        kl = blockIdx.x * kOcTpb + threadIdx.x;
+        k = k_base + kl;
+        live = k < K;
+    }
+    const int64_t part_rows = BATCH ? p.n : kOcCpBatch;
     const float ca = g[0] / fwd[4], cr = g[1] / fwd[5];
     float xk[DP], gxk[DP];
     float qk = 0.f, gqk = 0.f;
@@ -438,15 +594,15 @@ __global__ __launch_bounds__(kOcTpb) void oc_backward_cps_kernel(const OcParams 
     }
     const float r2 = p.radius * p.radius;
     // slice of the hits (whole LDS chunks)
-    const int64_t n_chunks = (p.n + kOcChunk - 1) / kOcChunk;
+    const int64_t n_chunks = (h_hi - h_lo + kOcChunk - 1) / kOcChunk;
     const int64_t per = (n_chunks + gridDim.y - 1) / gridDim.y;
-    const int64_t j_begin = (int64_t)blockIdx.y * per * kOcChunk;
-    const int64_t j_stop = ((int64_t)(blockIdx.y + 1) * per * kOcChunk < p.n) ? (int64_t)(blockIdx.y + 1) * per * kOcChunk : p.n;
+    const int64_t j_begin = h_lo + (int64_t)blockIdx.y * per * kOcChunk;
+    const int64_t j_stop = (h_lo + (int64_t)(blockIdx.y + 1) * per * kOcChunk < h_hi) ? h_lo + (int64_t)(blockIdx.y + 1) * per * kOcChunk : h_hi;
     for (int64_t j0 = j_begin; j0 < j_stop; j0 += kOcChunk) {
         __syncthreads();
         for (int i = threadIdx.x; i < kOcChunk; i += kOcTpb) {
             const int64_t j = j0 + i;
-            if (j < p.n) {
+            if (j < h_hi) {
 #pragma unroll
                 for (int d = 0; d < DP; ++d) s_x[i][d] = d < p.dim ? p.x[j * p.stride + d] : 0.f;
                 s_q[i] = oc_q(p.beta[j], p.q_min);
@@ -475,7 +631,7 @@ __global__ __launch_bounds__(kOcTpb) void oc_backward_cps_kernel(const OcParams 
         }
         __syncthreads();
         if (!live) continue;
-        const int jn = (int)((p.n - j0 < kOcChunk) ? (p.n - j0) : kOcChunk);
+        const int jn = (int)((h_hi - j0 < kOcChunk) ? (h_hi - j0) : kOcChunk);
         for (int i = 0; i < jn; ++i) {
             float t[DP];
             float d2 = 0.f;
@@ -502,14 +658,14 @@ __global__ __launch_bounds__(kOcTpb) void oc_backward_cps_kernel(const OcParams 
         }
     }
     if (live) {
-        float *o = part + ((int64_t)blockIdx.y * kOcCpBatch + kl) * (DP + 1);
+        float *o = part + ((int64_t)blockIdx.y * part_rows + kl) * (DP + 1);
 #pragma unroll
         for (int d = 0; d < DP; ++d) o[d] = gxk[d];
         o[DP] = gqk;
     }
 }
 
-template <int DP>
+template <int DP, bool BATCH>
 __global__ __launch_bounds__(kOcTpb) void oc_backward_cps_reduce_kernel(const OcParams p,
                                                                         const float *__restrict__ g,
                                                                         const float *__restrict__ fwd,
@@ -520,16 +676,20 @@ __global__ __launch_bounds__(kOcTpb) void oc_backward_cps_reduce_kernel(const Oc
     const int K = p.n_cp[0];
     const int kl = blockIdx.x * kOcTpb + threadIdx.x, k = k_base + kl;
     if (k >= K) return;
+    const int64_t part_rows = BATCH ? p.n : kOcCpBatch;
+    if constexpr (BATCH) fwd += oc_event_of(p.cp_ptr, p.n_seg, k) * 9;
     float acc[DP + 1];
 #pragma unroll
     for (int d = 0; d <= DP; ++d) acc[d] = 0.f;
     for (int sl = 0; sl < n_slices; ++sl) {  // fixed order: bit-reproducible
-        const float *o = part + ((int64_t)sl * kOcCpBatch + kl) * (DP + 1);
+        const float *o = part + ((int64_t)sl * part_rows + kl) * (DP + 1);
 #pragma unroll
         for (int d = 0; d <= DP; ++d) acc[d] += o[d];
     }
     const int32_t ak = p.alphas[k];
-    for (int d = 0; d < p.dim; ++d) gx[(int64_t)ak * p.stride + d] += acc[d];
+#pragma unroll
+    for (int d = 0; d < DP; ++d)   // (unrolled: acc stays in registers)
+        if (d < p.dim) gx[(int64_t)ak * p.stride + d] += acc[d];
     const float bk = p.beta[ak];
     const float a = atanhf(bk);
     gbeta[ak] += acc[DP] * 2.f * a / (1.f - bk * bk) - g[2] / fwd[6];  // coward: mean(1 - beta)
@@ -974,8 +1134,11 @@ struct SelectWs {
     int64_t *off;   // [n + 1]
     char *temp;
     size_t temp_bytes, total;
+    uint32_t *ekeys_a, *ekeys_b, *epos_a, *epos_b;  // a batch: the second sort, by event
+    char *etemp;
+    size_t etemp_bytes;
 };
-static SelectWs select_ws(void *base, int64_t n) {
+static SelectWs select_ws(void *base, int64_t n, bool batched = false) {
     const size_t nn = (size_t)(n > 0 ? n : 1);
     SelectWs w{};
     Carver ws{(char *)base};
@@ -988,6 +1151,14 @@ static SelectWs select_ws(void *base, int64_t n) {
     w.off = ws.take<int64_t>((size_t)(n + 1));
     w.temp_bytes = sort_pairs_u64_temp_bytes(n);
     w.temp = ws.take<char>(w.temp_bytes);
+    if (batched) {
+        w.ekeys_a = ws.take<uint32_t>(nn);
+        w.ekeys_b = ws.take<uint32_t>(nn);
+        w.epos_a = ws.take<uint32_t>(nn);
+        w.epos_b = ws.take<uint32_t>(nn);
+        w.etemp_bytes = sort_pairs_temp_bytes(n);
+        w.etemp = ws.take<char>(w.etemp_bytes);
+    }
     w.total = ws.off;
     return w;
 }
@@ -1008,6 +1179,7 @@ static OcParams oc_params(const gnntrk_oc_args *a) {
     p.keep = a->rep_keep_prob > 0.f ? a->rep_keep_prob : 1.f;   // (0 = field left unset: all pairs)
     p.seed = a->rep_seed;
     p.cap_nbr = a->cap_nbr;
+    p.seg_ptr = nullptr; p.cp_ptr = nullptr; p.n_seg = 0;
     return p;
 }
 
@@ -1071,28 +1243,58 @@ int gnntrk_good_node_mask(const float *pt, const int64_t *particle_id, const flo
 
 size_t gnntrk_oc_select_workspace_bytes(int64_t n) { return select_ws(nullptr, n).total; }
 
-int gnntrk_oc_select_cps(const float *score, const int64_t *particle_id, const uint8_t *mask, int64_t n, int32_t mode,
-                         int32_t *alphas, int32_t *gid, int32_t *n_cp, void *workspace, size_t workspace_bytes,
-                         void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+// seg_ptr != NULL: the selection of a batch
+static int oc_select(const float *score, const int64_t *particle_id, const uint8_t *mask, int64_t n, int32_t mode,
+                     const int64_t *seg_ptr, int32_t n_seg, int32_t *alphas, int32_t *gid, int32_t *cp_ptr, int32_t *n_cp,
+                     void *workspace, size_t workspace_bytes, hipStream_t stream) {
     if (!score || !particle_id || !mask || !alphas || !gid || !n_cp || n < 1 || (mode != 0 && mode != 1))
         return fail(GNNTRK_EINVAL, "oc_select_cps: bad argument");
     if (n > 0x7fffffff) return fail(GNNTRK_EUNSUPPORTED, "oc_select_cps: n must fit int32");
-    const SelectWs w = select_ws(workspace, n);
+    const SelectWs w = select_ws(workspace, n, seg_ptr != nullptr);
     if (!workspace || workspace_bytes < w.total) return fail(GNNTRK_EINVAL, "oc_select_cps: workspace too small");
     const int grid = oc_grid(n);
     hipLaunchKernelGGL(oc_keys_kernel, dim3(grid), dim3(kOcTpb), 0, stream, particle_id, n, w.keys_a, w.vals_a);
     int rc = sort_pairs_u64(w.keys_a, w.keys_b, w.vals_a, w.vals_b, n, w.temp, w.temp_bytes, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(oc_segment_best_kernel, dim3(grid), dim3(kOcTpb), 0, stream,
-                       (const u64 *)w.keys_b, (const uint32_t *)w.vals_b, score, mask, n, mode, w.flag, w.best);
+    const u64 *keys = w.keys_b;
+    const uint32_t *order = w.vals_b;
+    if (seg_ptr) {
+        int bits = 1;
+        while (bits < 31 && (1 << bits) < n_seg) ++bits;
+        hipLaunchKernelGGL(oc_event_keys_kernel, dim3(grid), dim3(kOcTpb), 0, stream, order, seg_ptr, n_seg, n, w.ekeys_a,
+                           w.epos_a);
+        rc = sort_pairs_u32(w.ekeys_a, w.ekeys_b, w.epos_a, w.epos_b, n, bits, w.etemp, w.etemp_bytes, stream);
+        if (rc) return rc;
+        hipLaunchKernelGGL(oc_event_gather_kernel, dim3(grid), dim3(kOcTpb), 0, stream, keys, order,
+                           (const uint32_t *)w.epos_b, n, w.keys_a, w.vals_a);
+        keys = w.keys_a;
+        order = w.vals_a;
+    }
+    hipLaunchKernelGGL(oc_segment_best_kernel, dim3(grid), dim3(kOcTpb), 0, stream, keys, order, score, mask, n, mode,
+                       seg_ptr, n_seg, w.flag, w.best);
     scan_counts_launch(w.flag, 0x7fffffff, n, w.off, stream);
     rc = check_hip(hipMemsetAsync(gid, 0xff, (size_t)n * sizeof(int32_t), stream), "oc_select_cps(memset)");
     if (rc) return rc;
-    hipLaunchKernelGGL(oc_assign_kernel, dim3(grid), dim3(kOcTpb), 0, stream, (const u64 *)w.keys_b,
-                       (const uint32_t *)w.vals_b, (const int32_t *)w.flag, (const int32_t *)w.best,
-                       (const int64_t *)w.off, n, alphas, gid, n_cp);
+    hipLaunchKernelGGL(oc_assign_kernel, dim3(grid), dim3(kOcTpb), 0, stream, keys, order, (const int32_t *)w.flag,
+                       (const int32_t *)w.best, (const int64_t *)w.off, n, seg_ptr, n_seg, alphas, gid, cp_ptr, n_cp);
     return check_launch("oc_select_cps");
+}
+
+int gnntrk_oc_select_cps(const float *score, const int64_t *particle_id, const uint8_t *mask, int64_t n, int32_t mode,
+                         int32_t *alphas, int32_t *gid, int32_t *n_cp, void *workspace, size_t workspace_bytes,
+                         void *stream_) {
+    return oc_select(score, particle_id, mask, n, mode, nullptr, 0, alphas, gid, nullptr, n_cp, workspace, workspace_bytes,
+                     (hipStream_t)stream_);
+}
+
+size_t gnntrk_oc_select_batched_workspace_bytes(int64_t n) { return select_ws(nullptr, n, true).total; }
+
+int gnntrk_oc_select_cps_batched(const float *score, const int64_t *particle_id, const uint8_t *mask, int64_t n,
+                                 int32_t mode, const int64_t *seg_ptr, int32_t n_seg, int32_t *alphas, int32_t *gid,
+                                 int32_t *cp_ptr, int32_t *n_cp, void *workspace, size_t workspace_bytes, void *stream_) {
+    if (!seg_ptr || !cp_ptr || n_seg < 1) return fail(GNNTRK_EINVAL, "oc_select_cps_batched: bad argument");
+    return oc_select(score, particle_id, mask, n, mode, seg_ptr, n_seg, alphas, gid, cp_ptr, n_cp, workspace,
+                     workspace_bytes, (hipStream_t)stream_);
 }
 
 size_t gnntrk_oc_forward_workspace_bytes(int64_t n) { return (size_t)oc_grid(n) * 4 * sizeof(double); }
@@ -1107,10 +1309,75 @@ int gnntrk_oc_forward(const gnntrk_oc_args *args, float *out, void *workspace, s
     const int grid = oc_grid(args->n);
     double *part = reinterpret_cast<double *>(workspace);
     dispatch_dp<2, 4, 8, 16, 32>(args->dim, [&](auto DP) {
-        hipLaunchKernelGGL(oc_forward_kernel<decltype(DP)::value>, dim3(grid), dim3(kOcTpb), 0, stream, p, part);
+        hipLaunchKernelGGL((oc_forward_kernel<decltype(DP)::value, false>), dim3(grid), dim3(kOcTpb), 0, stream, p, part);
     });
-    hipLaunchKernelGGL(oc_finalize_kernel, dim3(1), dim3(kOcTpb), 0, stream, p, (const double *)part, grid, out);
+    hipLaunchKernelGGL(oc_finalize_kernel<false>, dim3(1), dim3(kOcTpb), 0, stream, p, (const double *)part, grid, out);
     return check_launch("oc_forward");
+}
+
+// ---- a batch of events: the same launches, a block = a tile of ONE event (oc_block_tile) ------
+static int oc_batch_params(const gnntrk_oc_args *args, const int64_t *seg_ptr, const int32_t *cp_ptr, int32_t n_seg,
+                           OcParams &p) {
+    int rc = oc_check(args);
+    if (rc) return rc;
+    if (!seg_ptr || !cp_ptr || n_seg < 1) return fail(GNNTRK_EINVAL, "oc_potential (batched): seg_ptr, cp_ptr, n_seg >= 1");
+    if (args->rep_keep_prob > 0.f && args->rep_keep_prob < 1.f)
+        return fail(GNNTRK_EUNSUPPORTED, "oc_potential (batched): rep_keep_prob is per event; not supported in a batch");
+    p = oc_params(args);
+    p.seg_ptr = seg_ptr; p.cp_ptr = cp_ptr; p.n_seg = n_seg;
+    return GNNTRK_OK;
+}
+static int oc_batch_grid(int64_t n, int32_t n_seg) { return (int)(ceil_div(n, kOcTpb) + n_seg); }
+
+size_t gnntrk_oc_forward_batched_workspace_bytes(int64_t n, int32_t n_seg) {
+    return (size_t)oc_batch_grid(n, n_seg) * 4 * sizeof(double);
+}
+
+int gnntrk_oc_forward_batched(const gnntrk_oc_args *args, const int64_t *seg_ptr, const int32_t *cp_ptr, int32_t n_seg,
+                              float *out, void *workspace, size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    OcParams p;
+    int rc = oc_batch_params(args, seg_ptr, cp_ptr, n_seg, p);
+    if (rc) return rc;
+    if (!out || !workspace || workspace_bytes < gnntrk_oc_forward_batched_workspace_bytes(args->n, n_seg))
+        return fail(GNNTRK_EINVAL, "oc_forward_batched: workspace too small");
+    const int grid = oc_batch_grid(args->n, n_seg);
+    double *part = reinterpret_cast<double *>(workspace);
+    dispatch_dp<2, 4, 8, 16, 32>(args->dim, [&](auto DP) {
+        hipLaunchKernelGGL((oc_forward_kernel<decltype(DP)::value, true>), dim3(grid), dim3(kOcTpb), 0, stream, p, part);
+    });
+    hipLaunchKernelGGL(oc_finalize_kernel<true>, dim3(n_seg), dim3(kOcTpb), 0, stream, p, (const double *)part, 0, out);
+    return check_launch("oc_forward_batched");
+}
+
+// partial buffer of the point pass: [kOcBatchSlices][n][dim padded + 1] floats
+size_t gnntrk_oc_backward_batched_workspace_bytes(int64_t n, int32_t dim) {
+    const int dp = dim <= 2 ? 2 : dim <= 4 ? 4 : dim <= 8 ? 8 : dim <= 16 ? 16 : 32;
+    return (size_t)kOcBatchSlices * (size_t)(n > 0 ? n : 1) * (dp + 1) * sizeof(float);
+}
+
+int gnntrk_oc_backward_batched(const gnntrk_oc_args *args, const int64_t *seg_ptr, const int32_t *cp_ptr, int32_t n_seg,
+                               const float *g, const float *fwd, float *gx, float *gbeta, void *workspace,
+                               size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    OcParams p;
+    int rc = oc_batch_params(args, seg_ptr, cp_ptr, n_seg, p);
+    if (rc) return rc;
+    if (!g || !fwd || !gx || !gbeta) return fail(GNNTRK_EINVAL, "oc_backward_batched: bad argument");
+    if (!workspace || workspace_bytes < gnntrk_oc_backward_batched_workspace_bytes(args->n, args->dim))
+        return fail(GNNTRK_EINVAL, "oc_backward_batched: workspace too small");
+    // (at most n points in all: the tile bound of the hits holds for the points, cp_ptr in place of seg_ptr)
+    const int grid = oc_batch_grid(args->n, n_seg);
+    float *part = reinterpret_cast<float *>(workspace);
+    dispatch_dp<2, 4, 8, 16, 32>(args->dim, [&](auto DP) {
+        constexpr int dp = decltype(DP)::value;
+        hipLaunchKernelGGL((oc_backward_hits_kernel<dp, true>), dim3(grid), dim3(kOcTpb), 0, stream, p, g, fwd, gx, gbeta);
+        hipLaunchKernelGGL((oc_backward_cps_kernel<dp, true>), dim3(grid, kOcBatchSlices), dim3(kOcTpb), 0, stream, p, g,
+                           fwd, 0, part);
+        hipLaunchKernelGGL((oc_backward_cps_reduce_kernel<dp, true>), dim3(oc_grid(args->n)), dim3(kOcTpb), 0, stream, p, g,
+                           fwd, 0, (int)kOcBatchSlices, (const float *)part, gx, gbeta);
+    });
+    return check_launch("oc_backward_batched");
 }
 
 // partial buffer of the condensation-point pass: [slices][kOcCpBatch][dim padded + 1] floats
@@ -1131,8 +1398,8 @@ int gnntrk_oc_backward(const gnntrk_oc_args *args, const float *g, const float *
     const OcParams p = oc_params(args);
     const int grid = oc_grid(args->n);
     dispatch_dp<2, 4, 8, 16, 32>(args->dim, [&](auto DP) {
-        hipLaunchKernelGGL(oc_backward_hits_kernel<decltype(DP)::value>, dim3(grid), dim3(kOcTpb), 0, stream, p, g, fwd, gx,
-                           gbeta);
+        hipLaunchKernelGGL((oc_backward_hits_kernel<decltype(DP)::value, false>), dim3(grid), dim3(kOcTpb), 0, stream, p, g,
+                           fwd, gx, gbeta);
     });
     // condensation-point side in batches of kOcCpBatch (the count K lives on the device: batches
     // past it exit at once), each batch cut into hit slices
@@ -1144,9 +1411,9 @@ int gnntrk_oc_backward(const gnntrk_oc_args *args, const float *g, const float *
         const int kgrid = oc_grid(in_batch);
         dispatch_dp<2, 4, 8, 16, 32>(args->dim, [&](auto DP) {
             constexpr int dp = decltype(DP)::value;
-            hipLaunchKernelGGL(oc_backward_cps_kernel<dp>, dim3(kgrid, slices), dim3(kOcTpb), 0, stream, p, g, fwd,
+            hipLaunchKernelGGL((oc_backward_cps_kernel<dp, false>), dim3(kgrid, slices), dim3(kOcTpb), 0, stream, p, g, fwd,
                                (int)kb, part);
-            hipLaunchKernelGGL(oc_backward_cps_reduce_kernel<dp>, dim3(kgrid), dim3(kOcTpb), 0, stream, p, g, fwd,
+            hipLaunchKernelGGL((oc_backward_cps_reduce_kernel<dp, false>), dim3(kgrid), dim3(kOcTpb), 0, stream, p, g, fwd,
                                (int)kb, slices, (const float *)part, gx, gbeta);
         });
     }

@@ -26,11 +26,12 @@ from .hparams import HyperparametersMixin, obj_from_or_to_hparams
 _EF_FUSED_CUT = os.environ.get("GNNTRK_EF_FUSED_CUT", "0") != "0"
 
 
-def knn_with_max_radius(x: Tensor, k: int, max_radius: float | None = None) -> Tensor:
+def knn_with_max_radius(x: Tensor, k: int, max_radius: float | None = None, seg_ptr: Tensor | None = None) -> Tensor:
     """kNN graph that drops edges longer than ``max_radius`` (graph_construction.py:222-237).
 
-    Returns an int64 edge index ``[2, M]``: row 0 = neighbour, row 1 = query."""
-    return ops.knn_graph(x, k, max_radius)
+    Returns an int64 edge index ``[2, M]``: row 0 = neighbour, row 1 = query.  ``seg_ptr`` (row offsets of the events
+    of a collated batch): neighbours inside the query's own event."""
+    return ops.knn_graph(x, k, max_radius, seg_ptr=seg_ptr)
 
 
 def knn_scan(x: Tensor, ks, max_radius: float | None = None) -> dict[int, Tensor]:
@@ -39,6 +40,45 @@ def knn_scan(x: Tensor, ks, max_radius: float | None = None) -> dict[int, Tensor
     k).  The scanner itself, with its figures of merit, is ``k_scanner.GraphConstructionKNNScanner``;
     it evaluates every k from the neighbour table and never materialises these edge lists."""
     return ops.knn_scan(x, ks, max_radius)
+
+
+def _event_ptr(data) -> Tensor | None:
+    """int64 row offsets of the events of a collated ``data`` (its ``ptr``, or from its sorted ``batch``); None if it
+    holds one event"""
+    ptr = getattr(data, "ptr", None)
+    if ptr is None:
+        batch = getattr(data, "batch", None)
+        if batch is None:
+            return None
+        b = batch.long()
+        counts = torch.bincount(b)
+        if b.numel() > 1 and bool((b[1:] < b[:-1]).any()):
+            raise ValueError("MLGraphConstruction: `batch` must be sorted (PyG convention)")
+        ptr = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=b.device)
+        ptr[1:] = torch.cumsum(counts, 0)
+    return ptr.long() if ptr.numel() > 2 else None
+
+
+def _false_edges_per_event(edge_index: Tensor, y: Tensor, ptr: Tensor, ratio: float) -> tuple[Tensor, Tensor]:
+    """``ratio_of_false`` on a batch: per event its first ``int(n_true * ratio)`` false edges, then its true edges,
+    the events in turn - every event as it is treated alone.  The kNN edges are grouped by query, so the edges of an
+    event are contiguous; the ranks inside the event come from prefix sums on the device."""
+    n_ev, m = int(ptr.numel()) - 1, int(edge_index.shape[1])
+    yb = y.bool()
+    if m == 0:
+        return edge_index, y
+    ev = torch.bucketize(edge_index[1], ptr[1:], right=True)            # event of the edge (of its query)
+    true, false = yb.long(), (~yb).long()
+    zeros = torch.zeros(n_ev, dtype=torch.int64, device=y.device)
+    n_keep = (zeros.index_add(0, ev, true).to(torch.float64) * ratio).to(torch.int64)
+    n_edges = zeros.index_add(0, ev, torch.ones_like(true))
+    first = (torch.cumsum(n_edges, 0) - n_edges).clamp_(max=m - 1)      # first edge of the event
+    false_before = torch.cumsum(false, 0) - false                       # false edges before this one
+    rank = false_before - false_before[first][ev]                       # ... inside its event
+    keep = torch.nonzero(yb | (rank < n_keep[ev])).flatten()
+    order = torch.sort(2 * ev[keep] + true[keep], stable=True).indices   # per event: false edges, then true edges
+    keep = keep[order]
+    return edge_index[:, keep].contiguous(), yb[keep].to(y.dtype)
 
 
 def _freeze_if(module, freeze: bool):
@@ -88,6 +128,13 @@ class MLGraphConstruction(nn.Module, HyperparametersMixin):
             node_dim += self._ml.out_dim
         return node_dim, (2 * node_dim if self.hparams.build_edge_features else 0)
 
+    #: a collated ``data`` of more than one event (``ptr`` / ``batch``): neighbours are searched inside the query's own
+    #: event, ``ratio_of_false`` is applied per event and ``batch`` / ``ptr`` are carried into the result - every event
+    #: gives what it gives alone.  False: the reference's behaviour (graph_construction.py:233 searches without
+    #: ``batch``: edges between hits of different events).  A class attribute so that YAML configurations stay those of
+    #: the reference.
+    per_event = True
+
     def _score_before_features(self, x: Tensor) -> bool:
         ef = self._ef
         return (_EF_FUSED_CUT and isinstance(ef, EFMLP) and bool(self.hparams.build_edge_features)
@@ -104,14 +151,17 @@ class MLGraphConstruction(nn.Module, HyperparametersMixin):
         else:
             s = self.hparams.embedding_slice
             emb = data.x[:, s[0]:s[1]]
+        ptr = _event_ptr(data) if self.per_event else None
         edge_index = knn_with_max_radius(emb, max_radius=self.hparams.max_radius,
-                                         k=self.hparams.max_num_neighbors)
+                                         k=self.hparams.max_num_neighbors, seg_ptr=ptr)
         y = ops.edge_labels(data.particle_id, edge_index)
         if self._ml is None or not self.hparams.use_embedding_features:
             x = data.x
         else:
             x = torch.cat((mo["H"], data.x), dim=1)
-        if self.hparams.ratio_of_false and self.training:
+        if self.hparams.ratio_of_false and self.training and ptr is not None:
+            edge_index, y = _false_edges_per_event(edge_index, y, ptr, self.hparams.ratio_of_false)
+        elif self.hparams.ratio_of_false and self.training:
             yb = y.bool()
             n_keep = int(int(yb.sum()) * self.hparams.ratio_of_false)
             false_edges = edge_index[:, ~yb][:, :n_keep]
@@ -138,11 +188,17 @@ class MLGraphConstruction(nn.Module, HyperparametersMixin):
                 edge_index = edge_index[:, mask].contiguous()
                 y = y[mask]
                 edge_attr = edge_attr[mask]
-        return Data(x=x, edge_index=edge_index, true_edges=data.true_edge_index, y=y.long(),
-                    pt=data.pt, particle_id=data.particle_id,
-                    sector=getattr(data, "sector", None),
-                    reconstructable=data.reconstructable, edge_attr=edge_attr, eta=data.eta,
-                    layer=getattr(data, "layer", None))
+        out = Data(x=x, edge_index=edge_index, true_edges=data.true_edge_index, y=y.long(),
+                   pt=data.pt, particle_id=data.particle_id,
+                   sector=getattr(data, "sector", None),
+                   reconstructable=data.reconstructable, edge_attr=edge_attr, eta=data.eta,
+                   layer=getattr(data, "layer", None))
+        if ptr is not None:
+            batch = getattr(data, "batch", None)
+            out.ptr = ptr
+            out.batch = batch if batch is not None else torch.repeat_interleave(
+                torch.arange(ptr.numel() - 1, device=ptr.device), ptr[1:] - ptr[:-1])
+        return out
 
 
 class MLPCTransformer(nn.Module, HyperparametersMixin):

@@ -4,7 +4,8 @@ Reference: metrics/losses/__init__.py:13-41 (``MultiLossFctReturn``) and
 metrics/losses/oc.py:164-436 (``CondensationLossRG``, ``CondensationLossTiger``): same
 constructor keywords, ``hparams`` and return type.  Neither the N x K matrices of the Tiger
 variant nor the radius graph of the RG variant are materialised: both are sums over
-(hit, condensation point) pairs evaluated by ``gnntrk_oc_forward/backward`` (csrc/oc.hip).
+(hit, condensation point) pairs evaluated by ``gnntrk_oc_forward/backward`` (csrc/oc.hip).  A collated ``batch`` of
+several events is one launch sequence in which every event is its own problem (``_CondensationLoss.per_event``).
 
 ``sample_pids < 1`` and Tiger's ``max_n_rep > 0`` (random sub-sampling switches the reference
 has for memory) are honoured for parity of the training dynamics; the random draws differ from
@@ -74,10 +75,14 @@ class _CondensationPotentials(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, beta, x, particle_id, mask, q_min: float, radius: float, eps_sqrt: float,
-                mode: int, keep: float = 1.0, seed: int = 0, cap_nbr=None, stash=None):
+                mode: int, keep: float = 1.0, seed: int = 0, cap_nbr=None, stash=None, seg_ptr=None):
         """``stash`` (a dict): the condensation-point selection of a call is left in it / taken from
         it, so that a second pass over the same hits (``max_n_rep`` sub-sampling) does not select -
-        sort and scan - again."""
+        sort and scan - again.
+
+        ``seg_ptr`` (int64 ``[B + 1]``, B > 1): the hits are a collated batch of B events (sorted by event) and every
+        event is its own problem (``gnntrk_oc_*_batched``); the four terms are the means over the events, ``n_rep`` the
+        sum."""
         _capi.require_device(beta, x, particle_id, mask)
         lib = _capi.load()
         dev = x.device
@@ -87,6 +92,33 @@ class _CondensationPotentials(torch.autograd.Function):
         mask8 = mask.to(torch.uint8).contiguous()
         n, dim = int(x_c.shape[0]), int(x_c.shape[1])
         st = ops._stream(x_c)
+        ctx.batch = None
+        if seg_ptr is not None:
+            if keep < 1.0 or stash is not None:
+                raise ValueError("the sub-sampling of repulsive pairs is per event: not supported in a batch")
+            b = int(seg_ptr.numel()) - 1
+            alphas = torch.empty(n, dtype=torch.int32, device=dev)
+            gid = torch.empty(n, dtype=torch.int32, device=dev)
+            n_cp = torch.zeros(1, dtype=torch.int32, device=dev)
+            cp_ptr = torch.empty(b + 1, dtype=torch.int32, device=dev)
+            ws = ops._ws(lib.gnntrk_oc_select_batched_workspace_bytes(n), x_c)
+            _capi.check(lib.gnntrk_oc_select_cps_batched(ops._p(beta_c), ops._p(pid), ops._p(mask8), n, mode,
+                                                         ops._p(seg_ptr), b, ops._p(alphas), ops._p(gid), ops._p(cp_ptr),
+                                                         ops._p(n_cp), ops._p(ws), ws.numel(), st), lib)
+            a = _capi.OcArgs(ops._p(x_c), ops._p(beta_c), ops._p(pid), ops._p(mask8), ops._p(gid),
+                             ops._p(alphas), ops._p(n_cp), n, dim, dim, q_min, radius, eps_sqrt, mode,
+                             1.0, 0, 0, ops._p(cap_nbr))
+            out = torch.empty(b, 9, dtype=torch.float32, device=dev)
+            ws2 = ops._ws(lib.gnntrk_oc_forward_batched_workspace_bytes(n, b), x_c)
+            _capi.check(lib.gnntrk_oc_forward_batched(C.byref(a), ops._p(seg_ptr), ops._p(cp_ptr), b, ops._p(out),
+                                                      ops._p(ws2), ws2.numel(), st), lib)
+            ctx.save_for_backward(beta_c, x_c, pid, mask8, gid, alphas, n_cp, out)
+            ctx.cfg = (q_min, radius, eps_sqrt, mode, beta.dtype, x.dtype, 1.0, 0)
+            ctx.cap_nbr, ctx.batch, ctx.spatial = cap_nbr, (seg_ptr, cp_ptr), None
+            terms = out[:, :4].mean(0)
+            n_rep = out[:, 7].double().sum()
+            ctx.mark_non_differentiable(n_rep)
+            return terms[0], terms[1], terms[2], terms[3], n_rep
         if stash is not None and "sel" in stash:
             alphas, gid, n_cp = stash["sel"]
         else:
@@ -135,7 +167,15 @@ class _CondensationPotentials(torch.autograd.Function):
                          keep, 0, seed, ops._p(ctx.cap_nbr))
         gx = torch.empty_like(x_c)
         gbeta = torch.empty_like(beta_c)
-        if ctx.spatial is not None:
+        if ctx.batch is not None:
+            seg_ptr, cp_ptr = ctx.batch
+            b = int(seg_ptr.numel()) - 1
+            g = (g / b).contiguous()   # the terms are means over the events
+            ws = ops._ws(lib.gnntrk_oc_backward_batched_workspace_bytes(n, dim), x_c)
+            _capi.check(lib.gnntrk_oc_backward_batched(C.byref(a), ops._p(seg_ptr), ops._p(cp_ptr), b, ops._p(g),
+                                                       ops._p(out), ops._p(gx), ops._p(gbeta), ops._p(ws), ws.numel(),
+                                                       ops._stream(x_c)), lib)
+        elif ctx.spatial is not None:
             _capi.check(lib.gnntrk_oc_backward_spatial(C.byref(a), ops._p(g), ops._p(out), ops._p(gx), ops._p(gbeta),
                                                        n, ops._p(ctx.spatial), ctx.spatial.numel(),
                                                        ops._stream(x_c)), lib)
@@ -143,18 +183,39 @@ class _CondensationPotentials(torch.autograd.Function):
             ws = ops._ws(lib.gnntrk_oc_backward_workspace_bytes(n, dim), x_c)
             _capi.check(lib.gnntrk_oc_backward(C.byref(a), ops._p(g), ops._p(out), ops._p(gx),
                                                ops._p(gbeta), n, ops._p(ws), ws.numel(), ops._stream(x_c)), lib)
-        return gbeta.to(bdt), gx.to(xdt), None, None, None, None, None, None, None, None, None, None
+        return gbeta.to(bdt), gx.to(xdt), None, None, None, None, None, None, None, None, None, None, None
+
+
+def _event_ptr(batch: T) -> T | None:
+    """int64 ``[B + 1]`` row offsets of the events of ``batch`` (as ``losses_ml.radius_graph`` derives them); None if
+    it holds one event"""
+    counts = torch.bincount(batch.long())
+    if counts.numel() < 2:
+        return None
+    seg_ptr = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=batch.device)
+    seg_ptr[1:] = torch.cumsum(counts, 0)
+    return seg_ptr
 
 
 class _CondensationLoss(MultiLossFct, HyperparametersMixin):
     _mode = 0
     _eps_sqrt = 1e-9
+    #: a ``batch`` of more than one event: every event is its own problem (condensation points per (event, particle
+    #: id), attraction, repulsion and all norms inside the event) and each term is the mean over the events - the
+    #: gradient of accumulating over single-event steps.  False: the reference's behaviour, which ignores ``batch``
+    #: (particle ids repeat from event to event: hits of different events share a condensation point).  A class
+    #: attribute so that YAML configurations stay those of the reference.
+    per_event = True
 
-    def _neighbor_cap(self, x):   # (only the radius-graph variant has one)
+    def _neighbor_cap(self, x, seg_ptr=None):   # (only the radius-graph variant has one)
         return None
 
     def _forward(self, *, beta: T, x: T, particle_id: T, reconstructable: T, pt: T,
-                 ec_hit_mask: T | None, eta: T, mask_eta: bool) -> MultiLossFctReturn:
+                 ec_hit_mask: T | None, eta: T, mask_eta: bool, batch: T | None = None) -> MultiLossFctReturn:
+        if batch is not None and not self.per_event:
+            batch = None
+        if batch is not None and batch.shape[0] != particle_id.shape[0]:
+            raise ValueError(f"`batch` has {batch.shape[0]} entries for {particle_id.shape[0]} hits")
         if ec_hit_mask is not None and not getattr(ec_hit_mask, "_gnntrk_all_true", False):
             # model outputs already carry the post-EC node mask, data attributes do not
             particle_id = particle_id[ec_hit_mask]
@@ -162,6 +223,9 @@ class _CondensationLoss(MultiLossFct, HyperparametersMixin):
             pt = pt[ec_hit_mask]
             if mask_eta:
                 eta = eta[ec_hit_mask]
+            if batch is not None:
+                batch = batch[ec_hit_mask]
+        seg_ptr = _event_ptr(batch) if batch is not None else None
         mask = get_good_node_mask_tensors(pt=pt, particle_id=particle_id,
                                           reconstructable=reconstructable, eta=eta,
                                           pt_thld=self.hparams.pt_thld,
@@ -171,12 +235,25 @@ class _CondensationLoss(MultiLossFct, HyperparametersMixin):
             # it to save memory; kept for parity of the training dynamics)
             mask = mask & (torch.rand_like(beta, dtype=torch.float16) < self.hparams.sample_pids)
         # If there are no hits left after masking, then we get a NaN loss.
-        assert bool(mask.any()), "No hits left after masking"
-        args = (beta, x, particle_id, mask, float(self.hparams.q_min), 1.0, self._eps_sqrt, self._mode)
-        cap = self._neighbor_cap(x)
         max_n_rep = int(getattr(self.hparams, "max_n_rep", 0) or 0)
+        if seg_ptr is None:
+            assert bool(mask.any()), "No hits left after masking"
+        else:
+            if max_n_rep > 0:
+                raise ValueError("CondensationLossTiger(max_n_rep > 0) samples the repulsive pairs per event: not "
+                                 "supported with more than one event in `batch`")
+            # per event, and whether `batch` is sorted, in the one host read the assertion costs
+            seen = torch.cat((mask.new_zeros(1, dtype=torch.int64), torch.cumsum(mask, 0, dtype=torch.int64)))
+            b = batch.long()
+            flags = torch.cat(((seen[seg_ptr[1:]] > seen[seg_ptr[:-1]]), (b[1:] < b[:-1]).any().reshape(1))).tolist()
+            if flags[-1]:
+                raise ValueError("condensation loss: `batch` must be sorted (PyG convention)")
+            for e, left in enumerate(flags[:-1]):
+                assert left, f"No hits left after masking (event {e})"
+        args = (beta, x, particle_id, mask, float(self.hparams.q_min), 1.0, self._eps_sqrt, self._mode)
+        cap = self._neighbor_cap(x, seg_ptr)
         stash = {} if max_n_rep > 0 else None
-        att, rep, cow, noise, n_rep = _CondensationPotentials.apply(*args, 1.0, 0, cap, stash)
+        att, rep, cow, noise, n_rep = _CondensationPotentials.apply(*args, 1.0, 0, cap, stash, seg_ptr)
         if max_n_rep > 0 and int(n_rep) > max_n_rep:
             # oc.py:322-328: keep repulsive pairs with probability max_n_rep / n_rep and scale the
             # normalisation accordingly.  The pairs are chosen by a hash of (seed, hit, condensation
@@ -231,7 +308,9 @@ class CondensationLossRG(_CondensationLoss):
     neighbor_cap = "auto"
     cap_check_every = 64
 
-    def _neighbor_cap(self, x):
+    def _neighbor_cap(self, x, seg_ptr=None):
+        # a batch: the count below runs over the hits of all events together - an upper bound of every event's own
+        # count - and the k-th neighbour is searched inside the hit's event
         mode = self.neighbor_cap
         if mode == "off":
             return None
@@ -263,14 +342,14 @@ class CondensationLossRG(_CondensationLoss):
                     "CondensationLossRG: a hit has more than max_num_neighbors=%s hits inside the unit radius - the cap "
                     "is applied nearest first (torch_cluster.radius_graph keeps an implementation-defined subset there, "
                     "differently on CPU and GPU).", k)
-        return ops.knn_kth_neighbor(x, k, 1.0)
+        return ops.knn_kth_neighbor(x, k, 1.0, seg_ptr=seg_ptr)
 
     def forward(self, *, beta: T, x: T, particle_id: T, reconstructable: T, pt: T,
-                ec_hit_mask: T | None = None, eta: T, **kwargs) -> MultiLossFctReturn:
+                ec_hit_mask: T | None = None, eta: T, batch: T | None = None, **kwargs) -> MultiLossFctReturn:
         # NB: like the reference (oc.py:207-213) eta is NOT sliced by ec_hit_mask here
         return self._forward(beta=beta, x=x, particle_id=particle_id,
                              reconstructable=reconstructable, pt=pt, ec_hit_mask=ec_hit_mask,
-                             eta=eta, mask_eta=False)
+                             eta=eta, mask_eta=False, batch=batch)
 
 
 class CondensationLossTiger(_CondensationLoss):
@@ -289,7 +368,7 @@ class CondensationLossTiger(_CondensationLoss):
         self.save_hyperparameters()
 
     def forward(self, *, beta: T, x: T, particle_id: T, reconstructable: T, pt: T,
-                ec_hit_mask: T | None = None, eta: T, **kwargs) -> MultiLossFctReturn:
+                ec_hit_mask: T | None = None, eta: T, batch: T | None = None, **kwargs) -> MultiLossFctReturn:
         return self._forward(beta=beta, x=x, particle_id=particle_id,
                              reconstructable=reconstructable, pt=pt, ec_hit_mask=ec_hit_mask,
-                             eta=eta, mask_eta=True)
+                             eta=eta, mask_eta=True, batch=batch)

@@ -1273,10 +1273,11 @@ def knn_graph(x: Tensor, k: int, max_radius: Optional[float] = None, seg_ptr: Op
     return ei
 
 
-def knn_kth_neighbor(x: Tensor, k: int, max_radius: Optional[float] = None) -> Tensor:
+def knn_kth_neighbor(x: Tensor, k: int, max_radius: Optional[float] = None, seg_ptr: Optional[Tensor] = None) -> Tensor:
     """int32 ``[N]``: for every row the index of its ``k``-th nearest neighbour (inside
     ``max_radius``), -1 where it has fewer - the last column of one ``gnntrk_knn_search``.  Used
-    for the neighbour cap of ``CondensationLossRG``'s radius graph."""
+    for the neighbour cap of ``CondensationLossRG``'s radius graph.  ``seg_ptr`` as for ``knn_graph``:
+    the neighbours of a row are those inside its own event (indices of the whole batch)."""
     _capi.require_device(x)
     lib = _capi.load()
     x = _as_rows(x.detach().to(torch.float32))
@@ -1286,7 +1287,8 @@ def knn_kth_neighbor(x: Tensor, k: int, max_radius: Optional[float] = None) -> T
     nbr = torch.empty(n * k, dtype=torch.int32, device=x.device)
     cnt = torch.empty(n, dtype=torch.int32, device=x.device)
     r = float(max_radius) if max_radius is not None else -1.0
-    _knn_search(lib, x, int(k), r, None, nbr, cnt, _stream(x))
+    sp = seg_ptr.to(device=x.device, dtype=torch.int64).contiguous() if seg_ptr is not None else None
+    _knn_search(lib, x, int(k), r, sp, nbr, cnt, _stream(x))
     last = nbr.view(n, k)[:, k - 1]
     return torch.where(cnt >= k, last, torch.full_like(last, -1)).contiguous()
 

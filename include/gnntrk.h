@@ -681,6 +681,33 @@ int gnntrk_oc_backward(const gnntrk_oc_args *args, const float *g /*[4]*/, const
                        float *gx, float *gbeta, int64_t max_cps, void *workspace,
                        size_t workspace_bytes, void *stream);
 
+/* The same on a collated batch of events, every event its own problem.  seg_ptr: int64
+ * [n_seg + 1] row offsets of the events' hits (device; seg_ptr[n_seg] = n), the hits sorted by event.
+ *   select:   condensation points per (event, particle id); alphas ordered by (event, ascending id) and holding
+ *             hit indices of the whole batch, gid[h] = index into alphas of hit h's point or -1, cp_ptr[n_seg + 1]
+ *             = offsets of the events' points in alphas, n_cp[0] = their total.  Tie rule, candidates and the
+ *             skipped id 0 as gnntrk_oc_select_cps.  Two stable sorts: by id (64 bits), then by event.
+ *   forward:  out[n_seg][9], per event the columns of gnntrk_oc_forward's out (norms, K, n of that event).
+ *   backward: g[4] is shared by the events (a mean over events carries its 1 / n_seg in g), fwd = that out.
+ * A hit only meets the points of its event and a point only the hits of its event; the per-pair arithmetic is
+ * that of the entries above.  The events' sizes stay on the device: the launches cover ceil(n / 256) + n_seg
+ * tiles and a block finds its (event, tile) from seg_ptr / cp_ptr.  args->n_cp, args->n as above (the whole
+ * batch); args->rep_keep_prob in (0, 1) is refused (the sub-sampling is per event); cap_nbr holds indices of
+ * the whole batch (gnntrk_knn_search_ws with the same seg_ptr). */
+size_t gnntrk_oc_select_batched_workspace_bytes(int64_t n);
+int gnntrk_oc_select_cps_batched(const float *score, const int64_t *particle_id, const uint8_t *mask, int64_t n,
+                                 int32_t mode, const int64_t *seg_ptr, int32_t n_seg, int32_t *alphas, int32_t *gid,
+                                 int32_t *cp_ptr, int32_t *n_cp, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+size_t gnntrk_oc_forward_batched_workspace_bytes(int64_t n, int32_t n_seg);
+int gnntrk_oc_forward_batched(const gnntrk_oc_args *args, const int64_t *seg_ptr, const int32_t *cp_ptr,
+                              int32_t n_seg, float *out /*[n_seg, 9]*/, void *workspace, size_t workspace_bytes,
+                              void *stream);
+size_t gnntrk_oc_backward_batched_workspace_bytes(int64_t n, int32_t dim);
+int gnntrk_oc_backward_batched(const gnntrk_oc_args *args, const int64_t *seg_ptr, const int32_t *cp_ptr,
+                               int32_t n_seg, const float *g /*[4]*/, const float *fwd /*[n_seg, 9]*/, float *gx,
+                               float *gbeta, void *workspace, size_t workspace_bytes, void *stream);
+
 /* The same loss terms and gradients without the N x K walk (dim <= 16; workspace_bytes == 0: not
  * covered, use the entry points above).  A repulsive pair needs |x_j - x_k| < radius: the hits are
  * sorted into chunks of 64 with bounding boxes and a (chunk, condensation point) pair is only
