@@ -141,21 +141,28 @@ def _cut_plan(pt_thlds) -> tuple[list, list[float], list[int]]:
 
 
 def _counts(labels: Tensor, truth: Tensor, pts: Tensor, reconstructable: Tensor, eta: Tensor, cuts: list[float],
-            predicted_count_thld: int, max_eta: float) -> Tensor:
+            predicted_count_thld: int, max_eta: float, ptr: Tensor | None = None) -> Tensor:
     """One launch sequence for all trials of ``labels`` [T, n]: the device int64 output of
-    ``gnntrk_tracking_metrics`` (n_cuts + T * n_cuts * 4 + 1 values)."""
+    ``gnntrk_tracking_metrics`` (n_cuts + T * n_cuts * 4 + 1 values); with the events' offsets ``ptr`` [B + 1] that of
+    ``gnntrk_tracking_metrics_batched`` (B * n_cuts + T * B * n_cuts * 4 + 1 values)."""
     lib = _capi.load()
     _capi.require_device(labels, truth, pts, reconstructable, eta)
     n_trials, n = int(labels.shape[0]), int(labels.shape[1])
     if n_trials > _capi.TRACKING_MAX_TRIALS:
         raise ValueError(f"tracking_metrics: at most {_capi.TRACKING_MAX_TRIALS} trials per call")
     nc = len(cuts)
-    out = torch.empty(nc + n_trials * nc * 4 + 1, dtype=torch.int64, device=labels.device)
+    n_ev = 1 if ptr is None else int(ptr.numel()) - 1
+    out = torch.empty(n_ev * nc * (1 + n_trials * 4) + 1, dtype=torch.int64, device=labels.device)
     ws = ops._ws(lib.gnntrk_tracking_metrics_workspace_bytes(n, n_trials), labels)
     p = ops._p
-    _capi.check(lib.gnntrk_tracking_metrics(p(labels), n_trials, p(truth), p(pts), p(eta), p(reconstructable), n,
-                                            (C.c_float * nc)(*cuts), nc, float(max_eta), int(predicted_count_thld),
-                                            p(out), p(ws), ws.numel(), ops._stream(labels)), lib)
+    tail = ((C.c_float * nc)(*cuts), nc, float(max_eta), int(predicted_count_thld), p(out), p(ws), ws.numel(),
+            ops._stream(labels))
+    hits = (p(labels), n_trials, p(truth), p(pts), p(eta), p(reconstructable), n)
+    if ptr is None:
+        _capi.check(lib.gnntrk_tracking_metrics(*hits, *tail), lib)
+    else:
+        _capi.require_device(ptr)
+        _capi.check(lib.gnntrk_tracking_metrics_batched(*hits, p(ptr), n_ev, *tail), lib)
     return out
 
 
@@ -194,25 +201,58 @@ def tracking_metrics(*, truth, predicted, pts, reconstructable, eta, pt_thlds: I
     return _results(out.cpu().numpy(), 1, pts_l, idx)[0]
 
 
+def _results_per_event(host: np.ndarray, n_trials: int, sizes: list[int], pts: list, idx: list[int]) -> list[list[dict]]:
+    """``_results`` for the output of ``gnntrk_tracking_metrics_batched``: [trial][event] -> flat dict; an event
+    without hits gets the NaN results of ``n == 0``"""
+    n_ev = len(sizes)
+    nc = (host.size - 1) // (n_ev * (1 + 4 * n_trials))
+    if host[-1] != 0:
+        raise ValueError(f"tracking_metrics: {int(host[-1])} labels are >= the number of hits of their event")
+    n_part = host[:n_ev * nc].reshape(n_ev, nc)
+    cnt = host[n_ev * nc:-1].reshape(n_trials, n_ev, nc, 4)
+    nan = flatten_track_metrics({pt: dict(_tracking_metrics_nan_results) for pt in pts})
+    # (flatten_track_metrics with the flat names made once per call, not once per trial, event and value)
+    cols = {pt: (j, {k: denote_pt(k, pt) for k in TrackingMetrics.__annotations__}) for pt, j in zip(pts, idx)}
+
+    def flat(t, e):
+        return {names[k]: v for j, names in cols.values() for k, v in _from_counts(int(n_part[e, j]), cnt[t, e, j]).items()}
+
+    return [[flat(t, e) if sizes[e] else dict(nan) for e in range(n_ev)] for t in range(n_trials)]
+
+
 def tracking_metrics_trials(labels, *, truth, pts, reconstructable, eta, pt_thlds: Iterable[float] = (0.0, 0.5, 0.9, 1.5),
-                            predicted_count_thld=3, max_eta=4) -> list[dict[str, float]]:
+                            predicted_count_thld=3, max_eta=4, ptr=None):
     """The tracking metrics of many labellings of the same hits (``labels`` [n_trials, n], values in
     [-1, n) as DBSCAN gives them; any negative value is noise) from one C call and one host copy: per
-    trial the flattened dict of ``flatten_track_metrics(tracking_metrics(...))``."""
+    trial the flattened dict of ``flatten_track_metrics(tracking_metrics(...))``.
+
+    ``ptr`` ([B + 1] row offsets of the events of a collated batch, more than one event): every event on its own -
+    particles are (event, id) pairs and labels local to the event, in ``[-1, n_e)`` as
+    ``DBSCANFastRescan(..., ptr=ptr)`` gives them - still from one C call and one host copy; the result is
+    ``[trial][event] -> flat dict``, each what the event's rows alone give."""
     if not torch.is_tensor(labels):
         labels = torch.as_tensor(np.asarray(labels))
     if labels.dim() != 2:
         raise ValueError("tracking_metrics_trials: labels must be [n_trials, n]")
     n_trials, n = int(labels.shape[0]), int(labels.shape[1])
     pts_l, cuts, idx = _cut_plan(pt_thlds)
+    sizes = None
+    if ptr is not None and int(np.shape(ptr)[0]) > 2:
+        host = torch.as_tensor(ptr).cpu().long()
+        sizes = torch.diff(host).tolist()
+        if int(host[0]) != 0 or int(host[-1]) != n or min(sizes) < 0:
+            raise ValueError("tracking_metrics_trials: ptr must ascend from 0 to the number of hits")
     if n == 0 or n_trials == 0:
-        return [flatten_track_metrics({pt: dict(_tracking_metrics_nan_results) for pt in pts_l})
-                for _ in range(n_trials)]
+        nan = flatten_track_metrics({pt: dict(_tracking_metrics_nan_results) for pt in pts_l})
+        return [dict(nan) if sizes is None else [dict(nan) for _ in sizes] for _ in range(n_trials)]
     dev = _device_of(labels, truth, pts, reconstructable, eta)
     lab = _on(labels, torch.int64, dev)
     t, p, r, e = _hits(truth, pts, reconstructable, eta, dev)
     if int(t.shape[0]) != n:
         raise ValueError("tracking_metrics_trials: labels and truth differ in the number of hits")
+    if sizes is not None:
+        out = _counts(lab, t, p, r, e, cuts, predicted_count_thld, max_eta, _on(ptr, torch.int64, dev))
+        return _results_per_event(out.cpu().numpy(), n_trials, sizes, pts_l, idx)
     out = _counts(lab, t, p, r, e, cuts, predicted_count_thld, max_eta)
     return [flatten_track_metrics(m) for m in _results(out.cpu().numpy(), n_trials, pts_l, idx)]
 

@@ -54,16 +54,6 @@ __device__ __forceinline__ int knn_read_lane(int v, int src) {
 #endif
 }
 
-// segment (event) of row q: the last s with seg_ptr[s] <= q (seg_ptr ascending, seg_ptr[0] = 0)
-__device__ __forceinline__ int knn_segment_of(const int64_t *__restrict__ seg_ptr, int n_seg, int64_t q) {
-    int lo = 0, hi = n_seg - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (seg_ptr[mid] <= q) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 // FULL: dim == DP (no per-feature guard on the scalar loads).  BATCH: rows are grouped into
 // segments (the events of a collated batch, `batch` of torch_cluster's knn_graph / radius_graph:
 // metrics/losses/metric_learning.py:97); a query only sees candidates of its own segment.
@@ -108,7 +98,7 @@ __global__ __launch_bounds__(kKnnBlock) void knn_kernel(const float *__restrict_
     if (BATCH) {
         if (lane < 32) {
             const int64_t q = q0 + (lane < nq ? lane : nq - 1);
-            const int sg = knn_segment_of(seg_ptr, n_seg, q);
+            const int sg = segment_of(seg_ptr, n_seg, q);
             qlo[lane] = (int)seg_ptr[sg];
             qhi[lane] = (int)seg_ptr[sg + 1];
         }
@@ -347,7 +337,7 @@ __global__ __launch_bounds__(256) void knn_morton_kernel(const float *__restrict
         for (int d = 0; d < kSpMaxDim; ++d)
             if (d < dim) code = (code << 1) | (u64)((q[d] >> b) & 1u);
     if (seg_bits > 0) {
-        const u64 sg = (u64)knn_segment_of(seg_ptr, n_seg, i);
+        const u64 sg = (u64)segment_of(seg_ptr, n_seg, i);
         code |= sg << (64 - seg_bits);
     }
     keys[i] = code;
@@ -420,7 +410,7 @@ __global__ __launch_bounds__(kKnnBlock) void knn_pruned_kernel(const float *__re
         const int o = sidx[q0 + (lane < nq ? lane : nq - 1)];
         oq[lane] = o;
         if (BATCH) {
-            const int sg = knn_segment_of(seg_ptr, n_seg, o);
+            const int sg = segment_of(seg_ptr, n_seg, o);
             qlo[lane] = (int)seg_ptr[sg];
             qhi[lane] = (int)seg_ptr[sg + 1];
         }

@@ -22,6 +22,11 @@
 //
 // Every output is an integer count, so the result does not depend on the order in which atomics land.
 //
+// tracking_metrics_batched: the same counts for every event of a collated batch from the same launch sequence
+// (BATCH = true instantiations).  A particle is (event, particle id), a cluster (event, local label) with the dense
+// slot seg_ptr[event] + label, so the tables keep their sizes; tm_particle_batched_kernel and
+// tm_clusters_batched_kernel add to their event's rows of the output.
+//
 // Two more entries share the tables, the pair kernels and the tie rule:
 //   tracking_metrics_windows    the same counts for up to 32 two-sided (pt, eta) windows that may overlap
 //                               (tracking_metrics_vs_pt / _vs_eta, cluster_metrics.py:292-384).  Windows
@@ -93,9 +98,37 @@ struct WinSel {
     __device__ __forceinline__ static void merge(uint32_t *p, uint32_t c) { atomicOr(p, c); }
 };
 
-// the particle table's slot of pid (present: every particle id of the hits was inserted)
-__device__ __forceinline__ int64_t find_particle(const int32_t *ptab, const int64_t *pid, uint64_t mask, int64_t key) {
-    return (int64_t)table_find(ptab, mask, mix64((uint64_t)key), [&](int32_t h) { return pid[h] == key; });
+// The events of a collated batch: hits [ptr[s], ptr[s + 1]) are event s, every event its own problem.  The kernels'
+// BATCH = false instantiations (one event) never read it.  With BATCH a particle is the pair (event, particle id),
+// and a cluster the pair (event, local label) with the dense slot ptr[s] + label < n.
+struct Events {
+    const int64_t *ptr;
+    int32_t n;
+};
+// the rows [lo, hi) of the event of hit i (one event: all rows) and its number
+template <bool BATCH>
+__device__ __forceinline__ int event_rows(const Events &ev, int64_t n, int64_t i, int64_t &lo, int64_t &hi) {
+    lo = 0;
+    hi = n;
+    if (!BATCH) return 0;
+    const int e = segment_of(ev.ptr, ev.n, i);
+    lo = ev.ptr[e];
+    hi = ev.ptr[e + 1];
+    return e;
+}
+// hash of a particle: its id, with BATCH combined with its event
+template <bool BATCH>
+__device__ __forceinline__ uint64_t particle_hash(int64_t key, int e) {
+    return mix64(BATCH ? (uint64_t)key + 0x9e3779b97f4a7c15ull * (uint64_t)(e + 1) : (uint64_t)key);
+}
+
+// the particle table's slot of pid (present: every particle id of the hits was inserted); BATCH: of the
+// particle (e, pid), e the event with the rows [lo, hi) - the same id and the event of the slot's first hit
+template <bool BATCH>
+__device__ __forceinline__ int64_t find_particle(const int32_t *ptab, const int64_t *pid, uint64_t mask, int64_t key,
+                                                 int e, int64_t lo, int64_t hi) {
+    return (int64_t)table_find(ptab, mask, particle_hash<BATCH>(key, e),
+                               [&](int32_t h) { return pid[h] == key && (!BATCH || (h >= lo && h < hi)); });
 }
 
 struct Ws {
@@ -139,16 +172,20 @@ Ws make_ws(void *base, int64_t n, int32_t T) {
 }
 
 // ------------------------------------------------------------------ once per call
-template <class Sel>
+template <class Sel, bool BATCH>
 __global__ __launch_bounds__(kTpb) void tm_particles_kernel(const int64_t *__restrict__ pid,
                                                             const float *__restrict__ pt,
                                                             const float *__restrict__ eta,
-                                                            const float *__restrict__ reco, int64_t n, Sel sel, Ws w) {
+                                                            const float *__restrict__ reco, int64_t n, Events ev,
+                                                            Sel sel, Ws w) {
     const uint64_t mask = w.S - 1;
     for (int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTpb) {
         const int64_t key = pid[i];
-        const uint64_t s =
-            table_claim(w.ptab, mask, mix64((uint64_t)key), i, [&](int32_t h) { return pid[h] == key; });
+        int64_t lo, hi;
+        const int e = event_rows<BATCH>(ev, n, i, lo, hi);
+        const uint64_t s = table_claim(w.ptab, mask, particle_hash<BATCH>(key, e), i, [&](int32_t h) {
+            return pid[h] == key && (!BATCH || (h >= lo && h < hi));
+        });
         w.hslot[i] = (uint32_t)s;
         atomicAdd(&w.pcnt[s], 1u);
         const float v[kProps] = {pt[i], eta[i], reco[i]};
@@ -169,6 +206,17 @@ __device__ __forceinline__ float particle_mean(const Ws &w, int k, int64_t s) {
     return c ? (float)(w.psum[(size_t)k * w.S + s] / (double)c) : NAN;
 }
 
+// stores the cut class of the means of the particle in slot s (cluster mask of a cluster with this majority
+// particle: maj_pt >= cut, maj_reconstructable truthy - non-zero and not NaN -, |maj_eta| < max_eta) and returns
+// the highest cut class of its hits (hit mask)
+__device__ __forceinline__ uint32_t particle_classes(const Cuts &cuts, float max_eta, const Ws &w, int64_t s) {
+    float mean[kProps];
+    for (int k = 0; k < kProps; ++k) mean[k] = particle_mean(w, k, s);
+    const bool ok = mean[2] != 0.f && mean[2] == mean[2] && fabsf(mean[1]) < max_eta;
+    w.pcls[s] = ok ? (uint32_t)cut_class(mean[0], cuts) : 0u;
+    return w.phit[s];
+}
+
 __global__ __launch_bounds__(kTpb) void tm_particle_kernel(Cuts cuts, float max_eta, Ws w,
                                                            unsigned long long *__restrict__ n_particles) {
     __shared__ uint32_t acc[kMaxCuts];
@@ -179,13 +227,7 @@ __global__ __launch_bounds__(kTpb) void tm_particle_kernel(Cuts cuts, float max_
     for (int64_t base = (int64_t)blockIdx.x * kTpb; base < S; base += (int64_t)gridDim.x * kTpb) {
         const int64_t s = base + threadIdx.x;
         if (s >= S || w.ptab[s] == 0) continue;
-        float mean[kProps];
-        for (int k = 0; k < kProps; ++k) mean[k] = particle_mean(w, k, s);
-        // cluster mask of a cluster with this majority particle: maj_pt >= cut, maj_reconstructable
-        // truthy (non-zero and not NaN), |maj_eta| < max_eta
-        const bool ok = mean[2] != 0.f && mean[2] == mean[2] && fabsf(mean[1]) < max_eta;
-        w.pcls[s] = ok ? (uint32_t)cut_class(mean[0], cuts) : 0u;
-        const uint32_t hc = w.phit[s];
+        const uint32_t hc = particle_classes(cuts, max_eta, w, s);
         for (int c = 0; c < kMaxCuts; ++c) cnt[c] += (uint32_t)c < hc ? 1u : 0u;
     }
     for (int c = 0; c < cuts.n; ++c) {
@@ -196,57 +238,97 @@ __global__ __launch_bounds__(kTpb) void tm_particle_kernel(Cuts cuts, float max_
     if (threadIdx.x < cuts.n && acc[threadIdx.x]) atomicAdd(&n_particles[threadIdx.x], (unsigned long long)acc[threadIdx.x]);
 }
 
+// the same per event: n_particles[e][cut], e the event of the slot's first hit.  The slots of a block hold
+// particles of any event, so every particle adds to its event's counts with int64 atomics
+__global__ __launch_bounds__(kTpb) void tm_particle_batched_kernel(Cuts cuts, float max_eta, Ws w, Events ev,
+                                                                   unsigned long long *__restrict__ n_particles) {
+    const int64_t S = (int64_t)w.S;
+    for (int64_t s = (int64_t)blockIdx.x * kTpb + threadIdx.x; s < S; s += (int64_t)gridDim.x * kTpb) {
+        const int32_t first = w.ptab[s];
+        if (first == 0) continue;
+        const uint32_t hc = particle_classes(cuts, max_eta, w, s);
+        if (hc == 0) continue;
+        const int e = segment_of(ev.ptr, ev.n, first - 1);
+        for (uint32_t c = 0; c < hc; ++c) atomicAdd(&n_particles[(size_t)e * cuts.n + c], 1ull);
+    }
+}
+
 // ------------------------------------------------------------------- all trials
 // hits of every trial (flattened [T][n]); noise (label < 0) joins no cluster; labels >= n are
-// counted in *bad and otherwise ignored
+// counted in *bad and otherwise ignored.  BATCH: labels are local to the hit's event of n_e hits - a label >= n_e is
+// the bad one - and the cluster's slot is the event's first row + label.  A pair's key stays (label, particle slot):
+// the particle slot is the event's own
+template <bool BATCH>
 __global__ __launch_bounds__(kTpb) void tm_pairs_kernel(const int64_t *__restrict__ labels, int64_t n, int64_t tn,
-                                                        Ws w, unsigned long long *__restrict__ bad) {
+                                                        Events ev, Ws w, unsigned long long *__restrict__ bad) {
     const uint64_t mask = w.S - 1;
     for (int64_t idx = (int64_t)blockIdx.x * kTpb + threadIdx.x; idx < tn; idx += (int64_t)gridDim.x * kTpb) {
         const int64_t lab = labels[idx];
         if (lab < 0) continue;
-        if (lab >= n) {
+        const int64_t t = idx / n, i = idx - t * n;
+        int64_t lo, hi;
+        event_rows<BATCH>(ev, n, i, lo, hi);
+        if (lab >= hi - lo) {
             atomicAdd(bad, 1ull);
             continue;
         }
-        const int64_t t = idx / n, i = idx - t * n;
+        const int64_t cl = lo + lab;
         const int64_t *lt = labels + t * n;
         int32_t *tab = w.ttab + (size_t)t * w.S;
         const uint32_t ps = w.hslot[i];
-        const uint64_t s = table_claim(tab, mask, mix64(((uint64_t)lab << 32) | ps), i,
+        const uint64_t s = table_claim(tab, mask, mix64(((uint64_t)cl << 32) | ps), i,
                                        [&](int32_t h) { return lt[h] == lab; }, [&](int32_t h) { return w.hslot[h] == ps; });
         atomicAdd(&w.tcnt[(size_t)t * w.S + s], 1u);
-        atomicAdd(&w.csize[t * n + lab], 1u);
+        atomicAdd(&w.csize[t * n + cl], 1u);
     }
 }
 
-// the cluster of an occupied pair slot e of trial t (-1: empty)
-__device__ __forceinline__ int64_t pair_cluster(const int64_t *labels, int64_t n, const Ws &w, int64_t t, int64_t e,
-                                                int32_t &hit) {
+// the cluster slot of an occupied pair slot e of trial t (-1: empty)
+template <bool BATCH>
+__device__ __forceinline__ int64_t pair_cluster(const int64_t *labels, int64_t n, const Events &ev, const Ws &w,
+                                                int64_t t, int64_t e, int32_t &hit) {
     hit = w.ttab[e];
     if (hit == 0) return -1;
-    return labels[t * n + hit - 1];
+    int64_t lo, hi;
+    event_rows<BATCH>(ev, n, hit - 1, lo, hi);
+    return lo + labels[t * n + hit - 1];
 }
 
+template <bool BATCH>
 __global__ __launch_bounds__(kTpb) void tm_best_count_kernel(const int64_t *__restrict__ labels, int64_t n, int64_t ts,
-                                                             Ws w) {
+                                                             Events ev, Ws w) {
     for (int64_t e = (int64_t)blockIdx.x * kTpb + threadIdx.x; e < ts; e += (int64_t)gridDim.x * kTpb) {
         const int64_t t = e / (int64_t)w.S;
         int32_t hit;
-        const int64_t lab = pair_cluster(labels, n, w, t, e, hit);
-        if (lab >= 0) atomicMax(&w.cbest[t * n + lab], w.tcnt[e]);
+        const int64_t cl = pair_cluster<BATCH>(labels, n, ev, w, t, e, hit);
+        if (cl >= 0) atomicMax(&w.cbest[t * n + cl], w.tcnt[e]);
     }
 }
 
+template <bool BATCH>
 __global__ __launch_bounds__(kTpb) void tm_best_pid_kernel(const int64_t *__restrict__ labels,
                                                            const int64_t *__restrict__ pid, int64_t n, int64_t ts,
-                                                           Ws w) {
+                                                           Events ev, Ws w) {
     for (int64_t e = (int64_t)blockIdx.x * kTpb + threadIdx.x; e < ts; e += (int64_t)gridDim.x * kTpb) {
         const int64_t t = e / (int64_t)w.S;
         int32_t hit;
-        const int64_t lab = pair_cluster(labels, n, w, t, e, hit);
-        if (lab >= 0 && w.tcnt[e] == w.cbest[t * n + lab]) min_u64(&w.cpid[t * n + lab], pid_key(pid[hit - 1]));
+        const int64_t cl = pair_cluster<BATCH>(labels, n, ev, w, t, e, hit);
+        if (cl >= 0 && w.tcnt[e] == w.cbest[t * n + cl]) min_u64(&w.cpid[t * n + cl], pid_key(pid[hit - 1]));
     }
+}
+
+// the matches of a cluster of `size` hits, `maj` of them of its majority particle, which has `pid_hits` hits in
+// all (fp64 ratios as the reference evaluates them)
+struct Match {
+    uint32_t perfect, dm, lhc;
+};
+__device__ __forceinline__ Match match_flags(uint32_t maj, uint32_t size, uint32_t pid_hits) {
+    const double frac = (double)maj / (double)size, pid_frac = (double)maj / (double)pid_hits;
+    Match m;
+    m.perfect = (pid_hits == maj && frac > 0.99) ? 1u : 0u;
+    m.dm = (pid_frac > 0.5 && frac > 0.5) ? 1u : 0u;
+    m.lhc = frac > 0.75 ? 1u : 0u;
+    return m;
 }
 
 // one trial per blockIdx.y; a cluster is a label with at least one hit
@@ -265,21 +347,16 @@ __global__ __launch_bounds__(kTpb) void tm_clusters_kernel(const int64_t *__rest
         if (size == 0 || (int64_t)size < (int64_t)count_thld) continue;   // not a valid cluster
         const uint32_t maj = w.cbest[t * n + lab];
         const int64_t key = (int64_t)(w.cpid[t * n + lab] ^ (1ull << 63));
-        const int64_t ps = find_particle(w.ptab, pid, mask, key);
+        const int64_t ps = find_particle<false>(w.ptab, pid, mask, key, 0, 0, n);
         const uint32_t cls = w.pcls[ps];
         if (cls == 0) continue;
-        const uint32_t pid_hits = w.pcnt[ps];
-        // (fp64 ratios as the reference evaluates them)
-        const double frac = (double)maj / (double)size, pid_frac = (double)maj / (double)pid_hits;
-        const uint32_t perfect = (pid_hits == maj && frac > 0.99) ? 1u : 0u;
-        const uint32_t dm = (pid_frac > 0.5 && frac > 0.5) ? 1u : 0u;
-        const uint32_t lhc = frac > 0.75 ? 1u : 0u;
+        const Match m = match_flags(maj, size, w.pcnt[ps]);
         for (int c = 0; c < kMaxCuts; ++c) {
             if ((uint32_t)c >= cls) break;
             cnt[c][0] += 1u;
-            cnt[c][1] += perfect;
-            cnt[c][2] += dm;
-            cnt[c][3] += lhc;
+            cnt[c][1] += m.perfect;
+            cnt[c][2] += m.dm;
+            cnt[c][3] += m.lhc;
         }
     }
     for (int c = 0; c < cuts.n; ++c)
@@ -290,6 +367,55 @@ __global__ __launch_bounds__(kTpb) void tm_clusters_kernel(const int64_t *__rest
     __syncthreads();
     if (threadIdx.x < cuts.n * 4 && acc[threadIdx.x])
         atomicAdd(&out[(size_t)t * cuts.n * 4 + threadIdx.x], (unsigned long long)acc[threadIdx.x]);
+}
+
+// The same per event: one trial per blockIdx.y, one block per 256 cluster slots (no grid stride: a block's slots
+// are consecutive rows, so most blocks lie inside one event).  out[t][e][cut][4].  A block inside one event sums as
+// above - wave sums, LDS, one int64 atomic per value -; a block that spans an event edge adds every cluster to its
+// event's counts with int64 atomics.
+__global__ __launch_bounds__(kTpb) void tm_clusters_batched_kernel(const int64_t *__restrict__ pid, int64_t n, Cuts cuts,
+                                                                   int32_t count_thld, Events ev, Ws w,
+                                                                   unsigned long long *__restrict__ out) {
+    __shared__ uint32_t acc[kMaxCuts * 4];
+    if (threadIdx.x < kMaxCuts * 4) acc[threadIdx.x] = 0u;
+    __syncthreads();
+    const int64_t t = blockIdx.y;
+    const uint64_t mask = w.S - 1;
+    const int64_t c0 = (int64_t)blockIdx.x * kTpb, c1 = c0 + kTpb < n ? c0 + kTpb - 1 : n - 1;
+    const int e0 = segment_of(ev.ptr, ev.n, c0);
+    const bool one_event = e0 == segment_of(ev.ptr, ev.n, c1);
+    unsigned long long *out_t = out + (size_t)t * ev.n * cuts.n * 4;
+    uint32_t cnt[kMaxCuts][4] = {};
+    const int64_t cl = c0 + threadIdx.x;
+    if (cl < n) {
+        const uint32_t size = w.csize[t * n + cl];
+        if (size != 0 && (int64_t)size >= (int64_t)count_thld) {   // a valid cluster
+            int64_t lo, hi;
+            const int e = event_rows<true>(ev, n, cl, lo, hi);
+            const uint32_t maj = w.cbest[t * n + cl];
+            const int64_t key = (int64_t)(w.cpid[t * n + cl] ^ (1ull << 63));
+            const int64_t ps = find_particle<true>(w.ptab, pid, mask, key, e, lo, hi);
+            const uint32_t cls = w.pcls[ps];
+            const Match m = match_flags(maj, size, w.pcnt[ps]);
+            const uint32_t add[4] = {1u, m.perfect, m.dm, m.lhc};
+            for (int c = 0; c < kMaxCuts; ++c) {
+                if ((uint32_t)c >= cls) break;
+                for (int k = 0; k < 4; ++k) {
+                    if (one_event) cnt[c][k] += add[k];
+                    else if (add[k]) atomicAdd(&out_t[((size_t)e * cuts.n + c) * 4 + k], 1ull);
+                }
+            }
+        }
+    }
+    if (!one_event) return;   // (uniform in the block)
+    for (int c = 0; c < cuts.n; ++c)
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t s = wave_sum(cnt[c][k]);
+            if ((threadIdx.x & 63) == 0 && s) atomicAdd(&acc[c * 4 + k], s);
+        }
+    __syncthreads();
+    if (threadIdx.x < cuts.n * 4 && acc[threadIdx.x])
+        atomicAdd(&out_t[(size_t)e0 * cuts.n * 4 + threadIdx.x], (unsigned long long)acc[threadIdx.x]);
 }
 
 // ---------------------------------------------------------------------- windows
@@ -323,7 +449,7 @@ __device__ __forceinline__ Majority majority_of(const int64_t *pid, int64_t n, c
     m.size = w.csize[t * n + lab];
     m.hits = w.cbest[t * n + lab];
     m.pid = (int64_t)(w.cpid[t * n + lab] ^ (1ull << 63));
-    m.slot = find_particle(w.ptab, pid, w.S - 1, m.pid);
+    m.slot = find_particle<false>(w.ptab, pid, w.S - 1, m.pid, 0, 0, n);
     m.pid_hits = w.pcnt[m.slot];
     return m;
 }
@@ -343,17 +469,13 @@ __global__ __launch_bounds__(kTpb) void tmw_clusters_kernel(const int64_t *__res
         const Majority c = majority_of(pid, n, w, t, lab);
         uint32_t m = w.pcls[c.slot];
         if (m == 0) continue;
-        // (fp64 ratios as the reference evaluates them)
-        const double frac = (double)c.hits / (double)size, pid_frac = (double)c.hits / (double)c.pid_hits;
-        const bool perfect = c.pid_hits == c.hits && frac > 0.99;
-        const bool dm = pid_frac > 0.5 && frac > 0.5;
-        const bool lhc = frac > 0.75;
+        const Match f = match_flags(c.hits, size, c.pid_hits);
         for (; m; m &= m - 1u) {
             uint32_t *a = &acc[(__ffsll((unsigned long long)m) - 1) * 4];
             atomicAdd(&a[0], 1u);
-            if (perfect) atomicAdd(&a[1], 1u);
-            if (dm) atomicAdd(&a[2], 1u);
-            if (lhc) atomicAdd(&a[3], 1u);
+            if (f.perfect) atomicAdd(&a[1], 1u);
+            if (f.dm) atomicAdd(&a[2], 1u);
+            if (f.lhc) atomicAdd(&a[3], 1u);
         }
     }
     __syncthreads();
@@ -386,22 +508,23 @@ __global__ __launch_bounds__(kTpb) void tm_table_kernel(const int64_t *__restric
 }
 
 // clears the tables and fills them: the particle table with sel's hit words, then per trial the pair
-// table, cluster sizes, best counts and best particle ids; *bad counts the labels >= n
-template <class Sel>
+// table, cluster sizes, best counts and best particle ids; *bad counts the labels >= n.  BATCH: per event of ev
+template <class Sel, bool BATCH = false>
 int fill_tables(const char *what, const int64_t *labels, int32_t n_trials, const int64_t *pid, const float *pt,
                 const float *eta, const float *reco, int64_t n, const Sel &sel, const Ws &w, unsigned long long *bad,
-                hipStream_t stream) {
+                hipStream_t stream, Events ev = Events{}) {
     char msg[96];
     snprintf(msg, sizeof(msg), "%s: clear workspace", what);
     int rc;
     if ((rc = check_hip(hipMemsetAsync(w.psum, 0, w.zero_bytes, stream), msg))) return rc;
     if ((rc = check_hip(hipMemsetAsync(w.cpid, 0xFF, 8 * (size_t)n_trials * n, stream), msg))) return rc;
     const int64_t S = (int64_t)w.S, tn = (int64_t)n_trials * n, ts = (int64_t)n_trials * S;
-    hipLaunchKernelGGL(tm_particles_kernel<Sel>, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, pid, pt, eta, reco, n,
-                       sel, w);
-    hipLaunchKernelGGL(tm_pairs_kernel, dim3(blocks_for(tn, 8)), dim3(kTpb), 0, stream, labels, n, tn, w, bad);
-    hipLaunchKernelGGL(tm_best_count_kernel, dim3(blocks_for(ts, 8)), dim3(kTpb), 0, stream, labels, n, ts, w);
-    hipLaunchKernelGGL(tm_best_pid_kernel, dim3(blocks_for(ts, 8)), dim3(kTpb), 0, stream, labels, pid, n, ts, w);
+    hipLaunchKernelGGL((tm_particles_kernel<Sel, BATCH>), dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, pid, pt, eta,
+                       reco, n, ev, sel, w);
+    hipLaunchKernelGGL(tm_pairs_kernel<BATCH>, dim3(blocks_for(tn, 8)), dim3(kTpb), 0, stream, labels, n, tn, ev, w, bad);
+    hipLaunchKernelGGL(tm_best_count_kernel<BATCH>, dim3(blocks_for(ts, 8)), dim3(kTpb), 0, stream, labels, n, ts, ev, w);
+    hipLaunchKernelGGL(tm_best_pid_kernel<BATCH>, dim3(blocks_for(ts, 8)), dim3(kTpb), 0, stream, labels, pid, n, ts, ev,
+                       w);
     snprintf(msg, sizeof(msg), "%s: tables", what);
     return check_launch(msg);
 }
@@ -428,6 +551,51 @@ size_t tracking_metrics_ws_bytes(int64_t n, int32_t n_trials) {
     return make_ws(nullptr, n < 0 ? 0 : n, n_trials < 1 ? 1 : n_trials).total;
 }
 
+// gnntrk_tracking_metrics (BATCH = false, ev.n = 1) and gnntrk_tracking_metrics_batched
+template <bool BATCH>
+int tracking_metrics(const int64_t *labels, int32_t n_trials, const int64_t *particle_id, const float *pt,
+                     const float *eta, const float *reconstructable, int64_t n, Events ev, const float *cuts,
+                     int32_t n_cuts, float max_eta, int32_t predicted_count_thld, int64_t *out, void *workspace,
+                     size_t workspace_bytes, hipStream_t stream) {
+    char msg[160];
+    int rc = check_count_i30("tracking_metrics", "hit", n);
+    if (rc) return rc;
+    if (n_cuts < 1 || n_cuts > kMaxCuts) {
+        snprintf(msg, sizeof(msg), "tracking_metrics: n_cuts = %d, expected 1..%d", (int)n_cuts, kMaxCuts);
+        return fail(GNNTRK_EINVAL, msg);
+    }
+    if (!cuts) return fail(GNNTRK_EINVAL, "tracking_metrics: NULL cuts");
+    CutSel sel{};
+    sel.max_eta = max_eta;
+    if ((rc = fill_cuts(sel.cuts, cuts, n_cuts, "tracking_metrics"))) return rc;
+    if (!out) return fail(GNNTRK_EINVAL, "tracking_metrics: NULL output");
+    if ((rc = check_hits("tracking_metrics", n, n_trials, labels, particle_id, pt, eta, reconstructable, workspace,
+                         workspace_bytes)))
+        return rc;
+    const size_t n_ev = (size_t)ev.n;   // (one event: 1)
+    const size_t n_out = n_ev * n_cuts + (size_t)n_trials * n_ev * n_cuts * 4 + 1;
+    rc = check_hip(hipMemsetAsync(out, 0, sizeof(int64_t) * n_out, stream), "tracking_metrics: clear");
+    if (rc || n == 0) return rc;
+    const Ws w = make_ws(workspace, n, n_trials);
+    auto *o = reinterpret_cast<unsigned long long *>(out);
+    if ((rc = fill_tables<CutSel, BATCH>("tracking_metrics", labels, n_trials, particle_id, pt, eta, reconstructable, n,
+                                         sel, w, o + n_out - 1, stream, ev)))
+        return rc;
+    if (BATCH) {
+        hipLaunchKernelGGL(tm_particle_batched_kernel, dim3(blocks_for((int64_t)w.S, 4)), dim3(kTpb), 0, stream,
+                           sel.cuts, max_eta, w, ev, o);
+        hipLaunchKernelGGL(tm_clusters_batched_kernel, dim3((unsigned)ceil_div(n, kTpb), (unsigned)n_trials), dim3(kTpb),
+                           0, stream, particle_id, n, sel.cuts, predicted_count_thld, ev, w, o + n_ev * n_cuts);
+        return check_launch("tracking_metrics: clusters");
+    }
+    hipLaunchKernelGGL(tm_particle_kernel, dim3(blocks_for((int64_t)w.S, 4)), dim3(kTpb), 0, stream, sel.cuts, max_eta,
+                       w, o);
+    const int gx = (int)((blocks_for(n, 8) + n_trials - 1) / n_trials);
+    hipLaunchKernelGGL(tm_clusters_kernel, dim3(gx < 1 ? 1 : gx, (unsigned)n_trials), dim3(kTpb), 0, stream,
+                       particle_id, n, sel.cuts, predicted_count_thld, w, o + n_cuts);
+    return check_launch("tracking_metrics: clusters");
+}
+
 }  // namespace
 }  // namespace gnntrk
 
@@ -448,37 +616,21 @@ size_t gnntrk_cluster_table_workspace_bytes(int64_t n) { return tracking_metrics
 int gnntrk_tracking_metrics(const int64_t *labels, int32_t n_trials, const int64_t *particle_id, const float *pt,
                             const float *eta, const float *reconstructable, int64_t n, const float *cuts,
                             int32_t n_cuts, float max_eta, int32_t predicted_count_thld, int64_t *out, void *workspace,
-                            size_t workspace_bytes, void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    char msg[160];
-    int rc = check_count_i30("tracking_metrics", "hit", n);
-    if (rc) return rc;
-    if (n_cuts < 1 || n_cuts > kMaxCuts) {
-        snprintf(msg, sizeof(msg), "tracking_metrics: n_cuts = %d, expected 1..%d", (int)n_cuts, kMaxCuts);
-        return fail(GNNTRK_EINVAL, msg);
-    }
-    if (!cuts) return fail(GNNTRK_EINVAL, "tracking_metrics: NULL cuts");
-    CutSel sel{};
-    sel.max_eta = max_eta;
-    if ((rc = fill_cuts(sel.cuts, cuts, n_cuts, "tracking_metrics"))) return rc;
-    if (!out) return fail(GNNTRK_EINVAL, "tracking_metrics: NULL output");
-    if ((rc = check_hits("tracking_metrics", n, n_trials, labels, particle_id, pt, eta, reconstructable, workspace,
-                         workspace_bytes)))
-        return rc;
-    const size_t n_out = (size_t)n_cuts + (size_t)n_trials * n_cuts * 4 + 1;
-    rc = check_hip(hipMemsetAsync(out, 0, sizeof(int64_t) * n_out, stream), "tracking_metrics: clear");
-    if (rc || n == 0) return rc;
-    const Ws w = make_ws(workspace, n, n_trials);
-    auto *o = reinterpret_cast<unsigned long long *>(out);
-    if ((rc = fill_tables("tracking_metrics", labels, n_trials, particle_id, pt, eta, reconstructable, n, sel, w,
-                          o + n_out - 1, stream)))
-        return rc;
-    hipLaunchKernelGGL(tm_particle_kernel, dim3(blocks_for((int64_t)w.S, 4)), dim3(kTpb), 0, stream, sel.cuts, max_eta,
-                       w, o);
-    const int gx = (int)((blocks_for(n, 8) + n_trials - 1) / n_trials);
-    hipLaunchKernelGGL(tm_clusters_kernel, dim3(gx < 1 ? 1 : gx, (unsigned)n_trials), dim3(kTpb), 0, stream,
-                       particle_id, n, sel.cuts, predicted_count_thld, w, o + n_cuts);
-    return check_launch("tracking_metrics: clusters");
+                            size_t workspace_bytes, void *stream) {
+    return tracking_metrics<false>(labels, n_trials, particle_id, pt, eta, reconstructable, n, Events{nullptr, 1}, cuts,
+                                   n_cuts, max_eta, predicted_count_thld, out, workspace, workspace_bytes,
+                                   (hipStream_t)stream);
+}
+
+int gnntrk_tracking_metrics_batched(const int64_t *labels, int32_t n_trials, const int64_t *particle_id,
+                                    const float *pt, const float *eta, const float *reconstructable, int64_t n,
+                                    const int64_t *seg_ptr, int32_t n_seg, const float *cuts, int32_t n_cuts,
+                                    float max_eta, int32_t predicted_count_thld, int64_t *out, void *workspace,
+                                    size_t workspace_bytes, void *stream) {
+    if (!seg_ptr || n_seg < 1) return fail(GNNTRK_EINVAL, "tracking_metrics: seg_ptr needs n_seg >= 1 events");
+    return tracking_metrics<true>(labels, n_trials, particle_id, pt, eta, reconstructable, n, Events{seg_ptr, n_seg},
+                                  cuts, n_cuts, max_eta, predicted_count_thld, out, workspace, workspace_bytes,
+                                  (hipStream_t)stream);
 }
 
 int gnntrk_tracking_metrics_windows(const int64_t *labels, int32_t n_trials, const int64_t *particle_id,

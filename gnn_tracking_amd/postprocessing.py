@@ -13,12 +13,19 @@ every trial's labels into one device buffer, and the tracking metrics of all tri
 (``cluster_metrics.tracking_metrics_trials``) and one host copy.  ``DBSCANPerformanceDetails``
 (dbscanscanner.py:215-264) keeps per batch the hit record on the device and the cluster table, the
 inputs of ``cluster_metrics.tracking_metrics_vs_pt`` / ``_vs_eta``.
+
+A collated batch of several events (``batch`` / ``ptr``) is that many independent problems in one launch sequence:
+the radius graph has no edge between events, cluster labels are local to the event (noise -1, the clusters of an
+event numbered from 0, so ``labels[ptr[e]:ptr[e + 1]]`` is what the event alone gives), the tracking metrics come per
+event, and the scanners append one record per (event, trial) - exactly the results of the events fed one by one
+(``DBSCANHyperParamScanner.per_event``).
 """
 
 from __future__ import annotations
 
 import math
 import os
+import types
 from abc import ABC, abstractmethod
 from typing import Any
 
@@ -28,6 +35,7 @@ from torch import Tensor
 
 from . import _capi, ops
 from .cluster_metrics import _nanmean, _nanstd
+from .graph_construction import _event_ptr
 from .hparams import HyperparametersMixin
 
 
@@ -36,10 +44,16 @@ RADIUS_FLAGS = int(os.environ.get("GNNTRK_RADIUS_FLAGS", "0"))
 
 
 class DBSCANFastRescan:
-    def __init__(self, x, max_eps: float = 1.0, *, n_jobs: int | None = None, device=None):
+    def __init__(self, x, max_eps: float = 1.0, *, batch=None, ptr=None, n_jobs: int | None = None, device=None):
         """Args as fastrescanner.py:7-24 (``n_jobs`` is accepted and ignored).  ``x``: the
         cluster coordinates ``[N, D]``, D <= 32 - a device tensor, or a numpy array /
-        host tensor that is copied to ``device`` (default ``cuda:0``)."""
+        host tensor that is copied to ``device`` (default ``cuda:0``).
+
+        ``batch`` (sorted event id per hit) or ``ptr`` (``[B + 1]`` row offsets) of a collated batch: with more than
+        one event every event is clustered on its own, in the same launches - no neighbourhood crosses an event,
+        ``cluster_device`` / ``cluster`` return labels local to the event (noise -1, clusters from 0 in every event)
+        and ``cluster_ptr`` (int64 ``[B + 1]`` on the device: the number of clusters of the events before each, then
+        the total) is set by each call."""
         if not torch.is_tensor(x):
             x = torch.as_tensor(np.asarray(x))
         if not x.is_cuda and device is None and torch.cuda.is_available():
@@ -52,6 +66,14 @@ class DBSCANFastRescan:
         self.x = ops._as_rows(x.detach().to(torch.float32))
         self._max_eps = float(max_eps)
         self._n_jobs = n_jobs
+        self._ptr = None
+        self.cluster_ptr: Tensor | None = None
+        seg = _event_ptr(types.SimpleNamespace(batch=batch, ptr=ptr))
+        if seg is not None:
+            host = seg.cpu()
+            if int(host[0]) != 0 or int(host[-1]) != int(x.shape[0]) or bool((host[1:] < host[:-1]).any()):
+                raise ValueError("DBSCANFastRescan: the events' offsets must ascend from 0 to the number of points")
+            self._ptr = seg.to(device=self.x.device, dtype=torch.int64).contiguous()
         self._reset_graph(self._max_eps)
 
     def _reset_graph(self, max_eps: float) -> None:
@@ -66,21 +88,25 @@ class DBSCANFastRescan:
         # (the library prunes the N^2 walk with the sorted chunks it builds in ws_p; same output)
         nb = int(lib.gnntrk_radius_points_workspace_bytes(n, dim))
         ws_p = torch.empty(nb, dtype=torch.uint8, device=x.device) if nb else None
-        _capi.check(lib.gnntrk_radius_count_ws(ops._p(x), n, dim, ops._row_stride(x), float(max_eps), ops._p(cnt),
-                                               ops._p(self._off), ops._p(ws_p), nb, RADIUS_FLAGS, st), lib)
+        head = (ops._p(x), n, dim, ops._row_stride(x), float(max_eps))
+        if self._ptr is None:
+            count, fill = lib.gnntrk_radius_count_ws, lib.gnntrk_radius_fill_ws
+        else:   # (every event its own graph: the same entries with the events' offsets)
+            count, fill = lib.gnntrk_radius_count_batched_ws, lib.gnntrk_radius_fill_batched_ws
+            head += (ops._p(self._ptr), int(self._ptr.numel()) - 1)
+        _capi.check(count(*head, ops._p(cnt), ops._p(self._off), ops._p(ws_p), nb, RADIUS_FLAGS, st), lib)
         m = int(self._off[n].item())
         self._nbr = torch.empty(max(m, 1), dtype=torch.int32, device=x.device)
         self._dist = torch.empty(max(m, 1), dtype=torch.float64, device=x.device)
         ne = int(lib.gnntrk_radius_edges_workspace_bytes(m)) if nb else 0
         ws_e = torch.empty(ne, dtype=torch.uint8, device=x.device) if ne else None
-        _capi.check(lib.gnntrk_radius_fill_ws(ops._p(x), n, dim, ops._row_stride(x), float(max_eps),
-                                              ops._p(self._off), m, ops._p(self._nbr), ops._p(self._dist),
-                                              ops._p(ws_p), nb, ops._p(ws_e), ne, RADIUS_FLAGS, st), lib)
+        _capi.check(fill(*head, ops._p(self._off), m, ops._p(self._nbr), ops._p(self._dist), ops._p(ws_p), nb,
+                         ops._p(ws_e), ne, RADIUS_FLAGS, st), lib)
         self._n_edges = m
         self._max_eps = float(max_eps)
 
     def cluster_device(self, eps: float = 1.0, min_pts: int = 1) -> Tensor:
-        """Labels as an int64 device tensor."""
+        """Labels as an int64 device tensor (several events: local to the event, and ``cluster_ptr`` is set)."""
         if eps > self._max_eps:
             self._reset_graph(eps)
         lib = _capi.load()
@@ -108,9 +134,16 @@ class DBSCANFastRescan:
                 raise RuntimeError("DBSCAN label propagation did not converge")
             rounds = min(2 * rounds, 64)
         ws = torch.empty(max(int(lib.gnntrk_dbscan_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
-        n_clusters = torch.empty(1, dtype=torch.int64, device=dev)
-        _capi.check(lib.gnntrk_dbscan_labels(*args, ops._p(core), ops._p(root), ops._p(labels), ops._p(n_clusters),
-                                             ops._p(ws), ws.numel(), st), lib)
+        if self._ptr is None:
+            n_clusters = torch.empty(1, dtype=torch.int64, device=dev)
+            _capi.check(lib.gnntrk_dbscan_labels(*args, ops._p(core), ops._p(root), ops._p(labels), ops._p(n_clusters),
+                                                 ops._p(ws), ws.numel(), st), lib)
+        else:
+            n_ev = int(self._ptr.numel()) - 1
+            self.cluster_ptr = torch.empty(n_ev + 1, dtype=torch.int64, device=dev)
+            _capi.check(lib.gnntrk_dbscan_labels_batched(*args, ops._p(core), ops._p(root), ops._p(self._ptr), n_ev,
+                                                         ops._p(labels), ops._p(self.cluster_ptr), ops._p(ws),
+                                                         ws.numel(), st), lib)
         return labels
 
     def cluster(self, eps: float = 1.0, min_pts: int = 1) -> np.ndarray:
@@ -221,6 +254,14 @@ class OCScanResults:
 
 
 class DBSCANHyperParamScanner(ClusterScanner):
+    #: data of more than one event (``batch`` / ``ptr``): every event is its own problem (its own radius graph,
+    #: cluster numbers and particles - ids repeat from event to event, and id 0 is noise in all of them) and gets its
+    #: own record per trial - the records of the events fed one by one, from one launch sequence.  False: the
+    #: reference's behaviour, which ignores ``batch`` (one DBSCAN over the hits of all events: hits of different
+    #: events that share a latent position are clustered together).  A class attribute so that YAML configurations
+    #: stay those of the reference.
+    per_event = True
+
     def __init__(self, *, eps_range=(0, 1), min_samples_range=(1, 4), n_trials=10, keep_best=0,
                  n_jobs: int | None = None, guide: str = "double_majority_pt0.9", pt_thlds=(0.0, 0.5, 0.9, 1.5),
                  max_eta: float = 4.0):
@@ -274,7 +315,8 @@ class DBSCANHyperParamScanner(ClusterScanner):
             self.reset()
         if not self._trials:
             return
-        scanner = DBSCANFastRescan(out["H"].detach(), max_eps=max(v["eps"] for v in self._trials),
+        ptr = _event_ptr(data) if self.per_event else None
+        scanner = DBSCANFastRescan(out["H"].detach(), max_eps=max(v["eps"] for v in self._trials), ptr=ptr,
                                    n_jobs=self.hparams.n_jobs)
         n = int(scanner.x.shape[0])
         labels = torch.empty((len(self._trials), n), dtype=torch.int64, device=scanner.x.device)
@@ -282,9 +324,13 @@ class DBSCANHyperParamScanner(ClusterScanner):
             labels[k] = scanner.cluster_device(eps=trial["eps"], min_pts=trial["min_samples"])
         metrics = tracking_metrics_trials(labels, truth=data.particle_id, pts=data.pt, eta=data.eta,
                                           reconstructable=data.reconstructable, pt_thlds=self.hparams.pt_thlds,
-                                          max_eta=self.hparams.max_eta)
-        for trial, m in zip(self._trials, metrics):
-            self._results.append({"i_batch": i_batch, "eps": trial["eps"], "min_samples": trial["min_samples"], **m})
+                                          max_eta=self.hparams.max_eta, ptr=ptr)
+        if ptr is None:
+            metrics = [[m] for m in metrics]
+        for e in range(len(metrics[0])):       # (records grouped by event: as the events fed one by one)
+            for trial, per_event in zip(self._trials, metrics):
+                self._results.append({"i_batch": i_batch, "eps": trial["eps"], "min_samples": trial["min_samples"],
+                                      **per_event[e]})
 
 
 class DBSCANHyperParamScannerFixed(DBSCANHyperParamScanner):
@@ -304,7 +350,8 @@ class DBSCANPerformanceDetails(DBSCANHyperParamScanner):
         the device DBSCAN of ``out["H"]``, then the hit record (``c``, ``id``, ``reconstructable``,
         ``pt``, ``eta`` as device tensors) and the cluster table
         (``cluster_metrics.tracking_metric_table``: numpy columns) are kept; see ``get_results``.  As
-        the reference, it neither resets on ``i_batch == 0`` nor looks at ``ec_hit_mask``."""
+        the reference, it neither resets on ``i_batch == 0`` nor looks at ``ec_hit_mask``.  Data of several events
+        (``per_event``): one DBSCAN for all of them, then one hit record and one cluster table per event."""
         super().__init__()
         self.save_hyperparameters()
         self._h_dfs: list[dict[str, Tensor]] = []
@@ -313,13 +360,18 @@ class DBSCANPerformanceDetails(DBSCANHyperParamScanner):
     def __call__(self, data, out: dict[str, Tensor], i_batch: int) -> None:
         from . import cluster_metrics as CM
 
-        fr = DBSCANFastRescan(out["H"].detach(), max_eps=self.hparams.eps)
+        ptr = _event_ptr(data) if self.per_event else None
+        fr = DBSCANFastRescan(out["H"].detach(), max_eps=self.hparams.eps, ptr=ptr)
         labels = fr.cluster_device(eps=self.hparams.eps, min_pts=self.hparams.min_samples)
         dev = labels.device
         pid, pt, reco, eta = CM._hits(data.particle_id, data.pt, data.reconstructable, data.eta, dev)
-        self._h_dfs.append({"c": labels, "id": pid, "reconstructable": reco, "pt": pt, "eta": eta})
-        # (DBSCAN's labels are in [-1, n) already: no ranking pass)
-        self._c_dfs.append(CM._table(labels, None, pid, pt, reco, eta, 3))
+        # (several events: one DBSCAN for all, then per event its slice of the local labels - one record and one table)
+        rows = [0, int(labels.shape[0])] if ptr is None else ptr.tolist()
+        for a, b in zip(rows, rows[1:]):
+            lab, cols = labels[a:b], [v[a:b] for v in (pid, pt, reco, eta)]
+            self._h_dfs.append({"c": lab, "id": cols[0], "reconstructable": cols[2], "pt": cols[1], "eta": cols[3]})
+            # (DBSCAN's labels are in [-1, n) already: no ranking pass)
+            self._c_dfs.append(CM._table(lab.contiguous(), None, *(c.contiguous() for c in cols), 3))
 
     def get_results(self) -> tuple[list[dict[str, Tensor]], list[dict[str, np.ndarray]]]:
         """(h_dfs, c_dfs): per batch the hit record and the cluster table, as

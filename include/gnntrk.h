@@ -612,6 +612,20 @@ int gnntrk_radius_count_ws(const float *x, int64_t n, int32_t dim, int32_t x_str
 int gnntrk_radius_fill_ws(const float *x, int64_t n, int32_t dim, int32_t x_stride, double radius,
                           const int64_t *offsets, int64_t m_edges, int32_t *nbr, double *dist, void *ws_points,
                           size_t ws_points_bytes, void *ws_edges, size_t ws_edges_bytes, int32_t flags, void *stream);
+/* The graph of a collated batch: rows [seg_ptr[s], seg_ptr[s+1]) are event s (seg_ptr as
+ * gnntrk_knn_search_batched takes it; NULL: one event, the two entries above) and a query's neighbourhood
+ * holds hits of its own event only - all events in ONE launch sequence.  Neighbour ids stay global and
+ * ascending, the arithmetic is the one above, so the lists of event s are bit for bit those of its
+ * single-event graph with ids shifted by seg_ptr[s].  The pruned form sorts by (event, Morton code) and a
+ * wave walks the chunks of its queries' events only; with more than 65 536 events the brute-force form
+ * runs.  Workspaces and flags as above. */
+int gnntrk_radius_count_batched_ws(const float *x, int64_t n, int32_t dim, int32_t x_stride, double radius,
+                                   const int64_t *seg_ptr, int32_t n_seg, int32_t *cnt, int64_t *offsets,
+                                   void *ws_points, size_t ws_points_bytes, int32_t flags, void *stream);
+int gnntrk_radius_fill_batched_ws(const float *x, int64_t n, int32_t dim, int32_t x_stride, double radius,
+                                  const int64_t *seg_ptr, int32_t n_seg, const int64_t *offsets, int64_t m_edges,
+                                  int32_t *nbr, double *dist, void *ws_points, size_t ws_points_bytes,
+                                  void *ws_edges, size_t ws_edges_bytes, int32_t flags, void *stream);
 int gnntrk_dbscan_init(const int64_t *offsets, const double *dist, int64_t n, double eps, int32_t min_pts,
                        uint8_t *core, int32_t *root, void *stream);
 int gnntrk_dbscan_propagate(const int64_t *offsets, const int32_t *nbr, const double *dist, int64_t n, double eps,
@@ -620,6 +634,17 @@ size_t gnntrk_dbscan_workspace_bytes(int64_t n);
 int gnntrk_dbscan_labels(const int64_t *offsets, const int32_t *nbr, const double *dist, int64_t n, double eps,
                          const uint8_t *core, const int32_t *root, int64_t *labels, int64_t *n_clusters,
                          void *workspace, size_t workspace_bytes, void *stream);
+/* dbscan_labels on the graph of a collated batch (init and propagate need no events: the graph has no
+ * edge between events, so no component crosses one): labels are LOCAL to the event - noise -1, the clusters
+ * of event s numbered from 0 by ascending lowest core index inside it - so labels[seg_ptr[s] .. seg_ptr[s+1])
+ * is what dbscan_labels gives for event s alone.  cluster_ptr [n_seg + 1] int64: cluster_ptr[s] = number of
+ * clusters of the events before s, cluster_ptr[n_seg] = number of clusters.  An event of n_s hits has at most
+ * n_s clusters, so (event, label) has the dense slot seg_ptr[s] + label < n (gnntrk_tracking_metrics_batched).
+ * workspace: gnntrk_dbscan_workspace_bytes(n). */
+int gnntrk_dbscan_labels_batched(const int64_t *offsets, const int32_t *nbr, const double *dist, int64_t n,
+                                 double eps, const uint8_t *core, const int32_t *root, const int64_t *seg_ptr,
+                                 int32_t n_seg, int64_t *labels, int64_t *cluster_ptr, void *workspace,
+                                 size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------ condensation losses
  * utils/graph_masks.py:19-28: mask = pt > thld && pid > 0 && reconstructable > 0 && |eta| < max_eta */
@@ -995,6 +1020,27 @@ int gnntrk_tracking_metrics(const int64_t *labels, int32_t n_trials, const int64
                             const float *eta, const float *reconstructable, int64_t n, const float *cuts,
                             int32_t n_cuts, float max_eta, int32_t predicted_count_thld, int64_t *out,
                             void *workspace, size_t workspace_bytes, void *stream);
+/* The same counts for every event of a collated batch from one launch sequence: rows [seg_ptr[s],
+ * seg_ptr[s+1]) are event s (n_seg >= 1 events, seg_ptr on the device as gnntrk_knn_search_batched takes it).
+ * Every event is its own problem:
+ *   - a particle is a pair (event, particle id): the hits of one id in two events are two particles, and so is
+ *     id 0 (noise) of two events;
+ *   - labels are LOCAL to the event, as gnntrk_dbscan_labels_batched writes them: label l of a hit of event s
+ *     is the cluster (s, l); a label >= the event's number of hits is ignored and counted in the last output
+ *     value (0 <= l < n_s gives the dense cluster slot seg_ptr[s] + l < n).
+ * Everything else - masks, means, tie rule (the smallest id of the event), flags - as above, so the values of
+ * event s are those of gnntrk_tracking_metrics on its rows alone.
+ * out (int64, n_seg * n_cuts + n_trials * n_seg * n_cuts * 4 + 1 values, overwritten):
+ *   [s * n_cuts + c]                                        n_particles of event s at cut c;
+ *   [n_seg * n_cuts + ((t * n_seg + s) * n_cuts + c) * 4 + k]  trial t, event s, cut c: k as above;
+ *   [last]                                                  number of labels >= their event's hits.
+ * workspace: gnntrk_tracking_metrics_workspace_bytes(n, n_trials).  No host synchronisation.  Errors as above;
+ * GNNTRK_EINVAL also for NULL seg_ptr or n_seg < 1. */
+int gnntrk_tracking_metrics_batched(const int64_t *labels, int32_t n_trials, const int64_t *particle_id,
+                                    const float *pt, const float *eta, const float *reconstructable, int64_t n,
+                                    const int64_t *seg_ptr, int32_t n_seg, const float *cuts, int32_t n_cuts,
+                                    float max_eta, int32_t predicted_count_thld, int64_t *out, void *workspace,
+                                    size_t workspace_bytes, void *stream);
 
 /* The same counts for two-sided windows instead of nested cuts (tracking_metrics_vs_pt / _vs_eta,
  * metrics/cluster_metrics.py:292-384), arguments as gnntrk_tracking_metrics except:
