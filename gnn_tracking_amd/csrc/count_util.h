@@ -1,6 +1,7 @@
 // Device-side helpers shared by the integer-counting units (metrics.hip, tracking_metrics.hip,
 // kscan.hip): atomics, the open-addressing table keyed by "first hit + 1", the block reduction (wave
-// sum of wave_util.h -> LDS -> one global atomic per workgroup and value) and the pt cuts passed to kernels by value.
+// sum of wave_util.h -> LDS -> one global atomic per workgroup and value), the events of a collated batch with the
+// per-event form of that sum, and the pt cuts passed to kernels by value.
 #pragma once
 
 #include <stdio.h>
@@ -115,6 +116,54 @@ __device__ __forceinline__ void block_add(const uint32_t (&v)[NV], unsigned long
     }
     __syncthreads();
     if (threadIdx.x < NV && acc[threadIdx.x]) atomicAdd(&dst[threadIdx.x], acc[threadIdx.x]);
+}
+
+// ------------------------------------------------------------------- events of a collated batch
+// Hits [ptr[s], ptr[s + 1]) are event s, every event its own problem.  The kernels' BATCH = false instantiations
+// (one event) never read it.  With BATCH a particle is the pair (event, particle id).
+struct Events {
+    const int64_t *ptr;
+    int32_t n;
+};
+// the rows [lo, hi) of the event of hit i (one event: all rows) and its number
+template <bool BATCH>
+__device__ __forceinline__ int event_rows(const Events &ev, int64_t n, int64_t i, int64_t &lo, int64_t &hi) {
+    lo = 0;
+    hi = n;
+    if (!BATCH) return 0;
+    const int e = segment_of(ev.ptr, ev.n, i);
+    lo = ev.ptr[e];
+    hi = ev.ptr[e + 1];
+    return e;
+}
+// hash of a particle: its id, with BATCH combined with its event
+template <bool BATCH>
+__device__ __forceinline__ uint64_t particle_hash(int64_t key, int e) {
+    return mix64(BATCH ? (uint64_t)key + 0x9e3779b97f4a7c15ull * (uint64_t)(e + 1) : (uint64_t)key);
+}
+
+// wave-wide, every lane of the wave calls it: adds the per-lane counts v[0..NV) into dst[e * stride + 0..NV), e the
+// lane's event, and clears them.  Hits are sorted by event, so the lanes of a wave that walks consecutive hits have
+// one event unless an event edge falls among them: then a wave sum and one int64 atomic per value; otherwise every
+// lane adds its own counts.  The event of a lane without counts is not looked at.
+template <int NV>
+__device__ __forceinline__ void event_add(uint32_t (&v)[NV], int e, unsigned long long *dst, size_t stride) {
+    uint32_t any = 0u;
+    for (int k = 0; k < NV; ++k) any |= v[k];
+    const unsigned long long live = __ballot(any != 0u);
+    if (live == 0ull) return;   // (uniform in the wave, as the branch below)
+    const int lead = __builtin_ctzll(live);
+    const int e0 = __shfl(e, lead);
+    if (__ballot(any != 0u && e != e0) == 0ull) {
+        for (int k = 0; k < NV; ++k) {
+            const uint32_t s = wave_sum(v[k]);
+            if ((int)(threadIdx.x & 63) == lead && s) atomicAdd(&dst[(size_t)e0 * stride + k], (unsigned long long)s);
+        }
+    } else {
+        for (int k = 0; k < NV; ++k)
+            if (v[k]) atomicAdd(&dst[(size_t)e * stride + k], (unsigned long long)v[k]);
+    }
+    for (int k = 0; k < NV; ++k) v[k] = 0u;
 }
 
 // -------------------------------------------------------------------------------- pt cuts

@@ -98,29 +98,8 @@ struct WinSel {
     __device__ __forceinline__ static void merge(uint32_t *p, uint32_t c) { atomicOr(p, c); }
 };
 
-// The events of a collated batch: hits [ptr[s], ptr[s + 1]) are event s, every event its own problem.  The kernels'
-// BATCH = false instantiations (one event) never read it.  With BATCH a particle is the pair (event, particle id),
-// and a cluster the pair (event, local label) with the dense slot ptr[s] + label < n.
-struct Events {
-    const int64_t *ptr;
-    int32_t n;
-};
-// the rows [lo, hi) of the event of hit i (one event: all rows) and its number
-template <bool BATCH>
-__device__ __forceinline__ int event_rows(const Events &ev, int64_t n, int64_t i, int64_t &lo, int64_t &hi) {
-    lo = 0;
-    hi = n;
-    if (!BATCH) return 0;
-    const int e = segment_of(ev.ptr, ev.n, i);
-    lo = ev.ptr[e];
-    hi = ev.ptr[e + 1];
-    return e;
-}
-// hash of a particle: its id, with BATCH combined with its event
-template <bool BATCH>
-__device__ __forceinline__ uint64_t particle_hash(int64_t key, int e) {
-    return mix64(BATCH ? (uint64_t)key + 0x9e3779b97f4a7c15ull * (uint64_t)(e + 1) : (uint64_t)key);
-}
+// The events of a collated batch (Events, event_rows, particle_hash: count_util.h).  With BATCH a particle is the
+// pair (event, particle id), and a cluster the pair (event, local label) with the dense slot ptr[s] + label < n.
 
 // the particle table's slot of pid (present: every particle id of the hits was inserted); BATCH: of the
 // particle (e, pid), e the event with the rows [lo, hi) - the same id and the event of the slot's first hit

@@ -10,6 +10,10 @@ at ``max(ks)`` (the graph of a smaller k is a prefix of every row of its table),
 ``KScanResults`` interpolates the per-k means with a not-a-knot cubic spline in numpy (no pandas, scipy
 or networkx).
 
+A collated batch of B > 1 events (``ptr`` / ``batch``) is B scans from the same launch sequence: the search per
+event, ``gnntrk_kscan_counts_batched`` and ``gnntrk_tracking_metrics_batched``, still one host copy, and one record
+per (event, k) - the records of the events fed one by one (``GraphConstructionKNNScanner.per_event``).
+
 What differs from the reference, all of it outside what its results pin down:
 
 * ``subsample_pids`` exists there to make the host loop affordable.  It is accepted, a warning is given
@@ -36,8 +40,9 @@ from torch import Tensor
 
 from . import _capi, ops
 from .cluster_metrics import _counts as _tracking_counts, _cut_plan, _hits, _results as _tracking_results, \
-    _zdiv, flatten_track_metrics
+    _results_per_event as _tracking_results_per_event, _zdiv, flatten_track_metrics
 from .graph_analysis import efficiency_purity_from_counts
+from .graph_construction import _event_ptr
 from .graph_masks import get_good_node_mask
 from .hparams import HyperparametersMixin
 
@@ -231,10 +236,14 @@ def _mean_skipna(values: list[float]) -> float:
 
 
 def kscan_counts(nbr: Tensor, cnt: Tensor, k_stride: int, ks: typing.Sequence[int], particle_id: Tensor,
-                 node_mask: Tensor, true_edge_index: Tensor | None) -> tuple[Tensor, Tensor]:
+                 node_mask: Tensor, true_edge_index: Tensor | None, ptr: Tensor | None = None) -> tuple[Tensor, Tensor]:
     """``gnntrk_kscan_counts`` on one neighbour table (``nbr`` int32 ``[n * k_stride]``, ``cnt`` int32
     ``[n]`` of a search with ``k = k_stride``): the int64 table ``[len(ks), len(COUNT_COLUMNS)]`` and the
-    int64 labels ``[len(ks), n]`` of the same-id components on all hits, both on the device; no host read."""
+    int64 labels ``[len(ks), n]`` of the same-id components on all hits, both on the device; no host read.
+
+    ``ptr`` (int64 ``[B + 1]`` row offsets of the events of a collated batch, more than one event; the table of a
+    search per event): ``gnntrk_kscan_counts_batched`` - the table ``[B, len(ks), len(COUNT_COLUMNS)]`` of every
+    event on its own and labels local to the event, as ``_tracking_counts(..., ptr=ptr)`` takes them."""
     _capi.require_device(nbr, cnt, particle_id, node_mask)
     lib = _capi.load()
     n = int(cnt.shape[0])
@@ -252,13 +261,21 @@ def kscan_counts(nbr: Tensor, cnt: Tensor, k_stride: int, ks: typing.Sequence[in
     if true_edge_index is not None and true_edge_index.numel():
         te = true_edge_index.detach().to(device=dev, dtype=torch.int64).contiguous()
         m_te = int(te.shape[1])
-    out = torch.empty((len(ks), _capi.KSCAN_COLUMNS), dtype=torch.int64, device=dev)
+    n_ev = int(ptr.numel()) - 1 if ptr is not None and ptr.numel() > 2 else 0
+    shape = (len(ks), _capi.KSCAN_COLUMNS)
+    out = torch.empty((n_ev, *shape) if n_ev else shape, dtype=torch.int64, device=dev)
     labels = torch.empty((len(ks), n), dtype=torch.int64, device=dev)
-    ws = ops._ws(lib.gnntrk_kscan_counts_workspace_bytes(n), cnt)
     p = ops._p
-    _capi.check(lib.gnntrk_kscan_counts(p(nbr), p(cnt), n, int(k_stride), (C.c_int32 * len(ks))(*ks), len(ks), p(pid),
-                                        p(mask), p(te), m_te, p(out), p(labels), p(ws), ws.numel(),
-                                        ops._stream(cnt)), lib)
+    head = (p(nbr), p(cnt), n, int(k_stride), (C.c_int32 * len(ks))(*ks), len(ks), p(pid), p(mask), p(te), m_te)
+    if n_ev:
+        _capi.require_device(ptr)
+        seg = ptr.detach().to(device=dev, dtype=torch.int64).contiguous()
+        ws = ops._ws(lib.gnntrk_kscan_counts_batched_workspace_bytes(n, n_ev, len(ks)), cnt)
+        _capi.check(lib.gnntrk_kscan_counts_batched(*head, p(seg), n_ev, p(out), p(labels), p(ws), ws.numel(),
+                                                    ops._stream(cnt)), lib)
+    else:
+        ws = ops._ws(lib.gnntrk_kscan_counts_workspace_bytes(n), cnt)
+        _capi.check(lib.gnntrk_kscan_counts(*head, p(out), p(labels), p(ws), ws.numel(), ops._stream(cnt)), lib)
     return out, labels
 
 
@@ -279,7 +296,7 @@ class GraphConstructionKNNScanner(HyperparametersMixin):
             max_eta: eta cut of the good-node mask
             subsample_pids: accepted for compatibility; all particles are evaluated (module docstring)
             max_edges: the scan of a batch stops at the first k (in the given order) whose graph has more
-                edges than this
+                edges than this; on a collated batch (``per_event``) that of every event on its own
         """
         super().__init__()
         self.save_hyperparameters()
@@ -288,7 +305,7 @@ class GraphConstructionKNNScanner(HyperparametersMixin):
 
     @property
     def results_raw(self) -> list[dict[str, float]]:
-        """Raw results for all graphs and all k: one record per (batch, k), in scan order."""
+        """Raw results for all graphs and all k: one record per (batch, event, k), in scan order."""
         return self._results
 
     def get_results(self) -> KScanResults:
@@ -310,10 +327,17 @@ class GraphConstructionKNNScanner(HyperparametersMixin):
         """Reset the results; called on every batch with ``i_batch == 0``."""
         self._results = []
 
+    #: a collated ``data`` of more than one event (``ptr`` / ``batch``): every event is its own scan - neighbours,
+    #: components and true edges inside the event, particles as (event, id) pairs (ids repeat from event to event,
+    #: and id 0 is noise in all of them) - and gets its own record per k: the records of the events fed one by one,
+    #: from one launch sequence.  False: the reference's behaviour, which ignores ``batch`` (one point cloud).  A
+    #: class attribute so that YAML configurations stay those of the reference.
+    per_event = True
+
     def __call__(self, data, i_batch: int, *, progress=False, latent: Tensor | None = None) -> None:
-        """Run on a batch: ``data.x`` (or ``latent``) is the space the graph is built in; the whole batch
-        is one point cloud, as in the reference.  ``progress`` is accepted and ignored (there is no
-        per-k loop to show)."""
+        """Run on a batch: ``data.x`` (or ``latent``) is the space the graph is built in, every event of the
+        batch on its own (``per_event``).  ``progress`` is accepted and ignored (there is no per-k loop to
+        show)."""
         if i_batch == 0:
             self.reset()
         if self.hparams.subsample_pids is not None and not self._warned_subsample:
@@ -322,9 +346,22 @@ class GraphConstructionKNNScanner(HyperparametersMixin):
         x = (latent if latent is not None else data.x).detach()
         self._results.extend(self.evaluate(data, x))
 
+    @staticmethod
+    def _record(k: int, c: dict[str, int], upper: dict[str, float]) -> dict[str, float]:
+        """one record (k_scanner.py:248-285) from a row of the counts table and the flattened upper bounds"""
+        return {
+            "k": k,
+            "frac50": _zdiv(c["n50"], c["n_pids"]),
+            "frac75": _zdiv(c["n75"], c["n_pids"]),
+            "frac100": _zdiv(c["n100"], c["n_pids"]),
+            "n_edges": c["n_edges"],
+            **efficiency_purity_from_counts(c["n_true_masked"], c["n_true_edges_masked"], c["n_masked"]),
+            **{"max_" + key: v for key, v in upper.items()},
+        }
+
     def evaluate(self, data, x: Tensor) -> list[dict[str, float]]:
-        """The records of one batch (k_scanner.py:248-285 for every k): one search, one counts call, one
-        tracking-metrics call, one host copy."""
+        """The records of one batch (k_scanner.py:248-285 for every k, and with ``per_event`` for every event):
+        one search, one counts call, one tracking-metrics call, one host copy."""
         hp = self.hparams
         ks = [int(k) for k in hp.ks]
         if not ks:
@@ -333,23 +370,50 @@ class GraphConstructionKNNScanner(HyperparametersMixin):
         _capi.require_device(x)
         x = ops._as_rows(x.float() if x.dtype != torch.float32 else x)
         n, dev = int(x.shape[0]), x.device
+        ptr = _event_ptr(data) if self.per_event else None
         if n < 2:
-            raise ValueError("GraphConstructionKNNScanner: needs at least two hits")
+            if ptr is None:
+                raise ValueError("GraphConstructionKNNScanner: needs at least two hits")
+            return []   # (no event of the batch has a graph to scan)
+        if ptr is not None:
+            ptr = ptr.to(device=dev, dtype=torch.int64).contiguous()
         kmax = min(max(ks), n - 1)
         nbr = torch.empty(n * kmax, dtype=torch.int32, device=dev)
         cnt = torch.empty(n, dtype=torch.int32, device=dev)
         r = float(hp.max_radius) if hp.max_radius is not None else -1.0
-        ops._knn_search(lib, x, kmax, r, None, nbr, cnt, ops._stream(x))
+        ops._knn_search(lib, x, kmax, r, ptr, nbr, cnt, ops._stream(x))
         mask = get_good_node_mask(data, pt_thld=hp.pt_thld, max_eta=hp.max_eta)
         counts, labels = kscan_counts(nbr, cnt, kmax, [min(k, kmax) for k in ks], data.particle_id, mask,
-                                      getattr(data, "true_edge_index", None))
+                                      getattr(data, "true_edge_index", None), ptr=ptr)
         pts, cuts, idx = _cut_plan([0.9])   # (hard-coded in the reference: k_scanner.py:243)
         hits = _hits(data.particle_id, data.pt, data.reconstructable, data.eta, dev)
-        trk = _tracking_counts(labels, *hits, cuts, 3, 4)
-        host = torch.cat([counts.reshape(-1), trk]).cpu().numpy()   # the batch's one host copy
+        trk = _tracking_counts(labels, *hits, cuts, 3, 4, ptr=ptr)
+        # the batch's one host copy (the events' sizes ride along)
+        host = torch.cat([counts.reshape(-1), trk] + ([ptr] if ptr is not None else [])).cpu().numpy()
+        records = []
+        if ptr is not None:
+            n_ev = int(ptr.numel()) - 1
+            sizes = np.diff(host[-(n_ev + 1):]).tolist()
+            table = host[:counts.numel()].reshape(n_ev, len(ks), len(COUNT_COLUMNS))
+            upper = _tracking_results_per_event(host[counts.numel():-(n_ev + 1)], len(ks), sizes, pts, idx)
+            for e in range(n_ev):
+                n_bad = int(table[e, 0, COUNT_COLUMNS.index("n_bad")])
+                if n_bad:
+                    raise ValueError(f"GraphConstructionKNNScanner: {n_bad} neighbour or true-edge indices of event {e} "
+                                     f"are outside its {sizes[e]} hits")
+            for e, n_e in enumerate(sizes):
+                if n_e < 2:   # (alone it has no graph to scan)
+                    continue
+                for i, k in enumerate(ks):
+                    c = dict(zip(COUNT_COLUMNS, (int(v) for v in table[e, i])))
+                    if c["n_edges"] > hp.max_edges:
+                        logger.warning(f"Not scanning k>={k} in event {e} because max edges exceeded "
+                                       f"({c['n_edges']} > {hp.max_edges})")
+                        break
+                    records.append(self._record(k, c, upper[i][e]))
+            return records
         table = host[:counts.numel()].reshape(len(ks), len(COUNT_COLUMNS))
         upper = _tracking_results(host[counts.numel():], len(ks), pts, idx)
-        records = []
         for row, k, ub in zip(table, ks, upper):
             c = dict(zip(COUNT_COLUMNS, (int(v) for v in row)))
             if c["n_bad"]:
@@ -358,13 +422,5 @@ class GraphConstructionKNNScanner(HyperparametersMixin):
             if c["n_edges"] > hp.max_edges:
                 logger.warning(f"Not scanning k>={k} because max edges exceeded ({c['n_edges']} > {hp.max_edges})")
                 break
-            records.append({
-                "k": k,
-                "frac50": _zdiv(c["n50"], c["n_pids"]),
-                "frac75": _zdiv(c["n75"], c["n_pids"]),
-                "frac100": _zdiv(c["n100"], c["n_pids"]),
-                "n_edges": c["n_edges"],
-                **efficiency_purity_from_counts(c["n_true_masked"], c["n_true_edges_masked"], c["n_masked"]),
-                **{"max_" + key: v for key, v in flatten_track_metrics(ub).items()},
-            })
+            records.append(self._record(k, c, flatten_track_metrics(ub)))
         return records

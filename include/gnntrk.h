@@ -1153,9 +1153,29 @@ int gnntrk_cluster_spectra(const int64_t *labels, int32_t n_trials, const int64_
  * with n_trials = n_ks.  The graphs are nested in k: the ks are visited in ascending order and every
  * table edge is united once per call.  workspace: gnntrk_kscan_counts_workspace_bytes(n).
  * GNNTRK_EINVAL for n < 0, n_ks out of range, a k < 1 or > k_stride, NULL required pointers, a small
- * workspace; GNNTRK_EUNSUPPORTED for n >= 2^30. */
+ * workspace; GNNTRK_EUNSUPPORTED for n >= 2^30.
+ *
+ * gnntrk_kscan_counts_batched - the same for every event of a collated batch from ONE launch sequence, whose
+ * number of launches is that of gnntrk_kscan_counts with the same ks whatever n_seg.  Arguments as above, plus
+ *   seg_ptr   device int64 [n_seg + 1], ascending row offsets of the events, seg_ptr[0] = 0 and seg_ptr[n_seg] = n
+ *             (as gnntrk_knn_search_batched takes them; empty events are allowed); never read on the host;
+ *   n_seg     1..GNNTRK_KSCAN_MAX_EVENTS.
+ * out (int64 [n_seg][n_ks][GNNTRK_KSCAN_COLUMNS], overwritten): row (s, r) is what gnntrk_kscan_counts returns for
+ * the rows of event s alone with k = ks[r] (an empty event: zeros).  A particle is the pair (event, particle id):
+ * ids may repeat from event to event.  labels (int64 [n_ks][n]) are LOCAL to the event, the smallest hit index of
+ * the component minus seg_ptr[s]: the slice of event s is the labels of that event alone, in [0, n_s) as
+ * gnntrk_tracking_metrics_batched takes them.  Nothing joins two events: a neighbour entry outside its query's
+ * event and a true edge whose ends lie in two events are skipped and counted in [8] n_bad - of the query's event
+ * and of the event of the true edge's first end - with the indices outside [0, n) (a true edge with one end
+ * outside [0, n): the event of the other end; with both: the first event).
+ * workspace: gnntrk_kscan_counts_batched_workspace_bytes(n, n_seg, n_ks) - it holds the counter rows of every
+ * (event, k).  No host synchronisation; integer arithmetic only, so the outputs do not depend on the order in
+ * which atomics land.
+ * GNNTRK_EINVAL for NULL seg_ptr, n_seg < 1, a small workspace and everything gnntrk_kscan_counts refuses;
+ * GNNTRK_EUNSUPPORTED for n >= 2^30 or n_seg > GNNTRK_KSCAN_MAX_EVENTS. */
 #define GNNTRK_KSCAN_COLUMNS 9
 #define GNNTRK_KSCAN_MAX_KS 64
+#define GNNTRK_KSCAN_MAX_EVENTS 65536
 size_t gnntrk_cc_labels_workspace_bytes(int64_t n);
 int gnntrk_cc_labels(const int64_t *edge_index, int64_t n_edges, const int32_t *nbr, const int32_t *cnt,
                      int32_t k_stride, int32_t k, const int64_t *same_pid, const uint8_t *node_mask, int64_t n,
@@ -1165,6 +1185,12 @@ int gnntrk_kscan_counts(const int32_t *nbr, const int32_t *cnt, int64_t n, int32
                         int32_t n_ks, const int64_t *particle_id, const uint8_t *node_mask,
                         const int64_t *true_edge_index, int64_t n_true_edges, int64_t *out, int64_t *labels,
                         void *workspace, size_t workspace_bytes, void *stream);
+size_t gnntrk_kscan_counts_batched_workspace_bytes(int64_t n, int32_t n_seg, int32_t n_ks);
+int gnntrk_kscan_counts_batched(const int32_t *nbr, const int32_t *cnt, int64_t n, int32_t k_stride, const int32_t *ks,
+                                int32_t n_ks, const int64_t *particle_id, const uint8_t *node_mask,
+                                const int64_t *true_edge_index, int64_t n_true_edges, const int64_t *seg_ptr,
+                                int32_t n_seg, int64_t *out, int64_t *labels, void *workspace, size_t workspace_bytes,
+                                void *stream);
 
 #ifdef __cplusplus
 }
