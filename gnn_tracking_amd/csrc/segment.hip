@@ -337,9 +337,13 @@ __global__ __launch_bounds__(kTpb) void focal_bwd_kernel(const float *__restrict
         focal_terms(y, src_node, pt, thld, pos_weight, haughty, e, t, pw);
         const float p = w[e], q = 1.f - p;
         // d/dp [(1-p)^g log p] = -g (1-p)^(g-1) log p + (1-p)^g / p ;  d/dp [p^g log(1-p)] = g p^(g-1) log(1-p) - p^g / (1-p)
-        const float dpos = -focal_dpow(q, gamma) * logf(p) + focal_pow(q, gamma) / p;
+        // The coefficient of the positive term goes in BEFORE the division by p, as autograd's grad / p: a denormal p
+        // (an fp32 sigmoid below about -88) overflows 1 / p, and a zero coefficient (label 0, alpha 0) times inf is NaN
+        // where the derivative is 0.  (q = 1 - p is 0 or at least 2^-24: 1 / q does not overflow.)
+        const float cpos = -alpha * pw * t;
+        const float dpos = cpos * (-focal_dpow(q, gamma) * logf(p)) + cpos * focal_pow(q, gamma) / p;
         const float dneg = focal_dpow(p, gamma) * logf(q) - focal_pow(p, gamma) / q;
-        gw[e] = gs * (-alpha * pw * t * dpos - (1.f - alpha) * (1.f - t) * dneg);
+        gw[e] = gs * (dpos - (1.f - alpha) * (1.f - t) * dneg);
     }
 }
 

@@ -83,10 +83,12 @@ def make_module(device, data, *, loss_fct=None, seed=0, **model_kw):
 
 
 def run_steps(device, data_list, *, on: bool, scale=1.0, step="backward_step", hook=None, eval_mode=False,
-              module_kw=None):
+              module_kw=None, prepare=None):
     """One ``zero_grad`` + ``backward_step`` per entry of ``data_list`` (gradients accumulate) with the deferral
     ``on`` / off; returns (losses, W csr, node / edge embeddings of the last step, gradients, launch counts)."""
     mod = make_module(device, data_list[0], **(module_kw or {}))
+    if prepare is not None:
+        prepare(mod)   # (a case that sets parameters of the freshly seeded module)
     if eval_mode:
         mod.model.eval()
     got = {}
@@ -143,9 +145,9 @@ def case_fused_w_equals_forward_w(device, data):
                             f"{int(diff.nonzero()[0])}: {on['W'][diff][0].item()!r} vs {off['W'][diff][0].item()!r}")
 
 
-def case_on_off(device, data_list, *, scale=1.0, tag="", expect_fused=True, module_kw=None):
-    on = run_steps(device, data_list, on=True, scale=scale, module_kw=module_kw)
-    off = run_steps(device, data_list, on=False, scale=scale, module_kw=module_kw)
+def case_on_off(device, data_list, *, scale=1.0, tag="", expect_fused=True, module_kw=None, prepare=None):
+    on = run_steps(device, data_list, on=True, scale=scale, module_kw=module_kw, prepare=prepare)
+    off = run_steps(device, data_list, on=False, scale=scale, module_kw=module_kw, prepare=prepare)
     if expect_fused:
         assert on["fused_bwd"] == len(data_list) and on["head_fwd"] == 0, f"{tag}: the fused launch did not run"
     assert off["fused_bwd"] == 0 and off["head_fwd"] == len(data_list)
@@ -187,3 +189,32 @@ def case_metadata_does_not_resolve(device, data):
     E = data.edge_index.shape[1]
     assert seen["meta"] == ((E,), torch.float32, torch.device(device).type, E, 1) and seen["pending"]
     assert on["fused_bwd"] == 1 and on["head_fwd"] == 0
+
+
+def saturate_head(mod, scale=2.0 ** 18):
+    """Scale the head's last linear layer, weights and bias: logits far beyond the range of an fp32 sigmoid."""
+    lin = mod.model.W.linears()[-1]
+    with torch.no_grad():
+        lin.weight.mul_(scale)
+        if lin.bias is not None:
+            lin.bias.mul_(scale)
+
+
+def case_on_off_saturated(device, data):
+    """The on / off comparison with saturated logits: ``expf(-x)`` overflows or vanishes, the sigmoid is exactly 0 or
+    1 and its derivative exactly 0.  The head stores ``W = eps + (1 - 2 eps) sigmoid(x)`` with ``eps = 0.001``
+    (ECForGraphTCN.forward, as the reference), so the stored ends are ``0.001f`` and ``fl(0.001f + 0.998f)`` - an exact
+    0.0f or 1.0f cannot leave this head, whatever its parameters, and the ``-100`` / ``1e-12`` clamps of the BCE arm
+    are out of its reach.  What is asserted: both ends occur under both labels, at least 1 % of ``W`` is at an end,
+    everything ``case_on_off`` demands (loss, ``W`` and every parameter gradient bit-equal and finite), and the loss
+    against torch's BCE of the stored ``W`` in fp64 at 1e-6."""
+    on = case_on_off(device, [data], tag="saturated logits", prepare=saturate_head)
+    w, y = on["W_coo"].cpu(), data.y.cpu().bool()
+    lo, hi = torch.tensor(0.001, dtype=torch.float32), torch.tensor(0.001, dtype=torch.float32) + torch.tensor(0.998, dtype=torch.float32)
+    assert float(w.min()) == float(lo) and float(w.max()) == float(hi), (float(w.min()), float(w.max()))
+    for end in (lo, hi):
+        for lab in (False, True):
+            assert bool(((w == end) & (y == lab)).any()), f"no W = {float(end)!r} with label {lab}"
+    assert float(((w == lo) | (w == hi)).float().mean()) >= 0.01
+    ref = torch.nn.functional.binary_cross_entropy(w.double(), y.double())
+    P.assert_close(on["loss"][0], ref, 1e-6, "saturated logits: loss against torch's BCE of the stored W")

@@ -30,6 +30,11 @@ def test_backward_step_on_off_random_graph_tail_isolated_scaled():
                       tag="two micro-batches, scale 0.5")
 
 
+def test_backward_step_on_off_saturated_logits():
+    with emulated():
+        F.case_on_off_saturated("cpu", F.random_data("cpu"))
+
+
 def test_other_head_shapes_take_todays_launches_inside_the_backward():
     """A head that is not the buffer-addressed shape (no node embedding in its input) defers as well and runs the
     forward launch, the loss pass and the ordinary backward from the node's backward: same bits."""

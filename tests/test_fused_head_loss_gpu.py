@@ -22,6 +22,10 @@ def test_fused_launch_writes_the_forward_launch_w_small():
     F.case_fused_w_equals_forward_w("cuda", F.random_data("cuda"))
 
 
+def test_backward_step_on_off_saturated_logits():
+    F.case_on_off_saturated("cuda", F.random_data("cuda"))
+
+
 def test_backward_step_on_off_cfg3_event():
     on = F.case_on_off("cuda", [_event(100, 150_000, 2_000_000)], tag="cfg3 event, seed 100")
     assert 0.0 < float(on["loss"][0]) < 10.0
