@@ -279,12 +279,19 @@ _SIGNATURES = {
     "gnntrk_tracking_metrics_windows_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "gnntrk_tracking_metrics_windows": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_float),
                                                   C.c_int32, C.c_int32, _P, _P, C.c_size_t, _P]),
+    "gnntrk_tracking_metrics_windows_batched": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, C.c_int32,
+                                                          C.POINTER(C.c_float), C.c_int32, C.c_int32, _P, _P, C.c_size_t,
+                                                          _P]),
     "gnntrk_cluster_table_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gnntrk_cluster_table": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t,
                                        _P]),
+    "gnntrk_cluster_table_batched": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P,
+                                               _P, _P, C.c_size_t, _P]),
     "gnntrk_cluster_spectra_capacity": (C.c_int64, [C.c_int64]),
     "gnntrk_cluster_spectra_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "gnntrk_cluster_spectra": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, _P, C.c_size_t, _P]),
+    "gnntrk_cluster_spectra_batched_capacity": (C.c_int64, [C.c_int64, C.c_int32]),
+    "gnntrk_cluster_spectra_batched": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, _P, C.c_size_t, _P]),
     "gnntrk_cc_labels_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gnntrk_cc_labels": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P, _P, _P,
                                    C.c_size_t, _P]),

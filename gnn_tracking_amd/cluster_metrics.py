@@ -30,6 +30,12 @@ the host finishes v-measure, homogeneity, completeness, the adjusted Rand index 
 index from those few hundred integers (``clustering_scores_trials``: one C call and one host copy for all
 trials).  For these scores labels and truth ids are categories of any integer value, as for sklearn: the
 noise label -1 is ONE cluster and truth id 0 an ordinary class, unlike in the tracking metrics.
+
+A collated batch of several events (``ptr``: [B + 1] row offsets) is that many independent problems from one C call:
+``tracking_metrics_trials``, ``tracking_metric_table``, ``clustering_spectra`` and ``clustering_scores_trials`` take
+``ptr=`` and return per-event results (labels local to the event for the tracking entries), and
+``tracking_metrics_vs_pt`` / ``_vs_eta`` count the hit records that ``DBSCANPerformanceDetails`` sliced from one batch
+(``HitRecord``) in one call per 32 bins.  ``common_metrics`` and ``count_hits_per_cluster`` stay one event per call.
 """
 
 from __future__ import annotations
@@ -175,6 +181,18 @@ def _results(host: np.ndarray, n_trials: int, pts: list, idx: list[int]) -> list
     return [{pt: _from_counts(int(n_part[j]), cnt[t, j]) for pt, j in zip(pts, idx)} for t in range(n_trials)]
 
 
+def _event_sizes(ptr, n: int, who: str) -> list[int] | None:
+    """The hits per event of ``ptr`` ([B + 1] row offsets, checked on the host: ascending from 0 to ``n``); None for
+    ``ptr=None`` or one event - today's call."""
+    if ptr is None or int(np.shape(ptr)[0]) <= 2:
+        return None
+    host = torch.as_tensor(ptr).cpu().long()
+    sizes = torch.diff(host).tolist()
+    if int(host[0]) != 0 or int(host[-1]) != n or min(sizes) < 0:
+        raise ValueError(f"{who}: ptr must ascend from 0 to the number of hits")
+    return sizes
+
+
 def _hits(truth, pts, reconstructable, eta, device):
     return (_on(truth, torch.int64, device), _on(pts, torch.float32, device),
             _on(reconstructable, torch.float32, device), _on(eta, torch.float32, device))
@@ -236,12 +254,7 @@ def tracking_metrics_trials(labels, *, truth, pts, reconstructable, eta, pt_thld
         raise ValueError("tracking_metrics_trials: labels must be [n_trials, n]")
     n_trials, n = int(labels.shape[0]), int(labels.shape[1])
     pts_l, cuts, idx = _cut_plan(pt_thlds)
-    sizes = None
-    if ptr is not None and int(np.shape(ptr)[0]) > 2:
-        host = torch.as_tensor(ptr).cpu().long()
-        sizes = torch.diff(host).tolist()
-        if int(host[0]) != 0 or int(host[-1]) != n or min(sizes) < 0:
-            raise ValueError("tracking_metrics_trials: ptr must ascend from 0 to the number of hits")
+    sizes = _event_sizes(ptr, n, "tracking_metrics_trials")
     if n == 0 or n_trials == 0:
         nan = flatten_track_metrics({pt: dict(_tracking_metrics_nan_results) for pt in pts_l})
         return [dict(nan) if sizes is None else [dict(nan) for _ in sizes] for _ in range(n_trials)]
@@ -294,13 +307,22 @@ def _table(lab: Tensor, uniq: Tensor | None, t: Tensor, p: Tensor, r: Tensor, e:
                                          ops._stream(lab)), lib)
     rows = torch.nonzero(ints[0, :n] > 0).view(-1)
     c = rows if uniq is None else uniq[rows]
-    # (one copy: the label, four integer columns, three fp32 columns as their bits, then the bad-label count)
+    col = _table_rows(c, rows, ints, flts, "the number of hits")
+    return _table_columns(col, predicted_count_thld)
+
+
+def _table_rows(c: Tensor, rows: Tensor, ints: Tensor, flts: Tensor, limit: str) -> np.ndarray:
+    """The selected rows of the dense columns on the host, one copy: [8, m] int64 - the label, four integer
+    columns, three fp32 columns as their bits; refuses a bad-label count (``ints[4, 0]``) that is not 0."""
     packed = torch.cat([c.view(1, -1), ints[:4, rows], flts[:, rows].view(torch.int32).to(torch.int64)]).view(-1)
     host = torch.cat([packed, ints[4, :1]]).cpu().numpy()
     if host[-1] != 0:
-        raise ValueError(f"tracking_metric_table: {int(host[-1])} labels are >= the number of hits")
-    m = int(rows.shape[0])
-    col = host[:-1].reshape(8, m)
+        raise ValueError(f"tracking_metric_table: {int(host[-1])} labels are >= {limit}")
+    return host[:-1].reshape(8, int(rows.shape[0]))
+
+
+def _table_columns(col: np.ndarray, predicted_count_thld: int) -> dict[str, np.ndarray]:
+    """``tracking_metric_df``'s columns from the [8, m] rows of ``_table_rows``."""
     size, maj_hits, maj_pid, pid_hits = col[1], col[2], col[3], col[4]
     mpt, meta, mreco = (col[5 + k].astype(np.int32).view(np.float32) for k in range(3))
     valid = size >= predicted_count_thld
@@ -317,12 +339,45 @@ def _table(lab: Tensor, uniq: Tensor | None, t: Tensor, p: Tensor, r: Tensor, e:
     }
 
 
-def tracking_metric_table(labels, *, truth, pts, reconstructable, eta, predicted_count_thld=3) -> dict[str, np.ndarray]:
+def _table_batched(lab: Tensor, t: Tensor, p: Tensor, r: Tensor, e: Tensor, ptr: Tensor, sizes: list[int],
+                   predicted_count_thld: int) -> list[dict[str, np.ndarray]]:
+    """``gnntrk_cluster_table_batched`` of local labels [n] in [-1, n_e): one C call and one host copy for all events
+    of ``ptr`` (device, [B + 1]), then per event its rows as ``_table`` gives them (``c``: the local label)."""
+    lib = _capi.load()
+    _capi.require_device(lab, t, p, r, e, ptr)
+    n = int(lab.shape[0])
+    dev = lab.device
+    ints = torch.empty((5, max(n, 1)), dtype=torch.int64, device=dev)
+    flts = torch.empty((3, max(n, 1)), dtype=torch.float32, device=dev)
+    ws = ops._ws(lib.gnntrk_cluster_table_workspace_bytes(n), lab)
+    q = ops._p
+    _capi.check(lib.gnntrk_cluster_table_batched(q(lab), q(t), q(p), q(e), q(r), n, q(ptr), len(sizes), q(ints[0]),
+                                                 q(ints[1]), q(ints[2]), q(ints[3]), q(flts[0]), q(flts[1]), q(flts[2]),
+                                                 q(ints[4]), q(ws), ws.numel(), ops._stream(lab)), lib)
+    rows = torch.nonzero(ints[0, :n] > 0).view(-1)   # (cluster slots ptr[e] + label, ascending: grouped by event)
+    # (the slot rides along as the label column; the local label is taken on the host, where the events' rows are)
+    col = _table_rows(rows, rows, ints, flts, "the number of hits of their event")
+    starts = np.concatenate([[0], np.cumsum(sizes)])
+    cut = np.searchsorted(col[0], starts)
+    tables = []
+    for k in range(len(sizes)):
+        part = col[:, cut[k]:cut[k + 1]].copy()
+        part[0] -= starts[k]
+        tables.append(_table_columns(part, predicted_count_thld))
+    return tables
+
+
+def tracking_metric_table(labels, *, truth, pts, reconstructable, eta, predicted_count_thld=3, ptr=None):
     """``tracking_metric_df`` (cluster_metrics.py:76-149) of one labelling as a dict of numpy columns:
     the index ``c`` (ascending cluster labels) and the reference's 13 columns in its order and dtypes.
     Inputs as ``tracking_metrics`` takes them.  Differences from the reference: only clusters (labels
     >= 0) have rows - the reference also lists its negative labels, as rows that are never valid - and
-    ties for the majority particle go to the smallest id."""
+    ties for the majority particle go to the smallest id.
+
+    ``ptr`` ([B + 1] row offsets of the events of a collated batch, more than one event): every event on its own, as
+    ``tracking_metrics_trials`` takes it - particles are (event, id) pairs, labels local to the event, in
+    ``[-1, n_e)``.  The result is a list with one table per event, each what the event's rows alone give (``c``: the
+    local label; an event without hits has a table of no rows), from one C call and one host copy."""
     if not torch.is_tensor(labels):
         labels = torch.as_tensor(np.asarray(labels))
     if labels.dim() != 1:
@@ -331,6 +386,10 @@ def tracking_metric_table(labels, *, truth, pts, reconstructable, eta, predicted
     t, p, r, e = _hits(truth, pts, reconstructable, eta, dev)
     if int(t.shape[0]) != int(labels.shape[0]):
         raise ValueError("tracking_metric_table: labels and truth differ in the number of hits")
+    sizes = _event_sizes(ptr, int(labels.shape[0]), "tracking_metric_table")
+    if sizes is not None:
+        return _table_batched(_on(labels, torch.int64, dev), t, p, r, e, _on(ptr, torch.int64, dev), sizes,
+                              predicted_count_thld)
     lab, uniq = _dense_labels(_on(labels, torch.int64, dev))
     return _table(lab, uniq, t, p, r, e, predicted_count_thld)
 
@@ -368,6 +427,97 @@ def _window_counts(h: dict, windows: np.ndarray, predicted_count_thld: int) -> t
     return n_part, counts
 
 
+def _window_counts_batched(h: dict, ptr, windows: np.ndarray, predicted_count_thld: int) -> tuple[np.ndarray, np.ndarray]:
+    """``_window_counts`` for the hit record of a whole collated batch with the events' offsets ``ptr`` [B + 1] (labels
+    local to the event, in [-1, n_e)) -> (n_particles [B, n], counts [B, n, 4]): one
+    ``gnntrk_tracking_metrics_windows_batched`` call and one host copy per 32 windows for ALL events."""
+    lib = _capi.load()
+    dev = _device_of(h["c"], h["id"], h["pt"], h["reconstructable"], h["eta"])
+    t, p, r, e = _hits(h["id"], h["pt"], h["reconstructable"], h["eta"], dev)
+    lab = _on(h["c"], torch.int64, dev).view(-1)
+    n = int(lab.shape[0])
+    if int(t.shape[0]) != n:
+        raise ValueError("tracking_metrics_vs: a hit record's columns differ in length")
+    sizes = _event_sizes(ptr, n, "tracking_metrics_vs")
+    if sizes is None:
+        raise ValueError("tracking_metrics_vs: ptr of more than one event expected")
+    n_ev = len(sizes)
+    n_part = np.zeros((n_ev, len(windows)), dtype=np.int64)
+    counts = np.zeros((n_ev, len(windows), 4), dtype=np.int64)
+    if n == 0:
+        return n_part, counts
+    seg = _on(ptr, torch.int64, dev)
+    _capi.require_device(lab, t, p, r, e, seg)
+    ws = ops._ws(lib.gnntrk_tracking_metrics_windows_workspace_bytes(n, 1), lab)
+    q = ops._p
+    for lo in range(0, len(windows), _capi.TRACKING_MAX_WINDOWS):
+        win = np.ascontiguousarray(windows[lo:lo + _capi.TRACKING_MAX_WINDOWS], dtype=np.float32)
+        nw = len(win)
+        out = torch.empty(n_ev * nw * 5 + 1, dtype=torch.int64, device=dev)
+        _capi.check(lib.gnntrk_tracking_metrics_windows_batched(q(lab), 1, q(t), q(p), q(e), q(r), n, q(seg), n_ev,
+                                                                win.ctypes.data_as(C.POINTER(C.c_float)), nw,
+                                                                int(predicted_count_thld), q(out), q(ws), ws.numel(),
+                                                                ops._stream(lab)), lib)
+        host = out.cpu().numpy()
+        if host[-1] != 0:
+            raise ValueError(f"tracking_metrics_vs: {int(host[-1])} labels are >= the number of hits of their event")
+        n_part[:, lo:lo + nw] = host[:n_ev * nw].reshape(n_ev, nw)
+        counts[:, lo:lo + nw] = host[n_ev * nw:-1].reshape(n_ev, nw, 4)
+    return n_part, counts
+
+
+class HitRecord(dict):
+    """The hit record of one event that ``DBSCANPerformanceDetails`` sliced from a collated batch: a dict with the
+    five keys of every hit record.  ``origin`` - an attribute, not a key - remembers the batch (``EventBatch``) and
+    the event's index in it, so that ``tracking_metrics_vs_pt`` / ``_vs_eta`` can count all events of the batch in
+    one call."""
+
+    origin = None   # (EventBatch, index of the event)
+
+
+class EventBatch:
+    """The hits of a collated batch behind its ``HitRecord``s: the whole columns (``record``: ``c`` holds labels local
+    to the event), the events' offsets on the device and the per-event records that were handed out."""
+
+    def __init__(self, record: dict, ptr: Tensor):
+        self.record, self.ptr = record, ptr
+        rows = ptr.tolist()
+        self.sizes = [b - a for a, b in zip(rows, rows[1:])]
+        self.records, self._views = [], []
+        for k, (a, b) in enumerate(zip(rows, rows[1:])):
+            rec = HitRecord({key: v[a:b] for key, v in record.items()})
+            rec.origin = (self, k)
+            self.records.append(rec)
+            self._views.append(tuple(rec.values()))
+
+    def holds(self, rec) -> bool:
+        """whether ``rec`` still has the columns it was handed out with (a record whose columns were replaced is
+        counted on its own)"""
+        views = self._views[rec.origin[1]]
+        return list(rec) == list(self.record) and all(v is w for v, w in zip(rec.values(), views))
+
+
+def _per_record_counts(h_dfs: list, windows: np.ndarray, predicted_count_thld: int) -> list:
+    """(n_particles, counts) of every hit record, in the records' order.  Records that ``DBSCANPerformanceDetails``
+    sliced from one collated batch are counted together - ``_window_counts_batched``, once per batch instead of
+    once per event -, every other record on its own."""
+    out: list = [None] * len(h_dfs)
+    groups: dict[int, list[int]] = {}
+    for i, h in enumerate(h_dfs):
+        origin = getattr(h, "origin", None)
+        if origin is not None and origin[0].holds(h):
+            groups.setdefault(id(origin[0]), []).append(i)
+    for members in groups.values():
+        if len(members) < 2:
+            continue
+        batch = h_dfs[members[0]].origin[0]
+        n_part, counts = _window_counts_batched(batch.record, batch.ptr, windows, predicted_count_thld)
+        for i in members:
+            k = h_dfs[i].origin[1]
+            out[i] = (n_part[k], counts[k])
+    return [_window_counts(h, windows, predicted_count_thld) if o is None else o for h, o in zip(h_dfs, out)]
+
+
 def _binned(h_dfs, c_dfs, edges, window_of, names: tuple[str, str], predicted_count_thld: int) -> list[dict]:
     h_dfs, edges = list(h_dfs), list(edges)
     if len(list(c_dfs)) != len(h_dfs):
@@ -377,7 +527,7 @@ def _binned(h_dfs, c_dfs, edges, window_of, names: tuple[str, str], predicted_co
         return []
     # (edges rounded to fp32: numpy 2 compares float32 columns with Python scalars in fp32)
     windows = np.array([window_of(lo, hi) for lo, hi in bins], dtype=np.float32).reshape(len(bins), 4)
-    per_batch = [_window_counts(h, windows, predicted_count_thld) for h in h_dfs]
+    per_batch = _per_record_counts(h_dfs, windows, predicted_count_thld)
     rows = []
     for j, (lo, hi) in enumerate(bins):
         ms = [_from_counts(int(n_part[j]), counts[j]) for n_part, counts in per_batch]
@@ -444,12 +594,54 @@ def _spectrum(row: np.ndarray, cap: int) -> tuple[np.ndarray, np.ndarray]:
     return pairs[:, 0].copy(), pairs[:, 1].copy()
 
 
-def clustering_spectra(labels, truth=None) -> list[dict[str, tuple[np.ndarray, np.ndarray]]]:
+def _spectra_batched(lab: Tensor, tru: Tensor | None, ptr: Tensor, sizes: list[int]) -> list[list[dict]]:
+    """``gnntrk_cluster_spectra_batched`` of ``lab`` [T, n]: one C call and one host copy, then
+    ``[trial][event] -> spectra``; every spectrum arrives as one pooled list of (event, size, multiplicity)."""
+    lib = _capi.load()
+    _capi.require_device(lab, tru, ptr)
+    n_trials, n = int(lab.shape[0]), int(lab.shape[1])
+    if n_trials > _capi.TRACKING_MAX_TRIALS:
+        raise ValueError(f"clustering_spectra: at most {_capi.TRACKING_MAX_TRIALS} trials per call")
+    n_ev = len(sizes)
+    cap = int(lib.gnntrk_cluster_spectra_batched_capacity(n, n_ev))
+    out = torch.empty((1 + 2 * n_trials, 1 + 3 * cap), dtype=torch.int64, device=lab.device)
+    ws = ops._ws(lib.gnntrk_cluster_spectra_workspace_bytes(n, n_trials), lab)
+    p = ops._p
+    _capi.check(lib.gnntrk_cluster_spectra_batched(p(lab), n_trials, p(tru) if tru is not None else None, n, p(ptr), n_ev,
+                                                   p(out), p(ws), ws.numel(), ops._stream(lab)), lib)
+    host = out.cpu().numpy()
+    caps = [int(lib.gnntrk_cluster_spectra_capacity(m)) for m in sizes]
+
+    def per_event(row: np.ndarray) -> list[tuple[np.ndarray, np.ndarray]]:
+        d = int(row[0])
+        if not 0 <= d <= cap:
+            raise RuntimeError(f"clustering_spectra: spectra of {d} entries, at most {cap} are possible")
+        triples = row[1:1 + 3 * d].reshape(d, 3)
+        triples = triples[np.argsort(triples[:, 0], kind="stable")]
+        cut = np.searchsorted(triples[:, 0], np.arange(n_ev + 1))
+        # (the event's pairs behind their number: a row as gnntrk_cluster_spectra writes it, checked against D(n_e))
+        return [_spectrum(np.concatenate([[cut[k + 1] - cut[k]], triples[cut[k]:cut[k + 1], 1:].reshape(-1)]), caps[k])
+                for k in range(n_ev)]
+
+    classes = per_event(host[0])
+    res = []
+    for t in range(n_trials):
+        clusters, cells = per_event(host[1 + 2 * t]), per_event(host[2 + 2 * t])
+        res.append([{"classes": classes[k], "clusters": clusters[k], "cells": cells[k]} for k in range(n_ev)])
+    return res
+
+
+def clustering_spectra(labels, truth=None, ptr=None):
     """The size spectra of ``labels`` ([n] or [n_trials, n]) against ``truth`` ([n], optional): one dict per
     trial with ``classes`` (truth classes; the same for every trial), ``clusters`` and ``cells`` (non-zero
     cells of the contingency table), each a pair of ascending int64 arrays ``(sizes, multiplicities)``.
     Labels and ids are categories of any integer value (-1 is one cluster).  Without ``truth``, ``classes``
-    and ``cells`` are empty.  One C call and one host copy."""
+    and ``cells`` are empty.  One C call and one host copy.
+
+    ``ptr`` ([B + 1] row offsets of the events of a collated batch, more than one event): every event on its own -
+    a class is (event, truth id), a cluster (event, label), so equal labels or ids of two events stay apart - still
+    from one C call and one host copy; the result is ``[trial][event] -> dict``, each what the event's rows alone
+    give (an event without hits: empty spectra)."""
     if not torch.is_tensor(labels):
         labels = torch.as_tensor(np.asarray(labels))
     if labels.dim() == 1:
@@ -459,11 +651,15 @@ def clustering_spectra(labels, truth=None) -> list[dict[str, tuple[np.ndarray, n
     n_trials, n = int(labels.shape[0]), int(labels.shape[1])
     if truth is not None and int(np.shape(truth)[0] if not torch.is_tensor(truth) else truth.shape[0]) != n:
         raise ValueError("clustering_spectra: labels and truth differ in the number of hits")
+    sizes = _event_sizes(ptr, n, "clustering_spectra")
     if n == 0 or n_trials == 0:
-        return [{"classes": _EMPTY, "clusters": _EMPTY, "cells": _EMPTY} for _ in range(n_trials)]
+        empty = {"classes": _EMPTY, "clusters": _EMPTY, "cells": _EMPTY}
+        return [dict(empty) if sizes is None else [dict(empty) for _ in sizes] for _ in range(n_trials)]
     dev = _device_of(labels, truth)
     lab = _on(labels, torch.int64, dev)
     tru = _on(truth, torch.int64, dev).view(-1) if truth is not None else None
+    if sizes is not None:
+        return _spectra_batched(lab, tru, _on(ptr, torch.int64, dev), sizes)
     host, cap = _spectra_host(lab, tru)
     classes = _spectrum(host[0], cap)
     return [{"classes": classes, "clusters": _spectrum(host[1 + 2 * t], cap), "cells": _spectrum(host[2 + 2 * t], cap)}
@@ -508,14 +704,21 @@ def _scores_from_spectra(sp: dict[str, tuple[np.ndarray, np.ndarray]]) -> dict[s
     return dict(zip(SCORE_KEYS, (v, hom, com, ari, fmi)))
 
 
-def clustering_scores_trials(labels, *, truth) -> list[dict[str, float]]:
+def clustering_scores_trials(labels, *, truth, ptr=None):
     """sklearn's clustering scores of many labellings of the same hits (``labels`` [n_trials, n] or [n]) from
     one C call and one host copy: per trial a dict with ``v_measure``, ``homogeneity``, ``completeness``,
     ``adjusted_rand`` and ``fowlkes_mallows``, as the reference's ``common_metrics`` give them one by one.
-    The sibling of ``tracking_metrics_trials`` for a scanner that ranks DBSCAN trials by such a score."""
+    The sibling of ``tracking_metrics_trials`` for a scanner that ranks DBSCAN trials by such a score.
+
+    ``ptr`` (more than one event, as ``clustering_spectra`` takes it): ``[trial][event] -> dict``, each event scored
+    on its own - without it a collated batch would be scored as one mixture, in which equal labels and truth ids of
+    different events merge.  ``common_metrics`` and ``count_hits_per_cluster`` stay one event per call."""
     if truth is None:
         raise ValueError("clustering_scores_trials: truth is required")
-    return [_scores_from_spectra(sp) for sp in clustering_spectra(labels, truth)]
+    spectra = clustering_spectra(labels, truth, ptr)
+    if spectra and isinstance(spectra[0], list):
+        return [[_scores_from_spectra(sp) for sp in per_event] for per_event in spectra]
+    return [_scores_from_spectra(sp) for sp in spectra]
 
 
 def count_hits_per_cluster(predicted) -> np.ndarray:

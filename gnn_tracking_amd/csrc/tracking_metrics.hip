@@ -35,6 +35,10 @@
 //                               stores the windows of its means, tmw_clusters_kernel walks the set bits
 //   cluster_table               one labelling's per-cluster rows (tracking_metric_df, :76-149) as dense
 //                               per-label columns: tm_table_kernel
+// Both have their batched entry too (tracking_metrics_windows_batched, cluster_table_batched): the BATCH = true
+// tables of fill_tables, tmw_particle_batched_kernel / tmw_clusters_batched_kernel after their cut-class siblings, and
+// tm_table_kernel<true>, whose row is the cluster slot seg_ptr[event] + label; majority_of<true> finds the majority
+// particle among those of the cluster's event.
 // Tie rule: the majority particle of a cluster is the one with the most hits in it and, among equals,
 // the smallest particle id (pandas' value_counts leaves ties to an unstable sort).
 #include <math.h>
@@ -418,17 +422,42 @@ __global__ __launch_bounds__(kTpb) void tmw_particle_kernel(Windows win, Ws w,
         atomicAdd(&n_particles[threadIdx.x], (unsigned long long)acc[threadIdx.x]);
 }
 
+// the same per event: n_particles[e][window], e the event of the slot's first hit.  The slots of a block hold
+// particles of any event, so every set bit adds to its event's counts with an int64 atomic
+__global__ __launch_bounds__(kTpb) void tmw_particle_batched_kernel(Windows win, Ws w, Events ev,
+                                                                    unsigned long long *__restrict__ n_particles) {
+    const int64_t S = (int64_t)w.S;
+    for (int64_t s = (int64_t)blockIdx.x * kTpb + threadIdx.x; s < S; s += (int64_t)gridDim.x * kTpb) {
+        const int32_t first = w.ptab[s];
+        if (first == 0) continue;
+        const float reco = particle_mean(w, 2, s);
+        const bool ok = reco != 0.f && reco == reco;
+        w.pcls[s] = ok ? window_mask(particle_mean(w, 0, s), particle_mean(w, 1, s), win) : 0u;
+        uint32_t m = w.phit[s];
+        if (m == 0u) continue;
+        const int e = segment_of(ev.ptr, ev.n, first - 1);
+        for (; m; m &= m - 1u)
+            atomicAdd(&n_particles[(size_t)e * win.n + (__ffsll((unsigned long long)m) - 1)], 1ull);
+    }
+}
+
 // what the tables hold about the cluster of label lab in trial t
 struct Majority {
     uint32_t size, hits, pid_hits;   // cluster size, hits of the majority particle in it and anywhere
     int64_t pid, slot;               // the majority particle and its slot in the particle table
 };
-__device__ __forceinline__ Majority majority_of(const int64_t *pid, int64_t n, const Ws &w, int64_t t, int64_t lab) {
+// lab: the cluster's dense slot - its label, with BATCH the first row of its event + its local label; the majority
+// particle is looked up among the particles of that event, whose number is returned in e
+template <bool BATCH>
+__device__ __forceinline__ Majority majority_of(const int64_t *pid, int64_t n, const Events &ev, const Ws &w, int64_t t,
+                                                int64_t lab, int &e) {
     Majority m;
     m.size = w.csize[t * n + lab];
     m.hits = w.cbest[t * n + lab];
     m.pid = (int64_t)(w.cpid[t * n + lab] ^ (1ull << 63));
-    m.slot = find_particle<false>(w.ptab, pid, w.S - 1, m.pid, 0, 0, n);
+    int64_t lo, hi;
+    e = event_rows<BATCH>(ev, n, lab, lo, hi);
+    m.slot = find_particle<BATCH>(w.ptab, pid, w.S - 1, m.pid, e, lo, hi);
     m.pid_hits = w.pcnt[m.slot];
     return m;
 }
@@ -445,7 +474,8 @@ __global__ __launch_bounds__(kTpb) void tmw_clusters_kernel(const int64_t *__res
     for (int64_t lab = (int64_t)blockIdx.x * kTpb + threadIdx.x; lab < n; lab += (int64_t)gridDim.x * kTpb) {
         const uint32_t size = w.csize[t * n + lab];
         if (size == 0 || (int64_t)size < (int64_t)count_thld) continue;   // not a valid cluster
-        const Majority c = majority_of(pid, n, w, t, lab);
+        int e;
+        const Majority c = majority_of<false>(pid, n, Events{}, w, t, lab, e);
         uint32_t m = w.pcls[c.slot];
         if (m == 0) continue;
         const Match f = match_flags(c.hits, size, c.pid_hits);
@@ -462,9 +492,51 @@ __global__ __launch_bounds__(kTpb) void tmw_clusters_kernel(const int64_t *__res
         atomicAdd(&out[(size_t)t * n_win * 4 + threadIdx.x], (unsigned long long)acc[threadIdx.x]);
 }
 
+// The same per event: one trial per blockIdx.y, one block per 256 cluster slots, as tm_clusters_batched_kernel (a
+// block's slots are consecutive rows, so most blocks lie inside one event).  out[t][e][window][4].  A block inside
+// one event counts in LDS and adds one int64 atomic per non-zero value; a block that spans an event edge adds every
+// cluster to its event's counts with int64 atomics.
+__global__ __launch_bounds__(kTpb) void tmw_clusters_batched_kernel(const int64_t *__restrict__ pid, int64_t n,
+                                                                    int32_t n_win, int32_t count_thld, Events ev, Ws w,
+                                                                    unsigned long long *__restrict__ out) {
+    __shared__ uint32_t acc[kMaxWin * 4];
+    if (threadIdx.x < kMaxWin * 4) acc[threadIdx.x] = 0u;
+    __syncthreads();
+    const int64_t t = blockIdx.y;
+    const int64_t c0 = (int64_t)blockIdx.x * kTpb, c1 = c0 + kTpb < n ? c0 + kTpb - 1 : n - 1;
+    const int e0 = segment_of(ev.ptr, ev.n, c0);
+    const bool one_event = e0 == segment_of(ev.ptr, ev.n, c1);
+    unsigned long long *out_t = out + (size_t)t * ev.n * n_win * 4;
+    const int64_t cl = c0 + threadIdx.x;
+    if (cl < n) {
+        const uint32_t size = w.csize[t * n + cl];
+        if (size != 0 && (int64_t)size >= (int64_t)count_thld) {   // a valid cluster
+            int e;
+            const Majority c = majority_of<true>(pid, n, ev, w, t, cl, e);
+            uint32_t m = w.pcls[c.slot];
+            const Match f = match_flags(c.hits, size, c.pid_hits);
+            const uint32_t add[4] = {1u, f.perfect, f.dm, f.lhc};
+            for (; m; m &= m - 1u) {
+                const int j = __ffsll((unsigned long long)m) - 1;
+                for (int k = 0; k < 4; ++k) {
+                    if (!add[k]) continue;
+                    if (one_event) atomicAdd(&acc[j * 4 + k], 1u);
+                    else atomicAdd(&out_t[((size_t)e * n_win + j) * 4 + k], 1ull);
+                }
+            }
+        }
+    }
+    if (!one_event) return;   // (uniform in the block)
+    __syncthreads();
+    if (threadIdx.x < n_win * 4 && acc[threadIdx.x])
+        atomicAdd(&out_t[(size_t)e0 * n_win * 4 + threadIdx.x], (unsigned long long)acc[threadIdx.x]);
+}
+
 // ----------------------------------------------------------------- cluster table
-// the rows of tracking_metric_df of one labelling, one per label (cluster_size 0: no such cluster)
-__global__ __launch_bounds__(kTpb) void tm_table_kernel(const int64_t *__restrict__ pid, int64_t n, Ws w,
+// the rows of tracking_metric_df of one labelling, one per cluster slot (cluster_size 0: no such cluster); BATCH: the
+// slot is the event's first row + the local label, the majority particle one of the event
+template <bool BATCH>
+__global__ __launch_bounds__(kTpb) void tm_table_kernel(const int64_t *__restrict__ pid, int64_t n, Events ev, Ws w,
                                                         int64_t *__restrict__ cluster_size,
                                                         int64_t *__restrict__ maj_hits, int64_t *__restrict__ maj_pid,
                                                         int64_t *__restrict__ maj_pid_hits, float *__restrict__ maj_pt,
@@ -473,7 +545,8 @@ __global__ __launch_bounds__(kTpb) void tm_table_kernel(const int64_t *__restric
         Majority c{};
         float mean[kProps] = {0.f, 0.f, 0.f};
         if (w.csize[lab]) {
-            c = majority_of(pid, n, w, 0, lab);
+            int e;
+            c = majority_of<BATCH>(pid, n, ev, w, 0, lab, e);
             for (int k = 0; k < kProps; ++k) mean[k] = particle_mean(w, k, c.slot);
         }
         cluster_size[lab] = (int64_t)c.size;
@@ -575,6 +648,77 @@ int tracking_metrics(const int64_t *labels, int32_t n_trials, const int64_t *par
     return check_launch("tracking_metrics: clusters");
 }
 
+// gnntrk_tracking_metrics_windows (BATCH = false, ev.n = 1) and gnntrk_tracking_metrics_windows_batched
+template <bool BATCH>
+int tracking_metrics_windows(const int64_t *labels, int32_t n_trials, const int64_t *particle_id, const float *pt,
+                             const float *eta, const float *reconstructable, int64_t n, Events ev, const float *windows,
+                             int32_t n_win, int32_t predicted_count_thld, int64_t *out, void *workspace,
+                             size_t workspace_bytes, hipStream_t stream) {
+    char msg[160];
+    int rc = check_count_i30("tracking_metrics_windows", "hit", n);
+    if (rc) return rc;
+    if (n_win < 1 || n_win > kMaxWin) {
+        snprintf(msg, sizeof(msg), "tracking_metrics_windows: n_win = %d, expected 1..%d", (int)n_win, kMaxWin);
+        return fail(GNNTRK_EINVAL, msg);
+    }
+    if (!windows) return fail(GNNTRK_EINVAL, "tracking_metrics_windows: NULL windows");
+    if (!out) return fail(GNNTRK_EINVAL, "tracking_metrics_windows: NULL output");
+    if ((rc = check_hits("tracking_metrics_windows", n, n_trials, labels, particle_id, pt, eta, reconstructable,
+                         workspace, workspace_bytes)))
+        return rc;
+    WinSel sel{};
+    sel.win.n = n_win;
+    for (int j = 0; j < n_win; ++j)
+        for (int k = 0; k < 4; ++k) sel.win.v[j][k] = windows[4 * j + k];
+    const size_t n_ev = (size_t)ev.n;   // (one event: 1)
+    const size_t n_out = n_ev * n_win + (size_t)n_trials * n_ev * n_win * 4 + 1;
+    rc = check_hip(hipMemsetAsync(out, 0, sizeof(int64_t) * n_out, stream), "tracking_metrics_windows: clear");
+    if (rc || n == 0) return rc;
+    const Ws w = make_ws(workspace, n, n_trials);
+    auto *o = reinterpret_cast<unsigned long long *>(out);
+    if ((rc = fill_tables<WinSel, BATCH>("tracking_metrics_windows", labels, n_trials, particle_id, pt, eta,
+                                         reconstructable, n, sel, w, o + n_out - 1, stream, ev)))
+        return rc;
+    if (BATCH) {
+        hipLaunchKernelGGL(tmw_particle_batched_kernel, dim3(blocks_for((int64_t)w.S, 4)), dim3(kTpb), 0, stream,
+                           sel.win, w, ev, o);
+        hipLaunchKernelGGL(tmw_clusters_batched_kernel, dim3((unsigned)ceil_div(n, kTpb), (unsigned)n_trials),
+                           dim3(kTpb), 0, stream, particle_id, n, n_win, predicted_count_thld, ev, w, o + n_ev * n_win);
+        return check_launch("tracking_metrics_windows: clusters");
+    }
+    hipLaunchKernelGGL(tmw_particle_kernel, dim3(blocks_for((int64_t)w.S, 4)), dim3(kTpb), 0, stream, sel.win, w, o);
+    const int gx = (int)((blocks_for(n, 8) + n_trials - 1) / n_trials);
+    hipLaunchKernelGGL(tmw_clusters_kernel, dim3(gx < 1 ? 1 : gx, (unsigned)n_trials), dim3(kTpb), 0, stream,
+                       particle_id, n, n_win, predicted_count_thld, w, o + n_win);
+    return check_launch("tracking_metrics_windows: clusters");
+}
+
+// gnntrk_cluster_table (BATCH = false) and gnntrk_cluster_table_batched
+template <bool BATCH>
+int cluster_table(const int64_t *labels, const int64_t *particle_id, const float *pt, const float *eta,
+                  const float *reconstructable, int64_t n, Events ev, int64_t *cluster_size, int64_t *maj_hits,
+                  int64_t *maj_pid, int64_t *maj_pid_hits, float *maj_pt, float *maj_eta, float *maj_reconstructable,
+                  int64_t *n_bad, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+    int rc = check_count_i30("cluster_table", "hit", n);
+    if (rc) return rc;
+    if (!n_bad) return fail(GNNTRK_EINVAL, "cluster_table: NULL n_bad");
+    if (n > 0 &&
+        (!cluster_size || !maj_hits || !maj_pid || !maj_pid_hits || !maj_pt || !maj_eta || !maj_reconstructable))
+        return fail(GNNTRK_EINVAL, "cluster_table: NULL output column");
+    if ((rc = check_hits("cluster_table", n, 1, labels, particle_id, pt, eta, reconstructable, workspace, workspace_bytes)))
+        return rc;
+    rc = check_hip(hipMemsetAsync(n_bad, 0, sizeof(int64_t), stream), "cluster_table: clear");
+    if (rc || n == 0) return rc;
+    const Ws w = make_ws(workspace, n, 1);
+    // (no windows: the hits leave no mask, only the particle table and its sums are wanted)
+    if ((rc = fill_tables<WinSel, BATCH>("cluster_table", labels, 1, particle_id, pt, eta, reconstructable, n, WinSel{},
+                                         w, reinterpret_cast<unsigned long long *>(n_bad), stream, ev)))
+        return rc;
+    hipLaunchKernelGGL(tm_table_kernel<BATCH>, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, particle_id, n, ev, w,
+                       cluster_size, maj_hits, maj_pid, maj_pid_hits, maj_pt, maj_eta, maj_reconstructable);
+    return check_launch("cluster_table: rows");
+}
+
 }  // namespace
 }  // namespace gnntrk
 
@@ -615,63 +759,42 @@ int gnntrk_tracking_metrics_batched(const int64_t *labels, int32_t n_trials, con
 int gnntrk_tracking_metrics_windows(const int64_t *labels, int32_t n_trials, const int64_t *particle_id,
                                     const float *pt, const float *eta, const float *reconstructable, int64_t n,
                                     const float *windows, int32_t n_win, int32_t predicted_count_thld, int64_t *out,
-                                    void *workspace, size_t workspace_bytes, void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    char msg[160];
-    int rc = check_count_i30("tracking_metrics_windows", "hit", n);
-    if (rc) return rc;
-    if (n_win < 1 || n_win > kMaxWin) {
-        snprintf(msg, sizeof(msg), "tracking_metrics_windows: n_win = %d, expected 1..%d", (int)n_win, kMaxWin);
-        return fail(GNNTRK_EINVAL, msg);
-    }
-    if (!windows) return fail(GNNTRK_EINVAL, "tracking_metrics_windows: NULL windows");
-    if (!out) return fail(GNNTRK_EINVAL, "tracking_metrics_windows: NULL output");
-    if ((rc = check_hits("tracking_metrics_windows", n, n_trials, labels, particle_id, pt, eta, reconstructable,
-                         workspace, workspace_bytes)))
-        return rc;
-    WinSel sel{};
-    sel.win.n = n_win;
-    for (int j = 0; j < n_win; ++j)
-        for (int k = 0; k < 4; ++k) sel.win.v[j][k] = windows[4 * j + k];
-    const size_t n_out = (size_t)n_win + (size_t)n_trials * n_win * 4 + 1;
-    rc = check_hip(hipMemsetAsync(out, 0, sizeof(int64_t) * n_out, stream), "tracking_metrics_windows: clear");
-    if (rc || n == 0) return rc;
-    const Ws w = make_ws(workspace, n, n_trials);
-    auto *o = reinterpret_cast<unsigned long long *>(out);
-    if ((rc = fill_tables("tracking_metrics_windows", labels, n_trials, particle_id, pt, eta, reconstructable, n, sel, w,
-                          o + n_out - 1, stream)))
-        return rc;
-    hipLaunchKernelGGL(tmw_particle_kernel, dim3(blocks_for((int64_t)w.S, 4)), dim3(kTpb), 0, stream, sel.win, w, o);
-    const int gx = (int)((blocks_for(n, 8) + n_trials - 1) / n_trials);
-    hipLaunchKernelGGL(tmw_clusters_kernel, dim3(gx < 1 ? 1 : gx, (unsigned)n_trials), dim3(kTpb), 0, stream,
-                       particle_id, n, n_win, predicted_count_thld, w, o + n_win);
-    return check_launch("tracking_metrics_windows: clusters");
+                                    void *workspace, size_t workspace_bytes, void *stream) {
+    return tracking_metrics_windows<false>(labels, n_trials, particle_id, pt, eta, reconstructable, n,
+                                           Events{nullptr, 1}, windows, n_win, predicted_count_thld, out, workspace,
+                                           workspace_bytes, (hipStream_t)stream);
+}
+
+int gnntrk_tracking_metrics_windows_batched(const int64_t *labels, int32_t n_trials, const int64_t *particle_id,
+                                            const float *pt, const float *eta, const float *reconstructable, int64_t n,
+                                            const int64_t *seg_ptr, int32_t n_seg, const float *windows, int32_t n_win,
+                                            int32_t predicted_count_thld, int64_t *out, void *workspace,
+                                            size_t workspace_bytes, void *stream) {
+    if (!seg_ptr || n_seg < 1) return fail(GNNTRK_EINVAL, "tracking_metrics_windows: seg_ptr needs n_seg >= 1 events");
+    return tracking_metrics_windows<true>(labels, n_trials, particle_id, pt, eta, reconstructable, n,
+                                          Events{seg_ptr, n_seg}, windows, n_win, predicted_count_thld, out, workspace,
+                                          workspace_bytes, (hipStream_t)stream);
 }
 
 int gnntrk_cluster_table(const int64_t *labels, const int64_t *particle_id, const float *pt, const float *eta,
                          const float *reconstructable, int64_t n, int64_t *cluster_size, int64_t *maj_hits,
                          int64_t *maj_pid, int64_t *maj_pid_hits, float *maj_pt, float *maj_eta,
                          float *maj_reconstructable, int64_t *n_bad, void *workspace, size_t workspace_bytes,
-                         void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    int rc = check_count_i30("cluster_table", "hit", n);
-    if (rc) return rc;
-    if (!n_bad) return fail(GNNTRK_EINVAL, "cluster_table: NULL n_bad");
-    if (n > 0 &&
-        (!cluster_size || !maj_hits || !maj_pid || !maj_pid_hits || !maj_pt || !maj_eta || !maj_reconstructable))
-        return fail(GNNTRK_EINVAL, "cluster_table: NULL output column");
-    if ((rc = check_hits("cluster_table", n, 1, labels, particle_id, pt, eta, reconstructable, workspace, workspace_bytes)))
-        return rc;
-    rc = check_hip(hipMemsetAsync(n_bad, 0, sizeof(int64_t), stream), "cluster_table: clear");
-    if (rc || n == 0) return rc;
-    const Ws w = make_ws(workspace, n, 1);
-    // (no windows: the hits leave no mask, only the particle table and its sums are wanted)
-    if ((rc = fill_tables("cluster_table", labels, 1, particle_id, pt, eta, reconstructable, n, WinSel{}, w,
-                          reinterpret_cast<unsigned long long *>(n_bad), stream)))
-        return rc;
-    hipLaunchKernelGGL(tm_table_kernel, dim3(blocks_for(n, 8)), dim3(kTpb), 0, stream, particle_id, n, w, cluster_size,
-                       maj_hits, maj_pid, maj_pid_hits, maj_pt, maj_eta, maj_reconstructable);
-    return check_launch("cluster_table: rows");
+                         void *stream) {
+    return cluster_table<false>(labels, particle_id, pt, eta, reconstructable, n, Events{nullptr, 1}, cluster_size,
+                                maj_hits, maj_pid, maj_pid_hits, maj_pt, maj_eta, maj_reconstructable, n_bad, workspace,
+                                workspace_bytes, (hipStream_t)stream);
+}
+
+int gnntrk_cluster_table_batched(const int64_t *labels, const int64_t *particle_id, const float *pt, const float *eta,
+                                 const float *reconstructable, int64_t n, const int64_t *seg_ptr, int32_t n_seg,
+                                 int64_t *cluster_size, int64_t *maj_hits, int64_t *maj_pid, int64_t *maj_pid_hits,
+                                 float *maj_pt, float *maj_eta, float *maj_reconstructable, int64_t *n_bad,
+                                 void *workspace, size_t workspace_bytes, void *stream) {
+    if (!seg_ptr || n_seg < 1) return fail(GNNTRK_EINVAL, "cluster_table: seg_ptr needs n_seg >= 1 events");
+    return cluster_table<true>(labels, particle_id, pt, eta, reconstructable, n, Events{seg_ptr, n_seg}, cluster_size,
+                               maj_hits, maj_pid, maj_pid_hits, maj_pt, maj_eta, maj_reconstructable, n_bad, workspace,
+                               workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -351,7 +351,9 @@ class DBSCANPerformanceDetails(DBSCANHyperParamScanner):
         ``pt``, ``eta`` as device tensors) and the cluster table
         (``cluster_metrics.tracking_metric_table``: numpy columns) are kept; see ``get_results``.  As
         the reference, it neither resets on ``i_batch == 0`` nor looks at ``ec_hit_mask``.  Data of several events
-        (``per_event``): one DBSCAN for all of them, then one hit record and one cluster table per event."""
+        (``per_event``): one DBSCAN and one cluster-table call for all of them, then one hit record
+        (``cluster_metrics.HitRecord``: a dict with the same five keys that remembers its batch, so that the binned
+        metrics count the events of a batch in one call) and one cluster table per event."""
         super().__init__()
         self.save_hyperparameters()
         self._h_dfs: list[dict[str, Tensor]] = []
@@ -365,13 +367,18 @@ class DBSCANPerformanceDetails(DBSCANHyperParamScanner):
         labels = fr.cluster_device(eps=self.hparams.eps, min_pts=self.hparams.min_samples)
         dev = labels.device
         pid, pt, reco, eta = CM._hits(data.particle_id, data.pt, data.reconstructable, data.eta, dev)
-        # (several events: one DBSCAN for all, then per event its slice of the local labels - one record and one table)
-        rows = [0, int(labels.shape[0])] if ptr is None else ptr.tolist()
-        for a, b in zip(rows, rows[1:]):
-            lab, cols = labels[a:b], [v[a:b] for v in (pid, pt, reco, eta)]
-            self._h_dfs.append({"c": lab, "id": cols[0], "reconstructable": cols[2], "pt": cols[1], "eta": cols[3]})
-            # (DBSCAN's labels are in [-1, n) already: no ranking pass)
-            self._c_dfs.append(CM._table(lab.contiguous(), None, *(c.contiguous() for c in cols), 3))
+        record = {"c": labels, "id": pid, "reconstructable": reco, "pt": pt, "eta": eta}
+        # (DBSCAN's labels are in [-1, n) - several events: in [-1, n_e) - already: no ranking pass)
+        if ptr is None:
+            self._h_dfs.append(record)
+            self._c_dfs.append(CM._table(labels, None, pid, pt, reco, eta, 3))
+            return
+        # several events: one DBSCAN and one table call for all, then per event its slice of the hits (a record that
+        # remembers the batch: tracking_metrics_vs_pt / _vs_eta count the events of a batch in one call) and its table
+        ptr = ptr.to(device=dev, dtype=torch.int64).contiguous()
+        batch = CM.EventBatch(record, ptr)
+        self._h_dfs.extend(batch.records)
+        self._c_dfs.extend(CM._table_batched(labels, pid, pt, reco, eta, ptr, batch.sizes, 3))
 
     def get_results(self) -> tuple[list[dict[str, Tensor]], list[dict[str, np.ndarray]]]:
         """(h_dfs, c_dfs): per batch the hit record and the cluster table, as

@@ -1063,6 +1063,20 @@ int gnntrk_tracking_metrics_windows(const int64_t *labels, int32_t n_trials, con
                                     const float *pt, const float *eta, const float *reconstructable, int64_t n,
                                     const float *windows, int32_t n_win, int32_t predicted_count_thld, int64_t *out,
                                     void *workspace, size_t workspace_bytes, void *stream);
+/* The window counts of every event of a collated batch from one launch sequence; events, particles (event, id),
+ * local labels and the bad-label count as gnntrk_tracking_metrics_batched, windows as above.  The values of event s
+ * are those of gnntrk_tracking_metrics_windows on its rows alone.
+ * out (int64, n_seg * n_win + n_trials * n_seg * n_win * 4 + 1 values, overwritten):
+ *   [s * n_win + j]                                        n_particles of event s in window j;
+ *   [n_seg * n_win + ((t * n_seg + s) * n_win + j) * 4 + k]  trial t, event s, window j: k as above;
+ *   [last]                                                 number of labels >= their event's hits.
+ * workspace: gnntrk_tracking_metrics_windows_workspace_bytes(n, n_trials).  No host synchronisation.  Errors as
+ * above; GNNTRK_EINVAL also for NULL seg_ptr or n_seg < 1. */
+int gnntrk_tracking_metrics_windows_batched(const int64_t *labels, int32_t n_trials, const int64_t *particle_id,
+                                            const float *pt, const float *eta, const float *reconstructable, int64_t n,
+                                            const int64_t *seg_ptr, int32_t n_seg, const float *windows, int32_t n_win,
+                                            int32_t predicted_count_thld, int64_t *out, void *workspace,
+                                            size_t workspace_bytes, void *stream);
 
 /* The per-cluster rows of tracking_metric_df (metrics/cluster_metrics.py:76-149) of ONE labelling
  * (labels [n], as above) as dense columns of length n indexed by label (device pointers):
@@ -1079,6 +1093,17 @@ int gnntrk_cluster_table(const int64_t *labels, const int64_t *particle_id, cons
                          int64_t *maj_pid, int64_t *maj_pid_hits, float *maj_pt, float *maj_eta,
                          float *maj_reconstructable, int64_t *n_bad, void *workspace, size_t workspace_bytes,
                          void *stream);
+/* The same rows for every event of a collated batch from one launch sequence (events, particles and local labels
+ * as gnntrk_tracking_metrics_batched): the seven columns keep their length n, row seg_ptr[s] + l is the cluster
+ * with the local label l of event s; its majority particle is one of event s (tie: the smallest id of the event).
+ * n_bad counts the labels >= their event's number of hits.  The rows of event s are those of gnntrk_cluster_table
+ * on its rows alone.  workspace: gnntrk_cluster_table_workspace_bytes(n).  No host synchronisation.  Errors as
+ * above; GNNTRK_EINVAL also for NULL seg_ptr or n_seg < 1. */
+int gnntrk_cluster_table_batched(const int64_t *labels, const int64_t *particle_id, const float *pt, const float *eta,
+                                 const float *reconstructable, int64_t n, const int64_t *seg_ptr, int32_t n_seg,
+                                 int64_t *cluster_size, int64_t *maj_hits, int64_t *maj_pid, int64_t *maj_pid_hits,
+                                 float *maj_pt, float *maj_eta, float *maj_reconstructable, int64_t *n_bad,
+                                 void *workspace, size_t workspace_bytes, void *stream);
 
 /* The size spectra behind the clustering scores of metrics/cluster_metrics.py:400-456 (common_metrics'
  * v_measure, homogeneity, completeness, adjusted_rand and fowlkes_mallows, which the reference hands to
@@ -1108,6 +1133,22 @@ int64_t gnntrk_cluster_spectra_capacity(int64_t n);
 size_t gnntrk_cluster_spectra_workspace_bytes(int64_t n, int32_t n_trials);
 int gnntrk_cluster_spectra(const int64_t *labels, int32_t n_trials, const int64_t *truth, int64_t n, int64_t *out,
                            void *workspace, size_t workspace_bytes, void *stream);
+/* The spectra of every event of a collated batch from one launch sequence: rows [seg_ptr[s], seg_ptr[s+1]) are
+ * event s (n_seg >= 1 events, seg_ptr on the device).  A class is the pair (event, truth id), a cluster the pair
+ * (event, label) - labels stay categories of any int64 value, so -1 of two events is two clusters -, a cell
+ * belongs to the event of its class.  The spectra of event s are those of gnntrk_cluster_spectra on its rows alone.
+ * out (int64, (1 + 2 * n_trials) spectra as above, of 1 + 3 * cap values each, overwritten): a spectrum is ONE
+ * pooled list for all events, [0] = d, then d triples (event, size, multiplicity) in NO particular order, every
+ * (event, size) once; the values behind them are 0.
+ * cap = gnntrk_cluster_spectra_batched_capacity(n, n_seg) = n_seg * (D(ceil(n / n_seg)) + 1), 0 for n <= 0.  It
+ * bounds the entries of all events together, sum_s D(n_s): D(x) <= f(x) = (sqrt(8 x + 1) - 1) / 2, f is concave
+ * with f(0) = 0, so sum_s D(n_s) <= sum_s f(n_s) <= n_seg f(n / n_seg) < n_seg (D(ceil(n / n_seg)) + 1).
+ * workspace: gnntrk_cluster_spectra_workspace_bytes(n, n_trials).  No host synchronisation.  Errors as above;
+ * GNNTRK_EINVAL also for NULL seg_ptr or n_seg < 1. */
+int64_t gnntrk_cluster_spectra_batched_capacity(int64_t n, int32_t n_seg);
+int gnntrk_cluster_spectra_batched(const int64_t *labels, int32_t n_trials, const int64_t *truth, int64_t n,
+                                   const int64_t *seg_ptr, int32_t n_seg, int64_t *out, void *workspace,
+                                   size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------ k-scan (metric learning)
  * The device part of GraphConstructionKNNScanner (graph_construction/k_scanner.py:203-285) beyond the

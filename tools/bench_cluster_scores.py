@@ -5,7 +5,11 @@ host copy for all trials) against the host: sklearn's five functions per trial, 
 common_metrics call them, when sklearn is importable, otherwise the numpy restatement of
 tests/cluster_scores_ref.py (the output says which).
 
-Usage:  python tools/bench_cluster_scores.py [--hits 200000] [--trials 10] [--reps 10] [--host-reps 1]
+With ``--events B`` it measures a collated batch instead: B events of ``--hits`` hits each (default 6000), scored per
+event by one ``clustering_scores_trials(..., ptr=ptr)`` call, against the loop of one call per event on the event's rows,
+alternating the two in one process.
+
+Usage:  python tools/bench_cluster_scores.py [--hits 200000] [--trials 10] [--reps 10] [--host-reps 1] [--events B]
 Prints one JSON line.
 """
 
@@ -43,13 +47,54 @@ def event(seed, n, n_trials, n_particles=6000):
     return truth, labels
 
 
+def events_main(args) -> None:
+    from gnn_tracking_amd import cluster_metrics as CM
+
+    dev = torch.device("cuda")
+    n = args.hits if args.hits != 200_000 else 6000
+    parts = [event(21 + i, n, args.trials, n_particles=max(8, n // 10)) for i in range(args.events)]
+    truth_d = torch.from_numpy(np.concatenate([p[0] for p in parts])).to(dev)
+    labels_d = torch.from_numpy(np.concatenate([p[1] for p in parts], axis=1)).to(dev)
+    ptr = torch.arange(args.events + 1, device=dev) * n
+    rows = ptr.tolist()
+
+    def batched():
+        return CM.clustering_scores_trials(labels_d, truth=truth_d, ptr=ptr)
+
+    def per_event():
+        per = [CM.clustering_scores_trials(labels_d[:, a:b], truth=truth_d[a:b]) for a, b in zip(rows, rows[1:])]
+        return [[per[e][t] for e in range(args.events)] for t in range(args.trials)]
+
+    ms = {"batched": [], "per_event": []}
+    fns = {"batched": batched, "per_event": per_event}
+    for rep in range(args.reps + 2):
+        got = {}
+        for name in (("batched", "per_event") if rep % 2 else ("per_event", "batched")):   # (alternating)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got[name] = fns[name]()
+            torch.cuda.synchronize()
+            if rep >= 2:   # (two repetitions warm up)
+                ms[name].append((time.perf_counter() - t0) * 1e3)
+        assert got["batched"] == got["per_event"], "the batched call and the per-event loop differ"
+    line = {"bench": "cluster_scores_events", "events": args.events, "hits_per_event": n, "trials": args.trials,
+            "device": torch.cuda.get_device_name(dev), "reps": args.reps,
+            "v_measure_first_last": [round(got["batched"][0][0]["v_measure"], 6), round(got["batched"][-1][-1]["v_measure"], 6)]}
+    for name, v in ms.items():
+        line[name + "_ms"] = {"median": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}
+    print(json.dumps(line))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--hits", type=int, default=200_000)
     ap.add_argument("--trials", type=int, default=10)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--host-reps", type=int, default=1)
+    ap.add_argument("--events", type=int, default=0, help="a collated batch of this many events of --hits hits (default 6000)")
     args = ap.parse_args()
+    if args.events:
+        return events_main(args)
     from gnn_tracking_amd import cluster_metrics as CM
 
     dev = torch.device("cuda")

@@ -5,7 +5,12 @@ the reference's algorithm on the host (a pandas value_counts / groupby chain and
 when pandas is importable, otherwise the numpy restatement of tests/tracking_binned_ref.py; the
 output says which).
 
-Usage:  python tools/bench_tracking_binned.py [--hits 200000] [--bins 20] [--reps 10] [--host-reps 1]
+With ``--events B`` it measures a collated batch instead: B events of ``--hits`` hits each (default 6000) through
+``DBSCANPerformanceDetails.__call__`` and ``tracking_metrics_vs_pt`` - one DBSCAN, one batched table call and one batched
+windows call per 32 bins for all events - against the per-event loop that preceded the batched entries (one DBSCAN, then
+per event a table call and a windows call with a host copy each), alternating the two in one process.
+
+Usage:  python tools/bench_tracking_binned.py [--hits 200000] [--bins 20] [--reps 10] [--host-reps 1] [--events B]
 Prints one JSON line.
 """
 
@@ -70,13 +75,95 @@ def pandas_binned(pd, labels, pid, pt, eta, reco, edges, thld=3, max_eta=4.0):
     return out
 
 
+class PerEventDetails:
+    """``DBSCANPerformanceDetails.__call__`` as it was before the batched entries: one DBSCAN for the batch, then per event
+    a plain hit record and one ``gnntrk_cluster_table`` launch sequence with its host copy."""
+
+    def __init__(self, eps, min_samples):
+        self.eps, self.min_samples, self.h_dfs, self.c_dfs = eps, min_samples, [], []
+
+    def __call__(self, data, out, i_batch):
+        from gnn_tracking_amd import cluster_metrics as CM
+        from gnn_tracking_amd.postprocessing import DBSCANFastRescan
+
+        fr = DBSCANFastRescan(out["H"].detach(), max_eps=self.eps, ptr=data.ptr)
+        labels = fr.cluster_device(eps=self.eps, min_pts=self.min_samples)
+        pid, pt, reco, eta = CM._hits(data.particle_id, data.pt, data.reconstructable, data.eta, labels.device)
+        rows = data.ptr.tolist()
+        for a, b in zip(rows, rows[1:]):
+            lab, cols = labels[a:b], [v[a:b] for v in (pid, pt, reco, eta)]
+            self.h_dfs.append({"c": lab, "id": cols[0], "reconstructable": cols[2], "pt": cols[1], "eta": cols[3]})
+            self.c_dfs.append(CM._table(lab.contiguous(), None, *(c.contiguous() for c in cols), 3))
+
+
+def spread(ms):
+    return {"median": round(statistics.median(ms), 3), "min": round(min(ms), 3), "max": round(max(ms), 3)}
+
+
+def events_main(args) -> None:
+    import gnn_tracking_amd as G
+    from gnn_tracking_amd import cluster_metrics as CM
+    from gnn_tracking_amd import synthetic
+    from gnn_tracking_amd.postprocessing import DBSCANPerformanceDetails
+
+    dev = torch.device("cuda")
+    n = args.hits if args.hits != 200_000 else 6000
+    events = []
+    for i in range(args.events):
+        ev = synthetic.make_pileup_event(900 + i, n, 8, n_particles=max(8, n // 10), n_clusters=max(4, n // 30))
+        events.append(G.Data(x=ev["x"].to(dev), edge_index=torch.zeros(2, 0, dtype=torch.long, device=dev),
+                             **{k: ev[k].to(dev) for k in ("particle_id", "pt", "eta", "reconstructable")}))
+    data = G.collate(events)
+    edges = np.concatenate([np.linspace(0.0, 3.0, args.bins), [np.inf]]).tolist()
+    eps, min_samples = 0.25, 2
+
+    def run(make):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        sc = make(eps, min_samples)
+        sc(data, {"H": data.x}, 0)
+        h_dfs, c_dfs = (sc.h_dfs, sc.c_dfs) if isinstance(sc, PerEventDetails) else sc.get_results()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        rows = CM.tracking_metrics_vs_pt(h_dfs, c_dfs, edges)
+        torch.cuda.synchronize()
+        return (t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3, rows, c_dfs
+
+    ms = {"batched": ([], []), "per_event": ([], [])}
+    kinds = {"batched": DBSCANPerformanceDetails, "per_event": PerEventDetails}
+    for rep in range(args.reps + 2):
+        got = {}
+        for name in (("batched", "per_event") if rep % 2 else ("per_event", "batched")):   # (alternating)
+            call_ms, vs_ms, rows, c_dfs = run(kinds[name])
+            got[name] = (rows, c_dfs)
+            if rep >= 2:   # (two repetitions warm up)
+                ms[name][0].append(call_ms)
+                ms[name][1].append(vs_ms)
+        same = all(a == b or (a != a and b != b) for ra, rb in zip(got["batched"][0], got["per_event"][0])
+                   for a, b in zip(ra.values(), rb.values()))
+        same = same and all(np.array_equal(ta[k], tb[k], equal_nan=ta[k].dtype.kind == "f")
+                            for ta, tb in zip(got["batched"][1], got["per_event"][1]) for k in ta)
+        assert same, "the batched path and the per-event loop differ"
+    line = {"bench": "tracking_binned_events", "events": args.events, "hits_per_event": n, "bins": len(edges) - 1,
+            "clusters": int(sum(len(t["c"]) for t in got["batched"][1])), "device": torch.cuda.get_device_name(dev),
+            "reps": args.reps}
+    for name, (call_ms, vs_ms) in ms.items():
+        line[name + "_call_ms"] = spread(call_ms)
+        line[name + "_vs_pt_ms"] = spread(vs_ms)
+        line[name + "_total_ms"] = spread([a + b for a, b in zip(call_ms, vs_ms)])
+    print(json.dumps(line))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--hits", type=int, default=200_000)
     ap.add_argument("--bins", type=int, default=20)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--host-reps", type=int, default=1)
+    ap.add_argument("--events", type=int, default=0, help="a collated batch of this many events of --hits hits (default 6000)")
     args = ap.parse_args()
+    if args.events:
+        return events_main(args)
     from gnn_tracking_amd import cluster_metrics as CM
 
     dev = torch.device("cuda")
