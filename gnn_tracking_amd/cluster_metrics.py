@@ -31,11 +31,15 @@ index from those few hundred integers (``clustering_scores_trials``: one C call 
 trials).  For these scores labels and truth ids are categories of any integer value, as for sklearn: the
 noise label -1 is ONE cluster and truth id 0 an ordinary class, unlike in the tracking metrics.
 
-A collated batch of several events (``ptr``: [B + 1] row offsets) is that many independent problems from one C call:
-``tracking_metrics_trials``, ``tracking_metric_table``, ``clustering_spectra`` and ``clustering_scores_trials`` take
-``ptr=`` and return per-event results (labels local to the event for the tracking entries), and
-``tracking_metrics_vs_pt`` / ``_vs_eta`` count the hit records that ``DBSCANPerformanceDetails`` sliced from one batch
-(``HitRecord``) in one call per 32 bins.  ``common_metrics`` and ``count_hits_per_cluster`` stay one event per call.
+A collated batch of several events is that many independent problems from one C call.  The rule, once for this module:
+``ptr=`` is the [B + 1] row offsets of the events (``events.py`` derives and checks them); ``None`` or one event is
+today's single-event call with today's return type, more than one event calls the ``_batched`` C entry and returns
+per-event results (``[trial][event]``, or a list of tables).  The host functions below exist once and treat one event as
+B = 1 of the batched layouts; the only thing ``ptr`` selects is the C entry.  Labels: the public single-event calls
+accept any integers and rank them with ``torch.unique``; with ``ptr`` labels are local to their event, in ``[-1, n_e)``,
+as ``DBSCANFastRescan(..., ptr=ptr)`` gives them.  ``tracking_metrics_vs_pt`` / ``_vs_eta`` count the hit records that
+``DBSCANPerformanceDetails`` sliced from one batch (``HitRecord``) in one call per 32 bins.  ``common_metrics`` and
+``count_hits_per_cluster`` stay one event per call.
 """
 
 from __future__ import annotations
@@ -49,7 +53,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import _capi, ops
+from . import _capi, events, ops
 from .metrics import denote_pt
 
 __all__ = ["TrackingMetrics", "tracking_metrics", "tracking_metrics_data", "tracking_metrics_trials",
@@ -172,25 +176,28 @@ def _counts(labels: Tensor, truth: Tensor, pts: Tensor, reconstructable: Tensor,
     return out
 
 
-def _results(host: np.ndarray, n_trials: int, pts: list, idx: list[int]) -> list[dict[float, TrackingMetrics]]:
-    nc = (host.size - 1) // (1 + 4 * n_trials)
+def _count_arrays(host: np.ndarray, n_trials: int, n_ev: int, per_event: bool) -> tuple[np.ndarray, np.ndarray]:
+    """The host copy of ``_counts``' output as (particles [B, n_cuts], cluster counts [T, B, n_cuts, 4]) - one event is
+    B = 1 of the batched layout; refuses a bad-label count (the last value) that is not 0."""
     if host[-1] != 0:
-        raise ValueError(f"tracking_metrics: {int(host[-1])} labels are >= the number of hits")
-    n_part = host[:nc]
-    cnt = host[nc:nc + n_trials * nc * 4].reshape(n_trials, nc, 4)
-    return [{pt: _from_counts(int(n_part[j]), cnt[t, j]) for pt, j in zip(pts, idx)} for t in range(n_trials)]
+        raise ValueError(f"tracking_metrics: {int(host[-1])} labels are >= the number of hits"
+                         + (" of their event" if per_event else ""))
+    nc = (host.size - 1) // (n_ev * (1 + 4 * n_trials))
+    return host[:n_ev * nc].reshape(n_ev, nc), host[n_ev * nc:-1].reshape(n_trials, n_ev, nc, 4)
 
 
-def _event_sizes(ptr, n: int, who: str) -> list[int] | None:
-    """The hits per event of ``ptr`` ([B + 1] row offsets, checked on the host: ascending from 0 to ``n``); None for
-    ``ptr=None`` or one event - today's call."""
-    if ptr is None or int(np.shape(ptr)[0]) <= 2:
-        return None
-    host = torch.as_tensor(ptr).cpu().long()
-    sizes = torch.diff(host).tolist()
-    if int(host[0]) != 0 or int(host[-1]) != n or min(sizes) < 0:
-        raise ValueError(f"{who}: ptr must ascend from 0 to the number of hits")
-    return sizes
+def _results(host: np.ndarray, n_trials: int, sizes: list[int], pts: list, idx: list[int], per_event: bool) -> list[list[dict]]:
+    """``[trial][event] -> flatten_track_metrics(...)`` of ``_counts``' output for events of ``sizes`` hits; an event
+    without hits gets the NaN results of ``n == 0``"""
+    n_part, cnt = _count_arrays(host, n_trials, len(sizes), per_event)
+    nan = flatten_track_metrics({pt: dict(_tracking_metrics_nan_results) for pt in pts})
+    # (flatten_track_metrics with the flat names made once per call, not once per trial, event and value)
+    cols = {pt: (j, {k: denote_pt(k, pt) for k in TrackingMetrics.__annotations__}) for pt, j in zip(pts, idx)}
+
+    def flat(t, e):
+        return {names[k]: v for j, names in cols.values() for k, v in _from_counts(int(n_part[e, j]), cnt[t, e, j]).items()}
+
+    return [[flat(t, e) if sizes[e] else dict(nan) for e in range(len(sizes))] for t in range(n_trials)]
 
 
 def _hits(truth, pts, reconstructable, eta, device):
@@ -210,32 +217,35 @@ def tracking_metrics(*, truth, predicted, pts, reconstructable, eta, pt_thlds: I
     if n == 0:
         return {pt: dict(_tracking_metrics_nan_results) for pt in pts_l}
     dev = _device_of(truth, predicted, pts, reconstructable, eta)
-    lab = _on(predicted, torch.int64, dev)
-    # (labels may be any integers: negatives -> -1, the rest -> dense ranks below n; no host sync)
-    _, inv = torch.unique(lab, return_inverse=True)
-    lab = torch.where(lab < 0, torch.full_like(lab, -1), inv).view(1, n)
+    lab = _dense_labels(_on(predicted, torch.int64, dev))[0].view(1, n)
     t, p, r, e = _hits(truth, pts, reconstructable, eta, dev)
     out = _counts(lab, t, p, r, e, cuts, predicted_count_thld, max_eta)
-    return _results(out.cpu().numpy(), 1, pts_l, idx)[0]
+    n_part, cnt = _count_arrays(out.cpu().numpy(), 1, 1, False)
+    return {pt: _from_counts(int(n_part[0, j]), cnt[0, 0, j]) for pt, j in zip(pts_l, idx)}
 
 
-def _results_per_event(host: np.ndarray, n_trials: int, sizes: list[int], pts: list, idx: list[int]) -> list[list[dict]]:
-    """``_results`` for the output of ``gnntrk_tracking_metrics_batched``: [trial][event] -> flat dict; an event
-    without hits gets the NaN results of ``n == 0``"""
-    n_ev = len(sizes)
-    nc = (host.size - 1) // (n_ev * (1 + 4 * n_trials))
-    if host[-1] != 0:
-        raise ValueError(f"tracking_metrics: {int(host[-1])} labels are >= the number of hits of their event")
-    n_part = host[:n_ev * nc].reshape(n_ev, nc)
-    cnt = host[n_ev * nc:-1].reshape(n_trials, n_ev, nc, 4)
-    nan = flatten_track_metrics({pt: dict(_tracking_metrics_nan_results) for pt in pts})
-    # (flatten_track_metrics with the flat names made once per call, not once per trial, event and value)
-    cols = {pt: (j, {k: denote_pt(k, pt) for k in TrackingMetrics.__annotations__}) for pt, j in zip(pts, idx)}
-
-    def flat(t, e):
-        return {names[k]: v for j, names in cols.values() for k, v in _from_counts(int(n_part[e, j]), cnt[t, e, j]).items()}
-
-    return [[flat(t, e) if sizes[e] else dict(nan) for e in range(n_ev)] for t in range(n_trials)]
+def _metrics_per_event(labels, *, truth, pts, reconstructable, eta, pt_thlds, predicted_count_thld, max_eta,
+                       ptr) -> list[list[dict]]:
+    """``tracking_metrics_trials`` as ``[trial][event] -> flat dict`` whatever ``ptr`` is: one event is B = 1"""
+    who = "tracking_metrics_trials"
+    if not torch.is_tensor(labels):
+        labels = torch.as_tensor(np.asarray(labels))
+    if labels.dim() != 2:
+        raise ValueError(f"{who}: labels must be [n_trials, n]")
+    n_trials, n = int(labels.shape[0]), int(labels.shape[1])
+    pts_l, cuts, idx = _cut_plan(pt_thlds)
+    ptr = events.event_ptr(ptr=ptr)
+    sizes = events.event_sizes(ptr, n, who) or [n]
+    if n == 0 or n_trials == 0:
+        nan = flatten_track_metrics({pt: dict(_tracking_metrics_nan_results) for pt in pts_l})
+        return [[dict(nan) for _ in sizes] for _ in range(n_trials)]
+    dev = _device_of(labels, truth, pts, reconstructable, eta)
+    lab = _on(labels, torch.int64, dev)
+    t, p, r, e = _hits(truth, pts, reconstructable, eta, dev)
+    if int(t.shape[0]) != n:
+        raise ValueError(f"{who}: labels and truth differ in the number of hits")
+    out = _counts(lab, t, p, r, e, cuts, predicted_count_thld, max_eta, None if ptr is None else _on(ptr, torch.int64, dev))
+    return _results(out.cpu().numpy(), n_trials, sizes, pts_l, idx, ptr is not None)
 
 
 def tracking_metrics_trials(labels, *, truth, pts, reconstructable, eta, pt_thlds: Iterable[float] = (0.0, 0.5, 0.9, 1.5),
@@ -244,30 +254,11 @@ def tracking_metrics_trials(labels, *, truth, pts, reconstructable, eta, pt_thld
     [-1, n) as DBSCAN gives them; any negative value is noise) from one C call and one host copy: per
     trial the flattened dict of ``flatten_track_metrics(tracking_metrics(...))``.
 
-    ``ptr`` ([B + 1] row offsets of the events of a collated batch, more than one event): every event on its own -
-    particles are (event, id) pairs and labels local to the event, in ``[-1, n_e)`` as
-    ``DBSCANFastRescan(..., ptr=ptr)`` gives them - still from one C call and one host copy; the result is
-    ``[trial][event] -> flat dict``, each what the event's rows alone give."""
-    if not torch.is_tensor(labels):
-        labels = torch.as_tensor(np.asarray(labels))
-    if labels.dim() != 2:
-        raise ValueError("tracking_metrics_trials: labels must be [n_trials, n]")
-    n_trials, n = int(labels.shape[0]), int(labels.shape[1])
-    pts_l, cuts, idx = _cut_plan(pt_thlds)
-    sizes = _event_sizes(ptr, n, "tracking_metrics_trials")
-    if n == 0 or n_trials == 0:
-        nan = flatten_track_metrics({pt: dict(_tracking_metrics_nan_results) for pt in pts_l})
-        return [dict(nan) if sizes is None else [dict(nan) for _ in sizes] for _ in range(n_trials)]
-    dev = _device_of(labels, truth, pts, reconstructable, eta)
-    lab = _on(labels, torch.int64, dev)
-    t, p, r, e = _hits(truth, pts, reconstructable, eta, dev)
-    if int(t.shape[0]) != n:
-        raise ValueError("tracking_metrics_trials: labels and truth differ in the number of hits")
-    if sizes is not None:
-        out = _counts(lab, t, p, r, e, cuts, predicted_count_thld, max_eta, _on(ptr, torch.int64, dev))
-        return _results_per_event(out.cpu().numpy(), n_trials, sizes, pts_l, idx)
-    out = _counts(lab, t, p, r, e, cuts, predicted_count_thld, max_eta)
-    return [flatten_track_metrics(m) for m in _results(out.cpu().numpy(), n_trials, pts_l, idx)]
+    ``ptr`` (the events of a collated batch, module docstring): particles are (event, id) pairs and labels local to the
+    event, as ``DBSCANFastRescan(..., ptr=ptr)`` gives them; the result is ``[trial][event] -> flat dict``."""
+    res = _metrics_per_event(labels, truth=truth, pts=pts, reconstructable=reconstructable, eta=eta, pt_thlds=pt_thlds,
+                             predicted_count_thld=predicted_count_thld, max_eta=max_eta, ptr=ptr)
+    return res if events.event_ptr(ptr=ptr) is not None else [r[0] for r in res]
 
 
 def tracking_metrics_data(data, labels, pt_thlds: Iterable[float], predicted_count_thld=3,
@@ -290,25 +281,42 @@ def _dense_labels(lab: Tensor) -> tuple[Tensor, Tensor]:
     return torch.where(lab < 0, torch.full_like(lab, -1), inv), uniq
 
 
-def _table(lab: Tensor, uniq: Tensor | None, t: Tensor, p: Tensor, r: Tensor, e: Tensor,
-           predicted_count_thld: int) -> dict[str, np.ndarray]:
-    """``gnntrk_cluster_table`` of dense labels [n] in [-1, n), its rows with a cluster selected on the
-    device, one host copy; ``uniq``: the label value of every dense label (None: itself)."""
+def _table(lab: Tensor, uniq: Tensor | None, t: Tensor, p: Tensor, r: Tensor, e: Tensor, predicted_count_thld: int,
+           ptr: Tensor | None = None, sizes: list[int] | None = None):
+    """``gnntrk_cluster_table`` of dense labels [n] in [-1, n), its rows with a cluster selected on the device, one host
+    copy; ``uniq``: the label value of every dense label (None: itself).  With the events' offsets ``ptr`` (device,
+    [B + 1]) and ``sizes``: ``gnntrk_cluster_table_batched`` of local labels in [-1, n_e), still one C call and one host
+    copy, and a list with every event's rows as it gives them alone (``c``: the local label)."""
     lib = _capi.load()
-    _capi.require_device(lab, t, p, r, e)
+    _capi.require_device(lab, t, p, r, e, ptr)
     n = int(lab.shape[0])
     dev = lab.device
     ints = torch.empty((5, max(n, 1)), dtype=torch.int64, device=dev)   # size, maj_hits, maj_pid, maj_pid_hits | bad
     flts = torch.empty((3, max(n, 1)), dtype=torch.float32, device=dev)
     ws = ops._ws(lib.gnntrk_cluster_table_workspace_bytes(n), lab)
     q = ops._p
-    _capi.check(lib.gnntrk_cluster_table(q(lab), q(t), q(p), q(e), q(r), n, q(ints[0]), q(ints[1]), q(ints[2]),
-                                         q(ints[3]), q(flts[0]), q(flts[1]), q(flts[2]), q(ints[4]), q(ws), ws.numel(),
-                                         ops._stream(lab)), lib)
+    hits = (q(lab), q(t), q(p), q(e), q(r), n)
+    tail = (q(ints[0]), q(ints[1]), q(ints[2]), q(ints[3]), q(flts[0]), q(flts[1]), q(flts[2]), q(ints[4]), q(ws),
+            ws.numel(), ops._stream(lab))
+    if ptr is None:
+        _capi.check(lib.gnntrk_cluster_table(*hits, *tail), lib)
+    else:
+        _capi.check(lib.gnntrk_cluster_table_batched(*hits, q(ptr), len(sizes), *tail), lib)
+    # (cluster slots - a batch: ptr[e] + label - ascending, so grouped by event; there the slot rides along as the
+    # label column and the local label is taken on the host, where the events' rows are)
     rows = torch.nonzero(ints[0, :n] > 0).view(-1)
-    c = rows if uniq is None else uniq[rows]
-    col = _table_rows(c, rows, ints, flts, "the number of hits")
-    return _table_columns(col, predicted_count_thld)
+    col = _table_rows(rows if uniq is None else uniq[rows], rows, ints, flts,
+                      "the number of hits" + (" of their event" if ptr is not None else ""))
+    if ptr is None:
+        return _table_columns(col, predicted_count_thld)
+    starts = np.concatenate([[0], np.cumsum(sizes)])
+    cut = np.searchsorted(col[0], starts)
+    tables = []
+    for k in range(len(sizes)):
+        part = col[:, cut[k]:cut[k + 1]].copy()
+        part[0] -= starts[k]
+        tables.append(_table_columns(part, predicted_count_thld))
+    return tables
 
 
 def _table_rows(c: Tensor, rows: Tensor, ints: Tensor, flts: Tensor, limit: str) -> np.ndarray:
@@ -339,34 +347,6 @@ def _table_columns(col: np.ndarray, predicted_count_thld: int) -> dict[str, np.n
     }
 
 
-def _table_batched(lab: Tensor, t: Tensor, p: Tensor, r: Tensor, e: Tensor, ptr: Tensor, sizes: list[int],
-                   predicted_count_thld: int) -> list[dict[str, np.ndarray]]:
-    """``gnntrk_cluster_table_batched`` of local labels [n] in [-1, n_e): one C call and one host copy for all events
-    of ``ptr`` (device, [B + 1]), then per event its rows as ``_table`` gives them (``c``: the local label)."""
-    lib = _capi.load()
-    _capi.require_device(lab, t, p, r, e, ptr)
-    n = int(lab.shape[0])
-    dev = lab.device
-    ints = torch.empty((5, max(n, 1)), dtype=torch.int64, device=dev)
-    flts = torch.empty((3, max(n, 1)), dtype=torch.float32, device=dev)
-    ws = ops._ws(lib.gnntrk_cluster_table_workspace_bytes(n), lab)
-    q = ops._p
-    _capi.check(lib.gnntrk_cluster_table_batched(q(lab), q(t), q(p), q(e), q(r), n, q(ptr), len(sizes), q(ints[0]),
-                                                 q(ints[1]), q(ints[2]), q(ints[3]), q(flts[0]), q(flts[1]), q(flts[2]),
-                                                 q(ints[4]), q(ws), ws.numel(), ops._stream(lab)), lib)
-    rows = torch.nonzero(ints[0, :n] > 0).view(-1)   # (cluster slots ptr[e] + label, ascending: grouped by event)
-    # (the slot rides along as the label column; the local label is taken on the host, where the events' rows are)
-    col = _table_rows(rows, rows, ints, flts, "the number of hits of their event")
-    starts = np.concatenate([[0], np.cumsum(sizes)])
-    cut = np.searchsorted(col[0], starts)
-    tables = []
-    for k in range(len(sizes)):
-        part = col[:, cut[k]:cut[k + 1]].copy()
-        part[0] -= starts[k]
-        tables.append(_table_columns(part, predicted_count_thld))
-    return tables
-
-
 def tracking_metric_table(labels, *, truth, pts, reconstructable, eta, predicted_count_thld=3, ptr=None):
     """``tracking_metric_df`` (cluster_metrics.py:76-149) of one labelling as a dict of numpy columns:
     the index ``c`` (ascending cluster labels) and the reference's 13 columns in its order and dtypes.
@@ -374,10 +354,9 @@ def tracking_metric_table(labels, *, truth, pts, reconstructable, eta, predicted
     >= 0) have rows - the reference also lists its negative labels, as rows that are never valid - and
     ties for the majority particle go to the smallest id.
 
-    ``ptr`` ([B + 1] row offsets of the events of a collated batch, more than one event): every event on its own, as
-    ``tracking_metrics_trials`` takes it - particles are (event, id) pairs, labels local to the event, in
-    ``[-1, n_e)``.  The result is a list with one table per event, each what the event's rows alone give (``c``: the
-    local label; an event without hits has a table of no rows), from one C call and one host copy."""
+    ``ptr`` (the events of a collated batch, module docstring): a list with one table per event, each what the event's
+    rows alone give (``c``: the local label; an event without hits has a table of no rows), from one C call and one
+    host copy."""
     if not torch.is_tensor(labels):
         labels = torch.as_tensor(np.asarray(labels))
     if labels.dim() != 1:
@@ -386,51 +365,19 @@ def tracking_metric_table(labels, *, truth, pts, reconstructable, eta, predicted
     t, p, r, e = _hits(truth, pts, reconstructable, eta, dev)
     if int(t.shape[0]) != int(labels.shape[0]):
         raise ValueError("tracking_metric_table: labels and truth differ in the number of hits")
-    sizes = _event_sizes(ptr, int(labels.shape[0]), "tracking_metric_table")
-    if sizes is not None:
-        return _table_batched(_on(labels, torch.int64, dev), t, p, r, e, _on(ptr, torch.int64, dev), sizes,
-                              predicted_count_thld)
+    ptr = events.event_ptr(ptr=ptr)
+    if ptr is not None:
+        sizes = events.event_sizes(ptr, int(labels.shape[0]), "tracking_metric_table")
+        return _table(_on(labels, torch.int64, dev), None, t, p, r, e, predicted_count_thld, _on(ptr, torch.int64, dev), sizes)
     lab, uniq = _dense_labels(_on(labels, torch.int64, dev))
     return _table(lab, uniq, t, p, r, e, predicted_count_thld)
 
 
-def _window_counts(h: dict, windows: np.ndarray, predicted_count_thld: int) -> tuple[np.ndarray, np.ndarray]:
-    """One batch's hit record and fp32 windows [n, 4] -> (n_particles [n], counts [n, 4]); one
-    ``gnntrk_tracking_metrics_windows`` call and one host copy per 32 windows."""
-    lib = _capi.load()
-    dev = _device_of(h["c"], h["id"], h["pt"], h["reconstructable"], h["eta"])
-    t, p, r, e = _hits(h["id"], h["pt"], h["reconstructable"], h["eta"], dev)
-    lab, _ = _dense_labels(_on(h["c"], torch.int64, dev).view(-1))
-    n = int(lab.shape[0])
-    if int(t.shape[0]) != n:
-        raise ValueError("tracking_metrics_vs: a hit record's columns differ in length")
-    n_part = np.zeros(len(windows), dtype=np.int64)
-    counts = np.zeros((len(windows), 4), dtype=np.int64)
-    if n == 0:
-        return n_part, counts
-    _capi.require_device(lab, t, p, r, e)
-    ws = ops._ws(lib.gnntrk_tracking_metrics_windows_workspace_bytes(n, 1), lab)
-    q = ops._p
-    for lo in range(0, len(windows), _capi.TRACKING_MAX_WINDOWS):
-        win = np.ascontiguousarray(windows[lo:lo + _capi.TRACKING_MAX_WINDOWS], dtype=np.float32)
-        nw = len(win)
-        out = torch.empty(nw * 5 + 1, dtype=torch.int64, device=dev)
-        _capi.check(lib.gnntrk_tracking_metrics_windows(q(lab), 1, q(t), q(p), q(e), q(r), n,
-                                                        win.ctypes.data_as(C.POINTER(C.c_float)), nw,
-                                                        int(predicted_count_thld), q(out), q(ws), ws.numel(),
-                                                        ops._stream(lab)), lib)
-        host = out.cpu().numpy()
-        if host[-1] != 0:
-            raise ValueError(f"tracking_metrics_vs: {int(host[-1])} labels are >= the number of hits")
-        n_part[lo:lo + nw] = host[:nw]
-        counts[lo:lo + nw] = host[nw:nw * 5].reshape(nw, 4)
-    return n_part, counts
-
-
-def _window_counts_batched(h: dict, ptr, windows: np.ndarray, predicted_count_thld: int) -> tuple[np.ndarray, np.ndarray]:
-    """``_window_counts`` for the hit record of a whole collated batch with the events' offsets ``ptr`` [B + 1] (labels
-    local to the event, in [-1, n_e)) -> (n_particles [B, n], counts [B, n, 4]): one
-    ``gnntrk_tracking_metrics_windows_batched`` call and one host copy per 32 windows for ALL events."""
+def _window_counts(h: dict, windows: np.ndarray, predicted_count_thld: int, ptr=None) -> tuple[np.ndarray, np.ndarray]:
+    """A hit record and fp32 windows [n, 4] -> (n_particles [B, n], counts [B, n, 4]), B = 1 without ``ptr``: one
+    ``gnntrk_tracking_metrics_windows`` call and one host copy per 32 windows.  With ``ptr`` (more than one event) the
+    record is that of a whole collated batch and the calls are ``gnntrk_tracking_metrics_windows_batched``: still one per
+    32 windows, for ALL events."""
     lib = _capi.load()
     dev = _device_of(h["c"], h["id"], h["pt"], h["reconstructable"], h["eta"])
     t, p, r, e = _hits(h["id"], h["pt"], h["reconstructable"], h["eta"], dev)
@@ -438,29 +385,31 @@ def _window_counts_batched(h: dict, ptr, windows: np.ndarray, predicted_count_th
     n = int(lab.shape[0])
     if int(t.shape[0]) != n:
         raise ValueError("tracking_metrics_vs: a hit record's columns differ in length")
-    sizes = _event_sizes(ptr, n, "tracking_metrics_vs")
-    if sizes is None:
-        raise ValueError("tracking_metrics_vs: ptr of more than one event expected")
-    n_ev = len(sizes)
+    ptr = events.event_ptr(ptr=ptr)
+    n_ev = len(events.event_sizes(ptr, n, "tracking_metrics_vs") or [n])
     n_part = np.zeros((n_ev, len(windows)), dtype=np.int64)
     counts = np.zeros((n_ev, len(windows), 4), dtype=np.int64)
     if n == 0:
         return n_part, counts
-    seg = _on(ptr, torch.int64, dev)
-    _capi.require_device(lab, t, p, r, e, seg)
-    ws = ops._ws(lib.gnntrk_tracking_metrics_windows_workspace_bytes(n, 1), lab)
     q = ops._p
+    if ptr is None:
+        lab, _ = _dense_labels(lab)
+        entry, seg = lib.gnntrk_tracking_metrics_windows, ()
+    else:
+        ptr = _on(ptr, torch.int64, dev)
+        entry, seg = lib.gnntrk_tracking_metrics_windows_batched, (q(ptr), n_ev)
+    _capi.require_device(lab, t, p, r, e, ptr)
+    ws = ops._ws(lib.gnntrk_tracking_metrics_windows_workspace_bytes(n, 1), lab)
     for lo in range(0, len(windows), _capi.TRACKING_MAX_WINDOWS):
         win = np.ascontiguousarray(windows[lo:lo + _capi.TRACKING_MAX_WINDOWS], dtype=np.float32)
         nw = len(win)
         out = torch.empty(n_ev * nw * 5 + 1, dtype=torch.int64, device=dev)
-        _capi.check(lib.gnntrk_tracking_metrics_windows_batched(q(lab), 1, q(t), q(p), q(e), q(r), n, q(seg), n_ev,
-                                                                win.ctypes.data_as(C.POINTER(C.c_float)), nw,
-                                                                int(predicted_count_thld), q(out), q(ws), ws.numel(),
-                                                                ops._stream(lab)), lib)
+        _capi.check(entry(q(lab), 1, q(t), q(p), q(e), q(r), n, *seg, win.ctypes.data_as(C.POINTER(C.c_float)), nw,
+                          int(predicted_count_thld), q(out), q(ws), ws.numel(), ops._stream(lab)), lib)
         host = out.cpu().numpy()
         if host[-1] != 0:
-            raise ValueError(f"tracking_metrics_vs: {int(host[-1])} labels are >= the number of hits of their event")
+            raise ValueError(f"tracking_metrics_vs: {int(host[-1])} labels are >= the number of hits"
+                             + (" of their event" if ptr is not None else ""))
         n_part[:, lo:lo + nw] = host[:n_ev * nw].reshape(n_ev, nw)
         counts[:, lo:lo + nw] = host[n_ev * nw:-1].reshape(n_ev, nw, 4)
     return n_part, counts
@@ -499,8 +448,8 @@ class EventBatch:
 
 def _per_record_counts(h_dfs: list, windows: np.ndarray, predicted_count_thld: int) -> list:
     """(n_particles, counts) of every hit record, in the records' order.  Records that ``DBSCANPerformanceDetails``
-    sliced from one collated batch are counted together - ``_window_counts_batched``, once per batch instead of
-    once per event -, every other record on its own."""
+    sliced from one collated batch are counted together - ``_window_counts`` with the batch's ``ptr``, once per batch
+    instead of once per event -, every other record on its own."""
     out: list = [None] * len(h_dfs)
     groups: dict[int, list[int]] = {}
     for i, h in enumerate(h_dfs):
@@ -511,11 +460,15 @@ def _per_record_counts(h_dfs: list, windows: np.ndarray, predicted_count_thld: i
         if len(members) < 2:
             continue
         batch = h_dfs[members[0]].origin[0]
-        n_part, counts = _window_counts_batched(batch.record, batch.ptr, windows, predicted_count_thld)
+        n_part, counts = _window_counts(batch.record, windows, predicted_count_thld, batch.ptr)
         for i in members:
             k = h_dfs[i].origin[1]
             out[i] = (n_part[k], counts[k])
-    return [_window_counts(h, windows, predicted_count_thld) if o is None else o for h, o in zip(h_dfs, out)]
+    for i, h in enumerate(h_dfs):
+        if out[i] is None:
+            n_part, counts = _window_counts(h, windows, predicted_count_thld)
+            out[i] = (n_part[0], counts[0])
+    return out
 
 
 def _binned(h_dfs, c_dfs, edges, window_of, names: tuple[str, str], predicted_count_thld: int) -> list[dict]:
@@ -568,23 +521,6 @@ SCORE_KEYS = ("v_measure", "homogeneity", "completeness", "adjusted_rand", "fowl
 _EMPTY = (np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64))
 
 
-def _spectra_host(labels: Tensor, truth: Tensor | None) -> tuple[np.ndarray, int]:
-    """``gnntrk_cluster_spectra`` of ``labels`` [T, n] (1 <= T, 1 <= n): its output on the host, one copy,
-    as rows of 1 + 2 D(n) values, and D(n)."""
-    lib = _capi.load()
-    _capi.require_device(labels, truth)
-    n_trials, n = int(labels.shape[0]), int(labels.shape[1])
-    if n_trials > _capi.TRACKING_MAX_TRIALS:
-        raise ValueError(f"clustering_spectra: at most {_capi.TRACKING_MAX_TRIALS} trials per call")
-    cap = int(lib.gnntrk_cluster_spectra_capacity(n))
-    out = torch.empty((1 + 2 * n_trials, 1 + 2 * cap), dtype=torch.int64, device=labels.device)
-    ws = ops._ws(lib.gnntrk_cluster_spectra_workspace_bytes(n, n_trials), labels)
-    p = ops._p
-    _capi.check(lib.gnntrk_cluster_spectra(p(labels), n_trials, p(truth) if truth is not None else None, n, p(out),
-                                           p(ws), ws.numel(), ops._stream(labels)), lib)
-    return out.cpu().numpy(), cap
-
-
 def _spectrum(row: np.ndarray, cap: int) -> tuple[np.ndarray, np.ndarray]:
     d = int(row[0])
     if not 0 <= d <= cap:
@@ -594,40 +530,50 @@ def _spectrum(row: np.ndarray, cap: int) -> tuple[np.ndarray, np.ndarray]:
     return pairs[:, 0].copy(), pairs[:, 1].copy()
 
 
-def _spectra_batched(lab: Tensor, tru: Tensor | None, ptr: Tensor, sizes: list[int]) -> list[list[dict]]:
-    """``gnntrk_cluster_spectra_batched`` of ``lab`` [T, n]: one C call and one host copy, then
-    ``[trial][event] -> spectra``; every spectrum arrives as one pooled list of (event, size, multiplicity)."""
+def _spectra(lab: Tensor, tru: Tensor | None, ptr: Tensor | None = None, sizes: list[int] | None = None) -> list[list[dict]]:
+    """``gnntrk_cluster_spectra`` of ``lab`` [T, n] (1 <= T, 1 <= n), with the events' offsets ``ptr`` (device) and
+    ``sizes`` ``gnntrk_cluster_spectra_batched``: one C call and one host copy, then ``[trial][event] -> spectra``.  The
+    two entries differ in layout: one event's spectrum is a row of (size, multiplicity) pairs, a batch's one pooled list
+    of (event, size, multiplicity) with its own capacity."""
     lib = _capi.load()
     _capi.require_device(lab, tru, ptr)
     n_trials, n = int(lab.shape[0]), int(lab.shape[1])
     if n_trials > _capi.TRACKING_MAX_TRIALS:
         raise ValueError(f"clustering_spectra: at most {_capi.TRACKING_MAX_TRIALS} trials per call")
-    n_ev = len(sizes)
-    cap = int(lib.gnntrk_cluster_spectra_batched_capacity(n, n_ev))
-    out = torch.empty((1 + 2 * n_trials, 1 + 3 * cap), dtype=torch.int64, device=lab.device)
-    ws = ops._ws(lib.gnntrk_cluster_spectra_workspace_bytes(n, n_trials), lab)
     p = ops._p
-    _capi.check(lib.gnntrk_cluster_spectra_batched(p(lab), n_trials, p(tru) if tru is not None else None, n, p(ptr), n_ev,
-                                                   p(out), p(ws), ws.numel(), ops._stream(lab)), lib)
+    if ptr is None:
+        entry, seg, width, cap = lib.gnntrk_cluster_spectra, (), 2, int(lib.gnntrk_cluster_spectra_capacity(n))
+    else:
+        entry, seg, width = lib.gnntrk_cluster_spectra_batched, (p(ptr), len(sizes)), 3
+        cap = int(lib.gnntrk_cluster_spectra_batched_capacity(n, len(sizes)))
+    out = torch.empty((1 + 2 * n_trials, 1 + width * cap), dtype=torch.int64, device=lab.device)
+    ws = ops._ws(lib.gnntrk_cluster_spectra_workspace_bytes(n, n_trials), lab)
+    _capi.check(entry(p(lab), n_trials, p(tru) if tru is not None else None, n, *seg, p(out), p(ws), ws.numel(),
+                      ops._stream(lab)), lib)
     host = out.cpu().numpy()
-    caps = [int(lib.gnntrk_cluster_spectra_capacity(m)) for m in sizes]
+    if ptr is None:
+        def per_event(row: np.ndarray) -> list[tuple[np.ndarray, np.ndarray]]:
+            return [_spectrum(row, cap)]
+    else:
+        n_ev = len(sizes)
+        caps = [int(lib.gnntrk_cluster_spectra_capacity(m)) for m in sizes]
 
-    def per_event(row: np.ndarray) -> list[tuple[np.ndarray, np.ndarray]]:
-        d = int(row[0])
-        if not 0 <= d <= cap:
-            raise RuntimeError(f"clustering_spectra: spectra of {d} entries, at most {cap} are possible")
-        triples = row[1:1 + 3 * d].reshape(d, 3)
-        triples = triples[np.argsort(triples[:, 0], kind="stable")]
-        cut = np.searchsorted(triples[:, 0], np.arange(n_ev + 1))
-        # (the event's pairs behind their number: a row as gnntrk_cluster_spectra writes it, checked against D(n_e))
-        return [_spectrum(np.concatenate([[cut[k + 1] - cut[k]], triples[cut[k]:cut[k + 1], 1:].reshape(-1)]), caps[k])
-                for k in range(n_ev)]
+        def per_event(row: np.ndarray) -> list[tuple[np.ndarray, np.ndarray]]:
+            d = int(row[0])
+            if not 0 <= d <= cap:
+                raise RuntimeError(f"clustering_spectra: spectra of {d} entries, at most {cap} are possible")
+            triples = row[1:1 + 3 * d].reshape(d, 3)
+            triples = triples[np.argsort(triples[:, 0], kind="stable")]
+            cut = np.searchsorted(triples[:, 0], np.arange(n_ev + 1))
+            # (the event's pairs behind their number: a row as gnntrk_cluster_spectra writes it, checked against D(n_e))
+            return [_spectrum(np.concatenate([[cut[k + 1] - cut[k]], triples[cut[k]:cut[k + 1], 1:].reshape(-1)]), caps[k])
+                    for k in range(n_ev)]
 
     classes = per_event(host[0])
     res = []
     for t in range(n_trials):
         clusters, cells = per_event(host[1 + 2 * t]), per_event(host[2 + 2 * t])
-        res.append([{"classes": classes[k], "clusters": clusters[k], "cells": cells[k]} for k in range(n_ev)])
+        res.append([{"classes": a, "clusters": b, "cells": c} for a, b, c in zip(classes, clusters, cells)])
     return res
 
 
@@ -638,10 +584,9 @@ def clustering_spectra(labels, truth=None, ptr=None):
     Labels and ids are categories of any integer value (-1 is one cluster).  Without ``truth``, ``classes``
     and ``cells`` are empty.  One C call and one host copy.
 
-    ``ptr`` ([B + 1] row offsets of the events of a collated batch, more than one event): every event on its own -
-    a class is (event, truth id), a cluster (event, label), so equal labels or ids of two events stay apart - still
-    from one C call and one host copy; the result is ``[trial][event] -> dict``, each what the event's rows alone
-    give (an event without hits: empty spectra)."""
+    ``ptr`` (the events of a collated batch, module docstring): a class is (event, truth id), a cluster (event, label),
+    so equal labels or ids of two events stay apart; the result is ``[trial][event] -> dict``, each what the event's
+    rows alone give (an event without hits: empty spectra)."""
     if not torch.is_tensor(labels):
         labels = torch.as_tensor(np.asarray(labels))
     if labels.dim() == 1:
@@ -651,7 +596,8 @@ def clustering_spectra(labels, truth=None, ptr=None):
     n_trials, n = int(labels.shape[0]), int(labels.shape[1])
     if truth is not None and int(np.shape(truth)[0] if not torch.is_tensor(truth) else truth.shape[0]) != n:
         raise ValueError("clustering_spectra: labels and truth differ in the number of hits")
-    sizes = _event_sizes(ptr, n, "clustering_spectra")
+    ptr = events.event_ptr(ptr=ptr)
+    sizes = events.event_sizes(ptr, n, "clustering_spectra")
     if n == 0 or n_trials == 0:
         empty = {"classes": _EMPTY, "clusters": _EMPTY, "cells": _EMPTY}
         return [dict(empty) if sizes is None else [dict(empty) for _ in sizes] for _ in range(n_trials)]
@@ -659,11 +605,8 @@ def clustering_spectra(labels, truth=None, ptr=None):
     lab = _on(labels, torch.int64, dev)
     tru = _on(truth, torch.int64, dev).view(-1) if truth is not None else None
     if sizes is not None:
-        return _spectra_batched(lab, tru, _on(ptr, torch.int64, dev), sizes)
-    host, cap = _spectra_host(lab, tru)
-    classes = _spectrum(host[0], cap)
-    return [{"classes": classes, "clusters": _spectrum(host[1 + 2 * t], cap), "cells": _spectrum(host[2 + 2 * t], cap)}
-            for t in range(n_trials)]
+        return _spectra(lab, tru, _on(ptr, torch.int64, dev), sizes)
+    return [per_event[0] for per_event in _spectra(lab, tru)]
 
 
 def _xlogx(s: tuple[np.ndarray, np.ndarray]) -> float:

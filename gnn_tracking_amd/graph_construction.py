@@ -20,6 +20,7 @@ from torch import Tensor, nn
 from . import graph_cut, ops
 from .data import Data
 from .edge_filter import EFMLP
+from .events import event_ptr
 from .hparams import HyperparametersMixin, obj_from_or_to_hparams
 
 
@@ -40,23 +41,6 @@ def knn_scan(x: Tensor, ks, max_radius: float | None = None) -> dict[int, Tensor
     k).  The scanner itself, with its figures of merit, is ``k_scanner.GraphConstructionKNNScanner``;
     it evaluates every k from the neighbour table and never materialises these edge lists."""
     return ops.knn_scan(x, ks, max_radius)
-
-
-def _event_ptr(data) -> Tensor | None:
-    """int64 row offsets of the events of a collated ``data`` (its ``ptr``, or from its sorted ``batch``); None if it
-    holds one event"""
-    ptr = getattr(data, "ptr", None)
-    if ptr is None:
-        batch = getattr(data, "batch", None)
-        if batch is None:
-            return None
-        b = batch.long()
-        counts = torch.bincount(b)
-        if b.numel() > 1 and bool((b[1:] < b[:-1]).any()):
-            raise ValueError("MLGraphConstruction: `batch` must be sorted (PyG convention)")
-        ptr = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=b.device)
-        ptr[1:] = torch.cumsum(counts, 0)
-    return ptr.long() if ptr.numel() > 2 else None
 
 
 def _false_edges_per_event(edge_index: Tensor, y: Tensor, ptr: Tensor, ratio: float) -> tuple[Tensor, Tensor]:
@@ -151,7 +135,7 @@ class MLGraphConstruction(nn.Module, HyperparametersMixin):
         else:
             s = self.hparams.embedding_slice
             emb = data.x[:, s[0]:s[1]]
-        ptr = _event_ptr(data) if self.per_event else None
+        ptr = event_ptr(data, who="MLGraphConstruction") if self.per_event else None
         edge_index = knn_with_max_radius(emb, max_radius=self.hparams.max_radius,
                                          k=self.hparams.max_num_neighbors, seg_ptr=ptr)
         y = ops.edge_labels(data.particle_id, edge_index)

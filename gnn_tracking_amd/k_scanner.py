@@ -10,9 +10,10 @@ at ``max(ks)`` (the graph of a smaller k is a prefix of every row of its table),
 ``KScanResults`` interpolates the per-k means with a not-a-knot cubic spline in numpy (no pandas, scipy
 or networkx).
 
-A collated batch of B > 1 events (``ptr`` / ``batch``) is B scans from the same launch sequence: the search per
-event, ``gnntrk_kscan_counts_batched`` and ``gnntrk_tracking_metrics_batched``, still one host copy, and one record
-per (event, k) - the records of the events fed one by one (``GraphConstructionKNNScanner.per_event``).
+A collated batch of B > 1 events (``data.ptr`` / ``data.batch``, as ``events.event_ptr`` reads them) is B scans from
+the same launch sequence: the search per event, ``gnntrk_kscan_counts_batched`` and ``gnntrk_tracking_metrics_batched``,
+still one host copy, and one record per (event, k) - the records of the events fed one by one
+(``GraphConstructionKNNScanner.per_event``).  One event is B = 1 of the same record loop, from the single-event entries.
 
 What differs from the reference, all of it outside what its results pin down:
 
@@ -38,11 +39,9 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import _capi, ops
-from .cluster_metrics import _counts as _tracking_counts, _cut_plan, _hits, _results as _tracking_results, \
-    _results_per_event as _tracking_results_per_event, _zdiv, flatten_track_metrics
+from . import _capi, events, ops
+from .cluster_metrics import _counts as _tracking_counts, _cut_plan, _hits, _results as _tracking_results, _zdiv
 from .graph_analysis import efficiency_purity_from_counts
-from .graph_construction import _event_ptr
 from .graph_masks import get_good_node_mask
 from .hparams import HyperparametersMixin
 
@@ -370,7 +369,7 @@ class GraphConstructionKNNScanner(HyperparametersMixin):
         _capi.require_device(x)
         x = ops._as_rows(x.float() if x.dtype != torch.float32 else x)
         n, dev = int(x.shape[0]), x.device
-        ptr = _event_ptr(data) if self.per_event else None
+        ptr = events.event_ptr(data, who="GraphConstructionKNNScanner") if self.per_event else None
         if n < 2:
             if ptr is None:
                 raise ValueError("GraphConstructionKNNScanner: needs at least two hits")
@@ -388,39 +387,26 @@ class GraphConstructionKNNScanner(HyperparametersMixin):
         pts, cuts, idx = _cut_plan([0.9])   # (hard-coded in the reference: k_scanner.py:243)
         hits = _hits(data.particle_id, data.pt, data.reconstructable, data.eta, dev)
         trk = _tracking_counts(labels, *hits, cuts, 3, 4, ptr=ptr)
-        # the batch's one host copy (the events' sizes ride along)
+        # the batch's one host copy (the events' sizes ride along); one event is B = 1 of the batched layouts
         host = torch.cat([counts.reshape(-1), trk] + ([ptr] if ptr is not None else [])).cpu().numpy()
+        sizes = [n] if ptr is None else np.diff(host[counts.numel() + trk.numel():]).tolist()
+        table = host[:counts.numel()].reshape(len(sizes), len(ks), len(COUNT_COLUMNS))
+        upper = _tracking_results(host[counts.numel():counts.numel() + trk.numel()], len(ks), sizes, pts, idx,
+                                  ptr is not None)
+        for e, n_e in enumerate(sizes):
+            n_bad = int(table[e, 0, COUNT_COLUMNS.index("n_bad")])   # (the same in every row of the event)
+            if n_bad:
+                where = f"are outside [0, {n})" if ptr is None else f"of event {e} are outside its {n_e} hits"
+                raise ValueError(f"GraphConstructionKNNScanner: {n_bad} neighbour or true-edge indices {where}")
         records = []
-        if ptr is not None:
-            n_ev = int(ptr.numel()) - 1
-            sizes = np.diff(host[-(n_ev + 1):]).tolist()
-            table = host[:counts.numel()].reshape(n_ev, len(ks), len(COUNT_COLUMNS))
-            upper = _tracking_results_per_event(host[counts.numel():-(n_ev + 1)], len(ks), sizes, pts, idx)
-            for e in range(n_ev):
-                n_bad = int(table[e, 0, COUNT_COLUMNS.index("n_bad")])
-                if n_bad:
-                    raise ValueError(f"GraphConstructionKNNScanner: {n_bad} neighbour or true-edge indices of event {e} "
-                                     f"are outside its {sizes[e]} hits")
-            for e, n_e in enumerate(sizes):
-                if n_e < 2:   # (alone it has no graph to scan)
-                    continue
-                for i, k in enumerate(ks):
-                    c = dict(zip(COUNT_COLUMNS, (int(v) for v in table[e, i])))
-                    if c["n_edges"] > hp.max_edges:
-                        logger.warning(f"Not scanning k>={k} in event {e} because max edges exceeded "
-                                       f"({c['n_edges']} > {hp.max_edges})")
-                        break
-                    records.append(self._record(k, c, upper[i][e]))
-            return records
-        table = host[:counts.numel()].reshape(len(ks), len(COUNT_COLUMNS))
-        upper = _tracking_results(host[counts.numel():], len(ks), pts, idx)
-        for row, k, ub in zip(table, ks, upper):
-            c = dict(zip(COUNT_COLUMNS, (int(v) for v in row)))
-            if c["n_bad"]:
-                raise ValueError(f"GraphConstructionKNNScanner: {c['n_bad']} neighbour or true-edge indices are "
-                                 f"outside [0, {n})")
-            if c["n_edges"] > hp.max_edges:
-                logger.warning(f"Not scanning k>={k} because max edges exceeded ({c['n_edges']} > {hp.max_edges})")
-                break
-            records.append(self._record(k, c, flatten_track_metrics(ub)))
+        for e, n_e in enumerate(sizes):
+            if n_e < 2:   # (an event of a batch that alone has no graph to scan)
+                continue
+            for i, k in enumerate(ks):
+                c = dict(zip(COUNT_COLUMNS, (int(v) for v in table[e, i])))
+                if c["n_edges"] > hp.max_edges:
+                    logger.warning(f"Not scanning k>={k}{'' if ptr is None else f' in event {e}'} because max edges "
+                                   f"exceeded ({c['n_edges']} > {hp.max_edges})")
+                    break
+                records.append(self._record(k, c, upper[i][e]))
         return records

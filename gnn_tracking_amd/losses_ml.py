@@ -22,7 +22,7 @@ import torch
 from torch import Tensor as T
 from torch import nn
 
-from . import ops
+from . import events, ops
 from .graph_masks import get_good_node_mask_tensors
 from .hparams import HyperparametersMixin
 from .losses_oc import MultiLossFctReturn
@@ -35,14 +35,9 @@ def radius_graph(x: T, r: float, batch: T | None = None, max_num_neighbors: int 
     if batch is None:
         return ops.knn_graph(xd, max_num_neighbors, r)
     # all events of the collated batch in ONE search (gnntrk_knn_search_batched): row offsets of
-    # the events from `batch` (sorted, as PyG's collate produces it - checked on the device
-    # together with the one unavoidable read of the edge count)
-    b = batch.long()
-    counts = torch.bincount(b)
-    seg_ptr = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=x.device)
-    seg_ptr[1:] = torch.cumsum(counts, 0)
-    if b.numel() > 1 and bool((b[1:] < b[:-1]).any()):
-        raise ValueError("radius_graph: `batch` must be sorted (PyG convention)")
+    # the events from `batch` (sorted, as PyG's collate produces it; one event keeps its offsets too: the same entry)
+    seg_ptr = events.offsets_of(batch)
+    events.require_sorted(batch, "radius_graph")
     return ops.knn_graph(xd, max_num_neighbors, r, seg_ptr=seg_ptr)
 
 

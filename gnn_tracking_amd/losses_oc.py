@@ -22,7 +22,7 @@ from typing import Any
 import torch
 from torch import Tensor as T
 
-from . import _capi, ops
+from . import _capi, events, ops
 from .graph_masks import get_good_node_mask_tensors
 from .hparams import HyperparametersMixin
 
@@ -91,82 +91,67 @@ class _CondensationPotentials(torch.autograd.Function):
         pid = particle_id.to(torch.int64).contiguous()
         mask8 = mask.to(torch.uint8).contiguous()
         n, dim = int(x_c.shape[0]), int(x_c.shape[1])
-        st = ops._stream(x_c)
-        ctx.batch = None
-        if seg_ptr is not None:
-            if keep < 1.0 or stash is not None:
-                raise ValueError("the sub-sampling of repulsive pairs is per event: not supported in a batch")
-            b = int(seg_ptr.numel()) - 1
-            alphas = torch.empty(n, dtype=torch.int32, device=dev)
-            gid = torch.empty(n, dtype=torch.int32, device=dev)
-            n_cp = torch.zeros(1, dtype=torch.int32, device=dev)
-            cp_ptr = torch.empty(b + 1, dtype=torch.int32, device=dev)
-            ws = ops._ws(lib.gnntrk_oc_select_batched_workspace_bytes(n), x_c)
-            _capi.check(lib.gnntrk_oc_select_cps_batched(ops._p(beta_c), ops._p(pid), ops._p(mask8), n, mode,
-                                                         ops._p(seg_ptr), b, ops._p(alphas), ops._p(gid), ops._p(cp_ptr),
-                                                         ops._p(n_cp), ops._p(ws), ws.numel(), st), lib)
-            a = _capi.OcArgs(ops._p(x_c), ops._p(beta_c), ops._p(pid), ops._p(mask8), ops._p(gid),
-                             ops._p(alphas), ops._p(n_cp), n, dim, dim, q_min, radius, eps_sqrt, mode,
-                             1.0, 0, 0, ops._p(cap_nbr))
-            out = torch.empty(b, 9, dtype=torch.float32, device=dev)
-            ws2 = ops._ws(lib.gnntrk_oc_forward_batched_workspace_bytes(n, b), x_c)
-            _capi.check(lib.gnntrk_oc_forward_batched(C.byref(a), ops._p(seg_ptr), ops._p(cp_ptr), b, ops._p(out),
-                                                      ops._p(ws2), ws2.numel(), st), lib)
-            ctx.save_for_backward(beta_c, x_c, pid, mask8, gid, alphas, n_cp, out)
-            ctx.cfg = (q_min, radius, eps_sqrt, mode, beta.dtype, x.dtype, 1.0, 0)
-            ctx.cap_nbr, ctx.batch, ctx.spatial = cap_nbr, (seg_ptr, cp_ptr), None
-            terms = out[:, :4].mean(0)
-            n_rep = out[:, 7].double().sum()
-            ctx.mark_non_differentiable(n_rep)
-            return terms[0], terms[1], terms[2], terms[3], n_rep
+        st, p = ops._stream(x_c), ops._p
+        b = int(seg_ptr.numel()) - 1 if seg_ptr is not None else 0
+        if b and (keep < 1.0 or stash is not None):
+            raise ValueError("the sub-sampling of repulsive pairs is per event: not supported in a batch")
+        cp_ptr = None
         if stash is not None and "sel" in stash:
             alphas, gid, n_cp = stash["sel"]
         else:
             alphas = torch.empty(n, dtype=torch.int32, device=dev)
             gid = torch.empty(n, dtype=torch.int32, device=dev)
             n_cp = torch.zeros(1, dtype=torch.int32, device=dev)
-            ws = ops._ws(lib.gnntrk_oc_select_workspace_bytes(n), x_c)
-            _capi.check(lib.gnntrk_oc_select_cps(ops._p(beta_c), ops._p(pid), ops._p(mask8), n, mode,
-                                                 ops._p(alphas), ops._p(gid), ops._p(n_cp), ops._p(ws),
-                                                 ws.numel(), st), lib)
+            hits = (p(beta_c), p(pid), p(mask8), n, mode)
+            if b:
+                cp_ptr = torch.empty(b + 1, dtype=torch.int32, device=dev)
+                ws = ops._ws(lib.gnntrk_oc_select_batched_workspace_bytes(n), x_c)
+                _capi.check(lib.gnntrk_oc_select_cps_batched(*hits, p(seg_ptr), b, p(alphas), p(gid), p(cp_ptr), p(n_cp),
+                                                             p(ws), ws.numel(), st), lib)
+            else:
+                ws = ops._ws(lib.gnntrk_oc_select_workspace_bytes(n), x_c)
+                _capi.check(lib.gnntrk_oc_select_cps(*hits, p(alphas), p(gid), p(n_cp), p(ws), ws.numel(), st), lib)
             if stash is not None:
                 stash["sel"] = (alphas, gid, n_cp)
-        a = _capi.OcArgs(ops._p(x_c), ops._p(beta_c), ops._p(pid), ops._p(mask8), ops._p(gid),
-                         ops._p(alphas), ops._p(n_cp), n, dim, dim, q_min, radius, eps_sqrt, mode,
-                         float(keep), 0, int(seed), ops._p(cap_nbr))
-        out = torch.empty(9, dtype=torch.float32, device=dev)
-        # large events: the pair loops only visit (chunk of hits, condensation point) pairs within the
-        # radius (csrc/oc.hip "spatial" passes; same pairs, same per-pair arithmetic); the buffer the
-        # forward fills is what the backward reads
-        nb = int(lib.gnntrk_oc_spatial_workspace_bytes(n, dim)) if _use_spatial(n) else 0
-        ctx.spatial = None
-        if nb:
+        saved = (beta_c, x_c, pid, mask8, gid, alphas, n_cp)
+        ctx.cfg = (q_min, radius, eps_sqrt, mode, beta.dtype, x.dtype, float(keep), int(seed))
+        ctx.cap_nbr, ctx.batch, ctx.spatial = cap_nbr, None, None
+        a = _oc_args(saved, ctx.cfg, cap_nbr)
+        out = torch.empty((b, 9) if b else 9, dtype=torch.float32, device=dev)
+        if b:
+            ctx.batch = (seg_ptr, cp_ptr)
+            ws2 = ops._ws(lib.gnntrk_oc_forward_batched_workspace_bytes(n, b), x_c)
+            _capi.check(lib.gnntrk_oc_forward_batched(C.byref(a), p(seg_ptr), p(cp_ptr), b, p(out), p(ws2), ws2.numel(),
+                                                      st), lib)
+        elif _use_spatial(n) and (nb := int(lib.gnntrk_oc_spatial_workspace_bytes(n, dim))):
+            # large events: the pair loops only visit (chunk of hits, condensation point) pairs within the
+            # radius (csrc/oc.hip "spatial" passes; same pairs, same per-pair arithmetic); the buffer the
+            # forward fills is what the backward reads
             ctx.spatial = ops._ws(nb, x_c)
-            _capi.check(lib.gnntrk_oc_forward_spatial(C.byref(a), ops._p(out), ops._p(ctx.spatial), nb, st), lib)
+            _capi.check(lib.gnntrk_oc_forward_spatial(C.byref(a), p(out), p(ctx.spatial), nb, st), lib)
         else:
             ws2 = ops._ws(lib.gnntrk_oc_forward_workspace_bytes(n), x_c)
-            _capi.check(lib.gnntrk_oc_forward(C.byref(a), ops._p(out), ops._p(ws2), ws2.numel(), st), lib)
-        ctx.save_for_backward(beta_c, x_c, pid, mask8, gid, alphas, n_cp, out)
-        ctx.cfg = (q_min, radius, eps_sqrt, mode, beta.dtype, x.dtype, float(keep), int(seed))
-        ctx.cap_nbr = cap_nbr
-        n_rep = out[7].clone()   # a plain count: no gradient, no hold on this node's saved tensors
+            _capi.check(lib.gnntrk_oc_forward(C.byref(a), p(out), p(ws2), ws2.numel(), st), lib)
+        ctx.save_for_backward(*saved, out)
+        # a batch: the terms are the means over the events, n_rep the sum.  n_rep is a plain count: no gradient, no
+        # hold on this node's saved tensors
+        terms, n_rep = (out[:, :4].mean(0), out[:, 7].double().sum()) if b else (out, out[7].clone())
         ctx.mark_non_differentiable(n_rep)
-        return out[0], out[1], out[2], out[3], n_rep
+        return terms[0], terms[1], terms[2], terms[3], n_rep
 
     @staticmethod
     def backward(ctx, g_att, g_rep, g_cow, g_noise, _g_nrep):
         lib = _capi.load()
-        beta_c, x_c, pid, mask8, gid, alphas, n_cp, out = ctx.saved_tensors
-        q_min, radius, eps_sqrt, mode, bdt, xdt, keep, seed = ctx.cfg
+        *saved, out = ctx.saved_tensors
+        x_c = saved[1]
+        bdt, xdt = ctx.cfg[4:6]
         n, dim = int(x_c.shape[0]), int(x_c.shape[1])
         g = torch.stack([t.to(torch.float32).reshape(()) if t is not None
                          else torch.zeros((), device=x_c.device)
                          for t in (g_att, g_rep, g_cow, g_noise)]).contiguous()
-        a = _capi.OcArgs(ops._p(x_c), ops._p(beta_c), ops._p(pid), ops._p(mask8), ops._p(gid),
-                         ops._p(alphas), ops._p(n_cp), n, dim, dim, q_min, radius, eps_sqrt, mode,
-                         keep, 0, seed, ops._p(ctx.cap_nbr))
+        a = _oc_args(saved, ctx.cfg, ctx.cap_nbr)
         gx = torch.empty_like(x_c)
-        gbeta = torch.empty_like(beta_c)
+        gbeta = torch.empty_like(saved[0])
         if ctx.batch is not None:
             seg_ptr, cp_ptr = ctx.batch
             b = int(seg_ptr.numel()) - 1
@@ -186,15 +171,13 @@ class _CondensationPotentials(torch.autograd.Function):
         return gbeta.to(bdt), gx.to(xdt), None, None, None, None, None, None, None, None, None, None, None
 
 
-def _event_ptr(batch: T) -> T | None:
-    """int64 ``[B + 1]`` row offsets of the events of ``batch`` (as ``losses_ml.radius_graph`` derives them); None if
-    it holds one event"""
-    counts = torch.bincount(batch.long())
-    if counts.numel() < 2:
-        return None
-    seg_ptr = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=batch.device)
-    seg_ptr[1:] = torch.cumsum(counts, 0)
-    return seg_ptr
+def _oc_args(saved, cfg, cap_nbr) -> "_capi.OcArgs":
+    """the argument block of every ``gnntrk_oc_*`` forward and backward entry, from the tensors a node saves"""
+    beta_c, x_c, pid, mask8, gid, alphas, n_cp = saved
+    q_min, radius, eps_sqrt, mode, _bdt, _xdt, keep, seed = cfg
+    n, dim = int(x_c.shape[0]), int(x_c.shape[1])
+    return _capi.OcArgs(ops._p(x_c), ops._p(beta_c), ops._p(pid), ops._p(mask8), ops._p(gid), ops._p(alphas),
+                        ops._p(n_cp), n, dim, dim, q_min, radius, eps_sqrt, mode, keep, 0, seed, ops._p(cap_nbr))
 
 
 class _CondensationLoss(MultiLossFct, HyperparametersMixin):
@@ -225,7 +208,7 @@ class _CondensationLoss(MultiLossFct, HyperparametersMixin):
                 eta = eta[ec_hit_mask]
             if batch is not None:
                 batch = batch[ec_hit_mask]
-        seg_ptr = _event_ptr(batch) if batch is not None else None
+        seg_ptr = events.event_ptr(batch=batch, who=None)   # (its order: in the read below)
         mask = get_good_node_mask_tensors(pt=pt, particle_id=particle_id,
                                           reconstructable=reconstructable, eta=eta,
                                           pt_thld=self.hparams.pt_thld,
@@ -244,8 +227,7 @@ class _CondensationLoss(MultiLossFct, HyperparametersMixin):
                                  "supported with more than one event in `batch`")
             # per event, and whether `batch` is sorted, in the one host read the assertion costs
             seen = torch.cat((mask.new_zeros(1, dtype=torch.int64), torch.cumsum(mask, 0, dtype=torch.int64)))
-            b = batch.long()
-            flags = torch.cat(((seen[seg_ptr[1:]] > seen[seg_ptr[:-1]]), (b[1:] < b[:-1]).any().reshape(1))).tolist()
+            flags = torch.cat(((seen[seg_ptr[1:]] > seen[seg_ptr[:-1]]), events.unsorted(batch).reshape(1))).tolist()
             if flags[-1]:
                 raise ValueError("condensation loss: `batch` must be sorted (PyG convention)")
             for e, left in enumerate(flags[:-1]):

@@ -14,18 +14,18 @@ every trial's labels into one device buffer, and the tracking metrics of all tri
 (dbscanscanner.py:215-264) keeps per batch the hit record on the device and the cluster table, the
 inputs of ``cluster_metrics.tracking_metrics_vs_pt`` / ``_vs_eta``.
 
-A collated batch of several events (``batch`` / ``ptr``) is that many independent problems in one launch sequence:
-the radius graph has no edge between events, cluster labels are local to the event (noise -1, the clusters of an
-event numbered from 0, so ``labels[ptr[e]:ptr[e + 1]]`` is what the event alone gives), the tracking metrics come per
-event, and the scanners append one record per (event, trial) - exactly the results of the events fed one by one
-(``DBSCANHyperParamScanner.per_event``).
+A collated batch of several events (``batch`` / ``ptr``, turned into row offsets and checked by ``events.py``) is that
+many independent problems in one launch sequence: the radius graph has no edge between events, cluster labels are local
+to the event (noise -1, the clusters of an event numbered from 0, so ``labels[ptr[e]:ptr[e + 1]]`` is what the event
+alone gives), the tracking metrics come per event, and the scanners append one record per (event, trial) - exactly the
+results of the events fed one by one (``DBSCANHyperParamScanner.per_event``).  One event - no offsets, or offsets of one
+event - takes the single-event C entries.
 """
 
 from __future__ import annotations
 
 import math
 import os
-import types
 from abc import ABC, abstractmethod
 from typing import Any
 
@@ -33,9 +33,8 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import _capi, ops
+from . import _capi, events, ops
 from .cluster_metrics import _nanmean, _nanstd
-from .graph_construction import _event_ptr
 from .hparams import HyperparametersMixin
 
 
@@ -68,11 +67,10 @@ class DBSCANFastRescan:
         self._n_jobs = n_jobs
         self._ptr = None
         self.cluster_ptr: Tensor | None = None
-        seg = _event_ptr(types.SimpleNamespace(batch=batch, ptr=ptr))
+        seg = events.event_ptr(batch=batch, ptr=ptr, who="DBSCANFastRescan")
         if seg is not None:
-            host = seg.cpu()
-            if int(host[0]) != 0 or int(host[-1]) != int(x.shape[0]) or bool((host[1:] < host[:-1]).any()):
-                raise ValueError("DBSCANFastRescan: the events' offsets must ascend from 0 to the number of points")
+            events.event_sizes(seg, int(x.shape[0]), "DBSCANFastRescan",
+                               "the events' offsets must ascend from 0 to the number of points")
             self._ptr = seg.to(device=self.x.device, dtype=torch.int64).contiguous()
         self._reset_graph(self._max_eps)
 
@@ -134,16 +132,14 @@ class DBSCANFastRescan:
                 raise RuntimeError("DBSCAN label propagation did not converge")
             rounds = min(2 * rounds, 64)
         ws = torch.empty(max(int(lib.gnntrk_dbscan_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
-        if self._ptr is None:
-            n_clusters = torch.empty(1, dtype=torch.int64, device=dev)
-            _capi.check(lib.gnntrk_dbscan_labels(*args, ops._p(core), ops._p(root), ops._p(labels), ops._p(n_clusters),
-                                                 ops._p(ws), ws.numel(), st), lib)
+        if self._ptr is None:   # (as _reset_graph: the same entry with the events' offsets)
+            entry, seg, n_clusters = lib.gnntrk_dbscan_labels, (), torch.empty(1, dtype=torch.int64, device=dev)
         else:
             n_ev = int(self._ptr.numel()) - 1
-            self.cluster_ptr = torch.empty(n_ev + 1, dtype=torch.int64, device=dev)
-            _capi.check(lib.gnntrk_dbscan_labels_batched(*args, ops._p(core), ops._p(root), ops._p(self._ptr), n_ev,
-                                                         ops._p(labels), ops._p(self.cluster_ptr), ops._p(ws),
-                                                         ws.numel(), st), lib)
+            entry, seg = lib.gnntrk_dbscan_labels_batched, (ops._p(self._ptr), n_ev)
+            n_clusters = self.cluster_ptr = torch.empty(n_ev + 1, dtype=torch.int64, device=dev)
+        _capi.check(entry(*args, ops._p(core), ops._p(root), *seg, ops._p(labels), ops._p(n_clusters), ops._p(ws),
+                          ws.numel(), st), lib)
         return labels
 
     def cluster(self, eps: float = 1.0, min_pts: int = 1) -> np.ndarray:
@@ -306,7 +302,7 @@ class DBSCANHyperParamScanner(ClusterScanner):
         self._results = []
 
     def __call__(self, data, out: dict[str, Tensor], i_batch: int, *, progress=False):
-        from .cluster_metrics import tracking_metrics_trials
+        from .cluster_metrics import _metrics_per_event
 
         ec_hit_mask = out.get("ec_hit_mask")
         if ec_hit_mask is not None and not bool(ec_hit_mask.all()):
@@ -315,18 +311,16 @@ class DBSCANHyperParamScanner(ClusterScanner):
             self.reset()
         if not self._trials:
             return
-        ptr = _event_ptr(data) if self.per_event else None
+        ptr = events.event_ptr(data, who="DBSCANHyperParamScanner") if self.per_event else None
         scanner = DBSCANFastRescan(out["H"].detach(), max_eps=max(v["eps"] for v in self._trials), ptr=ptr,
                                    n_jobs=self.hparams.n_jobs)
         n = int(scanner.x.shape[0])
         labels = torch.empty((len(self._trials), n), dtype=torch.int64, device=scanner.x.device)
         for k, trial in enumerate(self._trials):
             labels[k] = scanner.cluster_device(eps=trial["eps"], min_pts=trial["min_samples"])
-        metrics = tracking_metrics_trials(labels, truth=data.particle_id, pts=data.pt, eta=data.eta,
-                                          reconstructable=data.reconstructable, pt_thlds=self.hparams.pt_thlds,
-                                          max_eta=self.hparams.max_eta, ptr=ptr)
-        if ptr is None:
-            metrics = [[m] for m in metrics]
+        metrics = _metrics_per_event(labels, truth=data.particle_id, pts=data.pt, eta=data.eta,
+                                     reconstructable=data.reconstructable, pt_thlds=self.hparams.pt_thlds,
+                                     predicted_count_thld=3, max_eta=self.hparams.max_eta, ptr=ptr)
         for e in range(len(metrics[0])):       # (records grouped by event: as the events fed one by one)
             for trial, per_event in zip(self._trials, metrics):
                 self._results.append({"i_batch": i_batch, "eps": trial["eps"], "min_samples": trial["min_samples"],
@@ -362,7 +356,7 @@ class DBSCANPerformanceDetails(DBSCANHyperParamScanner):
     def __call__(self, data, out: dict[str, Tensor], i_batch: int) -> None:
         from . import cluster_metrics as CM
 
-        ptr = _event_ptr(data) if self.per_event else None
+        ptr = events.event_ptr(data, who="DBSCANPerformanceDetails") if self.per_event else None
         fr = DBSCANFastRescan(out["H"].detach(), max_eps=self.hparams.eps, ptr=ptr)
         labels = fr.cluster_device(eps=self.hparams.eps, min_pts=self.hparams.min_samples)
         dev = labels.device
@@ -375,10 +369,9 @@ class DBSCANPerformanceDetails(DBSCANHyperParamScanner):
             return
         # several events: one DBSCAN and one table call for all, then per event its slice of the hits (a record that
         # remembers the batch: tracking_metrics_vs_pt / _vs_eta count the events of a batch in one call) and its table
-        ptr = ptr.to(device=dev, dtype=torch.int64).contiguous()
-        batch = CM.EventBatch(record, ptr)
+        batch = CM.EventBatch(record, ptr.to(device=dev, dtype=torch.int64).contiguous())
         self._h_dfs.extend(batch.records)
-        self._c_dfs.extend(CM._table_batched(labels, pid, pt, reco, eta, ptr, batch.sizes, 3))
+        self._c_dfs.extend(CM._table(labels, None, pid, pt, reco, eta, 3, batch.ptr, batch.sizes))
 
     def get_results(self) -> tuple[list[dict[str, Tensor]], list[dict[str, np.ndarray]]]:
         """(h_dfs, c_dfs): per batch the hit record and the cluster table, as

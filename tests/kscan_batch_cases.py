@@ -17,6 +17,7 @@ import torch
 
 import gnn_tracking_amd as G
 import kscan_ref as R
+from batch_util import assert_same, counted_calls, one_event_ptrs, ptr_of, records_equal, starts_of
 from gnn_tracking_amd import GraphConstructionKNNScanner
 from gnn_tracking_amd import k_scanner as KS
 from test_kscan_gpu import chain_event
@@ -32,14 +33,6 @@ UNMASKED_EVENT = 3
 SCAN_HITS = (300, 257, 40)
 N_BAD = R.COLUMNS.index("n_bad")
 N_PIDS = R.COLUMNS.index("n_pids")
-
-
-def starts_of(sizes):
-    return [0, *np.cumsum(sizes).tolist()]
-
-
-def ptr_of(sizes, device):
-    return torch.tensor(starts_of(sizes), dtype=torch.int64, device=device)
 
 
 def random_tables(sizes, kmax, seed, unmasked=None):
@@ -199,19 +192,6 @@ def scan_oracle_records(max_edges=5_000_000):
     return tuple(tuple(R.batch_records(*raw, list(range(1, 10)), max_edges=max_edges)) for raw in scan_events())
 
 
-def assert_same(got: dict, want: dict, what: str):
-    assert list(got) == list(want), f"{what}: keys {list(got)}"
-    for k, v in want.items():
-        g = float(got[k])
-        assert g == v or (g != g and v != v), f"{what}: {k} = {got[k]!r}, want {v!r}"
-
-
-def records_equal(got, want, what):
-    assert len(got) == len(want), f"{what}: {len(got)} records, want {len(want)}"
-    for i, (g, w) in enumerate(zip(got, want)):
-        assert_same(g, w, f"{what}: record {i}")
-
-
 def one_by_one(events, **kw):
     alone = GraphConstructionKNNScanner(**kw)
     for i, d in enumerate(events):
@@ -248,6 +228,31 @@ def case_scanner_batch(device):
     single = GraphConstructionKNNScanner()
     single(G.collate(events[:1]), 0)
     records_equal(single.results_raw, alone.results_raw[:9], "a one-event batch")
+
+
+def case_scanner_one_event(device):
+    """a ``Data`` without ``ptr`` and with a one-event ``ptr``: today's records, from the single-event entries alone"""
+    raw = scan_events()[0]
+    n, ks = SCAN_HITS[0], [1, 2, 3]
+    assert n == 300
+    want = R.batch_records(*raw, ks, max_edges=5_000_000)
+    assert len(want) == 3 and want[-1]["frac50"] > want[0]["frac50"]
+    entries = ("gnntrk_kscan_counts", "gnntrk_kscan_counts_batched", "gnntrk_tracking_metrics",
+               "gnntrk_tracking_metrics_batched")
+    first = None
+    for ptr in one_event_ptrs(n):
+        data = data_of(raw, device)
+        if ptr is not None:
+            data.ptr = ptr
+        scanner = GraphConstructionKNNScanner(ks=ks)
+        with counted_calls(entries) as calls:
+            scanner(data, 0)
+        assert calls == dict(zip(entries, (1, 0, 1, 0))), calls
+        got = scanner.results_raw
+        first = got if first is None else first
+        records_equal(got, first, f"one event: ptr={ptr!r} against no ptr")
+        assert [[type(v) for v in r.values()] for r in got] == [[type(v) for v in r.values()] for r in first]
+        records_equal(got, want, "one event against the restatement")
 
 
 def case_scanner_max_edges(device, caplog):

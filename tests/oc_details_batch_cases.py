@@ -12,7 +12,6 @@ file.  Each case asserts on the oracle's output that what it is there for occurs
 
 from __future__ import annotations
 
-import contextlib
 import functools
 import itertools
 import math
@@ -20,6 +19,7 @@ import math
 import numpy as np
 import torch
 
+import batch_util
 import cluster_scores_cases as S
 import cluster_scores_ref as SR
 import gnn_tracking_amd as G
@@ -27,6 +27,7 @@ import neighbor_cases as N
 import oc_validation_batch_cases as V
 import tracking_binned_cases as T
 import tracking_binned_ref as B
+from batch_util import one_event_ptrs, ptr_of, starts_of
 from gnn_tracking_amd import _capi
 from gnn_tracking_amd import cluster_metrics as CM
 from gnn_tracking_amd.postprocessing import DBSCANPerformanceDetails
@@ -45,16 +46,8 @@ BIG = 2100
 TABLE_KEYS = ("c",) + T.TABLE_COLUMNS
 
 
-def starts_of(sizes):
-    return V.starts_of(sizes)
-
-
 def dev(a, device):
     return torch.from_numpy(np.ascontiguousarray(a)).to(device)
-
-
-def ptr_of(sizes, device):
-    return N.seg_ptr_of(sizes).to(device)
 
 
 @functools.lru_cache(maxsize=None)
@@ -143,7 +136,7 @@ def case_windows_and_table(device, sizes=EVENTS):
     ptr = ptr_of(sizes, device)
     for t in range(labels.shape[0]):
         tables = CM.tracking_metric_table(dev(labels[t], device), ptr=ptr, **hit_kwargs(pid, pt, eta, reco, device))
-        n_part, counts = CM._window_counts_batched(record_of(labels[t], pid, pt, eta, reco, device), ptr, win, 3)
+        n_part, counts = CM._window_counts(record_of(labels[t], pid, pt, eta, reco, device), win, 3, ptr=ptr)
         assert isinstance(tables, list) and len(tables) == len(sizes)
         assert n_part.shape == (len(sizes), len(win)) and counts.shape == (len(sizes), len(win), 4)
         for e, (a, b) in enumerate(zip(s, s[1:])):
@@ -180,7 +173,7 @@ def case_tie(device):
     assert tables[0]["maj_pid"].tolist() == [7] and tables[0]["maj_hits"].tolist() == [2]
     assert tables[1]["maj_pid"].tolist() == [3] and tables[1]["c"].tolist() == [0]
     win = np.array([[0.9, np.nan, np.nan, np.nan]], dtype=np.float32)
-    n_part, counts = CM._window_counts_batched(record_of(lab, pid, pt, eta, reco, device), ptr, win, 3)
+    n_part, counts = CM._window_counts(record_of(lab, pid, pt, eta, reco, device), win, 3, ptr=ptr)
     assert counts[:, 0, 0].tolist() == [1, 0] and n_part[:, 0].tolist() == [1, 1]
     for e, (a, b) in enumerate(((0, 5), (5, 12))):
         rows = slice(a, b)
@@ -202,7 +195,7 @@ def case_bad_label(device):
     assert bad[7] < sum(sizes), "the unbatched entries take this value"
     ptr = ptr_of(sizes, device)
     calls = (lambda: CM.tracking_metric_table(dev(bad, device), ptr=ptr, **hit_kwargs(pid, pt, eta, reco, device)),
-             lambda: CM._window_counts_batched(record_of(bad, pid, pt, eta, reco, device), ptr, windows40()[:3], 3))
+             lambda: CM._window_counts(record_of(bad, pid, pt, eta, reco, device), windows40()[:3], 3, ptr=ptr))
     for call in calls:
         try:
             call()
@@ -327,7 +320,7 @@ def case_one_event(device):
     pid, pt, eta, reco, labels = hits_of((300,))
     truth, _ = S.random_case(np.random.default_rng(5), 300, 1)
     n = 300
-    for ptr in (None, torch.tensor([0, n]), [0, n]):
+    for ptr in one_event_ptrs(n):
         kw = {} if ptr is None else {"ptr": ptr}
         table = CM.tracking_metric_table(dev(labels[0], device), **hit_kwargs(pid, pt, eta, reco, device), **kw)
         assert isinstance(table, dict)
@@ -346,26 +339,9 @@ COUNTED = ("gnntrk_cluster_table", "gnntrk_cluster_table_batched", "gnntrk_track
            "gnntrk_tracking_metrics_windows_batched")
 
 
-@contextlib.contextmanager
 def counted_calls():
-    """wraps the table and windows entries of the bound library while the block runs: {entry: number of calls}"""
-    lib = _capi.load()
-    calls = dict.fromkeys(COUNTED, 0)
-    real = {name: getattr(lib, name) for name in COUNTED}
-
-    def wrapper(name):
-        def call(*args):
-            calls[name] += 1
-            return real[name](*args)
-        return call
-
-    for name in COUNTED:
-        setattr(lib, name, wrapper(name))
-    try:
-        yield calls
-    finally:
-        for name in COUNTED:
-            setattr(lib, name, real[name])
+    """the table and windows entries: {entry: number of calls}"""
+    return batch_util.counted_calls(COUNTED)
 
 
 def rows_identical(got, want, what):

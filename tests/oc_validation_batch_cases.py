@@ -12,6 +12,7 @@ that what it is there for occurs."""
 from __future__ import annotations
 
 import functools
+from functools import partial
 
 import numpy as np
 import torch
@@ -19,6 +20,8 @@ import torch
 import gnn_tracking_amd as G
 import neighbor_cases as N
 import tracking_metrics_ref as R
+from batch_util import assert_same, counted_calls, one_event_ptrs, starts_of
+from batch_util import records_equal as _records_equal
 from gnn_tracking_amd import cluster_metrics as CM
 from gnn_tracking_amd import postprocessing, synthetic
 from gnn_tracking_amd.postprocessing import (DBSCANFastRescan, DBSCANHyperParamScannerFixed, DBSCANPerformanceDetails)
@@ -35,10 +38,6 @@ METRIC_EVENTS = (40, 0, 300, 257)
 SCAN_HITS = (1500, 1100, 700)
 SCAN_TRIALS = ({"eps": 0.15, "min_samples": 2}, {"eps": 0.2, "min_samples": 3}, {"eps": 0.25, "min_samples": 2},
                {"eps": 0.3, "min_samples": 4})
-
-
-def starts_of(sizes):
-    return [0, *np.cumsum(sizes).tolist()]
 
 
 def rescanner(device, x, max_eps, flags, sizes):
@@ -261,13 +260,6 @@ def metric_events():
     return pid, pt, eta, reco, labels
 
 
-def assert_same(got: dict, want: dict, what: str, ordered=True):
-    assert (list(got) == list(want)) if ordered else (sorted(got) == sorted(want)), f"{what}: keys {list(got)}"
-    for k, v in want.items():
-        g = float(got[k])
-        assert g == v or (g != g and v != v), f"{what}: {k} = {got[k]!r}, want {v!r}"
-
-
 def case_metrics_events(device):
     sizes = METRIC_EVENTS
     pid, pt, eta, reco, labels = metric_events()
@@ -336,6 +328,31 @@ def case_metrics_tie(device):
     assert R.tracking_metrics_flat(lab[0], pid, pt, eta, reco, (0.0, 0.9))["n_cleaned_clusters_pt0.9"] == 0
 
 
+def case_metrics_one_event(device):
+    """``ptr=None`` and ``ptr=[0, n]``: today's return types and values, from the single-event entry alone"""
+    pid, pt, eta, reco, labels = metric_events()
+    s = starts_of(METRIC_EVENTS)
+    rows = slice(s[2], s[3])
+    n, lab = METRIC_EVENTS[2], labels[(0, 2), rows]
+    assert n == 300 and lab.max() < n and (lab >= 0).any()
+    hits = dict(truth=torch.from_numpy(pid[rows]).to(device), pts=torch.from_numpy(pt[rows]).to(device),
+                eta=torch.from_numpy(eta[rows]).to(device), reconstructable=torch.from_numpy(reco[rows]).to(device))
+    entries = ("gnntrk_tracking_metrics", "gnntrk_tracking_metrics_batched")
+    first = None
+    for ptr in one_event_ptrs(n):
+        with counted_calls(entries) as calls:
+            got = CM.tracking_metrics_trials(torch.from_numpy(lab).to(device), pt_thlds=CUTS, **hits,
+                                             **({} if ptr is None else {"ptr": ptr}))
+        assert calls == {entries[0]: 1, entries[1]: 0}, calls
+        assert isinstance(got, list) and len(got) == 2
+        first = got if first is None else first
+        for t in range(2):
+            assert isinstance(got[t], dict) and [type(v) for v in got[t].values()] == [type(v) for v in first[t].values()]
+            assert_same(got[t], first[t], f"one event, trial {t}: ptr={ptr!r} against ptr=None")
+            assert_same(got[t], R.tracking_metrics_flat(lab[t], pid[rows], pt[rows], eta[rows], reco[rows], CUTS),
+                        f"one event, trial {t}")
+
+
 # --------------------------------------------------------------------------------------------- scanners end to end
 @functools.lru_cache(maxsize=None)
 def scan_events():
@@ -353,11 +370,7 @@ def scan_data(raw, device):
                   **{k: raw[k].to(device) for k in ("particle_id", "pt", "eta", "reconstructable")})
 
 
-def records_equal(got, want, what):
-    assert len(got) == len(want), f"{what}: {len(got)} records, want {len(want)}"
-    for k, (g, w) in enumerate(zip(got, want)):
-        g, w = ({c: v for c, v in r.items() if c != "i_batch"} for r in (g, w))
-        assert_same(g, w, f"{what}: record {k}")
+records_equal = partial(_records_equal, skip=("i_batch",))
 
 
 def foms_equal(got, want, what, skip=("trk.i_batch", "trk.i_batch_std")):

@@ -47,6 +47,11 @@ def test_scanner_on_a_collated_batch():
         C.case_scanner_batch(DEVICE)
 
 
+def test_scanner_one_event_is_todays_call():
+    with emulated_cpu():
+        C.case_scanner_one_event(DEVICE)
+
+
 def test_scanner_max_edges_stops_one_event(caplog):
     with emulated_cpu():
         C.case_scanner_max_edges(DEVICE, caplog)

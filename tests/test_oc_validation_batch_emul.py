@@ -81,6 +81,11 @@ def test_majority_tie_inside_the_event():
         C.case_metrics_tie(DEVICE)
 
 
+def test_tracking_metrics_one_event_is_todays_call():
+    with emulated_cpu():
+        C.case_metrics_one_event(DEVICE)
+
+
 # ------------------------------------------------------------------------------------------------------- scanners
 def test_scanner_on_a_collated_batch():
     with emulated_cpu():

@@ -57,6 +57,10 @@ def test_majority_tie_inside_the_event():
     C.case_metrics_tie(DEVICE)
 
 
+def test_tracking_metrics_one_event_is_todays_call():
+    C.case_metrics_one_event(DEVICE)
+
+
 def test_scanner_on_a_collated_batch():
     C.case_scanner_batch(DEVICE)
 
