@@ -27,7 +27,9 @@ from .cluster_metrics import (TrackingMetrics, clustering_scores_trials, cluster
                               count_hits_per_cluster, flatten_track_metrics, hits_per_cluster_count_to_flat_dict,
                               tracking_metric_table, tracking_metrics, tracking_metrics_data, tracking_metrics_trials,
                               tracking_metrics_vs_eta, tracking_metrics_vs_pt)
-from .graph_analysis import get_cc_labels, get_efficiency_purity_edges, get_largest_segment_fracs
+from .graph_analysis import (OrphanCount, TrackGraphInfo, get_all_graph_construction_stats, get_basic_counts,
+                             get_cc_labels, get_efficiency_purity_edges, get_largest_segment_fracs, get_orphan_counts,
+                             get_track_graph_info_from_data, summarize_track_graph_info)
 from .k_scanner import GraphConstructionKNNScanner, KScanResults
 from .mlp import MLP
 from .locality import node_order
@@ -57,4 +59,6 @@ __all__ = ["Data", "collate", "MLP", "InteractionNetwork", "ResIN", "ECForGraphT
            "get_largest_segment_fracs", "get_efficiency_purity_edges", "GraphConstructionKNNScanner",
            "KScanResults", "EFMLP", "EFDeepSet", "GeometricEF", "tracking_metric_table", "tracking_metrics_vs_pt",
            "tracking_metrics_vs_eta", "DBSCANPerformanceDetails", "clustering_spectra", "clustering_scores_trials",
-           "count_hits_per_cluster", "hits_per_cluster_count_to_flat_dict", "common_metrics"]
+           "count_hits_per_cluster", "hits_per_cluster_count_to_flat_dict", "common_metrics", "TrackGraphInfo",
+           "OrphanCount", "get_track_graph_info_from_data", "summarize_track_graph_info", "get_orphan_counts",
+           "get_basic_counts", "get_all_graph_construction_stats"]

@@ -301,6 +301,14 @@ _SIGNATURES = {
     "gnntrk_kscan_counts_batched_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "gnntrk_kscan_counts_batched": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _P, _P,
                                               _P, C.c_int64, _P, C.c_int32, _P, _P, _P, C.c_size_t, _P]),
+    "gnntrk_track_graph_table_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gnntrk_track_graph_table": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "gnntrk_track_graph_adjacency_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gnntrk_track_graph_adjacency": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "gnntrk_track_graph_distance_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "gnntrk_track_graph_distance": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int32, _P, C.c_size_t, _P]),
+    "gnntrk_track_graph_distance_ex": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P,
+                                                 C.c_size_t, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -13,18 +13,34 @@ and everything else is an integer count (``gnntrk_kscan_counts`` for the k-scan,
   reference: the insertion order of a Python dict filled while walking networkx's components, then a
   ``set`` difference).  Only the multiset of fractions is contract; every use in the reference is a
   mean of a comparison.
+* ``get_track_graph_info_from_data`` ranks the segments of a particle by size and, among segments of ONE size,
+  by their smallest hit index (the reference: a stable sort over the iteration order of networkx's sets, which
+  is no contract).  ``distance_largest_segments`` is measured between the first two segments of that order, so
+  it can differ from the reference's where the second-largest segment is not unique.
+
+The track-graph statistics (``analysis/graphs.py:49-278``: ``get_track_graph_info_from_data``,
+``summarize_track_graph_info``, ``get_orphan_counts``, ``get_basic_counts``,
+``get_all_graph_construction_stats``) take one event or a ``collate([...])`` batch, every event its own problem
+and a particle the pair (event, particle id).  The reference walks networkx once per particle and runs one
+shortest-path search per pair of hits of its two largest segments; here the table is two ``gnntrk_cc_labels``
+calls, integer counting and one breadth-first search per split particle (``csrc/track_graph.hip``), and comes
+back in one host copy.
 """
 
 from __future__ import annotations
+
+import typing
 
 import numpy as np
 import torch
 from torch import Tensor
 
-from . import _capi, ops
+from . import _capi, events, ops
 from .graph_masks import get_good_node_mask
 
-__all__ = ["get_cc_labels", "get_largest_segment_fracs", "get_efficiency_purity_edges"]
+__all__ = ["get_cc_labels", "get_largest_segment_fracs", "get_efficiency_purity_edges", "TrackGraphInfo",
+           "OrphanCount", "get_track_graph_info_from_data", "summarize_track_graph_info", "get_orphan_counts",
+           "get_basic_counts", "get_all_graph_construction_stats"]
 
 
 def cc_labels(edge_index: Tensor, num_nodes: int, *, same_pid: Tensor | None = None,
@@ -120,3 +136,228 @@ def get_efficiency_purity_edges(data, pt_thld: float = 0.9, max_eta: float = 4.0
     edge_mask = mask[ei[0]] | mask[ei[1]]
     counts = torch.stack([(data.y.bool() & edge_mask).sum(), (mask[te[0]] & mask[te[1]]).sum(), edge_mask.sum()])
     return efficiency_purity_from_counts(*(int(v) for v in counts.tolist()))
+
+
+# ------------------------------------------------------------------------------------ track-graph statistics
+class TrackGraphInfo(typing.NamedTuple):
+    """Information about how well connected the hits of a track are in the graph (``analysis/graphs.py:49-72``).
+
+    "Component" means connected component of the graph, "segment" a connected component of the subgraph that
+    holds only the hits of the track.
+
+    Attributes:
+        pid: the particle id of the track
+        n_hits: the number of hits of the track
+        n_segments: the number of segments of the track
+        n_hits_largest_segment: the number of hits in the largest segment of the track
+        distance_largest_segments: the shortest path length between the two largest segments
+        n_hits_largest_component: the largest number of hits of the track in one component
+    """
+
+    pid: int
+    n_hits: int
+    n_segments: int
+    n_hits_largest_segment: int
+    distance_largest_segments: int
+    n_hits_largest_component: int
+
+
+# columns of gnntrk_track_graph_table's rows (include/gnntrk.h)
+_TABLE_COLUMNS = ("event", "pid", "n_hits", "n_segments", "n_hits_largest_segment", "n_hits_largest_component",
+                  "distance_largest_segments", "segment_a", "segment_b")
+
+
+def track_graph_table(edge_index: Tensor, particle_id: Tensor, node_mask: Tensor, ptr: Tensor | None = None, *,
+                      lds_hits: int | None = None) -> dict[str, np.ndarray]:
+    """The table of ``get_track_graph_info_from_data`` for the graph ``edge_index`` (``[2, M]``) on the hits
+    ``particle_id`` / ``node_mask`` (``[n]``), ``ptr`` the row offsets of the events of a collated batch (``None``: one
+    event): two ``gnntrk_cc_labels`` calls, ``gnntrk_track_graph_adjacency``, ``gnntrk_track_graph_table`` and
+    ``gnntrk_track_graph_distance`` on one stream, then ONE host copy.  The only host read before it is the bad-edge
+    count of ``cc_labels``.  ``lds_hits``: the search keeps its bitmaps in LDS for events of at most that many hits
+    (``gnntrk_track_graph_distance_ex``; tests send small events down the workspace path with it)."""
+    _capi.require_device(edge_index, particle_id, node_mask, ptr)
+    lib = _capi.load()
+    ei = edge_index.detach().to(torch.int64).contiguous()
+    dev = ei.device
+    pid = particle_id.detach().to(device=dev, dtype=torch.int64).contiguous()
+    mask = node_mask.detach().to(device=dev, dtype=torch.uint8).contiguous()
+    n, m = int(pid.shape[0]), int(ei.shape[1])
+    if ei.dim() != 2 or ei.shape[0] != 2 or pid.dim() != 1 or tuple(mask.shape) != (n,):
+        raise ValueError(f"track_graph_table: edge_index {tuple(ei.shape)}, particle_id {tuple(pid.shape)}, node_mask "
+                         f"{tuple(mask.shape)}: expected [2, M], [n], [n]")
+    if n == 0:
+        return {c: np.zeros(0, dtype=np.float64 if c == "distance_largest_segments" else np.int64)
+                for c in _TABLE_COLUMNS}
+    if m == 0:   # (an empty tensor has no address to hand over: the self loop (0, 0) joins nothing)
+        ei, m = torch.zeros((2, 1), dtype=torch.int64, device=dev), 1
+    seg_ptr = (torch.tensor([0, n], dtype=torch.int64, device=dev) if ptr is None
+               else ptr.detach().to(device=dev, dtype=torch.int64).contiguous())
+    n_ev = int(seg_ptr.numel()) - 1
+    segments = cc_labels(ei, n, same_pid=pid)            # (raises on an end outside [0, n): its one host read)
+    components = cc_labels(ei, n, check=False)
+    p, stream = ops._p, ops._stream(ei)
+    rowptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    nbrs = torch.empty(max(2 * m, 1), dtype=torch.int32, device=dev)
+    table = torch.empty((n, len(_TABLE_COLUMNS)), dtype=torch.int64, device=dev)
+    search = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    head = torch.empty(4, dtype=torch.int64, device=dev)   # rows, searches | edges out of range, edges across events
+    ws = ops._ws(lib.gnntrk_track_graph_adjacency_workspace_bytes(n), ei)
+    _capi.check(lib.gnntrk_track_graph_adjacency(p(ei), m, n, p(seg_ptr), n_ev, p(rowptr), p(nbrs), p(head[2:]), p(ws),
+                                                 ws.numel(), stream), lib)
+    ws = ops._ws(lib.gnntrk_track_graph_table_workspace_bytes(n), ei)
+    _capi.check(lib.gnntrk_track_graph_table(p(segments), p(components), p(pid), p(mask), n, p(seg_ptr), n_ev, p(table),
+                                             p(search), p(head), p(ws), ws.numel(), stream), lib)
+    cap = int(lds_hits) if lds_hits is not None else 0
+    ws = ops._ws(lib.gnntrk_track_graph_distance_workspace_bytes(n, cap), ei)
+    args = (p(table), p(search), p(head), p(segments), p(rowptr), p(nbrs), n, p(seg_ptr), n_ev)
+    if lds_hits is None:
+        _capi.check(lib.gnntrk_track_graph_distance(*args, p(ws), ws.numel(), stream), lib)
+    else:
+        _capi.check(lib.gnntrk_track_graph_distance_ex(*args, cap, p(ws), ws.numel(), stream), lib)
+    host = torch.cat([head, seg_ptr, table.reshape(-1)]).cpu().numpy()        # the one host copy
+    (n_rows, _, n_range, n_cross), offs = host[:4].tolist(), host[4:5 + n_ev]
+    if offs[0] != 0 or offs[-1] != n or (np.diff(offs) < 0).any():
+        raise ValueError("track_graph_table: ptr must ascend from 0 to the number of hits")
+    if n_range or n_cross:
+        raise ValueError(f"track_graph_table: {n_range} edges have an end outside [0, {n}), the ends of {n_cross} edges "
+                         "lie in two events")
+    rows = host[5 + n_ev:].reshape(n, len(_TABLE_COLUMNS))[:n_rows]
+    rows = rows[np.lexsort((rows[:, 1], rows[:, 0]))]                         # by (event, pid)
+    cols = {c: np.ascontiguousarray(rows[:, i]) for i, c in enumerate(_TABLE_COLUMNS)}
+    dist = cols["distance_largest_segments"]
+    assert (dist >= -1).all(), "a row of the search list was not searched"
+    cols["distance_largest_segments"] = np.where(dist < 0, np.inf, dist.astype(np.float64))
+    return cols
+
+
+def get_track_graph_info_from_data(data, *, w: Tensor | None = None, pt_thld=0.9, threshold: float | None = None,
+                                   max_eta: float = 4.0) -> dict[str, np.ndarray]:
+    """``analysis/graphs.py:143-192``: the ``TrackGraphInfo`` of every particle that has a hit in the good-node mask,
+    as a dict of numpy columns (the project's stand-in for a DataFrame): ``pid``, ``n_hits``, ``n_segments``,
+    ``n_hits_largest_segment`` and ``n_hits_largest_component`` int64, ``distance_largest_segments`` float64 (0 for
+    an unsplit particle, ``inf`` without a path) and ``event`` int64 (0 without a batch); rows ascend by
+    ``(event, pid)``.  ``data`` is one event or a collated batch (``events.event_ptr``): a particle is the pair
+    (event, id), and an edge whose ends lie in two events is refused.
+
+    ``w``: edge weights; an edge is kept iff ``w > threshold`` (``gnntrk_threshold_compact``; a NaN weight drops the
+    edge, where the reference asserts).  ``n_hits`` counts all hits of the id, masked or not; the graph is undirected.
+    The ranking of segments of one size: module docstring."""
+    mask = get_good_node_mask(data, pt_thld=pt_thld, max_eta=max_eta)
+    ei = data.edge_index
+    if w is not None:
+        if threshold is None:
+            raise ValueError("get_track_graph_info_from_data: `w` needs a `threshold`")
+        _capi.require_device(w, ei)
+        lib = _capi.load()
+        wf = w.detach().reshape(-1).to(torch.float32).contiguous()
+        m = int(wf.shape[0])
+        if m != int(ei.shape[1]):
+            raise ValueError(f"get_track_graph_info_from_data: {m} weights for {int(ei.shape[1])} edges")
+        keep = torch.empty(m, dtype=torch.uint8, device=wf.device)
+        idx = torch.empty(max(m, 1), dtype=torch.int32, device=wf.device)
+        n_kept = torch.empty(1, dtype=torch.int64, device=wf.device)
+        ws = ops._ws(lib.gnntrk_compact_workspace_bytes(m), wf)
+        _capi.check(lib.gnntrk_threshold_compact(ops._p(wf), m, float(threshold), ops._p(keep), ops._p(idx),
+                                                 ops._p(n_kept), ops._p(ws), ws.numel(), ops._stream(wf)), lib)
+        # a dropped edge becomes the self loop (0, 0), which joins nothing: the number of kept edges stays on the device
+        ei = ei.to(torch.int64) * keep.to(torch.int64)
+    ptr = events.event_ptr(data, who="get_track_graph_info_from_data")
+    cols = track_graph_table(ei, data.particle_id, mask, None if ptr is None else ptr.to(ei.device))
+    return {c: cols[c] for c in (*TrackGraphInfo._fields, "event")}
+
+
+_SUMMARY_KEYS = ("frac_segment100", "frac_component100", "frac_segment50", "frac_component50", "frac_segment75",
+                 "frac_component75", "n_segments", "frac_hits_largest_segment", "frac_hits_largest_component")
+
+
+def summarize_track_graph_info(tgi: dict, per_event: bool = False, n_events: int | None = None):
+    """``analysis/graphs.py:195-217``: the nine figures of a table of ``get_track_graph_info_from_data`` (the
+    fractions of particles whose largest segment / component holds all, >= 75 %, >= 50 % of their hits, and three
+    means), evaluated in float64 as pandas does; an empty table gives NaN.  ``per_event``: a list with one such dict
+    per event ``0 .. n_events - 1`` (default: up to the last event that has a row) of the ``event`` column."""
+    if per_event:
+        ev = np.asarray(tgi["event"])
+        n_events = (int(ev.max()) + 1 if ev.size else 0) if n_events is None else int(n_events)
+        return [summarize_track_graph_info({k: np.asarray(v)[ev == e] for k, v in tgi.items()}) for e in range(n_events)]
+    n_hits = np.asarray(tgi["n_hits"], dtype=np.float64)
+    n = len(n_hits)
+    if n == 0:
+        return dict.fromkeys(_SUMMARY_KEYS, float("nan"))
+    seg = np.asarray(tgi["n_hits_largest_segment"], dtype=np.float64) / n_hits
+    comp = np.asarray(tgi["n_hits_largest_component"], dtype=np.float64) / n_hits
+    return {
+        "frac_segment100": int((seg == 1).sum()) / n,
+        "frac_component100": int((comp == 1).sum()) / n,
+        "frac_segment50": int((seg >= 0.50).sum()) / n,
+        "frac_component50": int((comp >= 0.50).sum()) / n,
+        "frac_segment75": int((seg >= 0.75).sum()) / n,
+        "frac_component75": int((comp >= 0.75).sum()) / n,
+        "n_segments": float(np.mean(np.asarray(tgi["n_segments"], dtype=np.float64))),
+        "frac_hits_largest_segment": float(seg.mean()),
+        "frac_hits_largest_component": float(comp.mean()),
+    }
+
+
+class OrphanCount(typing.NamedTuple):
+    """Stats about the number of orphan nodes in a graph (``analysis/graphs.py:220-232``).
+
+    Attributes:
+        n_orphan_correct: number of orphan nodes that are bad nodes (low pt or noise)
+        n_orphan_incorrect: number of orphan nodes that are good nodes
+        n_orphan_total: total number of orphan nodes
+    """
+
+    n_orphan_correct: int
+    n_orphan_incorrect: int
+    n_orphan_total: int
+
+
+def get_orphan_counts(data, *, pt_thld=0.9, max_eta: float = 4.0) -> OrphanCount:
+    """``analysis/graphs.py:235-247``: the hits without an incident edge, split by the good-node mask (over all
+    events of a batch).  DEVIATION: the reference clears entries of a mask that it has just zeroed
+    (``orphan_mask[connected_nodes] = False`` on ``zeros_like``), so it returns zeros for every graph; this is the
+    documented meaning of ``OrphanCount``.  The hit flags are ``gnntrk_connected_nodes``'."""
+    from .graph_cut import connected_nodes
+
+    n = int(data.particle_id.shape[0])
+    hit, _, _ = connected_nodes(data.edge_index, n)
+    good = get_good_node_mask(data, pt_thld=pt_thld, max_eta=max_eta)
+    orphan = ~hit
+    counts = torch.stack([(orphan & ~good).sum(), (orphan & good).sum(), orphan.sum()]).tolist()
+    return OrphanCount(*(int(v) for v in counts))
+
+
+def get_basic_counts(data, *, pt_thld: float = 0.9, max_eta: float = 4.0) -> dict[str, int]:
+    """``analysis/graphs.py:250-265``: basic counts of edges and nodes, the reference's arithmetic as written
+    (``n_true_edges_thld`` counts the edges with ``y == 0`` whose first end is a good hit), as Python ints.  On a
+    collated batch a track is the pair (event, particle id)."""
+    good = get_good_node_mask(data, pt_thld=pt_thld, max_eta=max_eta)
+    pid, ei, y = data.particle_id, data.edge_index, data.y
+    n = int(pid.shape[0])
+    ptr = events.event_ptr(data, who="get_basic_counts")
+    if ptr is None:
+        n_tracks = pid.unique().numel()
+    else:
+        event = torch.bucketize(torch.arange(n, device=pid.device), ptr.to(pid.device)[1:], right=True)
+        n_tracks = torch.unique(torch.stack([event, pid.long()], dim=1), dim=0).shape[0]
+    good_edges = (y == 0) & (good[ei[0].long()] > 0)
+    sums = torch.stack([(pid <= 0).sum(), good.sum(), y.sum(), good_edges.sum()]).tolist()
+    return {
+        "n_hits": n,
+        "n_hits_noise": int(sums[0]),
+        "n_hits_thld": int(sums[1]),
+        "n_edges": int(ei.shape[1]),
+        "n_tracks": int(n_tracks),
+        "n_true_edges": int(sums[2]),
+        "n_true_edges_thld": int(sums[3]),
+    }
+
+
+def get_all_graph_construction_stats(data, pt_thld=0.9, max_eta: float = 4.0) -> dict[str, float]:
+    """``analysis/graphs.py:268-278``: orphan counts, the summary of the track-graph table (which, as in the
+    reference, is built with the default ``max_eta``) and the basic counts of one batch."""
+    return {
+        **get_orphan_counts(data, pt_thld=pt_thld, max_eta=max_eta)._asdict(),
+        **summarize_track_graph_info(get_track_graph_info_from_data(data, pt_thld=pt_thld)),
+        **get_basic_counts(data, pt_thld=pt_thld, max_eta=max_eta),
+    }

@@ -1233,6 +1233,67 @@ int gnntrk_kscan_counts_batched(const int32_t *nbr, const int32_t *cnt, int64_t 
                                 int32_t n_seg, int64_t *out, int64_t *labels, void *workspace, size_t workspace_bytes,
                                 void *stream);
 
+/* ------------------------------------------------------------ track-graph statistics
+ * The device part of get_track_graph_info_from_data (analysis/graphs.py:143-192), which applies
+ * get_track_graph_info (graphs.py:86-140) to every selected particle of a built graph: three entries that run
+ * back to back on one stream without a host read (csrc/track_graph.hip).  All of them take the events of a
+ * collated batch as gnntrk_kscan_counts_batched does (seg_ptr device int64 [n_seg + 1], n_seg in
+ * 1..GNNTRK_KSCAN_MAX_EVENTS; one event: seg_ptr = {0, n}); a particle is the pair (event, particle id).
+ *
+ * gnntrk_track_graph_table - one row per particle that has a hit in node_mask (graphs.py:178-180; the id of such a
+ * hit must be > 0, as get_good_node_mask makes it), from
+ *   segment_labels    gnntrk_cc_labels of the graph with same_pid = particle_id: the segments (graphs.py:104-108);
+ *   component_labels  gnntrk_cc_labels of the graph without a filter (graphs.py:115-119);
+ * both int64 [n], the smallest hit index of the component.  table (int64 [n][GNNTRK_TRACK_GRAPH_COLUMNS], the first
+ * counts[0] rows are written, in no particular order) holds per row
+ *   [0] event   [1] particle id
+ *   [2] n_hits                    all hits of the id in the event, masked or not (graphs.py:101-102)
+ *   [3] n_segments                (graphs.py:136)
+ *   [4] n_hits_largest_segment    (graphs.py:126)
+ *   [5] n_hits_largest_component  the largest number of the particle's hits in one component (graphs.py:109-119)
+ *   [6] distance_largest_segments 0 for one segment, -1 if the two largest segments lie in different components
+ *                                 (no path), -2 if they share one: the row waits for gnntrk_track_graph_distance
+ *   [7] [8]                       labels of the largest and the second-largest segment (-1: none); segments of one
+ *                                 size rank by ascending label (the reference: by networkx's set order)
+ * search (int32 [n]): the counts[1] rows with [6] = -2.  counts: device int64 [2].
+ * workspace: gnntrk_track_graph_table_workspace_bytes(n).
+ *
+ * gnntrk_track_graph_adjacency - the undirected graph of to_networkx(..., to_undirected=True) (graphs.py:172) as
+ * rows: rowptr (int64 [n + 1]) and neighbors (int32 [2 * n_edges], the first rowptr[n] are written; the order
+ * inside a row is not defined).  An edge with an end outside [0, n) is left out and counted in n_bad[0], one whose
+ * ends lie in two events in n_bad[1] (device int64 [2]); a self loop is left out.
+ * workspace: gnntrk_track_graph_adjacency_workspace_bytes(n).
+ *
+ * gnntrk_track_graph_distance - shortest_path_length_multi(graph, segments[0], segments[1]) (graphs.py:121-125) for
+ * every row of the search list: the fewest edges on a path in the event's graph from a hit of the largest segment
+ * to a hit of the second-largest, written to [6] of the row (-1 if the rows hold no such path).  One workgroup per
+ * row runs a level-synchronous breadth-first search over bitmaps of the event's hits, in LDS for an event of at
+ * most 163 840 hits, else in the workspace.  gnntrk_track_graph_distance_ex: the same with that capacity given as
+ * lds_hits (1..163 840), for tests of the workspace path.
+ * workspace: gnntrk_track_graph_distance_workspace_bytes(n, lds_hits) (lds_hits < 1: the default; 0 bytes when
+ * n <= lds_hits).
+ *
+ * GNNTRK_EINVAL for n < 0, n_edges < 0, NULL seg_ptr, n_seg < 1, lds_hits out of range, NULL required pointers and
+ * a small workspace; GNNTRK_EUNSUPPORTED for n >= 2^30, n_edges >= 2^30 or n_seg > GNNTRK_KSCAN_MAX_EVENTS. */
+#define GNNTRK_TRACK_GRAPH_COLUMNS 9
+size_t gnntrk_track_graph_table_workspace_bytes(int64_t n);
+int gnntrk_track_graph_table(const int64_t *segment_labels, const int64_t *component_labels, const int64_t *particle_id,
+                             const uint8_t *node_mask, int64_t n, const int64_t *seg_ptr, int32_t n_seg, int64_t *table,
+                             int32_t *search, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+size_t gnntrk_track_graph_adjacency_workspace_bytes(int64_t n);
+int gnntrk_track_graph_adjacency(const int64_t *edge_index, int64_t n_edges, int64_t n, const int64_t *seg_ptr,
+                                 int32_t n_seg, int64_t *rowptr, int32_t *neighbors, int64_t *n_bad, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+size_t gnntrk_track_graph_distance_workspace_bytes(int64_t n, int32_t lds_hits);
+int gnntrk_track_graph_distance(int64_t *table, const int32_t *search, const int64_t *counts,
+                                const int64_t *segment_labels, const int64_t *rowptr, const int32_t *neighbors, int64_t n,
+                                const int64_t *seg_ptr, int32_t n_seg, void *workspace, size_t workspace_bytes,
+                                void *stream);
+int gnntrk_track_graph_distance_ex(int64_t *table, const int32_t *search, const int64_t *counts,
+                                   const int64_t *segment_labels, const int64_t *rowptr, const int32_t *neighbors,
+                                   int64_t n, const int64_t *seg_ptr, int32_t n_seg, int32_t lds_hits, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
