@@ -29,7 +29,8 @@ from .cluster_metrics import (TrackingMetrics, clustering_scores_trials, cluster
                               tracking_metrics_vs_eta, tracking_metrics_vs_pt)
 from .graph_analysis import (OrphanCount, TrackGraphInfo, get_all_graph_construction_stats, get_basic_counts,
                              get_cc_labels, get_efficiency_purity_edges, get_largest_segment_fracs, get_orphan_counts,
-                             get_track_graph_info_from_data, summarize_track_graph_info)
+                             get_track_graph_info_from_data, summarize_track_graph_info, ec_threshold_scan,
+                             get_all_ec_stats, collect_all_ec_stats)
 from .k_scanner import GraphConstructionKNNScanner, KScanResults
 from .mlp import MLP
 from .locality import node_order
@@ -61,4 +62,5 @@ __all__ = ["Data", "collate", "MLP", "InteractionNetwork", "ResIN", "ECForGraphT
            "tracking_metrics_vs_eta", "DBSCANPerformanceDetails", "clustering_spectra", "clustering_scores_trials",
            "count_hits_per_cluster", "hits_per_cluster_count_to_flat_dict", "common_metrics", "TrackGraphInfo",
            "OrphanCount", "get_track_graph_info_from_data", "summarize_track_graph_info", "get_orphan_counts",
-           "get_basic_counts", "get_all_graph_construction_stats"]
+           "get_basic_counts", "get_all_graph_construction_stats", "ec_threshold_scan", "get_all_ec_stats",
+           "collect_all_ec_stats"]

@@ -22,6 +22,7 @@ METRICS_MAX_CUTS, METRICS_MAX_THR, AUC_MAX_FPR, AUC_STRIDE = 8, 1024, 4, 28   # 
 TRACKING_MAX_TRIALS = 4096                                                      # gnntrk_tracking_metrics
 TRACKING_MAX_WINDOWS = 32                                                       # gnntrk_tracking_metrics_windows
 KSCAN_COLUMNS, KSCAN_MAX_KS = 9, 64                                             # gnntrk_kscan_counts
+EC_SCAN_MAX_THR = 256                                                           # gnntrk_ec_scan_prepare
 
 _PKG = pathlib.Path(__file__).resolve().parent
 LIB_PATH = _PKG / "libgnntrk.so"
@@ -309,6 +310,10 @@ _SIGNATURES = {
     "gnntrk_track_graph_distance": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int32, _P, C.c_size_t, _P]),
     "gnntrk_track_graph_distance_ex": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P,
                                                  C.c_size_t, _P]),
+    "gnntrk_ec_scan_prepare_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "gnntrk_ec_scan_prepare": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int32, _P, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32,
+                                         C.c_int32, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "gnntrk_ec_scan_steps": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int64, _P, _P, C.c_size_t, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -166,6 +166,16 @@ __device__ __forceinline__ void event_add(uint32_t (&v)[NV], int e, unsigned lon
     for (int k = 0; k < NV; ++k) v[k] = 0u;
 }
 
+// ----------------------------------------------------------------------------- edge labels
+// positive iff int(y) == 1 (BinaryClassificationStats: y.int() == 1), for labels held as bytes or as float32
+template <class Y> __device__ __forceinline__ uint32_t is_positive(const Y *y, int64_t i);
+template <> __device__ __forceinline__ uint32_t is_positive<uint8_t>(const uint8_t *y, int64_t i) { return y[i] == 1; }
+// int(v) == 1 (truncation toward zero) for every finite v; NaN compares false
+template <> __device__ __forceinline__ uint32_t is_positive<float>(const float *y, int64_t i) {
+    const float v = y[i];
+    return v >= 1.f && v < 2.f;
+}
+
 // -------------------------------------------------------------------------------- pt cuts
 struct Cuts {   // (a kernel argument by value: nothing to upload)
     float v[GNNTRK_METRICS_MAX_CUTS];

@@ -35,14 +35,6 @@ struct Fprs {   // (kernel arguments by value: nothing to upload)
     double v[kMaxFpr];
 };
 
-template <class Y> __device__ __forceinline__ uint32_t is_positive(const Y *y, int64_t i);
-template <> __device__ __forceinline__ uint32_t is_positive<uint8_t>(const uint8_t *y, int64_t i) { return y[i] == 1; }
-// int(v) == 1 (truncation toward zero) for every finite v; NaN compares false
-template <> __device__ __forceinline__ uint32_t is_positive<float>(const float *y, int64_t i) {
-    const float v = y[i];
-    return v >= 1.f && v < 2.f;
-}
-
 template <class ID>
 __device__ __forceinline__ int cut_class(const ID *src, const ID *tgt, const float *pt, int64_t i, const Cuts &cuts) {
     if (!pt) return cuts.n;

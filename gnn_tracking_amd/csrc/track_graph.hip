@@ -40,6 +40,7 @@
 #include <stdio.h>
 
 #include "count_util.h"
+#include "track_graph_util.h"
 
 namespace gnntrk {
 namespace {
@@ -53,29 +54,6 @@ constexpr int kSearchBlocksPerCu = 2;         // (what the LDS of a CU holds)
 // columns of a row
 enum { T_EVENT = 0, T_PID, T_HITS, T_SEGMENTS, T_LARGEST_SEGMENT, T_LARGEST_COMPONENT, T_DISTANCE, T_SEG_A, T_SEG_B };
 constexpr int64_t kNoPath = -1, kPending = -2;   // T_DISTANCE: no path / waits for the search
-
-__device__ __forceinline__ void max_u64(unsigned long long *p, unsigned long long v) {
-#ifdef __HIP_DEVICE_COMPILE__
-    atomicMax(p, v);
-#else
-    unsigned long long old = __atomic_load_n(p, __ATOMIC_RELAXED);
-    while (old < v && !__atomic_compare_exchange_n(p, &old, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {
-    }
-#endif
-}
-
-// the rows [lo, hi) of the event of hit i, clipped to [0, n): whatever seg_ptr holds, an index inside them is a hit
-__device__ __forceinline__ int tg_event_rows(const Events &ev, int64_t n, int64_t i, int64_t &lo, int64_t &hi) {
-    const int e = event_rows<true>(ev, n, i, lo, hi);
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > n ? n : hi;
-    return e;
-}
-
-__device__ __forceinline__ unsigned long long seg_key(uint32_t size, int64_t label) {
-    return ((unsigned long long)size << 32) | (unsigned long long)(0xffffffffu - (uint32_t)label);
-}
-__device__ __forceinline__ int64_t key_label(unsigned long long key) { return (int64_t)(0xffffffffu - (uint32_t)key); }
 
 // --------------------------------------------------------------------------- the table
 struct Ws {
@@ -329,20 +307,6 @@ size_t bitmap_words(int64_t n) { return (size_t)ceil_div(n < 1 ? 1 : n, 32); }
 size_t distance_ws_bytes(int64_t n, int32_t lds_hits) {
     if (n <= lds_hits) return 0;   // every event fits the LDS bitmaps
     return align_up((size_t)search_blocks(n) * 3 * bitmap_words(n) * sizeof(uint32_t), 256);
-}
-
-int check_events(const char *entry, const int64_t *seg_ptr, int32_t n_seg) {
-    char msg[160];
-    if (!seg_ptr || n_seg < 1) {
-        snprintf(msg, sizeof(msg), "%s: seg_ptr needs n_seg >= 1 events", entry);
-        return fail(GNNTRK_EINVAL, msg);
-    }
-    if (n_seg > GNNTRK_KSCAN_MAX_EVENTS) {
-        snprintf(msg, sizeof(msg), "%s: n_seg = %d, at most %d events per call", entry, (int)n_seg,
-                 GNNTRK_KSCAN_MAX_EVENTS);
-        return fail(GNNTRK_EUNSUPPORTED, msg);
-    }
-    return GNNTRK_OK;
 }
 
 int distance(int64_t *table, const int32_t *search, const int64_t *counts, const int64_t *segment_labels,

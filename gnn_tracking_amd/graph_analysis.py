@@ -25,10 +25,16 @@ and a particle the pair (event, particle id).  The reference walks networkx once
 shortest-path search per pair of hits of its two largest segments; here the table is two ``gnntrk_cc_labels``
 calls, integer counting and one breadth-first search per split particle (``csrc/track_graph.hip``), and comes
 back in one host copy.
+
+The EC threshold scan (``analysis/edge_classification.py:24-112``: ``get_all_ec_stats``, ``collect_all_ec_stats``) is
+``ec_threshold_scan``: the binary-classification counts and the summary of the track-graph table for ALL thresholds of
+a list from one pass over the edges and two union-find forests that grow from the largest threshold to the smallest
+(``csrc/ec_scan.hip``), with one host read and one host copy per scan.
 """
 
 from __future__ import annotations
 
+import types
 import typing
 
 import numpy as np
@@ -36,11 +42,14 @@ import torch
 from torch import Tensor
 
 from . import _capi, events, ops
+from .edge_order import as_tensor
 from .graph_masks import get_good_node_mask
+from .metrics import _thresholds_from_counts, bcs_from_counts
 
 __all__ = ["get_cc_labels", "get_largest_segment_fracs", "get_efficiency_purity_edges", "TrackGraphInfo",
            "OrphanCount", "get_track_graph_info_from_data", "summarize_track_graph_info", "get_orphan_counts",
-           "get_basic_counts", "get_all_graph_construction_stats"]
+           "get_basic_counts", "get_all_graph_construction_stats", "ec_threshold_scan", "get_all_ec_stats",
+           "collect_all_ec_stats"]
 
 
 def cc_labels(edge_index: Tensor, num_nodes: int, *, same_pid: Tensor | None = None,
@@ -361,3 +370,177 @@ def get_all_graph_construction_stats(data, pt_thld=0.9, max_eta: float = 4.0) ->
         **summarize_track_graph_info(get_track_graph_info_from_data(data, pt_thld=pt_thld)),
         **get_basic_counts(data, pt_thld=pt_thld, max_eta=max_eta),
     }
+
+
+# ------------------------------------------------------------------------------------------ EC threshold scan
+def _scan_records(thresholds, inverse, counts, orphans, summaries):
+    """the records of one event (or of all events together) in the caller's order: ``counts`` int64
+    [2 mask classes][2 labels][n_thr + 1], ``summaries`` one dict per ascending threshold"""
+    rates = []
+    for c in (counts[0] + counts[1], counts[1]):           # all edges | both ends in the good-node mask
+        tp, fp, P, N = _thresholds_from_counts(c)
+        rates.append([bcs_from_counts(int(a), int(b), P, N) for a, b in zip(tp.tolist(), fp.tolist())])
+    orphan = OrphanCount(*(int(v) for v in orphans))._asdict()
+    return [{"threshold": t, **rates[0][j], **{f"{k}_thld": v for k, v in rates[1][j].items()}, **orphan, **summaries[j]}
+            for t, j in zip(thresholds, inverse)]
+
+
+def ec_threshold_scan(data, w, thresholds, *, pt_thld=0.9, max_eta=4.0, per_event=False):
+    """``get_all_ec_stats`` (``analysis/edge_classification.py:24-64``) for every entry of ``thresholds``: a list
+    with one record per entry, in the given order (unsorted input and duplicates are fine; at most 256 different
+    float32 values).  A record holds ``threshold`` (the caller's value), the twelve keys of
+    ``BinaryClassificationStats.get_all()`` over all edges, the same with the suffix ``_thld`` over the edges whose both
+    ends are in the good-node mask, the three ``OrphanCount`` fields of the uncut graph and the nine keys of
+    ``summarize_track_graph_info`` of the graph cut at the threshold.  It equals the composition of those functions
+    bit for bit:
+
+    * an edge is in the graph of ``t`` iff ``w > t`` in float32 (a NaN weight: in none), and is predicted true iff
+      ``not (w < t)`` (a NaN score: always) - an edge with ``w == t`` counts as predicted true and is NOT in the graph;
+    * a label is positive iff ``int(y) == 1``; segments unite same-id edges, components all edges; ``n_hits`` counts all
+      hits of the id; a particle is selected iff one of its hits is in the good-node mask;
+    * ``get_orphan_counts`` as documented there (the reference returns zeros).
+
+    ``distance_largest_segments`` is NOT computed: no key of the summary reads it, and it is what the single-threshold
+    table spends most of its time on.  ``data`` is one event or a ``collate([...])`` batch (``events.event_ptr``), a
+    particle the pair (event, id); ``per_event=True`` returns one such list per event, with the classification and
+    orphan counts of that event's edges and hits.  An edge with an end outside ``[0, n)`` or with its ends in two
+    events raises ``ValueError`` before any record is built.  ``w`` may be an ``edge_order.EdgeOrdered``.
+
+    The graphs of the thresholds are nested, so every edge is united once per scan (``gnntrk_ec_scan_prepare`` /
+    ``gnntrk_ec_scan_steps``); the host reads four counters to size the output and copies everything back once."""
+    st = _scan_prepare(data, w, thresholds, pt_thld, max_eta, per_event)
+    if st.n_thr == 0:
+        return [[] for _ in range(st.n_ev)] if per_event else []
+    _scan_steps(st)
+    return _scan_finish(st)
+
+
+def _scan_prepare(data, w, thresholds, pt_thld, max_eta, per_event):
+    """the checks of ``ec_threshold_scan``, ``gnntrk_ec_scan_prepare`` and the scan's one host read"""
+    st = types.SimpleNamespace(per_event=bool(per_event))
+    st.given = [float(t) for t in thresholds]
+    thr32 = np.asarray(st.given, dtype=np.float32)
+    if np.isnan(thr32).any():
+        raise ValueError("ec_threshold_scan: a threshold is NaN")
+    uniq, st.inverse = np.unique(thr32, return_inverse=True)
+    st.n_thr = n_thr = len(uniq)
+    if n_thr > _capi.EC_SCAN_MAX_THR:
+        raise ValueError(f"ec_threshold_scan: {n_thr} different thresholds, at most {_capi.EC_SCAN_MAX_THR} per scan")
+    wt = as_tensor(w).detach().reshape(-1)
+    ei, y = data.edge_index, data.y.detach().reshape(-1)
+    _capi.require_device(wt, ei, y, data.particle_id)
+    mask = get_good_node_mask(data, pt_thld=pt_thld, max_eta=max_eta)
+    st.lib = lib = _capi.load()
+    st.ei = ei = ei.detach().to(torch.int64).contiguous()
+    dev = ei.device
+    wf = wt.to(device=dev, dtype=torch.float32).contiguous()
+    st.pid = pid = data.particle_id.detach().to(device=dev, dtype=torch.int64).contiguous()
+    mask = mask.detach().to(device=dev, dtype=torch.uint8).contiguous()
+    st.n, st.m = n, m = int(pid.shape[0]), int(ei.shape[1])
+    if ei.dim() != 2 or ei.shape[0] != 2 or tuple(mask.shape) != (n,):
+        raise ValueError(f"ec_threshold_scan: edge_index {tuple(ei.shape)}, {n} hits: expected [2, M]")
+    if int(wf.shape[0]) != m or int(y.shape[0]) != m:
+        raise ValueError(f"ec_threshold_scan: {int(wf.shape[0])} weights and {int(y.shape[0])} labels for {m} edges")
+    if y.dtype in (torch.bool, torch.uint8):       # (the y_kind of metrics._Edges)
+        y, y_kind = y.contiguous().view(torch.uint8), 0
+    elif y.dtype == torch.float32:
+        y, y_kind = y.contiguous(), 1
+    else:
+        y, y_kind = (y.int() == 1).view(torch.uint8), 0
+    y = y.to(dev)
+    ptr = events.event_ptr(data, who="ec_threshold_scan")
+    seg_ptr = (torch.tensor([0, n], dtype=torch.int64, device=dev) if ptr is None
+               else ptr.detach().to(device=dev, dtype=torch.int64).contiguous())
+    st.n_ev = n_ev = int(seg_ptr.numel()) - 1
+    st.n_out = n_out = n_ev if per_event else 1
+    if n_thr == 0:
+        return st
+    if n == 0 and m > 0:
+        raise ValueError(f"ec_threshold_scan: {m} edges have an end outside [0, 0), the ends of 0 edges lie in two events")
+    nb = n_thr + 1
+    thr = torch.from_numpy(uniq).to(dev)
+    head = torch.empty(4, dtype=torch.int64, device=dev)
+    st.particles = torch.empty((max(n, 1), 3), dtype=torch.int64, device=dev)
+    st.tail = torch.empty(n_out * (4 * nb + 3), dtype=torch.int64, device=dev)   # bcs | orphans
+    bcs, orphans = st.tail[:n_out * 4 * nb], st.tail[n_out * 4 * nb:]
+    st.ws = ws = ops._ws(lib.gnntrk_ec_scan_prepare_workspace_bytes(n, m, n_thr), ei)
+    p, st.stream = ops._p, ops._stream(ei)
+    _capi.check(lib.gnntrk_ec_scan_prepare(_addr(ei), m, _addr(wf), _addr(y), y_kind, _addr(pid), _addr(mask), n,
+                                           p(seg_ptr), n_ev, p(thr), n_thr, int(st.per_event), p(head), p(st.particles),
+                                           p(bcs), p(orphans), p(ws), ws.numel(), st.stream), lib)
+    first = torch.cat([head, seg_ptr]).cpu().numpy()                          # the one host read
+    (st.n_rows, _, n_range, n_cross), offs = first[:4].tolist(), first[4:]
+    if offs[0] != 0 or offs[-1] != n or (np.diff(offs) < 0).any():
+        raise ValueError("ec_threshold_scan: ptr must ascend from 0 to the number of hits")
+    if n_range or n_cross:
+        raise ValueError(f"ec_threshold_scan: {n_range} edges have an end outside [0, {n}), the ends of {n_cross} edges "
+                         "lie in two events")
+    return st
+
+
+def _addr(t: Tensor):
+    return ops._p(t) if t.numel() else None   # (an empty tensor has no address to hand over)
+
+
+def _scan_steps(st) -> None:
+    """``gnntrk_ec_scan_steps`` into a buffer sized by the particles that ``_scan_prepare`` read back"""
+    n_steps = st.n_thr * st.n_rows * 3
+    st.steps = torch.empty(n_steps + (n_steps & 1), dtype=torch.int32, device=st.ei.device)   # (even: copied as int64)
+    _capi.check(st.lib.gnntrk_ec_scan_steps(_addr(st.ei), st.m, _addr(st.pid), st.n, st.n_thr, st.n_rows, _addr(st.steps),
+                                            ops._p(st.ws), st.ws.numel(), st.stream), st.lib)
+
+
+def _scan_finish(st):
+    """the one host copy and the records"""
+    n_rows, n_out, n_thr, nb = st.n_rows, st.n_out, st.n_thr, st.n_thr + 1
+    host = torch.cat([st.particles[:n_rows].reshape(-1), st.tail, st.steps.view(torch.int64)]).cpu().numpy()
+    rows = host[:3 * n_rows].reshape(n_rows, 3)
+    counts = host[3 * n_rows:3 * n_rows + n_out * 4 * nb].reshape(n_out, 2, 2, nb)
+    orph = host[3 * n_rows + n_out * 4 * nb:3 * n_rows + n_out * (4 * nb + 3)].reshape(n_out, 3)
+    steps = host[3 * n_rows + n_out * (4 * nb + 3):].view(np.int32)[:n_thr * n_rows * 3].reshape(n_thr, n_rows, 3)
+    order = np.lexsort((rows[:, 1], rows[:, 0]))                              # by (event, pid), as track_graph_table
+    rows, steps = rows[order], steps[:, order].astype(np.int64)
+
+    def summaries(sel):
+        return [summarize_track_graph_info({"n_hits": rows[sel, 2], "n_segments": steps[j, sel, 0],
+                                            "n_hits_largest_segment": steps[j, sel, 1],
+                                            "n_hits_largest_component": steps[j, sel, 2]}) for j in range(n_thr)]
+
+    if not st.per_event:
+        return _scan_records(st.given, st.inverse, counts[0], orph[0], summaries(slice(None)))
+    return [_scan_records(st.given, st.inverse, counts[e], orph[e], summaries(rows[:, 0] == e)) for e in range(st.n_ev)]
+
+
+def get_all_ec_stats(threshold: float, w, data, *, pt_thld=0.9, max_eta=4) -> dict[str, float]:
+    """``analysis/edge_classification.py:24-64``: edge-classification and graph-construction performance of one batch
+    at one threshold - ``ec_threshold_scan`` with a single threshold (see there for the keys and the semantics)."""
+    return ec_threshold_scan(data, w, [threshold], pt_thld=pt_thld, max_eta=max_eta)[0]
+
+
+def collect_all_ec_stats(model, data_loader, thresholds, n_batches: int | None = None, max_workers=6,
+                         pt_thld=0.9) -> dict[str, np.ndarray]:
+    """``analysis/edge_classification.py:67-112``: ``get_all_ec_stats`` at every threshold for the first ``n_batches``
+    batches of ``data_loader`` (``w = model(data)["W"]`` under ``model.eval()`` and ``torch.no_grad()``, one
+    ``ec_threshold_scan`` per batch), then per threshold the mean over the batches of every key and
+    ``f"{key}_err" = np.std(values) / sqrt(number of batches)``.  Returns a dict of columns of length
+    ``len(thresholds)`` (the project's stand-in for a DataFrame).  ``max_workers`` is accepted for the reference's
+    signature and ignored: there is no host loop over thresholds to spread."""
+    thresholds = list(thresholds)
+    model.eval()
+    r = []
+    with torch.no_grad():
+        for idx, data in enumerate(data_loader):
+            r.append(ec_threshold_scan(data, model(data)["W"], thresholds, pt_thld=pt_thld))
+            if n_batches is not None and idx >= n_batches - 1:
+                break
+    if not r or not thresholds:
+        return {}
+    n = len(r)
+    cols: dict[str, list] = {}
+    for i in range(len(thresholds)):
+        batched = {k: np.array([records[i][k] for records in r]) for k in r[0][0]}
+        for k, batch in batched.items():
+            cols.setdefault(k, []).append(np.mean(batch))
+        for k, batch in batched.items():
+            cols.setdefault(f"{k}_err", []).append(np.std(batch) / np.sqrt(n))
+    return {k: np.array(v) for k, v in cols.items()}

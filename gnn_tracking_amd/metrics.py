@@ -33,8 +33,8 @@ from torch import Tensor
 from . import _capi, ops
 from .edge_order import as_tensor
 
-__all__ = ["BinaryClassificationStats", "zero_divide", "get_maximized_bcs", "roc_auc_score", "get_roc_auc_scores",
-           "ec_validation_metrics", "denote_pt"]
+__all__ = ["BinaryClassificationStats", "bcs_from_counts", "zero_divide", "get_maximized_bcs", "roc_auc_score",
+           "get_roc_auc_scores", "ec_validation_metrics", "denote_pt"]
 
 
 def zero_divide(a: float, b: float) -> float:
@@ -200,6 +200,19 @@ def _auc_from_row(row: np.ndarray, fprs) -> list[float]:
     return res
 
 
+def bcs_from_counts(TP: int, FP: int, P: int, N: int) -> dict[str, float]:
+    """``BinaryClassificationStats.get_all()`` (binary_classification.py:14-132) from the exact counts of one
+    threshold: true and false positives, positives ``P`` and negatives ``N``, as Python ints.  The reference's
+    expressions with ``zero_divide``; the class and the EC threshold scan (``graph_analysis.ec_threshold_scan``) share
+    them."""
+    FN, TN = P - TP, N - FP
+    TPR, TNR = zero_divide(TP, TP + FN), zero_divide(TN, TN + FP)
+    return {"acc": zero_divide(TP + TN, TP + TN + FP + FN), "TPR": TPR, "TNR": TNR, "FPR": zero_divide(FP, FP + TN),
+            "FNR": zero_divide(FN, FN + TP), "balanced_acc": (TPR + TNR) / 2, "F1": zero_divide(2 * TP, 2 * TP + FP + FN),
+            "MCC": zero_divide(TP * TN - FP * FN, np.sqrt(float((TP + FP) * (TP + FN) * (TN + FP) * (TN + FN)))),
+            "n_true": P, "n_false": N, "n_predicted_true": TP + FP, "n_predicted_false": TN + FN}
+
+
 # ---------------------------------------------------------------------- public API
 class BinaryClassificationStats:
     def __init__(self, output: Tensor, y: Tensor, thld: Tensor | float):
@@ -248,53 +261,16 @@ class BinaryClassificationStats:
     def TN(self) -> int:
         return self.n_false - self.FP
 
-    @property
-    def n_predicted_true(self) -> int:
-        return self.TP + self.FP
-
-    @property
-    def n_predicted_false(self) -> int:
-        return self.TN + self.FN
-
-    @property
-    def acc(self) -> float:
-        return zero_divide(self.TP + self.TN, self.TP + self.TN + self.FP + self.FN)
-
-    @property
-    def TPR(self) -> float:
-        return zero_divide(self.TP, self.TP + self.FN)
-
-    @property
-    def TNR(self) -> float:
-        return zero_divide(self.TN, self.TN + self.FP)
-
-    @property
-    def FPR(self) -> float:
-        return zero_divide(self.FP, self.FP + self.TN)
-
-    @property
-    def FNR(self) -> float:
-        return zero_divide(self.FN, self.FN + self.TP)
-
-    @property
-    def balanced_acc(self) -> float:
-        return (self.TPR + self.TNR) / 2
-
-    @property
-    def F1(self) -> float:
-        return zero_divide(2 * self.TP, 2 * self.TP + self.FP + self.FN)
-
-    @property
-    def MCC(self) -> float:
-        return zero_divide(self.TP * self.TN - self.FP * self.FN,
-                           np.sqrt(float((self.TP + self.FP) * (self.TP + self.FN) * (self.TN + self.FP)
-                                         * (self.TN + self.FN))))
-
     def get_all(self) -> dict[str, float]:
-        return {"acc": self.acc, "TPR": self.TPR, "TNR": self.TNR, "FPR": self.FPR, "FNR": self.FNR,
-                "balanced_acc": self.balanced_acc, "F1": self.F1, "MCC": self.MCC, "n_true": self.n_true,
-                "n_false": self.n_false, "n_predicted_true": self.n_predicted_true,
-                "n_predicted_false": self.n_predicted_false}
+        return bcs_from_counts(*self._counts())
+
+
+def _bcs_property(key):
+    return property(lambda self: self.get_all()[key])
+
+
+for _key in ("n_predicted_true", "n_predicted_false", "acc", "TPR", "TNR", "FPR", "FNR", "balanced_acc", "F1", "MCC"):
+    setattr(BinaryClassificationStats, _key, _bcs_property(_key))
 
 
 def get_maximized_bcs(*, output: Tensor, y: Tensor, n_samples=200) -> dict[str, float]:

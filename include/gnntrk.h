@@ -1294,6 +1294,49 @@ int gnntrk_track_graph_distance_ex(int64_t *table, const int32_t *search, const 
                                    int64_t n, const int64_t *seg_ptr, int32_t n_seg, int32_t lds_hits, void *workspace,
                                    size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------- EC threshold scan
+ * The device part of get_all_ec_stats / collect_all_ec_stats (analysis/edge_classification.py:24-112) for ALL
+ * thresholds of a list at once (csrc/ec_scan.hip): per threshold t the binary-classification counts of the edge
+ * scores and, per selected particle, three figures of the graph of the edges with w > t.  Two entries on one stream
+ * share one caller-owned workspace of gnntrk_ec_scan_prepare_workspace_bytes(n, n_edges, n_thr) bytes, which the
+ * caller leaves alone between them; the caller reads head[0] in between to size `steps`.  Events: seg_ptr / n_seg as
+ * for the track-graph entries; a particle is the pair (event, particle id).
+ *
+ * gnntrk_ec_scan_prepare - once per scan.
+ *   edge_index  int64 [2][n_edges];  w float32 [n_edges];  y [n_edges]: bytes (y_kind 0, positive iff == 1) or
+ *               float32 (y_kind 1, positive iff int(y) == 1), as gnntrk_bcs_counts;  particle_id int64 [n];
+ *               node_mask uint8 [n] (the id of a masked hit must be > 0)
+ *   thresholds  DEVICE float32 [n_thr], strictly ascending, n_thr in 1..GNNTRK_EC_SCAN_MAX_THR
+ *   per_event   0: one set of counts over all events; else one per event
+ *   head        device int64 [4]: selected particles P, 0, edges with an end outside [0, n), edges across two events.
+ *               Either kind of bad edge is in no graph; the caller refuses the call when one is counted.
+ *   particles   int64 [n][3], the first P rows written in no particular order: event, particle id, n_hits (all hits
+ *               of the id in the event).  The row number of a particle is its row in `steps`.
+ *   bcs         int64 [E][2][2][n_thr + 1] (E = n_seg with per_event, else 1): edges per event (of the first end),
+ *               mask class (1: both ends in node_mask), label and bin k = #{j : !(w < t_j)} (a NaN score: bin n_thr).
+ *               TP / FP of threshold j are the sums over the bins > j; an edge with an end outside [0, n) is in no bin.
+ *   orphans     int64 [E][3]: hits that are no end of any edge of edge_index, outside node_mask | inside | all
+ * An edge is in the graph of threshold j iff w > t_j (a NaN weight: in none): its graph bin g = #{j : w > t_j}.
+ *
+ * gnntrk_ec_scan_steps - the thresholds from the largest to the smallest on two union-find forests that are never
+ * reset (every edge is united once).  steps: int32 [n_thr][n_particles][3], n_particles = head[0]; steps[j][r] =
+ * n_segments, n_hits_largest_segment, n_hits_largest_component of the particle of row r in the graph of threshold j
+ * (the columns of gnntrk_track_graph_table).  distance_largest_segments is not part of the scan.
+ *
+ * GNNTRK_EINVAL for n < 0, n_edges < 0, n_thr < 1, NULL seg_ptr, n_seg < 1, y_kind not 0 / 1, n_particles outside
+ * 0..n, NULL required pointers and a small or NULL workspace; GNNTRK_EUNSUPPORTED for n >= 2^30, n_edges >= 2^30,
+ * n_thr > GNNTRK_EC_SCAN_MAX_THR or n_seg > GNNTRK_KSCAN_MAX_EVENTS.  n == 0 and n_edges == 0 succeed. */
+#define GNNTRK_EC_SCAN_MAX_THR 256
+size_t gnntrk_ec_scan_prepare_workspace_bytes(int64_t n, int64_t n_edges, int32_t n_thr);
+int gnntrk_ec_scan_prepare(const int64_t *edge_index, int64_t n_edges, const float *w, const void *y, int32_t y_kind,
+                           const int64_t *particle_id, const uint8_t *node_mask, int64_t n, const int64_t *seg_ptr,
+                           int32_t n_seg, const float *thresholds, int32_t n_thr, int32_t per_event, int64_t *head,
+                           int64_t *particles, int64_t *bcs, int64_t *orphans, void *workspace, size_t workspace_bytes,
+                           void *stream);
+int gnntrk_ec_scan_steps(const int64_t *edge_index, int64_t n_edges, const int64_t *particle_id, int64_t n,
+                         int32_t n_thr, int64_t n_particles, int32_t *steps, void *workspace, size_t workspace_bytes,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif
