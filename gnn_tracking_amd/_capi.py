@@ -314,6 +314,14 @@ _SIGNATURES = {
     "gnntrk_ec_scan_prepare": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int32, _P, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32,
                                          C.c_int32, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "gnntrk_ec_scan_steps": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int64, _P, _P, C.c_size_t, _P]),
+    "gnntrk_graph_builder_count_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, _P, C.c_int32]),
+    "gnntrk_graph_builder_count": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P,
+                                             C.c_size_t, _P]),
+    "gnntrk_graph_builder_fill": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, _P, C.c_int32, _P, _P, C.c_int32, _P,
+                                            C.c_int64, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "gnntrk_graph_builder_truth_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gnntrk_graph_builder_truth": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P,
+                                             _P, C.c_size_t, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

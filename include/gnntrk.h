@@ -1337,6 +1337,59 @@ int gnntrk_ec_scan_steps(const int64_t *edge_index, int64_t n_edges, const int64
                          int32_t n_thr, int64_t n_particles, int32_t *steps, void *workspace, size_t workspace_bytes,
                          void *stream);
 
+/* ------------------------------------------------------------------- geometric graph builder
+ * The device part of GraphBuilder.build_edges / correct_truth_labels / get_n_truth_edges and of the measurement
+ * record (graph_construction/graph_builder.py:162-394, 457-469, 531-549): the edges between the hits of the layer
+ * pairs of a list that pass the cuts, in the reference's order (csrc/graph_builder.hip).  Events: seg_ptr / n_seg as
+ * for the track-graph entries; pairs are formed inside an event only and the edges are event-major.
+ *
+ *   x        float32 [n][x_stride], columns 0..2 = r, phi, z;  layer int64 [n], a hit on a layer outside
+ *            [0, GNNTRK_GB_MAX_LAYERS) is counted and takes part in no pair
+ *   pairs    HOST int32 [n_pairs][2] (layer 1, layer 2), n_pairs <= GNNTRK_GB_MAX_PAIRS
+ *   radius   HOST float64 [n_pairs]: radius of the intersecting-line cut of the pair, 0 for none
+ *   cuts     HOST float64 [4]: phi_slope_max, z0_max, dR_max, remove_intersecting (0 / not 0)
+ * A pair of hits (1 on layer 1, 2 on layer 2) is an edge iff, all in float64 from the float32 columns with IEEE
+ * division: |dphi / dr| < phi_slope_max, |z1 - r1 dz / dr| < z0_max, sqrt(deta^2 + dphi^2) < dR_max and, with
+ * remove_intersecting and a radius, NOT -490.975 < radius dz / dr + z0 < 490.975; dphi = phi2 - phi1, reduced by 2 pi
+ * if > pi, then raised by 2 pi if < -pi; eta = -log(tan(atan2(r, z) / 2)).  Order: event, pair, hit 1, hit 2, the hits
+ * ascending in index.
+ *
+ * gnntrk_graph_builder_count - groups the hits, counts the edges of every row (event, pair, hit 1) and scans the
+ *   counts.  head: device int64 [2] = number of edges, hits on a layer out of range.  The workspace
+ *   (gnntrk_graph_builder_count_workspace_bytes, 0 for n <= 0 or no pairs) keeps the groups and the offsets for
+ * gnntrk_graph_builder_fill - the same arguments and workspace, n_edges = head[0] read by the caller: writes edge_index
+ *   int64 [2][n_edges], edge_attr float32 [4][n_edges] = dr / 1000, dphi / pi, dz / 1000, dR (rounded once from float64),
+ *   y float32 [n_edges] = (id 1 == id 2 and id 1 > 0), edge_pt float32 [n_edges] = pt of hit 1 and edge_ptr int64
+ *   [n_seg + 1], the first edge of every event.  Count and fill decide with one device function.
+ * gnntrk_graph_builder_truth - for the edges of a fill (or none: n_edges = 0): with `relabel`, a true edge of a
+ *   particle (event, id > 0) from a barrel layer 7..10 to layer 6 or 11 becomes false when the particle's true edges
+ *   hold more than one such layer pair and a pair of a higher barrel layer among them (correct_truth_labels); then
+ *   counts int64 [n_seg][GNNTRK_GB_COUNTS] per event: edges, true edges, true edges with edge_pt > 0, 0.1, 0.5, 0.9, 1.0
+ *   (float32 comparisons), relabelled edges, the five n_truth_edges of get_n_truth_edges (per particle with id > 0 the
+ *   products of its hit counts on consecutive occupied layers, counted where the pt of its first hit is > the cut),
+ *   hits on a layer out of range.  workspace: gnntrk_graph_builder_truth_workspace_bytes(n).
+ *
+ * GNNTRK_EINVAL for n < 0, n_edges < 0, NULL seg_ptr, n_seg < 1, a pair or radius out of range, x_stride < 3, NULL
+ * required pointers and a small or NULL workspace; GNNTRK_EUNSUPPORTED for n >= 2^30, n_edges >= 2^30, more than
+ * 2^30-1 rows, n_pairs > GNNTRK_GB_MAX_PAIRS or n_seg > GNNTRK_KSCAN_MAX_EVENTS.  n == 0 succeeds. */
+#define GNNTRK_GB_MAX_LAYERS 64
+#define GNNTRK_GB_MAX_PAIRS 128
+#define GNNTRK_GB_COUNTS 14
+size_t gnntrk_graph_builder_count_workspace_bytes(int64_t n, int32_t n_seg, const int32_t *pairs, int32_t n_pairs);
+int gnntrk_graph_builder_count(const float *x, int64_t x_stride, const int64_t *layer, int64_t n, const int64_t *seg_ptr,
+                               int32_t n_seg, const int32_t *pairs, const double *radius, int32_t n_pairs,
+                               const double *cuts, int64_t *head, void *workspace, size_t workspace_bytes, void *stream);
+int gnntrk_graph_builder_fill(const float *x, int64_t x_stride, const int64_t *layer, const int64_t *particle_id,
+                              const float *pt, int64_t n, const int64_t *seg_ptr, int32_t n_seg, const int32_t *pairs,
+                              const double *radius, int32_t n_pairs, const double *cuts, int64_t n_edges,
+                              int64_t *edge_index, float *edge_attr, float *y, float *edge_pt, int64_t *edge_ptr,
+                              void *workspace, size_t workspace_bytes, void *stream);
+size_t gnntrk_graph_builder_truth_workspace_bytes(int64_t n);
+int gnntrk_graph_builder_truth(const int64_t *edge_index, int64_t n_edges, float *y, const float *edge_pt,
+                               const int64_t *layer, const int64_t *particle_id, const float *pt, int64_t n,
+                               const int64_t *seg_ptr, int32_t n_seg, int32_t relabel, int64_t *counts, void *workspace,
+                               size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
