@@ -17,6 +17,7 @@ from .edge_filter import EFMLP, EFDeepSet, GeometricEF
 from .interaction_network import InteractionNetwork
 from .graph_construction import MLGraphConstruction, MLPCTransformer, knn_scan, knn_with_max_radius
 from .graph_builder import GraphBuilder, get_two_hop_tuples
+from .point_cloud_builder import PointCloudBuilder, get_truth_edge_index, load_detector, read_event
 from .graph_masks import get_good_node_mask, get_good_node_mask_tensors
 from .losses_ec import (EdgeWeightBCELoss, EdgeWeightFocalLoss, HaughtyFocalLoss, binary_focal_loss,
                         falsify_low_pt_edges)
@@ -64,4 +65,5 @@ __all__ = ["Data", "collate", "MLP", "InteractionNetwork", "ResIN", "ECForGraphT
            "count_hits_per_cluster", "hits_per_cluster_count_to_flat_dict", "common_metrics", "TrackGraphInfo",
            "OrphanCount", "get_track_graph_info_from_data", "summarize_track_graph_info", "get_orphan_counts",
            "get_basic_counts", "get_all_graph_construction_stats", "ec_threshold_scan", "get_all_ec_stats",
-           "collect_all_ec_stats", "GraphBuilder", "get_two_hop_tuples"]
+           "collect_all_ec_stats", "GraphBuilder", "get_two_hop_tuples", "PointCloudBuilder", "get_truth_edge_index",
+           "load_detector", "read_event"]

@@ -322,6 +322,18 @@ _SIGNATURES = {
     "gnntrk_graph_builder_truth_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gnntrk_graph_builder_truth": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P,
                                              _P, C.c_size_t, _P]),
+    "gnntrk_point_cloud_select_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "gnntrk_point_cloud_select": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P,
+                                            C.c_int64, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, _P, _P, _P,
+                                            _P, _P, _P, _P, C.c_size_t, _P]),
+    "gnntrk_point_cloud_sectors_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "gnntrk_point_cloud_sectors": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.c_double,
+                                             C.c_double, C.c_double, C.c_double, _P, _P, _P, C.c_size_t, _P]),
+    "gnntrk_point_cloud_gather": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int64, _P, _P,
+                                            _P, _P, C.c_size_t, _P]),
+    "gnntrk_truth_edges_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gnntrk_truth_edges_count": (C.c_int, [_P, C.c_int64, _P, C.c_int32, _P, _P, C.c_size_t, _P]),
+    "gnntrk_truth_edges_fill": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P, C.c_size_t, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -1390,6 +1390,80 @@ int gnntrk_graph_builder_truth(const int64_t *edge_index, int64_t n_edges, float
                                const int64_t *seg_ptr, int32_t n_seg, int32_t relabel, int64_t *counts, void *workspace,
                                size_t workspace_bytes, void *stream);
 
+/* ---- point cloud builder on the device: the tables of a TrackML event to sector point clouds
+ * (preprocessing/point_cloud_builder.py:156-353, 397-450; exatrkx_cell_features.py:174-250; csrc/point_cloud.hip).
+ * Every join is by key (hit_id, particle_id as int64), never by position.  All arrays but those marked HOST are device
+ * arrays.  One event per call.
+ *
+ * gnntrk_point_cloud_select - joins the tables, selects the hits and writes the columns of the kept hits in the order
+ *   of the hit table:
+ *   hit_id int64 [n_hits], hit_xyz float64 [n_hits][3], hit_vlm int32 [n_hits][3] (volume_id, layer_id, module_id);
+ *   cell_hit_id int64 [n_cells], cell_ch int32 [n_cells][2] (ch0, ch1), cell_value float64 [n_cells];
+ *   part_id int64 [n_particles], part_p float64 [n_particles][3] (px, py, pz);
+ *   truth_hit_id, truth_pid int64 [n_truth];
+ *   layer_map int32 [GNNTRK_PC_MAX_IDS][GNNTRK_PC_MAX_IDS]: (volume_id, layer_id) -> layer, -1: the hit is dropped;
+ *   det_index int32 [det_dims[0]][det_dims[1]][det_dims[2]]: (volume, layer, module) -> row of det_rows or -1, det_dims
+ *   HOST int32 [3], det_rows float64 [n_modules][12]: the rotation (row-major 3 x 3), module_t, pitch_u, pitch_v;
+ *   feat_code HOST int32 [n_feat] in [0, GNNTRK_PC_FEATURE_CODES): x, y, z, r, phi, eta_rz, u, v, charge_frac,
+ *   cell_count, cell_val, leta, lphi, lx, ly, lz, geta, gphi, V7, V8, V9, V12, V13, V14, V16, V17, V18 in this order;
+ *   feat_scale HOST float64 [n_feat].  A hit is kept when it has a layer, a truth row, and a particle id that is 0
+ *   (unless remove_noise) or in part_id.  Outputs, every one with room for n_hits rows, the first head[0] filled:
+ *   x float32 [n_hits][n_feat] (float64 / scale, rounded once), cols int64 [GNNTRK_PC_COLUMNS][n_hits] = layer,
+ *   particle_id, reconstructable, n_hits, n_layers_hit (distinct layer_id), index in the hit table; pt_eta float32
+ *   [2][n_hits] (noise: 0 and NaN); uv float64 [n_hits][2]; slot int32 [n_hits]: row of the particle, n_particles for
+ *   noise.  head int64 [GNNTRK_PC_HEAD]: kept hits, duplicate hit_ids, hits on a layer without a cell, kept hits on a
+ *   module that det_index lacks, hits with a volume_id or layer_id outside [0, GNNTRK_PC_MAX_IDS), further truth rows of
+ *   one hit, duplicate particle ids, distinct particle ids of the kept hits (0 is one), noise hits; the rest 0.
+ * gnntrk_point_cloud_sectors - for the columns of a select (capacity = its n_hits, n_kept = its head): the sector
+ *   predicate of every (kept hit, sector), with sector_cs float64 [n_sectors][2] = cos, sin of 2 s pi / n_sectors,
+ *   slope = arctan(pi / n_sectors); n_sectors == 1: every hit, nothing evaluated.  counts int64
+ *   [n_sectors][GNNTRK_PC_SECTOR_COUNTS]: hits in the wedge, in the extended wedge, distinct ids there, the numerator and
+ *   denominator of majority_contained (pt >= thld / pt > thld), pairs of hits of one id > 0 there.  head int64 [2]: rows
+ *   of all clouds, pairs of all clouds.  The workspace keeps the rows for
+ * gnntrk_point_cloud_gather - n_rows = head[0] read by the caller: x_out float32 [n_rows][n_feat], cols_out int64
+ *   [GNNTRK_PC_COLUMNS][n_rows] = layer, particle_id, reconstructable, n_hits, n_layers_hit, sector; pt_eta_out float32
+ *   [2][n_rows]: the clouds one after the other, each in hit order.  sector = s where a hit of the particle (id > 0)
+ *   lies in the wedge of s, else -1 (n_sectors == 1: 0): the reference divides the hits in the wedge by the length of
+ *   the particle's row of its per-particle table, which is 1, before it compares with 0.5; majority_contained likewise.
+ * gnntrk_truth_edges_count / _fill - every pair i < j of hits with one non-zero particle id inside a segment
+ *   (seg_ptr int64 [n_seg + 1]), in lexicographic order: counts int64 [n_seg]; then, n_edges = their sum, edge_index
+ *   int64 [2][n_edges] with global ids (global_ids != 0), or per segment its own block [2][m_s] of ids local to the
+ *   segment, the blocks one after the other; edge_ptr int64 [n_seg + 1].
+ *
+ * GNNTRK_EINVAL for negative sizes, NULL required pointers, a feature code out of range, n_sectors < 1, a small or NULL
+ * workspace; GNNTRK_EUNSUPPORTED for a table of 2^30 rows or more, hits x sectors or particles x sectors of 2^30 or more,
+ * n_feat > GNNTRK_PC_MAX_FEATURES, n_seg > GNNTRK_KSCAN_MAX_EVENTS.  Empty tables succeed. */
+#define GNNTRK_PC_MAX_FEATURES 32
+#define GNNTRK_PC_FEATURE_CODES 27
+#define GNNTRK_PC_MAX_IDS 64
+#define GNNTRK_PC_HEAD 12
+#define GNNTRK_PC_COLUMNS 6
+#define GNNTRK_PC_SECTOR_COUNTS 6
+size_t gnntrk_point_cloud_select_workspace_bytes(int64_t n_hits, int64_t n_cells, int64_t n_particles);
+int gnntrk_point_cloud_select(const int64_t *hit_id, const double *hit_xyz, const int32_t *hit_vlm, int64_t n_hits,
+                              const int64_t *cell_hit_id, const int32_t *cell_ch, const double *cell_value, int64_t n_cells,
+                              const int64_t *part_id, const double *part_p, int64_t n_particles,
+                              const int64_t *truth_hit_id, const int64_t *truth_pid, int64_t n_truth,
+                              const int32_t *layer_map, const int32_t *det_index, const int32_t *det_dims,
+                              const double *det_rows, int64_t n_modules, const int32_t *feat_code, const double *feat_scale,
+                              int32_t n_feat, int32_t remove_noise, float *x, int64_t *cols, float *pt_eta, double *uv,
+                              int32_t *slot, int64_t *head, void *workspace, size_t workspace_bytes, void *stream);
+size_t gnntrk_point_cloud_sectors_workspace_bytes(int64_t capacity, int64_t n_particles, int32_t n_sectors);
+int gnntrk_point_cloud_sectors(const double *uv, const int32_t *slot, const int64_t *n_kept,
+                               int64_t capacity, const double *part_p, int64_t n_particles, int32_t n_sectors,
+                               const double *sector_cs, double slope, double sector_ds, double sector_di, double thld,
+                               int64_t *counts, int64_t *head, void *workspace, size_t workspace_bytes, void *stream);
+int gnntrk_point_cloud_gather(const float *x, const int64_t *cols, const float *pt_eta, const int32_t *slot,
+                              int64_t capacity, int32_t n_feat, int64_t n_particles, int32_t n_sectors, int64_t n_rows,
+                              float *x_out, int64_t *cols_out, float *pt_eta_out, void *workspace, size_t workspace_bytes,
+                              void *stream);
+size_t gnntrk_truth_edges_workspace_bytes(int64_t n);
+int gnntrk_truth_edges_count(const int64_t *particle_id, int64_t n, const int64_t *seg_ptr, int32_t n_seg, int64_t *counts,
+                             void *workspace, size_t workspace_bytes, void *stream);
+int gnntrk_truth_edges_fill(const int64_t *particle_id, int64_t n, const int64_t *seg_ptr, int32_t n_seg, int64_t n_edges,
+                            int32_t global_ids, int64_t *edge_index, int64_t *edge_ptr, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
