@@ -15,6 +15,7 @@ from .io import GraphDataset, PrefetchLoader, ResidentDataset, load_graph, renum
 from .edge_classifier import ECForGraphTCN, PerfectEdgeClassification
 from .edge_filter import EFMLP, EFDeepSet, GeometricEF
 from .interaction_network import InteractionNetwork
+from .dynamic_edge_conv import DynamicEdgeConv
 from .graph_construction import MLGraphConstruction, MLPCTransformer, knn_scan, knn_with_max_radius
 from .graph_builder import GraphBuilder, get_two_hop_tuples
 from .point_cloud_builder import PointCloudBuilder, get_truth_edge_index, load_detector, read_event
@@ -42,7 +43,7 @@ from .postprocessing import (ClusterScanner, CombinedClusterScanner, DBSCANFastR
                              DBSCANHyperParamScannerFixed, DBSCANPerformanceDetails, OCScanResults, dbscan)
 from .track_condensation_networks import (GraphConstructionFCNN, GraphConstructionHeteroEncResFCNN,
                                             GraphConstructionHeteroResFCNN, GraphConstructionResIN, GraphTCN,
-                                            GraphTCNForMLGCPipeline, PerfectECGraphTCN,
+                                            GraphTCNForMLGCPipeline, INConvBlock, PerfectECGraphTCN, PointCloudTCN,
                                             HeterogeneousResFCNN, ModularGraphTCN, PreTrainedECGraphTCN,
                                             ResFCNN)
 
@@ -66,4 +67,4 @@ __all__ = ["Data", "collate", "MLP", "InteractionNetwork", "ResIN", "ECForGraphT
            "OrphanCount", "get_track_graph_info_from_data", "summarize_track_graph_info", "get_orphan_counts",
            "get_basic_counts", "get_all_graph_construction_stats", "ec_threshold_scan", "get_all_ec_stats",
            "collect_all_ec_stats", "GraphBuilder", "get_two_hop_tuples", "PointCloudBuilder", "get_truth_edge_index",
-           "load_detector", "read_event"]
+           "load_detector", "read_event", "DynamicEdgeConv", "INConvBlock", "PointCloudTCN"]

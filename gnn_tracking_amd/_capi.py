@@ -334,7 +334,16 @@ _SIGNATURES = {
     "gnntrk_truth_edges_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gnntrk_truth_edges_count": (C.c_int, [_P, C.c_int64, _P, C.c_int32, _P, _P, C.c_size_t, _P]),
     "gnntrk_truth_edges_fill": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P, C.c_size_t, _P]),
+    "gnntrk_edge_conv_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    "gnntrk_edge_conv_forward": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32,
+                                           _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
+                                           C.c_size_t, _P]),
+    "gnntrk_edge_conv_backward": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32,
+                                            _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
+                                            _P, _P, _P, _P, C.c_int32, _P, C.c_size_t, _P]),
 }
+
+EDGE_CONV_MAX_IN, EDGE_CONV_MAX_HIDDEN, EDGE_CONV_MAX_OUT, EDGE_CONV_MAX_SLOTS = 64, 128, 32, 64   # gnntrk_edge_conv_*
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

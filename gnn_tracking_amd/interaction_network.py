@@ -48,11 +48,13 @@ class InteractionNetwork(nn.Module, HyperparametersMixin):
         self.object_model = MLP(node_indim + edge_outdim, node_outdim, node_hidden_dim)
 
     def forward_csr(self, gi: ops.GraphIndex, x: Tensor, e_csr: Tensor, *, relu_in: bool = False,
-                    residue: Tensor | None = None, alpha_residue: float = 0.0):
+                    residue: Tensor | None = None, alpha_residue: float = 0.0,
+                    residue_mix: tuple[float, float] | None = None):
         """``x`` [N,Dn]; ``e_csr`` [E,De] in CSR order.  ``relu_in`` fuses the ReLU the
         residual stacks apply to both inputs (resin.py:103-104).  With ``residue`` the
         node output is ``sqrt(a)*residue + sqrt(1-a)*x~`` (resin.py:26), fused as the
-        object model's epilogue.  Returns ``(x_out, e_tilde_csr)``."""
+        object model's epilogue; ``residue_mix = (ca, cb)`` gives ``ca*residue + cb*x~`` instead (the plain convex
+        combination of ``INConvBlock``, track_condensation_networks.py:65).  Returns ``(x_out, e_tilde_csr)``."""
         rel_segs = [
             ops.Seg(x, gi.tgt, relu_in, ("tgt", gi)),
             ops.Seg(x, gi.src, relu_in, ("src", gi)),
@@ -79,6 +81,8 @@ class InteractionNetwork(nn.Module, HyperparametersMixin):
         segs = [ops.Seg(x_obj, None, relu_in), ops.Seg(aggr_obj)]
         if residue is not None:
             ca, cb = float(alpha_residue) ** 0.5, (1.0 - float(alpha_residue)) ** 0.5
+            if residue_mix is not None:
+                ca, cb = float(residue_mix[0]), float(residue_mix[1])
             x_out = self.object_model.fused(segs, epilogue=_capi.EPI_RESIDUAL, ca=ca, cb=cb,
                                             res=residue)
         else:

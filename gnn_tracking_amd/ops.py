@@ -1595,3 +1595,174 @@ def bce_loss(w: Tensor, y: Tensor, edge_index: Optional[Tensor] = None,
     else:
         pt = None
     return _BCE.apply(w, y, src_nodes, pt, float(pt_thld))
+
+
+# ------------------------------------------------------------------- dynamic edge convolution
+#: the fused kNN edge-conv kernel (csrc/edge_conv.hip) on / off.  Off (the default until the kernel path is measured
+#: faster than the composed path at every event-size shape): the same operator composed from the
+#: emitted edge list, ``fused_mlp`` and the segment sums.  ``GNNTRK_EDGE_CONV=1`` selects the kernel path.
+_EDGE_CONV_KERNEL = os.environ.get("GNNTRK_EDGE_CONV", "0") != "0"
+_EC_AGGR = {"add": 0, "mean": 1, "max": 2}
+
+
+def edge_conv_supported(dim: int, hidden: int, out_dim: int, slots: int) -> bool:
+    """Shapes ``gnntrk_edge_conv_*`` holds (include/gnntrk.h)."""
+    return (1 <= 2 * dim <= _capi.EDGE_CONV_MAX_IN and 1 <= hidden <= _capi.EDGE_CONV_MAX_HIDDEN
+            and 1 <= out_dim <= _capi.EDGE_CONV_MAX_OUT and 1 <= slots <= _capi.EDGE_CONV_MAX_SLOTS)
+
+
+def table_edges(nbr: Tensor, cnt: Tensor, k: int, include_self: bool) -> Tensor:
+    """The edge list of a neighbour table: int64 ``[2, M]``, row 0 the neighbour, row 1 the query, grouped by
+    query, the query itself first with ``include_self``, then its ``cnt`` table neighbours in table order (ids
+    clamped to ``[0, N)`` as the kernels clamp them).  One host synchronisation (the size is data dependent)."""
+    n = int(cnt.shape[0])
+    dev = nbr.device
+    if n == 0:
+        return torch.empty(2, 0, dtype=torch.int64, device=dev)
+    q = torch.arange(n, dtype=torch.int64, device=dev)
+    ids = nbr.reshape(n, -1)[:, :k].to(torch.int64).clamp(0, n - 1)
+    present = torch.arange(k, device=dev)[None, :] < cnt.to(torch.int64).clamp(0, k)[:, None]
+    if include_self:
+        ids = torch.cat([q[:, None], ids], dim=1)
+        present = torch.cat([torch.ones(n, 1, dtype=torch.bool, device=dev), present], dim=1)
+    tgt = q[:, None].expand_as(ids)
+    return torch.stack([ids[present], tgt[present]])
+
+
+def _ec_call_args(x, nbr, cnt, k, include_self, W1, b1, W2, b2, aggr, relu):
+    n, dim = int(x.shape[0]), int(x.shape[1])
+    return (_p(x), _row_stride(x), n, dim, _p(nbr), _p(cnt), k, int(nbr.shape[1]), int(include_self), _p(W1), _p(b1),
+            _p(W2), _p(b2), int(W1.shape[0]), int(W2.shape[0]), aggr, int(relu))
+
+
+class _EdgeConv(torch.autograd.Function):
+    """``gnntrk_edge_conv_forward`` / ``_backward``: nothing of size N k is kept between the two."""
+
+    @staticmethod
+    def forward(ctx, x, nbr, cnt, k: int, include_self: bool, aggr: int, relu: bool, edge_index, W1, b1, W2, b2):
+        _capi.require_device(x, nbr, cnt, W1, W2)
+        lib = _capi.load()
+        x = _as_rows(x)
+        W1, W2 = W1.contiguous(), W2.contiguous()
+        b1 = None if b1 is None else b1.contiguous()
+        b2 = None if b2 is None else b2.contiguous()
+        n, out_dim = int(x.shape[0]), int(W2.shape[0])
+        h = torch.empty(n, out_dim, dtype=torch.float32, device=x.device)
+        win = torch.empty(n, out_dim, dtype=torch.int32, device=x.device) if aggr == _EC_AGGR["max"] else None
+        ws = _ws(lib.gnntrk_edge_conv_workspace_bytes(int(x.shape[1]), int(W1.shape[0]), out_dim, n, 0), x)
+        _capi.check(lib.gnntrk_edge_conv_forward(*_ec_call_args(x, nbr, cnt, k, include_self, W1, b1, W2, b2, aggr, relu),
+                                                 _p(h), _p(win), _p(ws), ws.numel(), _stream(x)), lib)
+        ctx.cfg = (k, include_self, aggr, relu, b1 is not None, b2 is not None)
+        ctx.ei = edge_index
+        ctx.save_for_backward(x, nbr, cnt, h if relu else None, win, W1, W2, *[b for b in (b1, b2) if b is not None])
+        return h
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _capi.load()
+        k, include_self, aggr, relu, has_b1, has_b2 = ctx.cfg
+        x, nbr, cnt, h, win, W1, W2 = ctx.saved_tensors[:7]
+        rest = list(ctx.saved_tensors[7:])
+        b1 = rest.pop(0) if has_b1 else None
+        b2 = rest.pop(0) if has_b2 else None
+        n, dim, S = int(x.shape[0]), int(x.shape[1]), k + int(include_self)
+        need_x = ctx.needs_input_grad[0]
+        gW1, gW2 = torch.zeros_like(W1), torch.zeros_like(W2)
+        gb1 = None if b1 is None else torch.zeros_like(b1)
+        gb2 = None if b2 is None else torch.zeros_like(b2)
+        if n == 0:   # (the entry returns without a launch)
+            return (torch.zeros_like(x) if need_x else None, None, None, None, None, None, None, None, gW1, gb1, gW2, gb2)
+        g = g.contiguous().to(torch.float32)
+        gx = torch.empty(n, dim, dtype=torch.float32, device=x.device) if need_x else None
+        gslot = torch.empty(n * S, dim, dtype=torch.float32, device=x.device) if need_x else None
+        ws = _ws(lib.gnntrk_edge_conv_workspace_bytes(dim, int(W1.shape[0]), int(W2.shape[0]), n, 1), x)
+        _capi.check(lib.gnntrk_edge_conv_backward(*_ec_call_args(x, nbr, cnt, k, include_self, W1, b1, W2, b2, aggr, relu),
+                                                  _p(h), _p(win), _p(g), _p(gW1), _p(gb1), _p(gW2), _p(gb2), _p(gx),
+                                                  _p(gslot), 0, _p(ws), ws.numel(), _stream(x)), lib)
+        if need_x:
+            # the source side: the per-slot rows of the present slots are the rows of the table's edge list; summed
+            # per source over its graph index (deterministic segment sums, as the backward of ops.edge_features)
+            ei = ctx.ei if ctx.ei is not None else table_edges(nbr, cnt, k, include_self)
+            m = int(ei.shape[1])
+            if m == n * S:
+                rows = gslot
+            else:   # edge e is slot (e - first edge of its query) of its query: no compaction, no host read
+                count = cnt.to(torch.int64).clamp(0, k) + int(include_self)
+                first = torch.cumsum(count, 0) - count
+                slot_row = ei[1] * S + (torch.arange(m, device=x.device) - first[ei[1]])
+                rows = gslot.index_select(0, slot_row)
+            if m > 0:
+                gi = graph_index(ei, n, cache=ctx.ei is not None)
+                _segment_sum_raw(_permute_raw(rows, gi.perm, scatter=False), gi.rowptr_s, gi.spos, n, out=gx, accumulate=True)
+        return (gx, None, None, None, None, None, None, None, gW1, gb1, gW2, gb2)
+
+
+def edge_conv_composed(x: Tensor, nbr: Tensor, cnt: Tensor, k: int, message, *, aggr: str, include_self: bool,
+                       relu: bool = False, edge_index: Optional[Tensor] = None) -> Tensor:
+    """The same operator from the operators around it: the table's edge list, ``message`` (rows
+    ``[x[tgt], x[src] - x[tgt]]`` in CSR order -> message rows: the fused or wide MLP, or any module) and the
+    segment sums; ``scatter_reduce(amax)`` for max.  bf16 rows are converted: the messages are formed in fp32."""
+    n = int(x.shape[0])
+    x = x.float()
+    ei = edge_index if edge_index is not None else table_edges(nbr, cnt, k, include_self)
+    m = int(ei.shape[1])
+    gi = graph_index(ei, n, cache=edge_index is not None)
+    xt = _GatherRows.apply(x, gi.tgt, ("tgt", gi)) if m else x[:0]
+    xs = _GatherRows.apply(x, gi.src, ("src", gi)) if m else x[:0]
+    msg = message(torch.cat([xt, xs - xt], dim=1)).float()
+    out_dim = int(msg.shape[1])
+    if m == 0:
+        h = torch.zeros(n, out_dim, dtype=torch.float32, device=x.device) + msg.sum() * 0
+    elif aggr == "max":
+        idx = gi.tgt.to(torch.int64)[:, None].expand(m, out_dim)
+        h = torch.zeros(n, out_dim, dtype=torch.float32, device=x.device).scatter_reduce(0, idx, msg, "amax", include_self=False)
+    else:
+        h = segment_sum(msg.contiguous(), gi, "tgt")
+        if aggr == "mean":
+            deg = (gi.rowptr_t[1:] - gi.rowptr_t[:-1]).to(torch.float32).clamp(min=1.0)
+            h = h / deg[:, None]
+    return torch.relu(h) if relu else h
+
+
+def _mlp_message(weights, biases):
+    def message(rows: Tensor) -> Tensor:
+        if rows.shape[0] == 0:   # (no launch over no rows; the parameters stay in the graph)
+            out = rows.new_zeros(0, int(weights[-1].shape[0]))
+            return out + sum(p.sum() * 0 for p in [*weights, *biases] if p is not None)
+        return fused_mlp([Seg(rows)], weights, biases, n_rows=int(rows.shape[0]))
+    return message
+
+
+def edge_conv(x: Tensor, nbr: Tensor, cnt: Tensor, weights: Sequence[Tensor], biases: Sequence[Optional[Tensor]], *,
+              aggr: str, include_self: bool, relu: bool = False, k: Optional[int] = None,
+              edge_index: Optional[Tensor] = None) -> Tensor:
+    """``h[i] = aggr_{j in table(i)} nn(cat[x[i], x[j] - x[i]])`` (models/dynamic_edge_conv.py:36-61) on a neighbour
+    table as ``gnntrk_knn_search*`` writes it: ``nbr`` int32 ``[N, k_stride]``, ``cnt`` int32 ``[N]``, the first
+    ``k`` (default ``k_stride``) columns used.  ``include_self``: the query is its own first neighbour.  ``aggr``:
+    "add", "mean" or "max"; a query without a neighbour gives 0.  ``relu``: ReLU on the aggregated row.
+    ``edge_index``: ``table_edges`` of this table where the caller has it (the composed path and the input
+    gradient use it; built on demand otherwise).
+
+    A two-linear ``nn`` in fp32 inside the kernel's limits (2 D <= 64, hidden <= 128, out <= 32, k + self <= 64)
+    runs as one launch forward and one backward when the kernel path is on (``GNNTRK_EDGE_CONV=1``); everything
+    else - bf16 rows included - is composed from the library's operators."""
+    if aggr not in _EC_AGGR:
+        raise ValueError(f"edge_conv: aggr must be one of {sorted(_EC_AGGR)}, got {aggr!r}")
+    if x.dim() != 2 or nbr.dim() != 2 or nbr.dtype != torch.int32 or cnt.dtype != torch.int32:
+        raise ValueError("edge_conv: x [N, D], nbr int32 [N, k_stride] and cnt int32 [N] expected")
+    if nbr.shape[0] != x.shape[0] or cnt.shape[0] != x.shape[0]:
+        raise ValueError("edge_conv: one table row per row of x expected")
+    _capi.require_device(x, nbr, cnt)
+    k = int(nbr.shape[1]) if k is None else int(k)
+    if not 1 <= k <= int(nbr.shape[1]):
+        raise ValueError(f"edge_conv: k must be in 1..{int(nbr.shape[1])}, got {k}")
+    if int(weights[0].shape[1]) != 2 * int(x.shape[1]):
+        raise AssertionError(f"Expected feature dimension {int(weights[0].shape[1]) // 2}, got {int(x.shape[1])}")
+    nbr, cnt = nbr.contiguous(), cnt.contiguous()
+    fp32 = x.dtype == torch.float32 and all(w.dtype == torch.float32 for w in weights)
+    if (_EDGE_CONV_KERNEL and fp32 and len(weights) == 2
+            and edge_conv_supported(int(x.shape[1]), int(weights[0].shape[0]), int(weights[1].shape[0]), k + int(include_self))):
+        return _EdgeConv.apply(x, nbr, cnt, k, bool(include_self), _EC_AGGR[aggr], bool(relu), edge_index,
+                               weights[0], biases[0], weights[1], biases[1])
+    return edge_conv_composed(x, nbr, cnt, k, _mlp_message(list(weights), list(biases)), aggr=aggr,
+                              include_self=bool(include_self), relu=bool(relu), edge_index=edge_index)

@@ -1,7 +1,7 @@
 """Graph track-condensation networks on the fused HIP kernels.
 
 Reference: models/track_condensation_networks.py:118-403 (``ModularGraphTCN``, ``GraphTCN``,
-``PreTrainedECGraphTCN``), models/mlp.py:65-178 (``ResFCNN``, ``HeterogeneousResFCNN``) and
+``PreTrainedECGraphTCN``; :23-115 ``INConvBlock``, ``PointCloudTCN``), models/mlp.py:65-178 (``ResFCNN``, ``HeterogeneousResFCNN``) and
 models/graph_construction.py:25-132 (the ``GraphConstruction*FCNN`` embedding networks).  Same constructor
 keywords, ``hparams``, ``state_dict`` keys and output dict
 ``{"W", "H", "B", "ec_hit_mask", "ec_edge_mask"}``.
@@ -24,8 +24,10 @@ import torch
 from torch import Tensor, nn
 
 from . import _capi, edge_order, graph_cut, ops, ops_ml, precision
+from .dynamic_edge_conv import DynamicEdgeConv
 from .edge_classifier import ECForGraphTCN, PerfectEdgeClassification
 from .hparams import HyperparametersMixin, assert_feat_dim, obj_from_or_to_hparams
+from .interaction_network import InteractionNetwork as IN
 from .mlp import MLP
 from .resin import ResIN
 
@@ -402,3 +404,74 @@ class GraphTCNForMLGCPipeline(nn.Module, HyperparametersMixin):
 
     def forward(self, data) -> dict[str, Tensor | None]:
         return self._gtcn.forward(data=data)
+
+
+class INConvBlock(nn.Module):
+    def __init__(self, indim, h_dim, e_dim, L, k, hidden_dim=100):
+        """One block of ``PointCloudTCN`` (models/track_condensation_networks.py:23-66): a dynamic edge
+        convolution that builds a kNN graph from its input, an edge encoder on the convolved hits and ``L``
+        interaction networks on that graph.
+
+        The reference's ``MLP(..., L=1)`` builds TWO linears (keys ``layers.0``, ``layers.2``: its hidden loop
+        is empty, models/mlp.py:44-49); this package's ``MLP`` counts linears, so the encoders are built with
+        ``L=2`` - the reference's keys and shapes.  ``node_encoder`` is also registered as ``edge_conv.nn``, as
+        in the reference: both key sets are in the ``state_dict``."""
+        super().__init__()
+        self.relu = nn.ReLU()
+        self.node_encoder = MLP(2 * indim, h_dim, hidden_dim=hidden_dim, L=2)
+        self.edge_conv = DynamicEdgeConv(self.node_encoder, aggr="add", k=k)
+        self.edge_encoder = MLP(2 * h_dim, e_dim, hidden_dim=hidden_dim, L=2)
+        self.layers = nn.ModuleList([
+            IN(node_indim=h_dim, edge_indim=e_dim, node_outdim=h_dim, edge_outdim=e_dim, node_hidden_dim=hidden_dim,
+               edge_hidden_dim=hidden_dim) for _ in range(L)])
+
+    def forward(self, x: Tensor, alpha: float = 0.5, *, batch: Tensor | None = None) -> Tensor:
+        """``batch`` (not in the reference): every event of a collated batch is its own neighbour search."""
+        h, edge_index = self.edge_conv(x, batch, relu=True)   # relu(edge_conv(x)): the kernel's epilogue
+        h = h.float()
+        gi = ops.graph_index(edge_index, int(h.shape[0]))
+        # relu(edge_encoder(cat[h[src], h[tgt]])), source first: one fused gather-MLP, in the index's CSR order
+        edge_attr = self.edge_encoder.fused([ops.Seg(h, gi.src, False, ("src", gi)), ops.Seg(h, gi.tgt, False, ("tgt", gi))],
+                                            epilogue=_capi.EPI_RELU, n_rows=gi.n_edges)
+        for layer in self.layers:
+            # h = alpha * h + (1 - alpha) * delta_h: a plain convex combination, the object model's epilogue
+            h, edge_attr = layer.forward_csr(gi, h, edge_attr, residue=h, residue_mix=(alpha, 1 - alpha))
+        return h
+
+
+class PointCloudTCN(nn.Module):
+    #: with a collated ``batch`` every event is its own neighbour search; False: the reference's behaviour, which
+    #: ignores ``batch`` (one cloud, neighbours across events)
+    per_event = True
+
+    def __init__(self, node_indim: int, h_dim=10, e_dim=10, h_outdim=5, hidden_dim=100, N_blocks=3, L=3):
+        """Model to directly process point clouds rather than start with a graph
+        (models/track_condensation_networks.py:69-115).
+
+        Args:
+            node_indim: input feature dimension
+            h_dim: node dimension in latent space
+            e_dim: edge dimension in latent space
+            h_outdim: output dimension in clustering space
+            hidden_dim: hidden width of the two heads (as in the reference, the blocks are not handed it and
+                stay at their default 100)
+            N_blocks: number of edge_conv + IN blocks (after the first); block ``i`` uses ``k = N_blocks - i``
+            L: message passing depth in each block
+        """
+        super().__init__()
+        layers = [INConvBlock(node_indim, h_dim, e_dim, L=L, k=N_blocks)]
+        for i in range(N_blocks):
+            layers.append(INConvBlock(h_dim, h_dim, e_dim, L=L, k=N_blocks - i))
+        self.layers = nn.ModuleList(layers)
+        self.B = MLP(h_dim, 1, hidden_dim, L=3)
+        self.X = MLP(h_dim, h_outdim, hidden_dim, L=3)
+
+    def forward(self, data, alpha: float = 0.5) -> dict[str, Tensor | None]:
+        """As in the reference, ``alpha`` is not handed to the blocks (they mix with their default 0.5)."""
+        h = data.x
+        batch = getattr(data, "batch", None) if self.per_event else None
+        for layer in self.layers:
+            h = layer(h, batch=batch)
+        beta = torch.sigmoid(self.B(h).float()).squeeze() + 10e-12
+        h_out = self.X(h).float()
+        return {"W": None, "H": h_out, "B": beta, "P": None}

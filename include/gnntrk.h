@@ -1464,6 +1464,44 @@ int gnntrk_truth_edges_fill(const int64_t *particle_id, int64_t n, const int64_t
                             int32_t global_ids, int64_t *edge_index, int64_t *edge_ptr, void *workspace,
                             size_t workspace_bytes, void *stream);
 
+/* ---- dynamic edge convolution on a k-nearest-neighbour table (csrc/edge_conv.hip) ----------------------------------
+ * Reference: models/dynamic_edge_conv.py:14-64 (DynamicEdgeConv.forward :36-58 and .message :60-61), as INConvBlock
+ * uses it (models/track_condensation_networks.py:35-36, :57-58):
+ *     h[i] = aggr_{s < count[i]} nn(cat[x[i], x[j(i, s)] - x[i]]),   nn = Linear(2 dim, hidden) -> ReLU -> Linear(hidden, out_dim)
+ * x float32 [n][dim] with row stride x_stride; nbr int32 [n][k_stride] and cnt int32 [n] exactly as gnntrk_knn_search*
+ * writes them (cnt is clamped to 0 .. k, ids outside [0, n) are clamped: a bad table reads a wrong hit, never foreign
+ * memory).  include_self: slot 0 of every query is the query itself (message input [x[i], 0]), then its cnt[i]
+ * neighbours; count[i] = cnt[i] + include_self.  W1 [hidden][2 dim], W2 [out_dim][hidden] in nn.Linear storage, b1 /
+ * b2 or NULL.  aggr: 0 add, 1 mean (the sum over the present slots divided by their number), 2 max (ties: the lowest
+ * slot).  A query without a slot gives 0.  relu: ReLU on the aggregated row.  The difference x[j] - x[i] is formed in
+ * fp32 from the loaded rows and then contracted.
+ *
+ * gnntrk_edge_conv_forward - h float32 [n][out_dim]; win int32 [n][out_dim] (max only, NULL otherwise): the winning
+ *   slot of every (node, feature), -1 for a query without a slot.  Nothing of size n k is written.
+ * gnntrk_edge_conv_backward - recomputes the hidden layer per (node, slot).  h, win: what the forward wrote (h is read
+ *   for the ReLU gate only, win for max only).  gout float32 [n][out_dim].  gW1, gb1, gW2, gb2: set, or added to with
+ *   accumulate != 0; NULL: not wanted.  Per-workgroup partial sums, added in a fixed order (no atomics).
+ *   gx_tgt float32 [n][dim] and gx_slot float32 [n][k + include_self][dim] together or both NULL (no input-gradient
+ *   work): gx_tgt[i] = sum_s (g_a - g_b) and gx_slot[i][s] = g_b for s < count[i], the gradient of slot s for its
+ *   source row j(i, s), which the caller sums per source in a fixed order (rows of absent slots are undefined).
+ * gnntrk_edge_conv_workspace_bytes - of either entry (backward != 0: the backward's); 0 for refused shapes.
+ *
+ * GNNTRK_EINVAL for n < 0, k < 1, k_stride < k, aggr out of range, non-positive widths, NULL required pointers, a small
+ * or NULL workspace; GNNTRK_EUNSUPPORTED for 2 dim > GNNTRK_RESFCNN_MAX_IN, hidden > GNNTRK_RESFCNN_MAX_WIDTH, out_dim >
+ * GNNTRK_RESFCNN_MAX_OUT, k + include_self > 64, n >= 2^30.  n == 0 returns GNNTRK_OK without a launch. */
+size_t gnntrk_edge_conv_workspace_bytes(int32_t dim, int32_t hidden, int32_t out_dim, int64_t n, int32_t backward);
+int gnntrk_edge_conv_forward(const float *x, int32_t x_stride, int64_t n, int32_t dim, const int32_t *nbr,
+                             const int32_t *cnt, int32_t k, int32_t k_stride, int32_t include_self, const float *W1,
+                             const float *b1, const float *W2, const float *b2, int32_t hidden, int32_t out_dim,
+                             int32_t aggr, int32_t relu, float *h, int32_t *win, void *workspace, size_t workspace_bytes,
+                             void *stream);
+int gnntrk_edge_conv_backward(const float *x, int32_t x_stride, int64_t n, int32_t dim, const int32_t *nbr,
+                              const int32_t *cnt, int32_t k, int32_t k_stride, int32_t include_self, const float *W1,
+                              const float *b1, const float *W2, const float *b2, int32_t hidden, int32_t out_dim,
+                              int32_t aggr, int32_t relu, const float *h, const int32_t *win, const float *gout, float *gW1,
+                              float *gb1, float *gW2, float *gb2, float *gx_tgt, float *gx_slot, int32_t accumulate,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
