@@ -10,8 +10,10 @@ needed, builds) the HIP extension and fails loudly when that is impossible - the
 no CPU fallback.
 """
 
-from .data import Data, collate
-from .io import GraphDataset, PrefetchLoader, ResidentDataset, load_graph, renumber_nodes
+from .data import Data, EventLayout, collate, uncollate
+from .io import (GraphDataset, GraphWriter, PackedEvents, PrefetchLoader, ResidentDataset, load_graph, pack_events,
+                 renumber_nodes, save_graph, save_graphs)
+from .data_transformer import DataTransformer, ECCut, ECCutRefine, build_graphs, build_point_clouds
 from .edge_classifier import ECForGraphTCN, PerfectEdgeClassification
 from .edge_filter import EFMLP, EFDeepSet, GeometricEF
 from .interaction_network import InteractionNetwork
@@ -67,4 +69,6 @@ __all__ = ["Data", "collate", "MLP", "InteractionNetwork", "ResIN", "ECForGraphT
            "OrphanCount", "get_track_graph_info_from_data", "summarize_track_graph_info", "get_orphan_counts",
            "get_basic_counts", "get_all_graph_construction_stats", "ec_threshold_scan", "get_all_ec_stats",
            "collect_all_ec_stats", "GraphBuilder", "get_two_hop_tuples", "PointCloudBuilder", "get_truth_edge_index",
-           "load_detector", "read_event", "DynamicEdgeConv", "INConvBlock", "PointCloudTCN"]
+           "load_detector", "read_event", "DynamicEdgeConv", "INConvBlock", "PointCloudTCN", "uncollate", "EventLayout",
+           "save_graph", "save_graphs", "GraphWriter", "pack_events", "PackedEvents", "DataTransformer", "ECCut",
+           "ECCutRefine", "build_point_clouds", "build_graphs"]

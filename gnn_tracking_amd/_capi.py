@@ -341,7 +341,15 @@ _SIGNATURES = {
     "gnntrk_edge_conv_backward": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32,
                                             _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
                                             _P, _P, _P, _P, C.c_int32, _P, C.c_size_t, _P]),
+    "gnntrk_pack_plan_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "gnntrk_pack_segments": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P]),
 }
+
+# gnntrk_pack_segments: the chunk size, the caps and the modes; a descriptor is five int64 words (src, dst_off, n_bytes,
+# sub, mode in the low half of the last)
+PACK_CHUNK_BYTES, PACK_MAX_SEGS, PACK_MAX_CHUNKS = 16384, 1 << 20, 1 << 22
+PACK_RAW, PACK_SUB_I64, PACK_SUB_I32 = 0, 1, 2
+PACK_SEG_WORDS = 5
 
 EDGE_CONV_MAX_IN, EDGE_CONV_MAX_HIDDEN, EDGE_CONV_MAX_OUT, EDGE_CONV_MAX_SLOTS = 64, 128, 32, 64   # gnntrk_edge_conv_*
 

@@ -19,7 +19,7 @@ Contract:
 * A collated batch (``ptr`` or ``batch``): pairs inside an event only, edges event-major with global node ids;
   ``build(collate(clouds))`` equals ``collate([build(c) for c in clouds])`` field by field.
 * Layers must lie in ``[0, 64)``.  Strip layers have no pairs (``pixel_only=False`` gives an empty list, as in the
-  reference).  The directory loop ``process()`` is not part of this package.
+  reference).  The directory loop ``process()`` is ``data_transformer.build_graphs``.
 """
 
 from __future__ import annotations

@@ -20,7 +20,8 @@ Contract:
   the wedge by the length of the particle's ROW of its per-particle table (1), so a particle with id > 0 carries
   ``sector == s`` in every cloud ``s`` whose plain wedge holds at least one of its hits, and ``majority_contained`` is
   counted with the same denominator.
-* Not part of this package: the directory loop ``process()``, the ``.pt`` writer and the ``.pickle`` detector cache.
+* The directory loop ``process()`` is ``data_transformer.build_point_clouds``, the ``.pt`` writer ``io.GraphWriter``; the
+  ``.pickle`` detector cache is not part of this package.
 """
 
 from __future__ import annotations

@@ -1502,6 +1502,43 @@ int gnntrk_edge_conv_backward(const float *x, int32_t x_stride, int64_t n, int32
                               float *gb1, float *gW2, float *gb2, float *gx_tgt, float *gx_slot, int32_t accumulate,
                               void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- event packer: many byte ranges into one contiguous image, one launch (csrc/pack.hip) --------------------------
+ * What the dataset writer (gnn_tracking_amd/io.py) moves off the device: every (event, field) range of a collated batch
+ * is one SEGMENT, copied to `dst + dst_off`.  mode GNNTRK_PACK_RAW copies n_bytes bytes; GNNTRK_PACK_SUB_I64 /
+ * GNNTRK_PACK_SUB_I32 copy n_bytes / 8 int64 (n_bytes / 4 int32) elements minus `sub` (the node offset of the event,
+ * for the `*index*` fields).  `src` is the device address of the first byte.  Bytes of dst that no segment covers are
+ * not written; segments must not overlap (the result would depend on the order of the writers).
+ *
+ * The PLAN is the descriptor table followed by the chunk table: gnntrk_pack_seg [n_segs], then for every segment in
+ * order and every k < ceil(n_bytes / GNNTRK_PACK_CHUNK_BYTES) the pair int32 (segment, k), n_chunks pairs in all.  The
+ * caller builds it on the host and uploads it as one block:
+ *     segs - the plan's HOST image, which the entry checks completely before it launches anything;
+ *     plan - the plan's DEVICE image, a copy of the same bytes, which the kernel reads.
+ * gnntrk_pack_plan_bytes - the size of either (0 for counts out of range).
+ *
+ * GNNTRK_EINVAL, before any launch, for: negative sizes; n_segs > GNNTRK_PACK_MAX_SEGS or n_chunks >
+ * GNNTRK_PACK_MAX_CHUNKS; NULL segs, plan or dst; a dst that is not 16-byte aligned; a segment with a NULL src and
+ * n_bytes > 0, an unknown mode, dst_off + n_bytes beyond dst_bytes, in a sub mode an n_bytes that is no multiple of the
+ * element size, a src or dst_off that is not a multiple of it, or (int32) a sub outside int32; a chunk table that is
+ * not the one described above (the sizes do not fit n_chunks).  n_segs == 0 returns GNNTRK_OK without a launch. */
+#define GNNTRK_PACK_CHUNK_BYTES 16384
+#define GNNTRK_PACK_MAX_SEGS 1048576
+#define GNNTRK_PACK_MAX_CHUNKS 4194304
+#define GNNTRK_PACK_RAW 0
+#define GNNTRK_PACK_SUB_I64 1
+#define GNNTRK_PACK_SUB_I32 2
+typedef struct {
+    uint64_t src;     /* device address of the first source byte */
+    int64_t dst_off;  /* byte offset in the image */
+    int64_t n_bytes;
+    int64_t sub;
+    int32_t mode;
+    int32_t _pad;
+} gnntrk_pack_seg;
+size_t gnntrk_pack_plan_bytes(int64_t n_segs, int64_t n_chunks);
+int gnntrk_pack_segments(const gnntrk_pack_seg *segs, int64_t n_segs, const void *plan, int64_t n_chunks, void *dst,
+                         int64_t dst_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
